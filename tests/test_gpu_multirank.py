@@ -26,7 +26,7 @@ def torch_cuda():
 
 def run_bench(world, extra, env=None, timeout=900):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--same-device", "--verify-gather",
-           "--no-cpu", "--clock-warmup-ms", "0", "--warmup", "1"] + extra
+           "--full", "--no-cpu", "--clock-warmup-ms", "0", "--warmup", "1"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **(env or {})), cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
