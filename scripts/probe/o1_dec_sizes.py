@@ -13,7 +13,7 @@ import trc_testlib as T  # noqa: E402
 
 full = T.drift_bytes(100 * 1000 * 1000, 3)
 rows = int(os.environ.get("TRC_O1_ROWS", "0"))
-per_wave = {1: 8, 4: 16, 2: 32, 16: 16, 8: 8, 64: 64}.get(rows, 0)      # chunks per wave of the forced form (0: the default picks by size)
+per_wave = {1: 8, 4: 16}.get(rows, 0)      # chunks per wave of the forced form (0: the default picks by size)
 for mb in (25, 50, 67, 100):
     n = mb * 1000 * 1000
     d = full[:n]

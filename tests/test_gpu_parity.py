@@ -272,42 +272,29 @@ def test_static_rans_decoder_both_forms(torch_cuda):
         assert r.returncode == 0 and "ok" in r.stdout, (form, r.stdout[-2000:] + r.stderr[-3000:])
 
 
-def test_bitwise_rc_encoder_both_forms(torch_cuda):
-    """the bitwise range coder's encoder exists with the deepest tree level in LDS and with it in global memory (a 256-byte row
-    per lane in the workspace, filled by the wave itself); the launch picks by wave count.  Each form is forced in a process of
-    its own (TRC_RCB_L7G is read once): per-chunk parity with the oracle and round trip, ragged tails and a short last wave
-    (dead lanes have rows of their own) included."""
-    import subprocess, sys, textwrap
-    code = textwrap.dedent("""
-        import sys, numpy as np, torch
-        sys.path[:0] = [%r, %r]
-        import trc, trc_testlib as T
-        from golden.make_golden import gen
-        for kind, n, chunk in (("text", 300001, 512), ("zipf", 64 * 1024 * 2 + 5, 1024), ("uniform", 40000, 256), ("runs", 70001, 4096), ("text", 700, 256)):
-            d = gen(kind, n, 6)
-            dc = trc.DeviceCoder(trc.RCB, n, chunk, "cuda:0")
-            d_in = torch.from_numpy(np.concatenate([d, np.zeros(512, np.uint8)])).to("cuda:0")
-            for rep in range(2):                                   # twice: the second call finds the rows of the first in the workspace
-                dc.encode(d_in, n)
-                clen, payload = dc.result(n)
-                ep, ec, _ = T.orc_chunked_enc(trc.RCB, d, chunk, None, 0)
-                assert np.array_equal(clen, ec) and np.array_equal(payload, ep), (kind, n, chunk, rep)
-            out = torch.full((n + 512,), 0xA5, dtype=torch.uint8, device="cuda:0")
-            dc.decode(out, n); torch.cuda.synchronize()
-            assert np.array_equal(out.cpu().numpy()[:n], d), (kind, n, chunk)
-        print("ok")
-    """) % (os.path.dirname(os.path.abspath(trc.__file__)), os.path.dirname(os.path.abspath(__file__)))
-    for form in ("0", "1"):
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=dict(os.environ, TRC_RCB_L7G=form))
-        assert r.returncode == 0 and "ok" in r.stdout, (form, r.stdout[-2000:] + r.stderr[-3000:])
+def test_bitwise_rc_encoder(torch_cuda):
+    """the bitwise range coder's encoder (a model wave + a coder wave per 64 chunks): per-chunk parity with the oracle and round
+    trip, twice into the same workspace, ragged tails and a short last wave included."""
+    torch = torch_cuda
+    for kind, n, chunk in (("text", 300001, 512), ("zipf", 64 * 1024 * 2 + 5, 1024), ("uniform", 40000, 256), ("runs", 70001, 4096), ("text", 700, 256)):
+        d = gen(kind, n, 6)
+        dc = trc.DeviceCoder(trc.RCB, n, chunk, "cuda:0")
+        d_in = torch.from_numpy(np.concatenate([d, np.zeros(512, np.uint8)])).to("cuda:0")
+        for rep in range(2):                                       # twice: the second call finds the workspace as the first left it
+            dc.encode(d_in, n)
+            clen, payload = dc.result(n)
+            ep, ec, _ = T.orc_chunked_enc(trc.RCB, d, chunk, None, 0)
+            assert np.array_equal(clen, ec) and np.array_equal(payload, ep), (kind, n, chunk, rep)
+        out = torch.full((n + 512,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        dc.decode(out, n); torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy()[:n], d), (kind, n, chunk)
 
 
 def test_round4_kernel_forms(torch_cuda):
-    """round 4 gave the model-bound coders second forms that the launch code picks between: encoders as a model wave + a coder wave
-    (default) or one wave, `anscdf` pass 2 with four lanes per chunk (default) or one, the order-1 model pass as a hi wave + a lo
-    wave, decoders as two waves (measured slower, off by default), two histogram kernels.  Every form is forced in a process of its
-    own (the switches are read once): per-chunk parity with the oracle and round trip for the coders involved, ragged tails, a
-    short last wave, raw chunks."""
+    """round 4's forms of the model-bound coders (encoders as model waves + a coder wave, `anscdf` pass 2 with four lanes per
+    chunk, the order-1 model pass as a hi wave + a lo wave) and the histogram: per-chunk parity with the oracle and round trip for
+    the coders involved, ragged tails, a short last wave, raw chunks; the histogram also on its many-round path, forced in a
+    process of its own (TRC_HIST_ROUND_VECS is read once)."""
     import subprocess, sys, textwrap
     code = textwrap.dedent("""
         import sys, numpy as np, torch
@@ -337,10 +324,7 @@ def test_round4_kernel_forms(torch_cuda):
         assert np.array_equal(hist.cpu().numpy(), np.bincount(d, minlength=256))
         print("ok")
     """) % (os.path.dirname(os.path.abspath(trc.__file__)), os.path.dirname(os.path.abspath(__file__)))
-    forms = (dict(TRC_RCA_MC="0", TRC_RCB_MC="0", TRC_ANSA_MC="0", TRC_O1_MC="0", TRC_HIST_FORM="1"),      # everything as in round 3
-             dict(TRC_HIST_ROUND_VECS="3"),                                                                  # the histogram's many-round path (real inputs: beyond 4.29 GB)
-             dict(TRC_ANSA_CODEQ="0"),                                                                       # planar records, one lane per chunk in pass 2
-             dict(TRC_RCA_DMC="1", TRC_ANSA_DMC="1"),                                                        # the two-wave decoders
+    forms = (dict(TRC_HIST_ROUND_VECS="3"),                                                                  # the histogram's many-round path (real inputs: beyond 4.29 GB)
              dict())                                                                                         # the defaults, same inputs
     for env in forms:
         r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
@@ -377,7 +361,7 @@ def test_round5_workgroup_shapes(torch_cuda):
     """round 5: the launch code picks between two workgroup shapes by the size of the launch -- small workgroups (rounds 1-4), or
     one large workgroup per CU whose waves keep each other's pace (TrcPace, csrc/trc_dev.h) when the launch is one residency round:
     static rANS / range-coder encoders (1 / 4 vs 12 waves), the two-stream pair encoder (2 vs 12), the four-lanes-per-chunk rANS
-    coding passes (4 vs 16), the order-1 decoder (eight lanes per chunk by default; one lane per chunk with 64 / 16 / 8 chunks per wave).  The pace-keeping itself only moves wave priorities.
+    coding passes (4 vs 16), the order-1 decoder (four vs eight lanes per chunk).  The pace-keeping itself only moves wave priorities.
     Every shape is FORCED in a process of its own (the switches are read once) on inputs of a few groups -- which the automatic
     rule would never give the large shape: ragged tails, a short last workgroup, raw chunks -- per-chunk parity with the oracle
     and round trip."""
@@ -410,12 +394,63 @@ def test_round5_workgroup_shapes(torch_cuda):
                 assert np.array_equal(o[:n], d) and (o[n:] == 0xA5).all(), (trc.CODEC_NAMES[codec], kind, n, chunk)
         print("ok")
     """) % (os.path.dirname(os.path.abspath(trc.__file__)), os.path.dirname(os.path.abspath(__file__)))
-    forms = (dict(TRC_ENC_WPB="12", TRC_RCS_ENC_WPB="12", TRC_CODEQ_GPW="4", TRC_O1_ROWS="16", TRC_NIB_BIG="1"),    # the large shapes, on small inputs
-             dict(TRC_ENC_WPB="4", TRC_RCS_ENC_WPB="1", TRC_CODEQ_GPW="1", TRC_O1_ROWS="64", TRC_NIB_BIG="0"),      # the small shapes
-             dict(TRC_O1_ROWS="8"), dict(TRC_O1_ROWS="4"), dict(TRC_O1_ROWS="2"), dict(TRC_O1_ROWS="1"))     # (order-1 decoder: 4 / 2 / 1 = four / two / eight lanes per chunk)
+    forms = (dict(TRC_ENC_WPB="12", TRC_RCS_ENC_WPB="12", TRC_CODEQ_GPW="4", TRC_O1_ROWS="4", TRC_NIB_BIG="1"),     # the large shapes, on small inputs
+             dict(TRC_ENC_WPB="4", TRC_RCS_ENC_WPB="1", TRC_CODEQ_GPW="1", TRC_O1_ROWS="1", TRC_NIB_BIG="0"))      # the small shapes (order-1 decoder: four / eight lanes per chunk)
     for env in forms:
         r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=dict(os.environ, **env))
         assert r.returncode == 0 and "ok" in r.stdout, (env, r.stdout[-2000:] + r.stderr[-3000:])
+
+
+def test_static_rans_twelve_wave_encoder(torch_cuda):
+    """the static rANS encoder in twelve-wave workgroups (TRC_ENC_WPB=12, forced in a process of its own: the switch is read once)
+    on one workgroup / a few / a chip full of them, workgroups whose last waves have no chunks, raw chunks among coded ones,
+    nothing compressible, three calls into the same workspace, a second stream keeping the device busy.  Lengths, payload and
+    total equal the oracle's chunked encode, nothing is written past the payload, decodes return the input."""
+    import subprocess, sys, textwrap
+    code = textwrap.dedent("""
+        import sys, numpy as np, torch
+        sys.path[:0] = [%r, %r]
+        import trc, trc_testlib as T
+        from golden.make_golden import gen
+        def check(d, chunk, reps=3, busy=False):
+            n = d.size
+            _, cdf, cdfnum = T.orc_cdfini(d)
+            ep, ec, _ = T.orc_chunked_enc(trc.ANS4S, d, chunk, cdf, cdfnum)
+            dc = trc.DeviceCoder(trc.ANS4S, n, chunk, "cuda:0")
+            dc.work.fill_(0xA5)                                   # whatever the allocator handed out
+            dc.set_cdf(cdf, cdfnum)
+            d_in = torch.from_numpy(np.concatenate([d, np.zeros(512, np.uint8)])).to("cuda:0")
+            side = None
+            if busy:                                              # another coder's launches on a second stream
+                side = torch.cuda.Stream()
+                d2 = torch.from_numpy(gen("text", 1 << 22, 3)).to("cuda:0")
+                dc2 = trc.DeviceCoder(trc.RCB, 1 << 22, 1536, "cuda:0")
+                with torch.cuda.stream(side):
+                    for _ in range(6): dc2.encode(d2, 1 << 22)
+            for rep in range(reps):                               # the second and third call find the workspace as the call before left it
+                dc.payload.fill_(0x5A); dc.total.fill_(-1)
+                dc.encode(d_in, n)
+                clen, payload = dc.result(n)
+                assert np.array_equal(clen, ec), ("clen", n, chunk, rep)
+                assert payload.size == ep.size and np.array_equal(payload, ep), ("payload", n, chunk, rep, payload.size, ep.size)
+                assert int(dc.payload[ep.size:ep.size + 64].cpu().numpy().max()) == 0x5A and int(dc.payload[ep.size:ep.size + 64].cpu().numpy().min()) == 0x5A, "wrote past the payload"
+                out = torch.full((n + 512,), 0xA5, dtype=torch.uint8, device="cuda:0")
+                dc.decode(out, n, dir_ready=True); torch.cuda.synchronize()
+                o = out.cpu().numpy()
+                assert np.array_equal(o[:n], d) and (o[n:] == 0xA5).all(), ("roundtrip", n, chunk, rep)
+            if side is not None: side.synchronize()
+        mixed = np.concatenate([gen("zipf", 512 * 700, 1), gen("uniform", 512 * 37, 2), gen("const", 512 * 90, 3), gen("uniform", 512 * 3, 4),
+                                gen("text", 512 * 64 * 30 + 77, 5)])
+        check(gen("text", 300001, 11), 512)                       # 10 groups: one workgroup, two waves without chunks
+        check(gen("zipf", 64 * 512 * 41 + 5, 12), 512)            # 42 groups: four workgroups, the last with six waves; ragged last chunk
+        check(mixed, 512)                                         # raw chunks among coded ones
+        check(gen("text", 64 * 256 * 12 * 7, 13), 256)            # exactly seven full workgroups
+        check(gen("uniform", 64 * 512 * 13 + 1, 14), 512)         # nothing compresses: every piece is the input chunk
+        check(gen("text", 70 * 1000 * 1000, 15), 512, reps=2, busy=True)   # 2137 groups: the shape the library picks by itself at this size
+        print("ok")
+    """) % (os.path.dirname(os.path.abspath(trc.__file__)), os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, TRC_ENC_WPB="12"))
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-2000:] + r.stderr[-3000:])
 
 
 def test_order1_model_pass_by_chains_and_by_position(torch_cuda):

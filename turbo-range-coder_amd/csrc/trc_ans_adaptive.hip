@@ -17,6 +17,8 @@
 //   pass 2  trc_ansa_code_kernel  : pop the records in reverse, one rANS step each; words grow downward from the
 //           end of the chunk's scratch region.  The divisor changes every symbol, so st/f is an f32 estimate plus
 //           exact correction (st < 2^31).
+//   ANSA4 runs these two passes; ANSA runs pass 1 as trc_ansa_model2_kernel (two waves, planar record space) and pass 2 as
+//   trc_ansa_codeq_kernel (four lanes per chunk), below.
 //   Raw rule (mnflush): before EVERY record the reference tests ep <= op + 2 + 4*states; the test is monotone.
 // The decoders read the stream through a 16-byte register window per lane (trc_lane_io.h).  ANSA4's decoder takes
 // the n%4 tail from the state the ENCODER used (the reference decoder's tail reads the other state and does not
@@ -158,24 +160,11 @@ __global__ __launch_bounds__(128 * TRC_WPG) void trc_ansa_model2_kernel(
     NibTable T0 = m.load(m.table(0));                          // (hi wave)
 
     const u32 S = chunk / TRC_SEG;
-    // (TRC_ANSA_M2_PAIR: both 64-byte halves of a 128-byte input line requested together, QuadIn::take_fwd -- the pass then reads 200 MB
-    // from the fabric for its two walks of 100 MB instead of ~1.8 x that, and runs 6 % SLOWER (encode 0.587 -> 0.623 ms,
-    // profiles/r05k_ab.txt): the pass is not bound by its traffic.  Off.)
-#ifndef TRC_ANSA_M2_PAIR
     qin.issue(wc, 0);
-#else
-    qin.start_fwd(wc, S);
-#endif
     for (u32 s = 0; s < S; s++) {
-#ifndef TRC_ANSA_M2_NOPACE
         pace.step(s + 1u);
-#endif
-#ifndef TRC_ANSA_M2_PAIR
         qin.commit();
         if (s + 1 < S) qin.issue(wc, (s + 1) * TRC_SEG);
-#else
-        qin.take_fwd(wc, s, S);
-#endif
         uint4 pc0 = qin.read(0), pc1 = qin.read(1), pc2 = qin.read(2), pc3 = qin.read(3);
 #pragma nounroll
         for (u32 k = 0; k < 4; k++) {
@@ -277,73 +266,6 @@ __global__ __launch_bounds__(64 * TRC_WPG) void trc_ansa_code_kernel(
     if (alive) {
         if (!ovf) {
             for (int k = 0; k < (NIB ? 2 : 4); k++) { so.put16(st[k] >> 16); so.put16(st[k]); }
-            if (so.wpos >= len) ovf = true;
-        }
-        out_len = ovf ? len : so.wpos;
-    }
-    so.drain(true, alive && !ovf);
-    if (alive) clen[c] = out_len;
-    const u32 gs = trc_wave_sum(out_len);
-    if (lane == 0) gsum[wc.c0 >> 6] = gs;
-}
-
-// Pass 2 over the PLANAR record space (ANSA behind trc_ansa_model2_kernel): a block of 16 input bytes is two segments, hi records
-// and lo records; record 2j of the block is hi[j], record 2j + 1 is lo[j].  Everything else as above.
-#define ANSA_CODE_PLANAR_LDS (2u * TRC_TILE_BYTES + TRC_SRING_BYTES)
-__global__ __launch_bounds__(64 * TRC_WPG) void trc_ansa_code_planar_kernel(
-    const u8 *__restrict__ recs, u64 n, u32 chunk, u32 nchunks,
-    u8 *__restrict__ scratch, u32 stride, u32 *__restrict__ clen, u32 *__restrict__ gsum)
-{
-    TRC_QUAD_PROLOGUE(ANSA_CODE_PLANAR_LDS);
-    WaveChunks wc;
-    wc.c0 = grp_ * 64u; wc.chunk = chunk; wc.nchunks = nchunks;
-    wc.lastlen = (u32)(n - (u64)(nchunks - 1) * chunk);
-    wc.rows = nchunks - wc.c0 < 64u ? nchunks - wc.c0 : 64u;
-    const WaveChunks wr = ansa_record_space_planar(wc);
-    const bool alive = lane < wc.rows;
-    const u32 c = wc.c0 + lane;
-    const u32 len = alive ? wc.len_of(lane) : 0u;
-    const u32 nrec = 2u * (len + (len & 1u));                  // 4 per byte pair
-    const u32 room = 2u + 4u * 4u;                             // mnflush: ep <= op + sizeof(io_t) + states * 4  ->  raw
-
-    TileIn th, tl;
-    th.tile = smem; th.base = recs + (u64)wc.c0 * wr.chunk;
-    tl.tile = smem + TRC_TILE_BYTES; tl.base = th.base;
-    StreamOut<true> so;
-    so.rings = smem + 2u * TRC_TILE_BYTES;
-    so.scratch = scratch; so.stride = stride; so.c0 = wc.c0; so.wpos = 0; so.nfl = 0;
-    u32 st[4] = { TRC_ANS_LOW, TRC_ANS_LOW, TRC_ANS_LOW, TRC_ANS_LOW };
-    bool ovf = false;
-
-    const u32 T = wr.chunk / 128u;                             // blocks (32 records each) in a full chunk
-    const u32 top = alive && nrec ? (nrec - 1u) / 32u : 0u;
-    th.issue(wr, (T - 1u) * 128u); tl.issue(wr, (T - 1u) * 128u + 64u);
-    for (u32 t = T - 1u;; t--) {
-        th.commit(); tl.commit();
-        if (t) { th.issue(wr, (t - 1u) * 128u); tl.issue(wr, (t - 1u) * 128u + 64u); }
-        const bool act = alive && nrec != 0u && t <= top && !ovf;
-#pragma unroll
-        for (int half = 1; half >= 0; half--) {                // records 31..16, then 15..0 of the block
-            if (act) {
-                const uint4 qh[2] = { th.read(2u * (u32)half), th.read(2u * (u32)half + 1u) };
-                const uint4 ql[2] = { tl.read(2u * (u32)half), tl.read(2u * (u32)half + 1u) };
-                const u32 *hh = (const u32 *)qh, *ll = (const u32 *)ql;
-#pragma unroll
-                for (int i = 15; i >= 0; i--) {
-                    const bool can = 32u * t + 16u * (u32)half + (u32)i < nrec && !ovf;
-                    ovf = ovf || (can && so.wpos + room >= len);
-                    const bool go = can && !ovf;
-                    ansa_put(st[3 - (i & 3)], (i & 1) ? ll[i >> 1] : hh[i >> 1], so, go);
-                }
-            }
-            so.drain(false, alive);                            // <= 32 new bytes (16 records) per lane
-        }
-        if (t == 0) break;
-    }
-    u32 out_len = 0;
-    if (alive) {
-        if (!ovf) {
-            for (int k = 0; k < 4; k++) { so.put16(st[k] >> 16); so.put16(st[k]); }
             if (so.wpos >= len) ovf = true;
         }
         out_len = ovf ? len : so.wpos;
@@ -583,183 +505,11 @@ __global__ __launch_bounds__(64 * TRC_WPG) void trc_ansa_dec_kernel(
     if (!wc.prog) trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)wc.c0 * chunk, chunk, payload);
 }
 
-// ---- ANSA's decoder as two waves per 64 chunks (round 4; the scheme of trc_rca_dec_mc_kernel, trc_rc_adaptive.hip) -------
-// Wave D owns the four rANS states and the stream and READS tables; wave M owns the tables and adapts them.  Per byte:
-//     phase A   D: hi table -> slot search, state update, h -> mailbox      M: the byte before's lo table adapts by its l
-//     phase B   D: lo table (h) -> search, state update, l -> mailbox       M: hi table adapts by h; lo table (h) loaded
-// one LDS-only barrier behind each phase; the four renormalisations of a byte pair (their order is the word order) stay
-// with wave D behind the pair.
-#define ANSA_DMC_MBOX   512u
-#define ANSA_DMC_LDS    (TRC_NIB_BYTES + ANSA_DMC_MBOX)
-__global__ __launch_bounds__(128 * TRC_WPG) void trc_ansa_dec_mc_kernel(
-    const u8 *__restrict__ payload, const u32 *__restrict__ clen, const u64 *__restrict__ goff, const u32 *__restrict__ gsum,
-    u64 n, u32 chunk, u32 nchunks, u8 *__restrict__ out)
-{
-    typedef __attribute__((address_space(3))) u32 lds_u32;
-    extern __shared__ __attribute__((aligned(16))) u8 smem_wg_[];
-    const u32 wv_ = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const bool model = wv_ >= TRC_WPG;
-    const u32 grp_ = blockIdx.x * TRC_WPG + (wv_ & (TRC_WPG - 1u));
-    if (grp_ >= (nchunks + 63u) / 64u) return;                 // (both waves of the pair)
-    u8 *const smem = smem_wg_ + (wv_ & (TRC_WPG - 1u)) * ANSA_DMC_LDS;
-    const u32 lane = trc_lane();
-    NibModel<17> m;
-    if (model) m.init(smem); else m.attach(smem);
-    const u32 mb = trc_lds_addr(smem) + TRC_NIB_BYTES + lane * 4u;     // mailbox: h at +0, l at +256
-
-    WaveChunks wc;
-    wc.c0 = grp_ * 64u; wc.chunk = chunk; wc.nchunks = nchunks;
-    wc.lastlen = (u32)(n - (u64)(nchunks - 1) * chunk);
-    wc.rows = nchunks - wc.c0 < 64u ? nchunks - wc.c0 : 64u;
-    const bool alive = lane < wc.rows;
-    const u32 c = wc.c0 + lane;
-    const u32 len = alive ? wc.len_of(lane) : 0u;
-    const u32 cl = alive ? trc_min(clen[c], len) : 0u;        // a directory entry above the chunk length (corrupt input) reads as raw
-    const bool coded = alive && cl != len;
-    const u32 S = chunk / TRC_SEG;
-    trc_lds_barrier();                                         // the model's initial tables are in place
-
-    if (model) {
-        NibTable T0 = m.load(m.table(0)), TL = T0;
-        u32 hp = 0;
-        bool have = false;
-        for (u32 s = 0; s < S; s++) {
-#pragma nounroll
-            for (u32 k = 0; k < 4; k++) {
-                const u32 p0 = s * TRC_SEG + k * 16u;
-                if (!__ballot(coded && p0 < len)) continue;
-#pragma nounroll
-                for (u32 b = 0; b < 16u; b++) {
-                    if (have) {                                // phase A: the byte before's lo table
-                        const u32 l = *(const lds_u32 *)(uintptr_t)(mb + 256u);
-                        m.adapt(TL, l & 15u); m.store(m.table(1u + hp), TL);
-                    }
-                    have = true;
-                    trc_lds_barrier();
-                    const u32 h = *(const lds_u32 *)(uintptr_t)mb & 15u;         // phase B
-                    m.adapt(T0, h); m.store(m.table(0), T0);
-                    TL = m.load(m.table(1u + h)); hp = h;
-                    trc_lds_barrier();
-                }
-            }
-        }
-        return;
-    }
-
-    const u32 ex = trc_wave_incl_scan(cl) - cl;
-    const u64 off = trc_group_base(goff, gsum, wc.c0 >> 6) + ex;
-    u32 st[4] = { TRC_ANS_LOW, TRC_ANS_LOW, TRC_ANS_LOW, TRC_ANS_LOW };
-    if (coded) for (u32 k = 0; k < 4u; k++) st[k] = trc_ld32_a2(payload + off + 4u * k);   // decoder st[i] = encoder st[3-i] (mnfill)
-    LaneInWide si; si.prime(payload + off + 16u, coded, trc_sub_sat(cl, 16u));             // words follow the states
-
-    // cdf16ansdec without its model half: search + state update against the table at `tb` as wave M left it
-    auto get = [&](u32 &sx, const u8 *tb, bool act) __attribute__((always_inline)) -> u32 {
-        const u32 slot = sx & (TRC_PROB_ONE - 1);
-        const NibTable T = m.load(tb);
-        u32 c0, c1;
-        const u32 x = trc_nib_find(T, slot, c0, c1);
-        sx = act ? __umul24(c1 - c0, sx >> TRC_PROB_BITS) + slot - c0 : sx;
-        return x;
-    };
-    auto get_byte = [&](u32 &sh, u32 &sl, bool act) __attribute__((always_inline)) -> u32 {
-        const u32 h = get(sh, m.table(0), act);
-        *(lds_u32 *)(uintptr_t)mb = h;
-        trc_lds_barrier();
-        const u32 l = get(sl, m.table(1u + h), act);
-        *(lds_u32 *)(uintptr_t)(mb + 256u) = l;
-        trc_lds_barrier();
-        return h << 4 | l;
-    };
-    auto renorm = [&](u32 &sx, bool act) __attribute__((always_inline)) {
-        const u32 w = si.peek16();
-        const bool rn = act && sx < TRC_ANS_LOW;
-        sx = rn ? (sx << 16) | w : sx;
-        si.skip_if(rn);
-    };
-
-    QuadOut qout; qout.base = out + (u64)wc.c0 * chunk;
-    u8 *dst = out + (u64)c * chunk;
-    for (u32 s = 0; s < S; s++) {
-        uint4 pc0 = make_uint4(0, 0, 0, 0), pc1 = pc0, pc2 = pc0, pc3 = pc0;
-#pragma nounroll
-        for (u32 k = 0; k < 4; k++) {
-            const u32 p0 = s * TRC_SEG + k * 16u;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (__ballot(coded && p0 < len)) {
-#pragma nounroll
-                for (u32 d = 0; d < 4; d++) {
-                    const u32 q0 = p0 + d * 4u;
-                    u32 w = 0;
-#pragma nounroll
-                    for (u32 j = 0; j < 2; j++) {              // mndec8x2: two bytes, then four renorms in order st0..st3
-                        const bool act = coded && q0 + 2u * j < len;          // the second byte of an odd tail is the dummy
-                        const uint4 pre = si.prefetch();       // (<= 8 stream bytes per group: trc_lane_io.h LaneInWide)
-                        const u32 x0 = get_byte(st[0], st[1], act);
-                        const u32 x1 = get_byte(st[2], st[3], act);
-                        renorm(st[0], act); renorm(st[1], act); renorm(st[2], act); renorm(st[3], act);
-                        si.end_step(pre);
-                        w |= (x0 | x1 << 8) << (16u * j);
-                    }
-                    v.x = v.y; v.y = v.z; v.z = v.w; v.w = w;
-                }
-                if (coded && p0 < len && p0 + 16u > len) {      // ragged end of the last chunk: byte stores
-                    const u32 ww[4] = { v.x, v.y, v.z, v.w };
-                    for (u32 pos = p0; pos < len; pos++) dst[pos] = (u8)(ww[(pos - p0) >> 2] >> (8 * ((pos - p0) & 3u)));
-                }
-            }
-            pc0 = pc1; pc1 = pc2; pc2 = pc3; pc3 = v;
-        }
-        qout.put(0, pc0); qout.put(1, pc1); qout.put(2, pc2); qout.put(3, pc3);
-        qout.flush(wc, s * TRC_SEG);
-    }
-    trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)wc.c0 * chunk, chunk, payload);
-}
-
 // ------------------------------------------------------------------------------------- launch ---
-// TRC_ANSA_MC=0 selects the one-wave model pass of rounds 1-3 (A/B measurements, tests of both forms)
-static bool ansa_mc_enabled()
-{
-    static const int env = getenv("TRC_ANSA_MC") ? atoi(getenv("TRC_ANSA_MC")) : 1;
-    return env != 0;
-}
-bool trc_ansa_enc_gate_ok() { return ansa_mc_enabled(); }
-template <bool NIB>
-static void launch_ansa_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
-{
-    if (!NIB && ansa_mc_enabled()) {
-        TRC_RAISE_LDS_ONCE(trc_ansa_model2_kernel, TRC_WPG * ANSA_MODEL_LDS(false) + 64u);
-        TRC_RAISE_LDS_ONCE(trc_ansa_code_planar_kernel, TRC_WPG * ANSA_CODE_PLANAR_LDS);
-        TRC_LAUNCH_TIMED(trc_ansa_model2_kernel, TRC_QUAD_GRID(w.ngroups), dim3(128 * TRC_WPG), TRC_WPG * ANSA_MODEL_LDS(false) + 64u, s, d_in, (u64)n, chunk, w.nchunks, w.scratch2, trc_gate_tls.flag, trc_gate_tls.part);
-        trc_launch_ansa_code_planar(n, chunk, w, d_clen, s);
-        return;
-    }
-    if (NIB && trc_nib_big(w.ngroups)) {                       // one 12-wave workgroup per CU, pace-keeping (trc_dev.h)
-        TRC_RAISE_LDS_ONCE((trc_ansa_model_kernel<NIB>), TRC_LDS_ONE_PER_CU);
-        TRC_LAUNCH_TIMED((trc_ansa_model_kernel<NIB>), dim3((w.ngroups + TRC_NIB_WPG - 1u) / TRC_NIB_WPG), dim3(64 * TRC_NIB_WPG), TRC_LDS_ONE_PER_CU, s, d_in, (u64)n, chunk, w.nchunks, w.scratch2);
-    } else {
-    TRC_RAISE_LDS_ONCE((trc_ansa_model_kernel<NIB>), NIB ? TRC_LDS_ONE_PER_CU : TRC_WPG * ANSA_MODEL_LDS(NIB));   // (one limit for both shapes of the nibble form: the attribute is set once per call site)
-    TRC_LAUNCH_TIMED((trc_ansa_model_kernel<NIB>), TRC_QUAD_GRID(w.ngroups), dim3(64 * TRC_WPG), TRC_WPG * (ANSA_MODEL_LDS(NIB)), s, d_in, (u64)n, chunk, w.nchunks, w.scratch2);
-    }
-    TRC_LAUNCH_TIMED((trc_ansa_code_kernel<NIB>), TRC_QUAD_GRID(w.ngroups), dim3(64 * TRC_WPG), TRC_WPG * (ANSA_CODE_LDS), s,
-                       (const u8 *)w.scratch2, (u64)n, chunk, w.nchunks, w.scratch, w.stride, d_clen, w.gsum);
-}
-// TRC_ANSA_DMC=1 selects the two-wave decoder.  MEASURED AND NOT USED (profiles/r04_notes.md): bit-exact, 0.93 ms against 0.68.
-static bool ansa_dmc_enabled()
-{
-    static const int env = getenv("TRC_ANSA_DMC") ? atoi(getenv("TRC_ANSA_DMC")) : 0;
-    return env != 0;
-}
-bool trc_ansa_dec_prog_ok() { return !ansa_dmc_enabled(); }       // the one-wave decoder (the default) reports its progress
 template <bool NIB>
 static void launch_ansa_dec(const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                             const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    if (!NIB && ansa_dmc_enabled()) {
-        TRC_RAISE_LDS_ONCE(trc_ansa_dec_mc_kernel, TRC_WPG * ANSA_DMC_LDS);
-        TRC_LAUNCH_TIMED(trc_ansa_dec_mc_kernel, TRC_QUAD_GRID(w.ngroups), dim3(128 * TRC_WPG), TRC_WPG * ANSA_DMC_LDS, s,
-                           d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, d_out);
-        return;
-    }
     // (the nibble decoder in the 12-wave shape with TrcPace -- what the nibble range coders gained 8-10 % from -- measured 0.244 -> 0.322 ms:
     // not taken, profiles/r05q_ab.txt)
     TRC_RAISE_LDS_ONCE((trc_ansa_dec_kernel<NIB>), TRC_WPG * ANSA_MODEL_LDS(NIB));
@@ -769,24 +519,18 @@ static void launch_ansa_dec(const uint8_t *d_payload, const uint32_t *d_clen, si
 // pass 2 over the planar record space (ANSA's two-wave model pass, and the order-1 coder's)
 void trc_launch_ansa_code_planar(size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
-    static const int codeq = getenv("TRC_ANSA_CODEQ") ? atoi(getenv("TRC_ANSA_CODEQ")) : 1;     // 0: one lane per chunk (rounds 1-3)
     static const int gpw_env = getenv("TRC_CODEQ_GPW") ? atoi(getenv("TRC_CODEQ_GPW")) : 0;     // tuning aid: 1 / 4 force the workgroup shape
     const bool big = gpw_env ? gpw_env == 4 : (w.ngroups >= 512u && w.ngroups <= 4u * 256u);
-    if (codeq && big) {
+    if (big) {
         // (the LDS request is padded beyond half a CU's: one 16-wave workgroup per CU, four waves per SIMD.  At its real 71 KiB two fit,
         // and where the dispatcher doubles up a CU runs eight waves per SIMD while another idles -- the pass was bimodal, 0.20 / 0.30 ms)
         const size_t lds1 = ANSQ_LDS(4) > TRC_LDS_ONE_PER_CU ? ANSQ_LDS(4) : TRC_LDS_ONE_PER_CU;
         TRC_RAISE_LDS_ONCE(trc_ansa_codeq_kernel<4>, lds1);
         TRC_LAUNCH_TIMED(trc_ansa_codeq_kernel<4>, dim3((w.ngroups + 3u) / 4u), dim3(1024), lds1, s,
                            (const u8 *)w.scratch2, (u64)n, chunk, w.nchunks, w.scratch, w.stride, d_clen, w.gsum);
-    } else if (codeq)
+    } else
         TRC_LAUNCH_TIMED(trc_ansa_codeq_kernel<1>, dim3(w.ngroups), dim3(256), ANSQ_LDS(1), s,
                            (const u8 *)w.scratch2, (u64)n, chunk, w.nchunks, w.scratch, w.stride, d_clen, w.gsum);
-    else {
-        TRC_RAISE_LDS_ONCE(trc_ansa_code_planar_kernel, TRC_WPG * ANSA_CODE_PLANAR_LDS);
-        TRC_LAUNCH_TIMED(trc_ansa_code_planar_kernel, TRC_QUAD_GRID(w.ngroups), dim3(64 * TRC_WPG), TRC_WPG * (ANSA_CODE_PLANAR_LDS), s,
-                           (const u8 *)w.scratch2, (u64)n, chunk, w.nchunks, w.scratch, w.stride, d_clen, w.gsum);
-    }
 }
 // pass 2 alone (the order-1 coder of trc_ans_o1.hip produces the same record stack with its own pass 1)
 void trc_launch_ansa_code(int nibble, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
@@ -800,7 +544,19 @@ void trc_launch_ansa_code(int nibble, size_t n, uint32_t chunk, const TrcWork &w
 }
 void trc_launch_ansa_enc(int nibble, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
-    if (nibble) launch_ansa_enc<true>(d_in, n, chunk, w, d_clen, s); else launch_ansa_enc<false>(d_in, n, chunk, w, d_clen, s);
+    if (!nibble) {                                             // the two-wave model pass, then pass 2 over the planar record space
+        TRC_RAISE_LDS_ONCE(trc_ansa_model2_kernel, TRC_WPG * ANSA_MODEL_LDS(false) + 64u);
+        TRC_LAUNCH_TIMED(trc_ansa_model2_kernel, TRC_QUAD_GRID(w.ngroups), dim3(128 * TRC_WPG), TRC_WPG * ANSA_MODEL_LDS(false) + 64u, s, d_in, (u64)n, chunk, w.nchunks, w.scratch2, trc_gate_tls.flag, trc_gate_tls.part);
+        trc_launch_ansa_code_planar(n, chunk, w, d_clen, s);
+        return;
+    }
+    TRC_RAISE_LDS_ONCE((trc_ansa_model_kernel<true>), TRC_LDS_ONE_PER_CU);   // (one limit for both shapes: the attribute is set once per call site)
+    if (trc_nib_big(w.ngroups))                                // one 12-wave workgroup per CU, pace-keeping (trc_dev.h)
+        TRC_LAUNCH_TIMED((trc_ansa_model_kernel<true>), dim3((w.ngroups + TRC_NIB_WPG - 1u) / TRC_NIB_WPG), dim3(64 * TRC_NIB_WPG), TRC_LDS_ONE_PER_CU, s, d_in, (u64)n, chunk, w.nchunks, w.scratch2);
+    else
+        TRC_LAUNCH_TIMED((trc_ansa_model_kernel<true>), TRC_QUAD_GRID(w.ngroups), dim3(64 * TRC_WPG), TRC_WPG * (ANSA_MODEL_LDS(true)), s, d_in, (u64)n, chunk, w.nchunks, w.scratch2);
+    TRC_LAUNCH_TIMED((trc_ansa_code_kernel<true>), TRC_QUAD_GRID(w.ngroups), dim3(64 * TRC_WPG), TRC_WPG * (ANSA_CODE_LDS), s,
+                       (const u8 *)w.scratch2, (u64)n, chunk, w.nchunks, w.scratch, w.stride, d_clen, w.gsum);
 }
 void trc_launch_ansa_dec(int nibble, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                          const TrcWork &w, uint8_t *d_out, hipStream_t s)

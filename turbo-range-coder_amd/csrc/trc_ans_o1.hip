@@ -29,9 +29,6 @@
 #include "trc_launch.h"
 
 #define O1_MODEL_BYTES TRC_O1_MODEL_BYTES
-#ifndef TRC_O1_DEC_DEFAULT_ROWS                               // decoder form: 1 = eight lanes per chunk; 16 / 64 = one lane per chunk, that many chunks per wave
-#define TRC_O1_DEC_DEFAULT_ROWS(ngroups) ((ngroups) <= 128u ? 1 : 4)
-#endif                    // 139264 per chunk
 
 __device__ __forceinline__ NibTable o1_load(const u8 *tb)
 {
@@ -776,118 +773,8 @@ __global__ __launch_bounds__(256) void trc_o1_place_kernel(u64 n, u32 chunk, u32
     }
 }
 
-// ------------------------------------------------------------------------------------- decode ---
-// Round 5: R chunks per wave (lanes 0 .. R - 1; 64 / R waves per group of 64 chunks).  These kernels are chains of table round trips:
-// a wave makes one per nibble as long as ANY of its lanes needs a table it does not hold, so with 64 chunks per wave (some lane always
-// misses) a 4096-byte chunk is 8192 round trips of ~0.8 us, and at 100 MB / 4096 there are 382 such waves -- 0.37 per SIMD, the chip
-// idle.  With R = 16 there are four times the waves: 5.88 -> 5.36 ms, NOT the factor the idle SIMDs promised -- a wave of 16 lanes
-// still has some lane missing at almost every nibble (a lane misses on 61-70 % of them), so every wave still walks the same
-// chain of two dependent ~0.7 us round trips per byte; only its other costs shrink.  R = 8: 6.8 ms (every wave-instruction then
-// serves 8 lanes: issue-bound).  profiles/r05_notes.md.
-template <u32 R>
-__global__ __launch_bounds__(64) void trc_o1_dec_kernel(
-    const u8 *__restrict__ payload, const u32 *__restrict__ clen, const u64 *__restrict__ goff, const u32 *__restrict__ gsum,
-    u64 n, u32 chunk, u32 nchunks, u8 *__restrict__ model, u8 *__restrict__ out)
-{
-    __shared__ __attribute__((aligned(16))) u8 kb[TRC_NIBK_BYTES];
-    __shared__ __attribute__((aligned(16))) u8 seen[O1_SEEN_BYTES];
-    const u32 lane = threadIdx.x;
-    o1_init_k(kb);
-
-    constexpr u32 WPG = 64u / R;                               // waves per group of 64 chunks
-    const u32 g0 = (blockIdx.x / WPG) * 64u, wq = blockIdx.x % WPG;
-    WaveChunks wc;
-    wc.c0 = g0 + wq * R; wc.chunk = chunk; wc.nchunks = nchunks;
-    wc.lastlen = (u32)(n - (u64)(nchunks - 1) * chunk);
-    wc.rows = wc.c0 >= nchunks ? 0u : nchunks - wc.c0 < R ? nchunks - wc.c0 : R;
-    // the directory of the whole group (payload offsets are per group of 64 chunks): lane L reads chunk g0 + L, the wave's own R
-    // chunks take their numbers from lanes wq R ..
-    const u32 cg = g0 + lane;
-    const u32 lenL = cg < nchunks ? ((cg == nchunks - 1u) ? wc.lastlen : chunk) : 0u;
-    const u32 clL = cg < nchunks ? trc_min(clen[cg], lenL) : 0u;   // a directory entry above the chunk length (corrupt input) reads as raw
-    const u32 exL = trc_wave_incl_scan(clL) - clL;
-    const u32 srcl = (wq * R + lane) & 63u;
-    const u32 cl_s = (u32)__shfl((int)clL, (int)srcl, 64), ex_s = (u32)__shfl((int)exL, (int)srcl, 64), len_s = (u32)__shfl((int)lenL, (int)srcl, 64);
-    const bool alive = lane < wc.rows;
-    const u32 c = wc.c0 + lane;
-    const u32 len = alive ? len_s : 0u;
-    const u32 cl = alive ? cl_s : 0u;
-    const u32 ex = ex_s;
-    const u64 off = trc_group_base(goff, gsum, g0 >> 6) + ex;
-    const bool coded = alive && cl != len;
-    O1Cache tc;
-    tc.init(model + (u64)(wc.c0 + (alive ? lane : 0u)) * O1_MODEL_BYTES, seen);
-
-    u32 st[4] = { TRC_ANS_LOW, TRC_ANS_LOW, TRC_ANS_LOW, TRC_ANS_LOW };
-    if (coded) for (u32 k = 0; k < 4; k++) st[k] = trc_ld32_a2(payload + off + 4u * k);   // decoder st[i] = encoder st[3-i] (mnfill)
-    LaneIn<2> si; si.prime(payload + off + 16u, coded, trc_sub_sat(cl, 16u));
-    u32 cx = 0;
-
-    // cdf16ansdec on a cached table (only lanes with act touch memory, and only for a table they do not hold)
-    auto get_nibble = [&](u32 &s, NibTable &T) -> u32 {
-        const u32 slot = s & (TRC_PROB_ONE - 1);
-        u32 c0, c1;
-        const u32 x = trc_nib_find<true>(T, slot, c0, c1);    // (bit-select form: trc_nibmodel.h)
-        s = __umul24(c1 - c0, s >> TRC_PROB_BITS) + slot - c0;
-        o1_adapt(T, kb, x);
-        return x;
-    };
-    auto get_byte = [&](bool act, u32 &sh, u32 &sl) -> u32 {    // context cx -> byte, which becomes the context
-        tc.need_hi(act, cx);
-        u32 h = 0, l = 0;
-        if (act) h = get_nibble(sh, tc.H);
-        tc.need_lo(act, cx, h);
-        if (act) { l = get_nibble(sl, tc.L); cx = h << 4 | l; }
-        return h << 4 | l;
-    };
-    auto renorm = [&](u32 &s, bool act) {
-        const u32 w = si.peek16();
-        const bool rn = act && s < TRC_ANS_LOW;
-        s = rn ? (s << 16) | w : s;
-        si.skip_if(rn);
-    };
-
-    QuadOut qout; qout.base = out + (u64)wc.c0 * chunk;
-    u8 *dst = out + (u64)c * chunk;
-    const u32 S = chunk / TRC_SEG;
-    for (u32 s = 0; s < S; s++) {
-        uint4 pc0 = make_uint4(0, 0, 0, 0), pc1 = pc0, pc2 = pc0, pc3 = pc0;
-#pragma nounroll
-        for (u32 k = 0; k < 4; k++) {
-            const u32 p0 = s * TRC_SEG + k * 16u;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (__ballot(coded && p0 < len)) {
-#pragma nounroll
-                for (u32 d = 0; d < 4; d++) {
-                    const u32 q0 = p0 + d * 4u;
-                    u32 w = 0;
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {              // mndec8x2x: two bytes, then four renorms in order st0..st3
-                        const bool act = coded && q0 + 2u * (u32)j < len;     // the second byte of an odd tail is the dummy
-                        {
-                            const u32 x0 = get_byte(act, st[0], st[1]);
-                            const u32 x1 = get_byte(act, st[2], st[3]);
-                            w |= (x0 | x1 << 8) << (16 * j);
-                        }
-                        renorm(st[0], act); renorm(st[1], act); renorm(st[2], act); renorm(st[3], act);
-                    }
-                    v.x = v.y; v.y = v.z; v.z = v.w; v.w = w;
-                }
-                if (coded && p0 < len && p0 + 16u > len) {      // ragged end of the last chunk: byte stores
-                    const u32 ww[4] = { v.x, v.y, v.z, v.w };
-                    for (u32 pos = p0; pos < len; pos++) dst[pos] = (u8)(ww[(pos - p0) >> 2] >> (8 * ((pos - p0) & 3u)));
-                }
-            }
-            pc0 = pc1; pc1 = pc2; pc2 = pc3; pc3 = v;
-        }
-        qout.put(0, pc0); qout.put(1, pc1); qout.put(2, pc2); qout.put(3, pc3);
-        qout.flush(wc, s * TRC_SEG);
-    }
-    trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)wc.c0 * chunk, chunk, payload);
-}
-
 // ---------------------------------------------------------------------------- decode, by rows ---
-// Round 5 (late): EIGHT LANES PER CHUNK.  What the one-lane-per-chunk decoder above spends (timing ablation, 100 MB at chunk 4096,
+// Round 5 (late): EIGHT LANES PER CHUNK.  What the one-lane-per-chunk decoder of rounds 1-5 spent (timing ablation, 100 MB at chunk 4096,
 // profiles/r05_notes.md): 2.3-2.9 ms on its own instruction chain -- a nibble's search, select trees and 8-register update are ~100
 // instructions of a lone wave -- and 2.4-3.4 ms on table round trips, every one of them 64 scattered 16-byte lane accesses through the
 // texture-address unit.  Here a CDF16 table is spread over the eight lanes of a ROW (lane e holds entries 2e | 2e+1 as one packed
@@ -939,13 +826,10 @@ __global__ __launch_bounds__(64) void trc_o1_dec_rows_kernel(
     // address instruction per access).  Rows past the last chunk compute offsets beyond the model space and never use them.
     u8 *const mbase = model + (u64)(c0w < nchunks ? c0w : 0u) * O1_MODEL_BYTES;
     const u32 moff = row * O1_MODEL_BYTES + e * 4u;
-#ifndef TRC_O1_SWIZZLE
-#define TRC_O1_SWIZZLE 1
-#endif
     // Table `id` lies in slot id ^ (chunk & 127) of the chunk's block (4352 = 34 x 128 slots: the low seven bits permute inside their
     // 128).  The blocks are 34 x 4096 bytes apart, so without it table `id` of EVERY chunk sits at the same address modulo 4096 -- the
     // same L2 channel -- and the tables of the few contexts most bytes follow are hit by all the rows of the chip at once.
-    const u32 swz = TRC_O1_SWIZZLE ? (c & 127u) << 5 : 0u;     // (as a byte offset)
+    const u32 swz = (c & 127u) << 5;                           // (as a byte offset)
     const u32 seen = trc_lds_addr(seen_s) + row * O1R_SEEN_BYTES;
     const u32 fresh = trc_pk((2u * e) << 11, (2u * e + 1u) << 11);
     const u32 kbase1 = trc_pk(20u * e, 20u * e + 10u) + 0x7fe07fe0u;   // K of a lane none of whose entries is <= slot; every such entry takes 32736 off
@@ -1074,8 +958,8 @@ __global__ __launch_bounds__(64) void trc_o1_dec_rows_kernel(
                       out + (u64)c0w * chunk, chunk, payload);
 }
 
-// --------------------------------------------------------------- decode, FOUR or TWO lanes per chunk ---
-// Round 6.  The rows form above with a CDF16 table over LANES = 4 or 2 lanes (lane e = entries 2D e .. 2D e + 2D - 1 as D = 8 / LANES packed
+// --------------------------------------------------------------------- decode, FOUR lanes per chunk ---
+// Round 6.  The rows form above with a CDF16 table over LANES = 4 lanes (LANES = 2 measured slower) (lane e = entries 2D e .. 2D e + 2D - 1 as D = 8 / LANES packed
 // dwords: a table move is one 4D-byte access per lane, 32 bytes per row as before) and 64 / LANES chunks per wave.  Two findings behind it
 // (profiles/r06_notes.md): the eight-lane kernel is bound by what its SIMDs can issue (97 instructions per byte for eight chunks, three waves
 // per SIMD) -- this one issues ~115 for sixteen or ~150 for thirty-two -- and a wave's chain runs a third faster with its SIMD to itself (decode
@@ -1116,7 +1000,7 @@ __global__ __launch_bounds__(64) void trc_o1_dec_rowsn_kernel(
 
     u8 *const mbase = model + (u64)(c0w < nchunks ? c0w : 0u) * O1_MODEL_BYTES;
     const u32 moff = row * O1_MODEL_BYTES + e * (4u * D);      // this lane's dwords of table `id`: mbase[((32 id) ^ swz) + moff]
-    const u32 swz = TRC_O1_SWIZZLE ? (c & 127u) << 5 : 0u;
+    const u32 swz = (c & 127u) << 5;
     const u32 seen = trc_lds_addr(seen_s) + row * O1R_SEEN_BYTES;
     Tab fresh, kbase;
 #pragma unroll
@@ -1279,10 +1163,9 @@ bool trc_launch_anso1_model(const uint8_t *d_in, size_t n, uint32_t chunk, const
         TRC_LAUNCH_TIMED(trc_o1_place_kernel, dim3(w.nchunks), dim3(256), 0, s, (u64)n, chunk, w.nchunks, (const u8 *)w.model, w.scratch2);
         return true;
     }
-    static const int two = getenv("TRC_O1_MC") ? atoi(getenv("TRC_O1_MC")) : 1;      // 0: the one-wave pass of rounds 1-3 (interleaved records)
-    // ... up to 1024 pairs: beyond that (100 MB at chunk 1024: 1526) the unit is saturated by one wave per 64 chunks already and the
+    // the model wave pair up to 1024 pairs: beyond that (100 MB at chunk 1024: 1526) the unit is saturated by one wave per 64 chunks already and the
     // second wave only adds its own input loads and record stores (3.30 -> 3.93 ms); chunk 4096: 5.35 -> 3.80 ms, 2048: 3.39 -> 3.19
-    if (two && w.ngroups <= 1024u) {
+    if (w.ngroups <= 1024u) {
         // ONE pair per workgroup: these waves are bound by the texture-address unit of their CU (64 scattered 16-byte accesses per
         // table move), not by their SIMD -- four pairs per workgroup put 100 MB at chunk 4096 (382 pairs) on 96 CUs and ran 30 %
         // slower than the one-wave pass; as single pairs they spread over all 256 (profiles/r04_notes.md)
@@ -1296,22 +1179,14 @@ bool trc_launch_anso1_model(const uint8_t *d_in, size_t n, uint32_t chunk, const
 void trc_launch_anso1_dec(const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                           const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    static const int env_rows = getenv("TRC_O1_ROWS") ? atoi(getenv("TRC_O1_ROWS")) : 0;       // tuning aid: 64 / 16 / 8 force the form
-    // eight lanes per chunk at every size (100 MB: chunk 4096 5.28 -> 3.79 ms, 2048 3.67 -> 3.71, 1024 3.83 -> 3.71: profiles/r05_notes.md);
-    // the one-lane-per-chunk forms (64 / 16 / 8 chunks per wave) stay behind TRC_O1_ROWS
-    const int rows = env_rows ? env_rows : TRC_O1_DEC_DEFAULT_ROWS(w.ngroups);
+    // eight lanes per chunk up to 128 groups (100 MB: chunk 4096 5.28 -> 3.79 ms against one lane per chunk, 2048 3.67 -> 3.71, 1024
+    // 3.83 -> 3.71: profiles/r05_notes.md); four lanes per chunk above.  TRC_O1_ROWS = 1 / 4 forces the form (tuning aid, tests)
+    static const int env_rows = getenv("TRC_O1_ROWS") ? atoi(getenv("TRC_O1_ROWS")) : 0;
+    const int rows = env_rows == 1 || env_rows == 4 ? env_rows : w.ngroups <= 128u ? 1 : 4;
     if (rows == 4)                                              // four lanes per chunk
         TRC_LAUNCH_TIMED(trc_o1_dec_rowsn_kernel<4>, dim3(w.ngroups * 4u), dim3(64), 0, s, d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.model, d_out);
-    else if (rows == 2)                                         // two lanes per chunk
-        TRC_LAUNCH_TIMED(trc_o1_dec_rowsn_kernel<2>, dim3(w.ngroups * 2u), dim3(64), 0, s, d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.model, d_out);
-    else if (rows == 1)                                         // eight lanes per chunk (trc_o1_dec_rows_kernel)
+    else                                                        // eight lanes per chunk (trc_o1_dec_rows_kernel)
         TRC_LAUNCH_TIMED(trc_o1_dec_rows_kernel, dim3(w.ngroups * (64u / O1R_CHUNKS)), dim3(64), 0, s, d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.model, d_out);
-    else if (rows == 16)
-        TRC_LAUNCH_TIMED(trc_o1_dec_kernel<16>, dim3(w.ngroups * 4u), dim3(64), 0, s, d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.model, d_out);
-    else if (rows == 8)
-        TRC_LAUNCH_TIMED(trc_o1_dec_kernel<8>, dim3(w.ngroups * 8u), dim3(64), 0, s, d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.model, d_out);
-    else
-        TRC_LAUNCH_TIMED(trc_o1_dec_kernel<64>, dim3(w.ngroups), dim3(64), 0, s, d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.model, d_out);
 }
 #ifdef TRC_O1W_PROF
 extern "C" __attribute__((visibility("default"))) int trc_o1w_prof_read(void *dst, size_t bytes)

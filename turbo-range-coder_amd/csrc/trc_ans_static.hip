@@ -18,39 +18,20 @@
 #include <stdio.h>
 #include <string.h>
 #include "trc_io.h"
-#include "trc_gather.h"
 #include "trc_launch.h"
 
 #define ENC_WAVE_LDS (TRC_SRING_BYTES)       // input arrives through an in-register quad transpose
-#define ENC_PACE_LDS 192u                    // TrcPace's progress counters, behind the symbol table; then the fused gather's words:
-#define ENC_FUSE_WSUM   64u                  //   u32[16]  the waves' group sums
-#define ENC_FUSE_TICKET 128u                 //   u32      the workgroup's ticket
-#define ENC_FUSE_BASE   136u                 //   u64      the workgroup's place in the payload
-#ifndef TRC_ENC_FUSED
-#define TRC_ENC_FUSED 0                      // 1: the encoder's waves gather their own payload when the launch is one residency round (trc_gather.h) -- measured a wash, off
-#endif
-#ifndef TRC_ENC_BALANCE
-#define TRC_ENC_BALANCE 1                    // workgroups of twelve waves that keep each other's pace when the launch is one residency round
-#endif
+#define ENC_TAB_LDS 4096u                    // the symbol table, 256 x 16 B
+#define ENC_PACE_LDS 192u                    // TrcPace's progress counters, behind the symbol table (64 B used; the launches' LDS sizes count 192)
 #define DEC_WAVE_LDS (TRC_SRING_BYTES)       // 8.3 KiB: 12 waves + 34 KiB of tables fit one CU
-#ifndef TRC_DEC_LATE_FLUSH
-#define TRC_DEC_LATE_FLUSH 1    // decoder: a segment's output stores behind the next period's commit (0: before it, as in round 2)
-#endif
-#ifndef TRC_ENC_EARLY_COMMIT
-#define TRC_ENC_EARLY_COMMIT 1  // encoder: the next input segment lands before the current segment's last drain (0: after it, as in round 2)
-#endif
-#ifndef TRC_ENC_REP_DEFAULT
-#define TRC_ENC_REP_DEFAULT 1
-#endif
 
 // ------------------------------------------------------------------------------------- encode ---
 // LDS traffic of the symbol loop is written out by hand (inline asm, waits counted by hand: cdna_hip_programming.md 5.7):
-//   * the symbol table is REPLICATED REP times inside LDS, entry x of replica r at byte x*16*REP + r*16, and lane l reads
-//     replica l & (REP-1).  A ds_read_b128 is served in four groups of 16 lanes and a group finishes in one LDS cycle only
-//     if its lanes touch 16 different 16-byte bank groups (MI355X_MICROARCH.md, LDS): with one copy of the table, 16 random
-//     symbols take ~3 cycles (PMC round 1: 61 % of the LDS cycles were bank conflicts); with REP = 16 every lane of a
-//     group owns its own bank group (the lane sets {0-3,12-15,20-27} / {4-11,16-19,28-31} have distinct l & 15) and the
-//     read is conflict free whatever the symbols are; REP = 8 leaves two lanes per bank group.
+//   * one copy of the symbol table in LDS.  A ds_read_b128 is served in four groups of 16 lanes and a group finishes in one LDS
+//     cycle only if its lanes touch 16 different 16-byte bank groups (MI355X_MICROARCH.md, LDS): 16 random symbols take ~3
+//     cycles (PMC round 1: 61 % of the LDS cycles were bank conflicts).  A table replicated 8 or 16 times (lane l reading
+//     replica l & 15) is conflict free, and with the hand-issued b128 reads NOT faster (100 MB, chunk 512: 64 vs 63 us;
+//     profiles/r02_notes.md): the bank conflicts were not what the kernel waited for.
 //   * the compiler split part of these 16-byte reads into pairs of ds_read2_b32 (two LDS instructions, 32-bank rules);
 //     the asm form is always one ds_read_b128, and the reads of the NEXT four symbols are in flight while the current
 //     four are coded.
@@ -65,24 +46,9 @@
 // it as a mask on gfx950); speculative 16-bit store; st = VCC ? st >> 16 : st as ONE v_cndmask with an SDWA source
 // select (WORD_1 of st); cursor -= VCC (v_subbrev).  The division half (mul_hi, SDWA shift, mul24, add3) follows in the same
 // block (left to the compiler it came with an s_nop per symbol behind the asm block: 1-1.5 % of the kernel).
-#ifndef TRC_ENC_PRED_WRITE
-#define TRC_ENC_PRED_WRITE 0          // 1: store only in lanes that emit (EXEC = VCC around the ds_write): ablation
-#endif
 __device__ __forceinline__ void ans_put(u32 &st, const trc_v4u e, u32 rbase, u32 &wn)
 {
     u32 t;
-#if TRC_ENC_PRED_WRITE
-    u64 sv;
-    asm volatile("v_cmp_ge_u32_e32 vcc, %0, %4\n\t"
-                 "v_and_b32_e32 %2, 63, %1\n\t"
-                 "v_lshl_add_u32 %2, %2, 1, %5\n\t"
-                 "s_and_saveexec_b64 %3, vcc\n\t"
-                 "ds_write_b16 %2, %0\n\t"
-                 "s_mov_b64 exec, %3\n\t"
-                 "v_cndmask_b32_sdwa %0, %0, %0, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t"
-                 "v_subbrev_co_u32_e32 %1, vcc, 0, %1, vcc"
-                 : "+v"(st), "+v"(wn), "=&v"(t), "=&s"(sv) : "v"(e.z), "v"(rbase) : "vcc", "memory");
-#else
     // the whole step in one block, division included (mul_hi, SDWA shift by the entry's shift byte, mul24, add3): the compiler puts
     // a wait state behind an asm block whose result the next instruction reads (it cannot see which instruction wrote it),
     // which was an s_nop per symbol between the renorm block and the division -- 1-1.5 % of the kernel at every chunk size
@@ -97,31 +63,27 @@ __device__ __forceinline__ void ans_put(u32 &st, const trc_v4u e, u32 rbase, u32
                  "v_mul_u32_u24_e32 %2, %2, %6\n\t"
                  "v_add3_u32 %0, %0, %7, %2"
                  : "+v"(st), "+v"(wn), "=&v"(t) : "v"(e.z), "v"(rbase), "v"(e.x), "v"(e.y), "v"(e.w) : "vcc", "memory");
-    return;
-#endif
-    const u32 q = __umulhi(st, e.x) >> (e.y >> 24);
-    st = st + e.w + __umul24(q, e.y);                         // mul24 ignores the shift byte
 }
-// table address of byte k of w: (byte << SH) in one SDWA shift (+ the lane's replica offset when the table is replicated)
+// table address of byte k of w: (byte << 4) in one SDWA shift
 template <int K>
-__device__ __forceinline__ u32 ans_taddr(u32 w, u32 sh, u32 tbase, bool replicated)
+__device__ __forceinline__ u32 ans_taddr(u32 w, u32 sh)
 {
     u32 a;
     if (K == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(a) : "v"(sh), "v"(w));
     if (K == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(a) : "v"(sh), "v"(w));
     if (K == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(a) : "v"(sh), "v"(w));
     if (K == 3) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(a) : "v"(sh), "v"(w));
-    return replicated ? a + tbase : a;
+    return a;
 }
-// the four table entries of one input dword, requested together
+// the four table entries of one input dword, requested together (the table at LDS offset 0)
 struct EncQuad { trc_v4u e0, e1, e2, e3; };
-__device__ __forceinline__ void ans_fetch4(EncQuad &q, u32 w, u32 tbase, int shift)
+__device__ __forceinline__ void ans_fetch4(EncQuad &q, u32 w)
 {
-    const u32 sh = (u32)shift;
-    q.e3 = trc_lds_read128(ans_taddr<3>(w, sh, tbase, shift != 4));
-    q.e2 = trc_lds_read128(ans_taddr<2>(w, sh, tbase, shift != 4));
-    q.e1 = trc_lds_read128(ans_taddr<1>(w, sh, tbase, shift != 4));
-    q.e0 = trc_lds_read128(ans_taddr<0>(w, sh, tbase, shift != 4));
+    const u32 sh = 4u;
+    q.e3 = trc_lds_read128(ans_taddr<3>(w, sh));
+    q.e2 = trc_lds_read128(ans_taddr<2>(w, sh));
+    q.e1 = trc_lds_read128(ans_taddr<1>(w, sh));
+    q.e0 = trc_lds_read128(ans_taddr<0>(w, sh));
 }
 // all of q's registers become valid here: at most `pending` LDS operations were issued after its four reads
 #define ANS_WAIT4(q, pending)                                                                                        \
@@ -130,34 +92,24 @@ __device__ __forceinline__ void ans_fetch4(EncQuad &q, u32 w, u32 tbase, int shi
 #ifdef TRC_ENC_PROF                                              // variant builds only: wall clock (100 MHz) per wave: start, first symbol, last symbol, end
 __device__ unsigned long long trc_enc_wall[4 * 4096];
 #endif
-template <int BLOCK, int REP, bool FUSED>
+template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
     const u8 *__restrict__ in, u64 n, u32 chunk, u32 nchunks,
     const uint4 *__restrict__ etab_g, u8 *__restrict__ scratch, u32 stride,
-    u32 *__restrict__ clen, u32 *__restrict__ gsum,
-    u8 *__restrict__ payload, u64 *__restrict__ total, u64 *__restrict__ goff_out, u8 *__restrict__ sync)
+    u32 *__restrict__ clen, u32 *__restrict__ gsum)
 {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    constexpr u32 TAB = 4096u * REP;
-    constexpr int SH = REP == 16 ? 8 : REP == 8 ? 7 : REP == 4 ? 6 : 4;
-    static_assert(REP == 1 || REP == 8 || REP == 16, "replica count");
     const u32 tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
 #ifdef TRC_ENC_PROF
     const u64 ew0 = wall_clock64();
 #endif
-    u8 *wbase = smem + TAB + ENC_PACE_LDS + wv * ENC_WAVE_LDS;
-    u32 *const fuse_wsum = (u32 *)(smem + TAB + ENC_FUSE_WSUM);
-    if (FUSED) {                                                // the workgroup's place in the container: a ticket, not blockIdx (trc_gather.h)
-        if (tid == 0) *(u32 *)(smem + TAB + ENC_FUSE_TICKET) = __hip_atomic_fetch_add((u32 *)(sync + TRC_SYNC_TICKET), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid < 16u) fuse_wsum[tid] = 0u;
-    }
-    for (u32 i = tid; i < 256u * REP; i += BLOCK) ((uint4 *)smem)[i] = etab_g[i / REP];
-    TrcPace pace; pace.init(trc_lds_addr(smem) + TAB, tid, wv);
+    u8 *wbase = smem + ENC_TAB_LDS + ENC_PACE_LDS + wv * ENC_WAVE_LDS;
+    for (u32 i = tid; i < 256u; i += BLOCK) ((uint4 *)smem)[i] = etab_g[i];
+    TrcPace pace; pace.init(trc_lds_addr(smem) + ENC_TAB_LDS, tid, wv);
     __syncthreads();
-    const u32 wg = FUSED ? (u32)__builtin_amdgcn_readfirstlane((int)*(const u32 *)(smem + TAB + ENC_FUSE_TICKET)) : blockIdx.x;
 
     WaveChunks wc;
-    wc.c0 = (wg * (BLOCK / 64) + wv) * 64u; wc.chunk = chunk; wc.nchunks = nchunks;
+    wc.c0 = (blockIdx.x * (BLOCK / 64) + wv) * 64u; wc.chunk = chunk; wc.nchunks = nchunks;
     wc.lastlen = (u32)(n - (u64)(nchunks - 1) * chunk);
     if (wc.c0 >= nchunks) return;                               // (a barrier waits for the surviving waves only; wave 0 of a workgroup always has chunks)
     wc.rows = nchunks - wc.c0 < 64u ? nchunks - wc.c0 : 64u;
@@ -169,9 +121,8 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
     StreamOut<true, false, false, true> so;                   // (write-through drains: trc_io.h)
     so.rings = wbase;
     so.scratch = scratch; so.stride = stride; so.c0 = wc.c0; so.wpos = 0; so.nfl = 0;
-    const u32 tbase = (lane & (u32)(REP - 1)) << 4;                              // this lane's replica (table at LDS offset 0)
     const u32 rbase = (u32)(uintptr_t)(so.rings - smem) + trc_raddr(lane, 0);    // this lane's ring, as an LDS byte address
-    const uint4 *etab1 = (const uint4 *)smem;                                    // generic view for the ragged tail: replica 0
+    const uint4 *etab1 = (const uint4 *)smem;                                    // generic view for the ragged tail
 
     const u32 S = chunk / TRC_SEG;
     const u32 top = alive ? (len - 1u) / TRC_SEG : 0u;          // segment holding the chunk's last byte
@@ -183,7 +134,7 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
     if ((S - 1u) & 1u) { tin.issue_slot<1>(wc, S - 1u); tin.issue_slot<0>(wc, S - 2u); } else tin.issue_slot<0>(wc, S - 1u);
     // land segment sn (its registers become `p`) and request the line below it.  The compiler guards the landing with
     // s_waitcnt vmcnt(0), and on gfx950 stores count in vmcnt: done at the top of a segment (round 2) it sat out the latency
-    // of the drain stores issued just before; it now runs BEFORE the last drain of the segment above (TRC_ENC_EARLY_COMMIT).
+    // of the drain stores issued just before; it now runs BEFORE the last drain of the segment above.
     auto take = [&](u32 sn) {
         if (sn & 1u) tin.commit_slot<1>(); else tin.commit_slot<0>();
         if (!(sn & 1u) && sn >= 1u) {                           // the next line down: in flight during this segment (and the next)
@@ -197,9 +148,6 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
 #endif
     for (u32 s = S - 1u;; s--) {
         if (BLOCK > 256) pace.step(S - s);                     // (workgroups of more than four waves: some share a SIMD)
-#if !TRC_ENC_EARLY_COMMIT
-        if (s != S - 1u) take(s);
-#endif
         bool act = alive && s <= top && !ovf;
         const bool ragged = act && s == top && toplen != TRC_SEG;
         if (ragged) {                                           // last chunk only: byte by byte
@@ -207,7 +155,7 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
             const u8 *mine = in + (u64)c * chunk;               // (one lane in the whole grid: plain byte loads)
             for (u32 pos = len; pos > TRC_SEG * top;) {
                 pos--;
-                const uint4 e = etab1[(u32)mine[pos] * REP];
+                const uint4 e = etab1[(u32)mine[pos]];
                 const trc_v4u ev = { e.x, e.y, e.z, e.w };
                 u32 wn = ~(so.wpos >> 1);
                 if (pos >= body || !(pos & 1u)) ans_put(st0, ev, rbase, wn); else ans_put(st1, ev, rbase, wn);
@@ -223,14 +171,14 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
                 EncQuad a, b;
                 // four dwords, top first; the reads of dword d-1 fly while dword d is coded.  LDS operations issued
                 // after a's reads when a is waited for: 4 (b's reads) [+ 4 ring writes of the dword before]
-                ans_fetch4(a, v.w, tbase, SH);
-                ans_fetch4(b, v.z, tbase, SH);
+                ans_fetch4(a, v.w);
+                ans_fetch4(b, v.z);
                 ANS_WAIT4(a, 4);
                 ans_put(st1, a.e3, rbase, wn); ans_put(st0, a.e2, rbase, wn); ans_put(st1, a.e1, rbase, wn); ans_put(st0, a.e0, rbase, wn);
-                ans_fetch4(a, v.y, tbase, SH);
+                ans_fetch4(a, v.y);
                 ANS_WAIT4(b, 8);
                 ans_put(st1, b.e3, rbase, wn); ans_put(st0, b.e2, rbase, wn); ans_put(st1, b.e1, rbase, wn); ans_put(st0, b.e0, rbase, wn);
-                ans_fetch4(b, v.x, tbase, SH);
+                ans_fetch4(b, v.x);
                 ANS_WAIT4(a, 8);
                 ans_put(st1, a.e3, rbase, wn); ans_put(st0, a.e2, rbase, wn); ans_put(st1, a.e1, rbase, wn); ans_put(st0, a.e0, rbase, wn);
                 ANS_WAIT4(b, 4);
@@ -238,9 +186,7 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
                 so.wpos = (~wn) << 1;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the ring writes above are not in the compiler's books
-#if TRC_ENC_EARLY_COMMIT
             if (k == 0 && s > 0) take(s - 1u);                  // (this segment's last piece has been read)
-#endif
             so.drain(false, alive);                             // <= 32 new bytes per lane since the last drain
             ovf = ovf || (alive && so.wpos + 8u >= len);        // already incompressible: stop coding this chunk
             act = act && !ovf;
@@ -263,40 +209,6 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
     if (alive) clen[c] = out_len;
     const u32 gs = trc_wave_sum(out_len);
     if (lane == 0) gsum[wc.c0 >> 6] = gs;
-    if (FUSED) {
-        // the gather, by the waves that wrote the bytes (trc_gather.h)
-        __builtin_amdgcn_s_setprio(0);
-        if (lane == 0) fuse_wsum[wv] = gs;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's drains (asm stores: not in the compiler's books) have left for the L2
-        trc_lds_barrier();
-        u64 *const pub = (u64 *)(sync + TRC_SYNC_PUB);
-        const u32 nwg = ((nchunks + 63u) / 64u + (u32)(BLOCK / 64) - 1u) / (u32)(BLOCK / 64);
-        if (wv == 0) {
-            u32 wsum_all = 0;
-#pragma unroll
-            for (u32 k = 0; k < (u32)(BLOCK / 64); k++) wsum_all += fuse_wsum[k];
-            if (lane == 0) trc_sync_store(pub + wg, TRC_SYNC_VALID | wsum_all);
-            const u64 wgbase = trc_sync_prefix(pub, wg);
-            if (lane == 0) {
-                *(u64 *)(smem + TAB + ENC_FUSE_BASE) = wgbase;
-                if (wg == nwg - 1u && total) *total = wgbase + wsum_all;
-                // the last workgroup to have finished polling leaves the area as it found it: zero
-                const u32 done = __hip_atomic_fetch_add((u32 *)(sync + TRC_SYNC_DONE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (done == nwg - 1u) {
-                    for (u32 j = 0; j < nwg; j++) trc_sync_store(pub + j, 0ull);
-                    __hip_atomic_store((u32 *)(sync + TRC_SYNC_TICKET), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store((u32 *)(sync + TRC_SYNC_DONE), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-        trc_lds_barrier();
-        u64 base = *(const u64 *)(smem + TAB + ENC_FUSE_BASE);
-        for (u32 k = 0; k < wv; k++) base += fuse_wsum[k];
-        if (lane == 0 && goff_out) goff_out[wc.c0 >> 6] = base;  // (kept for a decode of this directory: TrcWork::goff_area)
-        const bool raw = out_len == len;
-        const u8 *src = raw ? in + (u64)c * chunk : scratch + (u64)(c + 1u) * stride - out_len;
-        trc_wave_gather64(payload + base, (u32 *)wbase, (u64 *)(wbase + 512), alive ? out_len : 0u, alive ? src : scratch);
-    }
 #ifdef TRC_ENC_PROF
     if (lane == 0) { const u32 wid = (wc.c0 >> 6) & 4095u; trc_enc_wall[4 * wid] = ew0; trc_enc_wall[4 * wid + 1] = ew1; trc_enc_wall[4 * wid + 2] = ew2; trc_enc_wall[4 * wid + 3] = wall_clock64(); }
 #endif
@@ -331,9 +243,6 @@ typedef __attribute__((address_space(3))) u32 trc_lds_u32;
 typedef StreamInT<true> AnsStreamIn;
 #define DEC_LDS_LUT   0u          // u8[32768]
 #define DEC_LDS_DTAB  32768u      // uint2[256]  { f, -c0 }
-#ifndef TRC_DEC_BALANCE
-#define TRC_DEC_BALANCE 2       // the waves of a SIMD keep each other's pace (TrcPace, trc_dev.h); 0: off; 1 / 2 / 3: every period / segment / second period
-#endif
 #define DEC_LDS_PROG  34816u      // u32[16]     progress counters, [SIMD][age]
 #define DEC_LDS_WAVES 34880u
 
@@ -366,14 +275,7 @@ __device__ __forceinline__ void ans_get_pair(u32 &s0, u32 &s1, u32 &sl0, u32 &sl
     const trc_v2u e1 = *(const trc_lds_u64 *)(uintptr_t)(DEC_LDS_DTAB + (x1 << 3));
     u32 t0 = __umul24(e0.x, s0 >> TRC_PROB_BITS) + e0.y + sl0;
     u32 t1 = __umul24(e1.x, s1 >> TRC_PROB_BITS) + e1.y + sl1;
-#ifndef TRC_DEC_ALIGNBYTE
-#define TRC_DEC_ALIGNBYTE 0                                     // measured: 60.7-61.0 us either way (profiles/r05zi_alignbyte.txt)
-#endif
-#if TRC_DEC_ALIGNBYTE                                            // v_alignbyte shifts by 8 x (operand & 3): 2 hc is a plain v_add (2.3 cycles per SIMD), hc << 4 a v_lshlrev (4.2-5)
-    const u32 w32 = __builtin_amdgcn_alignbyte(dw1, dw0, hc + hc);                       // units hc, hc + 1
-#else
     const u32 w32 = __builtin_amdgcn_alignbit(dw1, dw0, hc << 4);                        // units hc, hc + 1 (the shift uses 5 bits: 16 x parity)
-#endif
     u32 c0, c1, sl;
     u64 m1, cy;
     asm("v_cmp_gt_u32_e32 vcc, 0x8000, %[t0]\n\t"
@@ -457,9 +359,7 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec_kernel(
         }
     }
     PROF_T(pt1);
-#if TRC_DEC_BALANCE
-    TrcPace pace; pace.init(DEC_LDS_PROG, tid, wv);
-#endif
+    TrcPace pace; pace.init(DEC_LDS_PROG, tid, wv);            // the waves of a SIMD keep each other's pace (trc_dev.h)
 
     const u32 cl = alive ? trc_min(cl_raw, len) : 0u;         // a directory entry above the chunk length (corrupt input) reads as raw
     const u32 ex = trc_wave_incl_scan(cl) - cl;
@@ -497,18 +397,14 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec_kernel(
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const u32 p0 = s * TRC_SEG + (u32)k * 16u;          // chunk offset of this 16-byte piece
-#if TRC_DEC_BALANCE
-            // (policies measured, profiles/r05_notes.md: every period 64 us, every segment 62-63, every second period 62-63, graded
-            // priorities 63, laggards 3 / leader 1: 63; off: 67)
-            if (TRC_DEC_BALANCE == 1 || k == 0 || (TRC_DEC_BALANCE == 3 && k == 2)) pace.step(s * 4u + (u32)k + 1u);
-#endif
+            // once per segment (policies measured, profiles/r05_notes.md: every period 64 us, every segment 62-63, every second
+            // period 62-63, graded priorities 63, laggards 3 / leader 1: 63; off: 67)
+            if (k == 0) pace.step(s * 4u + 1u);
             // period boundary: land the round requested 16 symbols ago, request the next one
             PROF_T(qa);
             si.period(coded && p0 < len, k & 1);
             PROF_T(qb); PROF_ACC(acc_p, qa, qb);
-#if TRC_DEC_LATE_FLUSH
             if (k == 0 && s > 0) tout.flush(wc, (s - 1u) * TRC_SEG);   // the segment before: behind this period's commit (header comment)
-#endif
             PROF_T(qc); PROF_ACC(acc_f, qb, qc);
             if (coded && p0 + 16u <= len) {
                 u32 w[4];
@@ -529,13 +425,8 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec_kernel(
                     dst[pos] = (u8)((pos >= body4 || !(pos & 1u)) ? ans_get(sb, si) : ans_get(sa, si));
             }
         }
-#if !TRC_DEC_LATE_FLUSH
-        tout.flush(wc, s * TRC_SEG);
-#endif
     }
-#if TRC_DEC_LATE_FLUSH
     tout.flush(wc, (S - 1u) * TRC_SEG);
-#endif
     // chunks stored raw (clen == len): the whole wave copies them, one after the other
     trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)wc.c0 * chunk, chunk, payload);
 #ifdef TRC_DEC_PROF
@@ -700,52 +591,30 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec2_kernel(
 }
 
 // ------------------------------------------------------------------------------------- launch ---
-// Encoder launch shape.  LDS per workgroup = REP x 4 KiB of symbol table + 8.3 KiB per wave; a CU holds 160 KiB.
-//   REP 1 (default): 4 waves share one 4 KiB table, 37 KiB per workgroup -> 16 waves per CU
-//   REP 8 (TRC_ENC_REP=8, 32 KiB, 12 waves per workgroup): kept as a measuring aid -- with the hand-issued b128 reads the
-//   replicated table is NOT faster (100 MB, chunk 512: 64 vs 63 us; REP 16 at 11 waves per CU, chunk 576: 67 vs 68 us;
-//   profiles/r02_notes.md): the bank conflicts round 1's PMC showed were not what the kernel waited for.
-template <int REP>
-static void ans4s_enc_launch(u32 wpb, bool fused, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen,
-                             uint8_t *d_payload, uint64_t *d_total, hipStream_t s)
+// Encoder launch shape.  LDS per workgroup = 4 KiB of symbol table + 8.3 KiB per wave; a CU holds 160 KiB.
+void trc_launch_ans4s_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
     const uint4 *etab = (const uint4 *)(w.tables + TRC_TAB_ENC);
     const u32 nwaves = w.ngroups;
-    const size_t sm = 4096u * REP + ENC_PACE_LDS + wpb * ENC_WAVE_LDS;
-    u8 *const sync = w.tables + TRC_TAB_SYNC;
-#define TRC_ENC_CASE(W, F)                                                                                              \
-    TRC_RAISE_LDS_ONCE((trc_ans4s_enc_kernel<64 * W, REP, F>), 4096u * REP + ENC_PACE_LDS + W * ENC_WAVE_LDS);          \
-    TRC_LAUNCH_TIMED((trc_ans4s_enc_kernel<64 * W, REP, F>), dim3((nwaves + W - 1) / W), dim3(64 * W), sm, s,           \
-                     d_in, (u64)n, chunk, w.nchunks, etab, w.scratch, w.stride, d_clen, w.gsum, d_payload, d_total, w.goff_area, sync);
-    switch (wpb) {
-    case 1: TRC_ENC_CASE(1, false) break;
-    case 4: TRC_ENC_CASE(4, false) break;
-    case 12: if (fused) { TRC_ENC_CASE(12, true) } else { TRC_ENC_CASE(12, false) } break;
-    default: break;
-    }
-#undef TRC_ENC_CASE
-}
-// returns true when the encoder's waves have gathered the payload themselves (trc_gather.h): no gather launch behind it
-bool trc_launch_ans4s_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w,
-                          uint32_t *d_clen, uint8_t *d_payload, uint64_t *d_total, hipStream_t s)
-{
-    const u32 nwaves = w.ngroups;
-    static const int env_rep = getenv("TRC_ENC_REP") ? atoi(getenv("TRC_ENC_REP")) : 0;     // tuning aids
-    static const int env_wpb = getenv("TRC_ENC_WPB") ? atoi(getenv("TRC_ENC_WPB")) : 0;
-    static const int env_fused = getenv("TRC_ENC_FUSED") ? atoi(getenv("TRC_ENC_FUSED")) : TRC_ENC_FUSED;
-    int rep = env_rep ? env_rep : TRC_ENC_REP_DEFAULT;
-    u32 wpb = rep == 8 ? 12u : 4u;
+    static const int env_wpb = getenv("TRC_ENC_WPB") ? atoi(getenv("TRC_ENC_WPB")) : 0;     // tuning aid
     // one residency round (at most twelve waves per CU): one workgroup of twelve waves per CU, whose waves keep each other's pace
     // (TrcPace: they share SIMDs by construction); more than a round: workgroups of four, sixteen waves per CU, new ones moving in
     // as old ones end
-    if (TRC_ENC_BALANCE && nwaves <= 12u * 256u) wpb = 12u;
-    if (nwaves < 2048) { rep = 1; wpb = 1; }                 // few waves: one per workgroup so they spread over all CUs (12.4 KiB -> 12 per CU)
+    u32 wpb = nwaves <= 12u * 256u ? 12u : 4u;
+    if (nwaves < 2048) wpb = 1;                              // few waves: one per workgroup so they spread over all CUs (12.4 KiB -> 12 per CU)
     if (env_wpb == 1 || env_wpb == 4 || env_wpb == 12) wpb = (u32)env_wpb;      // (tuning aid / tests: forces the shape whatever the size)
-    // the twelve-wave workgroups of a one-round launch gather their own payload (no scan kernel in the way: w.goff == NULL)
-    const bool fused = env_fused && wpb == 12u && !w.goff && (nwaves + 11u) / 12u <= TRC_SYNC_MAX_WG;
-    if (fused) (void)hipMemsetAsync(w.tables + TRC_TAB_SYNC, 0, TRC_SYNC_BYTES, s);      // (not "left zero by the last launch": ADVICE r5)
-    if (rep == 8) ans4s_enc_launch<8>(wpb, fused, d_in, n, chunk, w, d_clen, d_payload, d_total, s);
-    else ans4s_enc_launch<1>(wpb, fused, d_in, n, chunk, w, d_clen, d_payload, d_total, s);
+    const size_t sm = ENC_TAB_LDS + ENC_PACE_LDS + wpb * ENC_WAVE_LDS;
+#define TRC_ENC_CASE(W)                                                                                                 \
+    TRC_RAISE_LDS_ONCE((trc_ans4s_enc_kernel<64 * W>), ENC_TAB_LDS + ENC_PACE_LDS + W * ENC_WAVE_LDS);                  \
+    TRC_LAUNCH_TIMED((trc_ans4s_enc_kernel<64 * W>), dim3((nwaves + W - 1) / W), dim3(64 * W), sm, s,                   \
+                     d_in, (u64)n, chunk, w.nchunks, etab, w.scratch, w.stride, d_clen, w.gsum);
+    switch (wpb) {
+    case 1: TRC_ENC_CASE(1) break;
+    case 4: TRC_ENC_CASE(4) break;
+    case 12: TRC_ENC_CASE(12) break;
+    default: break;
+    }
+#undef TRC_ENC_CASE
 #ifdef TRC_ENC_PROF
     {
         static int calls = 0;
@@ -768,7 +637,6 @@ bool trc_launch_ans4s_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const T
         }
     }
 #endif
-    return fused;
 }
 
 void trc_launch_ans4s_dec(const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,

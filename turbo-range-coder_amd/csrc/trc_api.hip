@@ -304,10 +304,8 @@ bool trc_gate_ok(int codec)
 {
     static const bool off = getenv("TRC_HOST_NO_GATE") != nullptr;       // tuning aid / tests: the slice pipeline for every coder
     if (off) return false;
-    switch (codec) {
-    case TRC_RCA: case TRC_RCAI: return trc_rca_enc_gate_ok();
-    case TRC_ANSA: return trc_ansa_enc_gate_ok();
-    case TRC_RCB: return trc_rcb_enc_gate_ok();
+    switch (codec) {                                                      // the encoders that wait at the gate (WaveChunks::gate)
+    case TRC_RCA: case TRC_RCAI: case TRC_ANSA: case TRC_RCB: return true;
     }
     return false;
 }
@@ -316,10 +314,8 @@ bool trc_prog_ok(int codec)
 {
     static const bool off = getenv("TRC_HOST_NO_GATE") != nullptr;
     if (off) return false;
-    switch (codec) {
-    case TRC_RCA: case TRC_RCAI: return trc_rca_dec_prog_ok();
-    case TRC_ANSA: return trc_ansa_dec_prog_ok();
-    case TRC_RCB: return trc_rcb_dec_prog_ok();
+    switch (codec) {                                                      // the decoders that report their progress (WaveChunks::prog)
+    case TRC_RCA: case TRC_RCAI: case TRC_ANSA: case TRC_RCB: return true;
     }
     return false;
 }
@@ -388,10 +384,9 @@ extern "C" int trc_encode_dev(int codec, const void *d_in, size_t n, uint32_t ch
     if ((rc = carve(codec, n, chunk, d_work, work_bytes, w))) return rc;
     if (is_static(codec) && !tables_ready) trc_launch_static_prep(d_cdf, cdfnum, w.tables, s);
     int from_end = 0;
-    bool gathered = false;                                       // the coder's own waves have put the payload in place (trc_gather.h)
     tm_begin(0);
     switch (codec) {
-    case TRC_ANS4S: gathered = trc_launch_ans4s_enc((const uint8_t *)d_in, n, chunk, w, d_clen, (uint8_t *)d_payload, d_total, s); from_end = 1; break;
+    case TRC_ANS4S: trc_launch_ans4s_enc((const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 1; break;
     case TRC_RCS1:  trc_launch_rcs_enc(1, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
     case TRC_RCS2:  trc_launch_rcs_enc(2, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 2; break;
     case TRC_RCSM:  trc_launch_rcs_enc(-1, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
@@ -413,12 +408,10 @@ extern "C" int trc_encode_dev(int codec, const void *d_in, size_t n, uint32_t ch
                     from_end = 1; break;
     }
     tm_end(0);
-    if (!gathered) {
-        tm_begin(2);
-        if (w.goff) trc_launch_scan_groups(w.gsum, w.ngroups, w.goff, d_total, s);
-        trc_launch_gather((const uint8_t *)d_in, n, chunk, w, from_end, d_clen, (uint8_t *)d_payload, d_total, s);
-        tm_end(2);
-    }
+    tm_begin(2);
+    if (w.goff) trc_launch_scan_groups(w.gsum, w.ngroups, w.goff, d_total, s);
+    trc_launch_gather((const uint8_t *)d_in, n, chunk, w, from_end, d_clen, (uint8_t *)d_payload, d_total, s);
+    tm_end(2);
     HIPCHK(hipGetLastError());
     return TRC_OK;
 }
@@ -475,7 +468,7 @@ extern "C" int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_p
 
 // The kernel that takes the longest in the DEFAULT dispatch of the coder at the bench configurations (100 MB, the library's chunk):
 // what a rocprofv3 --kernel-trace of bench.py lists first for that direction.  Two-pass encoders launch more than one kernel (the
-// timing pairs sum them); forms behind tuning variables or other sizes (one-lane order-1 decoder, one-wave model passes) have
+// timing pairs sum them); forms at other sizes (the order-1 coder's eight-lane decoder and position-order passes) have
 // other names.  Descriptive: nothing is dispatched by this string.
 extern "C" const char *trc_kernel_name(int codec, int decode)
 {

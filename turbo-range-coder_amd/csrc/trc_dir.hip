@@ -2,7 +2,6 @@
 // (per-group sums -> exclusive scan), the payload gather, and cdfini (histogram -> CDF) on device.
 #include <stdlib.h>
 #include "trc_dev.h"
-#include "trc_gather.h"
 #include "trc_launch.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -38,8 +37,6 @@ __global__ __launch_bounds__(256) void trc_static_prep_kernel(const u16 *__restr
         ((uint4 *)(tables + TRC_TAB_ENC))[tid] = e;
         ((u32 *)(tables + TRC_TAB_DEC))[tid] = d;
         for (u32 i = tid; i < 260; i += 256) ((u16 *)(tables + TRC_TAB_CDF))[i] = (u16)((i <= cdfnum) ? cdf[i] : TRC_PROB_ONE);
-        // the sync area of the encoders that gather their own payload (trc_gather.h) starts out zero; each such launch leaves it zero
-        for (u32 i = tid; i < TRC_SYNC_BYTES / 4u; i += 256) ((u32 *)(tables + TRC_TAB_SYNC))[i] = 0u;
     }
 }
 
@@ -243,80 +240,12 @@ void trc_launch_gather(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcW
 // ---------------------------------------------------------------------------------------------
 // cdfini on device (reference: rccdf.c:50-68).  Histogram with per-wave LDS privatisation, then
 // one wave builds the CDF with the reference's normalisation rule.
-// Histogram (round 3): every LANE counts into its own column -- 128 rows (bins 2r | 2r+1 packed as two 16-bit halves of a
-// dword) x 64 lanes per wave, 32 KiB of LDS per wave, a workgroup of four waves per CU.  The update is one ds_add_u32 whose 64
-// lanes touch 64 different dwords in two conflict-free groups (bank = lane mod 32): no two lanes ever meet on a counter, whatever
-// the data (rounds 1-2 used LDS atomics on 1 / 16 shared copies per workgroup: text puts 17 % of all bytes on one symbol and
-// the lanes of an instruction serialised on it -- 66 / 56 us for 100 MB).  A lane counts at most 65 520 bytes between two
-// reductions, so the halves cannot overflow.
-#define TRC_HIST_WAVE_LDS (128u * 64u * 4u)
-#define TRC_HIST_ROUND_VECS 4095u                                 // uint4 per lane per round: 65 520 bytes < 2^16
-__global__ __launch_bounds__(256) void trc_hist_kernel(const u8 *__restrict__ in, u64 n, u64 *__restrict__ hist)
-{
-    extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    typedef __attribute__((address_space(3))) u32 lds_u32;
-    const u32 tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    u32 *mine = (u32 *)(smem + wv * TRC_HIST_WAVE_LDS);            // [128 rows][64 lanes]
-    u64 *tot = (u64 *)(smem + 4u * TRC_HIST_WAVE_LDS);             // [256] per workgroup
-    const u32 col = trc_lds_addr(mine) + lane * 4u;
-    tot[tid] = 0;
-    const u64 nvec = n >> 4, stride = (u64)gridDim.x * 256;
-    const uint4 *v = (const uint4 *)in;
-    // four bytes -> four ds_add_u32 on this lane's column: per byte v_bfe (row) + v_lshl_add (address), v_bfe (parity) + v_mad_u32_u24
-    // (increment 1 or 0x10000) -- with one wave per SIMD the kernel's time is its instruction count plus whatever memory latency is
-    // left exposed
-    auto count = [&](u32 w) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const u32 a = (__builtin_amdgcn_ubfe(w, 8 * k + 1, 7) << 8) + col;
-            const u32 inc = __umul24(__builtin_amdgcn_ubfe(w, 8 * k, 1), 0xffffu) + 1u;
-            __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)a, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        }
-    };
-    auto count4 = [&](const uint4 q) { count(q.x); count(q.y); count(q.z); count(q.w); };
-    for (u64 r0 = 0; r0 == 0 || r0 < nvec; r0 += stride * TRC_HIST_ROUND_VECS) {      // (r0 is uniform: every wave runs every round)
-        for (u32 r = lane; r < 128u * 64u; r += 64u) mine[r] = 0;  // own wave's counters (row-major: lanes write consecutive dwords)
-        u64 i = r0 + (u64)blockIdx.x * 256 + tid;
-        u32 left = TRC_HIST_ROUND_VECS;
-        // Round 4: the NEXT four vectors are requested before the current four are counted (round 3 requested four and counted them
-        // at once: a memory round trip in front of every 64 bytes, ~24 of them per lane at 100 MB).
-        if (left >= 4u && i + 3 * stride < nvec) {
-            uint4 q0 = v[i], q1 = v[i + stride], q2 = v[i + 2 * stride], q3 = v[i + 3 * stride];
-            left -= 4u; i += 4 * stride;
-            for (; left >= 4u && i + 3 * stride < nvec; left -= 4u, i += 4 * stride) {
-                const uint4 n0 = v[i], n1 = v[i + stride], n2 = v[i + 2 * stride], n3 = v[i + 3 * stride];
-                count4(q0); count4(q1); count4(q2); count4(q3);
-                q0 = n0; q1 = n1; q2 = n2; q3 = n3;
-            }
-            count4(q0); count4(q1); count4(q2); count4(q3);
-        }
-        for (; left && i < nvec; left--, i += stride) count4(v[i]);
-        if (r0 == 0 && blockIdx.x == 0 && wv == 0)                  // the input's last n % 16 bytes, once
-            for (u64 t = (nvec << 4) + lane; t < n; t += 64) { const u32 b = in[t]; mine[(b >> 1) * 64u + lane] += (b & 1u) ? 0x10000u : 1u; }
-        // reduce this wave's columns: lane l sums rows l and l + 64, walking the columns rotated by l (bank = column mod 32)
-        u32 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
-        for (u32 c = 0; c < 64u; c++) {
-            const u32 cc = (c + lane) & 63u;
-            const u32 a = mine[lane * 64u + cc], b = mine[(lane + 64u) * 64u + cc];
-            lo0 += a & 0xffffu; hi0 += a >> 16; lo1 += b & 0xffffu; hi1 += b >> 16;
-        }
-        __syncthreads();                                            // (first round: orders the zeroing of tot[])
-        atomicAdd((unsigned long long *)&tot[2 * lane], (unsigned long long)lo0);
-        atomicAdd((unsigned long long *)&tot[2 * lane + 1], (unsigned long long)hi0);
-        atomicAdd((unsigned long long *)&tot[2 * (lane + 64)], (unsigned long long)lo1);
-        atomicAdd((unsigned long long *)&tot[2 * (lane + 64) + 1], (unsigned long long)hi1);
-    }
-    __syncthreads();
-    // 256 workgroups finish together and each adds up to 256 bins: rotated by the workgroup, so that at any moment they are at
-    // different bins (all starting at bin 0 serialises them on one L2 atomic after the other)
-    const u32 bin = (tid + 37u * blockIdx.x) & 255u;
-    if (tot[bin]) atomicAdd((unsigned long long *)&hist[bin], (unsigned long long)tot[bin]);
-}
-// Round 4 form: SIXTEEN waves per CU instead of four.  The per-lane columns above are conflict-free but cost 32 KiB per wave: one
-// wave per SIMD, whose ~8 500 instructions and every exposed load are the kernel's time (49 us per 100 MB).  Here a wave keeps
-// 16 copies of the packed histogram (128 rows x 16 dwords = 8 KiB; lanes l, l + 16, l + 32, l + 48 share copy l & 15): a
-// ds_add_u32 of random bytes meets ~2.5-way bank conflicts and the occasional same-counter pair, but four waves per SIMD hide
-// both that and the loads.  A copy counts at most 4 x 1023 x 16 = 65 472 bytes between two reductions (no 16-bit overflow).
+// Histogram (round 4): sixteen waves per CU.  A wave keeps 16 copies of the packed histogram (bins 2r | 2r+1 as the two 16-bit
+// halves of a dword; 128 rows x 16 dwords = 8 KiB; lanes l, l + 16, l + 32, l + 48 share copy l & 15): a ds_add_u32 of random
+// bytes meets ~2.5-way bank conflicts and the occasional same-counter pair, but four waves per SIMD hide both that and the loads
+// (round 3's per-lane columns were conflict-free at 32 KiB per wave, one wave per SIMD: 49 us per 100 MB; rounds 1-2's LDS
+// atomics on shared copies serialised on text's most frequent symbol).  A copy counts at most 4 x 1023 x 16 = 65 472 bytes
+// between two reductions (no 16-bit overflow).
 #define TRC_HIST2_WAVE_LDS (128u * 16u * 4u)
 #define TRC_HIST2_WAVES 16u
 #define TRC_HIST2_ROUND_VECS 1023u
@@ -409,25 +338,15 @@ __global__ __launch_bounds__(256) void trc_cdf_build_kernel(const u64 *__restric
 void trc_launch_hist(const uint8_t *d_in, size_t n, uint64_t *d_hist, hipStream_t s)
 {
     (void)hipMemsetAsync(d_hist, 0, 256 * sizeof(uint64_t), s);
-    u64 blocks = ((n >> 4) + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 256) blocks = 256;                             // one workgroup (4 x 32 KiB of counters) per CU
-    static const int form = getenv("TRC_HIST_FORM") ? atoi(getenv("TRC_HIST_FORM")) : 2;        // 1: the per-lane columns of round 3
-    if (form == 2) {
-        const size_t sm2 = TRC_HIST2_WAVES * TRC_HIST2_WAVE_LDS + 256u * sizeof(u64);
-        u64 b2 = ((n >> 4) + 1023) / 1024;
-        b2 = b2 < 1 ? 1 : b2 > 256 ? 256 : b2;                  // one workgroup of 16 waves per CU
-        TRC_RAISE_LDS_ONCE(trc_hist2_kernel, sm2);
-        // TRC_HIST_ROUND_VECS (test aid): vectors per lane between two reductions, so that a few MB exercise the many-round path
-        // that real inputs take only beyond 4.29 GB
-        static const u32 rv = getenv("TRC_HIST_ROUND_VECS") ? (u32)atoi(getenv("TRC_HIST_ROUND_VECS")) : TRC_HIST2_ROUND_VECS;
-        hipLaunchKernelGGL(trc_hist2_kernel, dim3((u32)b2), dim3(1024), sm2, s, d_in, (u64)n, d_hist,
-                           rv >= 1u && rv <= TRC_HIST2_ROUND_VECS ? rv : TRC_HIST2_ROUND_VECS);
-        return;
-    }
-    const size_t sm = 4u * TRC_HIST_WAVE_LDS + 256u * sizeof(u64);
-    TRC_RAISE_LDS_ONCE(trc_hist_kernel, sm);                    // per DEVICE (a process-wide flag left a second GPU at the 64 KiB default)
-    hipLaunchKernelGGL(trc_hist_kernel, dim3((u32)blocks), dim3(256), sm, s, d_in, (u64)n, d_hist);
+    const size_t sm2 = TRC_HIST2_WAVES * TRC_HIST2_WAVE_LDS + 256u * sizeof(u64);
+    u64 b2 = ((n >> 4) + 1023) / 1024;
+    b2 = b2 < 1 ? 1 : b2 > 256 ? 256 : b2;                      // one workgroup of 16 waves per CU
+    TRC_RAISE_LDS_ONCE(trc_hist2_kernel, sm2);                  // per DEVICE (a process-wide flag left a second GPU at the 64 KiB default)
+    // TRC_HIST_ROUND_VECS (test aid): vectors per lane between two reductions, so that a few MB exercise the many-round path
+    // that real inputs take only beyond 4.29 GB
+    static const u32 rv = getenv("TRC_HIST_ROUND_VECS") ? (u32)atoi(getenv("TRC_HIST_ROUND_VECS")) : TRC_HIST2_ROUND_VECS;
+    hipLaunchKernelGGL(trc_hist2_kernel, dim3((u32)b2), dim3(1024), sm2, s, d_in, (u64)n, d_hist,
+                       rv >= 1u && rv <= TRC_HIST2_ROUND_VECS ? rv : TRC_HIST2_ROUND_VECS);
 }
 void trc_launch_cdf_build(const uint64_t *d_hist, size_t n_total, uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status, hipStream_t s)
 {

@@ -30,13 +30,9 @@
 // Byte address, inside one wave's ring array, of ring offset `off` (0..127) of lane `lane`.
 //   default: lane-major rows of 132 bytes (33 dwords: conflict-free while lanes sit at equal offsets,
 //     ~3-way conflicts once the data-dependent offsets drift apart).
-//   TRC_RING_INTERLEAVED: dword d of every lane's ring in row d -> ((off>>2)*64 + lane)*4 + (off&3): never
-//     conflicts, but costs one more VALU op per access.  Measured on MI355X (same box, interleaved runs):
-//     decode 124 vs 113 us, encode 101 vs 99 us in favour of the linear form -- the ring is not where the
-//     LDS conflict cycles come from (the random table reads are).
-#ifdef TRC_RING_INTERLEAVED
-#error "TRC_RING_INTERLEAVED is gone: StreamInT<true> is the interleaved ring (static rANS decoder); StreamOut / StreamInT<false> assume the lane-major rows"
-#endif
+//   (dword d of every lane's ring in row d never conflicts, but costs one more VALU op per access: measured decode 124 vs 113 us,
+//     encode 101 vs 99 us in favour of the linear form -- the ring is not where the LDS conflict cycles come from.  StreamInT<true>,
+//     the static rANS decoder's ring, is interleaved for another reason: trc_ans_static.hip.)
 __device__ __forceinline__ u32 trc_raddr(u32 lane, u32 off) { return lane * TRC_SRING_STRIDE + off; }
 
 __device__ __forceinline__ u32 trc_mbcnt(u64 mask)   // number of set bits of mask below this lane
@@ -146,14 +142,10 @@ struct TileIn {
 // 4q..4q+3 and every store instruction again writes whole 64-byte segments.  Frees 5 KiB of LDS per
 // wave -- what it takes to keep 12 decoder waves per CU resident next to the 34 KiB symbol tables.
 __device__ __forceinline__ u32 trc_quad_xor1(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false); }
-__device__ __forceinline__ u32 trc_quad_xor2(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false); }
 // 4x4 transpose of uint4 blocks inside every quad of lanes: afterwards m[j] of lane i is what m[i] of lane
 // (quad base + j) held (an involution, used in both directions).
 // Round 3: the DPP lane swap folded into the select (v_cndmask_b32_dpp: D = VCC ? src1 : quad_perm(src0)) -- one VALU per
-// dword and stage, 32 per 64 bytes, where the C form below costs 64 (select the word to send, v_mov_dpp, two selects).
-#ifndef TRC_QUAD_DPP
-#define TRC_QUAD_DPP 1
-#endif
+// dword and stage, 32 per 64 bytes, where the C form of rounds 1-2 cost 64 (select the word to send, v_mov_dpp, two selects).
 // Round 5: runs of v_cndmask_b32 in the encodings that read VCC implicitly (VOP2, DPP, SDWA) are pathological on gfx950 -- from the
 // third one on EACH occupies the SIMD for ~22.7 cycles whatever else is resident (scripts/probe/valu_occ.hip, profiles/r05_valu_rates.txt:
 // "cnd_dpp vcc b2b" 22.7 cycles per instruction at 1..8 waves per SIMD; an s_nop or a scalar instruction between them changes
@@ -199,35 +191,7 @@ __device__ __forceinline__ void trc_quad_transpose_dpp(u32 (&m)[4][4])
     TRC_QT_PAIR("quad_perm:[2,3,0,1]", lo2, hi2, m[1][0], m[1][1], m[1][2], m[1][3], m[3][0], m[3][1], m[3][2], m[3][3],
                 a[1][0], a[1][1], a[1][2], a[1][3], a[3][0], a[3][1], a[3][2], a[3][3]);
 }
-__device__ __forceinline__ void trc_quad_transpose_c(u32 (&m)[4][4]);
-__device__ __forceinline__ void trc_quad_transpose(u32 (&m)[4][4])
-{
-#if TRC_QUAD_DPP
-    trc_quad_transpose_dpp(m);
-#else
-    trc_quad_transpose_c(m);
-#endif
-}
-__device__ __forceinline__ void trc_quad_transpose_c(u32 (&m)[4][4])
-{
-    const u32 lane = trc_lane();
-    const bool b0 = lane & 1u, b1 = lane & 2u;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-#pragma unroll
-        for (int k = 0; k < 4; k += 2) {                       // swap bit 0 of (lane, piece) with lane^1
-            const u32 r = trc_quad_xor1(b0 ? m[k][c] : m[k + 1][c]);
-            const u32 n0 = b0 ? r : m[k][c], n1 = b0 ? m[k + 1][c] : r;
-            m[k][c] = n0; m[k + 1][c] = n1;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; k++) {                          // swap bit 1 with lane^2
-            const u32 r = trc_quad_xor2(b1 ? m[k][c] : m[k + 2][c]);
-            const u32 n0 = b1 ? r : m[k][c], n1 = b1 ? m[k + 2][c] : r;
-            m[k][c] = n0; m[k + 2][c] = n1;
-        }
-    }
-}
+__device__ __forceinline__ void trc_quad_transpose(u32 (&m)[4][4]) { trc_quad_transpose_dpp(m); }
 
 // QuadIn: TileIn without the LDS tile (same quad-coalesced 64-byte loads, transposed in registers).
 struct QuadIn {
@@ -293,22 +257,6 @@ struct QuadIn {
 #pragma unroll
         for (int k = 0; k < 4; k++) p[k] = make_uint4(m[k][0], m[k][1], m[k][2], m[k][3]);
     }
-    // The same for kernels that walk their chunks UPWARD (round 5: the model passes of the adaptive coders read 1.8 x their input
-    // from the fabric -- each nontemporal 64-byte request pulled its 128-byte line, and the line's other half was asked for one
-    // segment-time later, when it was gone).  Segments s (even) and s + 1 are requested together, one segment ahead of their use:
-    //   start_fwd(w, S);   every s: take_fwd(w, s, S); code segment s (read(k))
-    __device__ __forceinline__ void start_fwd(const WaveChunks &w, u32 S)
-    {
-        issue_slot<0>(w, 0);
-        if (S > 1u) issue_slot<1>(w, 1);
-    }
-    __device__ __forceinline__ void take_fwd(const WaveChunks &w, u32 s, u32 S)
-    {
-        if (s & 1u) {
-            commit_slot<1>();
-            if (s + 1u < S) { issue_slot<0>(w, s + 1u); if (s + 2u < S) issue_slot<1>(w, s + 2u); }     // both register sets are free now
-        } else commit_slot<0>();
-    }
 };
 
 struct QuadOut {
@@ -354,7 +302,7 @@ struct QuadOut {
 // passes of `anscdf` / `ansb`): nothing in the kernel loads from, or stores again into, a segment that has been drained -- the store is
 // inline asm, outside the compiler's vmcnt accounting, so neither a later access nor a release at the kernel's end would wait for it
 // on the compiler's say-so.  A coder that patches a header behind a drain (the two-stream range coders) must keep WT = false; code that
-// READS drained bytes in the same kernel (the fused gather, trc_gather.h) puts its own `s_waitcnt vmcnt(0)` + barrier in between.
+// READS drained bytes in the same kernel must put its own `s_waitcnt vmcnt(0)` + barrier in between.
 template <bool DOWN, bool PAIR = false, bool QUAD = false, bool WT = false>
 struct StreamOut {
     u8 *rings;           // this wave's ring array (LDS)
@@ -504,13 +452,9 @@ struct StreamInT {
     // profiles/r04_pmc_traffic.txt).
     __device__ __forceinline__ u32 align_start(bool on)
     {
-#ifdef TRC_DEC_NOALIGN
-        return 0u;
-#else
         const u32 r0 = on ? trc_min((u32)(((uintptr_t)gbase + soff) & 63u), soff < 62u ? (u32)soff : 62u) & ~1u : 0u;
         soff -= r0; lim += r0;
         return r0;
-#endif
     }
     __device__ __forceinline__ u32 peek16() const { return *(const u16 *)(rings + ra(trc_lane(), rpos & (TRC_SRING - 1))); }
     __device__ __forceinline__ u32 peek32() const { return *(const u32 *)(rings + ra(trc_lane(), rpos & (TRC_SRING - 1))); }

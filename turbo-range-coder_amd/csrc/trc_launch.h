@@ -46,14 +46,8 @@ struct TrcGate { const uint32_t *flag; uint32_t part; };
 extern thread_local TrcGate trc_gate_tls;
 struct TrcProg { uint32_t *counters; uint32_t *host_flags; uint32_t part; };  // ... and the progress counters of the next DECODE (WaveChunks::prog)
 extern thread_local TrcProg trc_prog_tls;
-bool trc_prog_ok(int codec);                                   // the default decoder form of `codec` reports its progress
-bool trc_rca_dec_prog_ok();
-bool trc_ansa_dec_prog_ok();
-bool trc_rcb_dec_prog_ok();
-bool trc_gate_ok(int codec);                                   // the default encoder form of `codec` waits at the gate (trc_api.hip)
-bool trc_rca_enc_gate_ok();
-bool trc_ansa_enc_gate_ok();
-bool trc_rcb_enc_gate_ok();
+bool trc_prog_ok(int codec);                                   // the decoder of `codec` reports its progress (trc_api.hip)
+bool trc_gate_ok(int codec);                                   // the encoder of `codec` waits at the gate (trc_api.hip)
 
 // Workspace carve-up shared by encode and decode (all offsets 256-byte aligned).
 struct TrcWork {
@@ -78,8 +72,7 @@ struct TrcWork {
 #define TRC_TAB_DEC   4096       // u32[256]     decoder symbol table
 #define TRC_TAB_LUT   8192       // u8[32768]    slot -> symbol
 #define TRC_TAB_CDF   40960      // u16[260]     sanitised CDF copy
-#define TRC_TAB_SYNC  41984      // 2112 B       sync area of the encoders that gather their own payload (trc_gather.h): zero between calls
-#define TRC_TAB_BYTES 45056
+#define TRC_TAB_BYTES 45056      // (the bytes from 41984 are unused; the size callers see stays)
 
 // static-table prep (ANS4S / RCS1 / RCS2)
 void trc_launch_static_prep(const uint16_t *d_cdf, unsigned cdfnum, uint8_t *tables, hipStream_t s);
@@ -94,9 +87,7 @@ void trc_launch_gather(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcW
                        const uint32_t *d_clen, uint8_t *d_payload, uint64_t *d_total, hipStream_t s);
 
 // ANS4S: static-CDF rANS (anscdf4senc / anscdf4sdec)
-// returns true when the payload is already in place (the encoder's waves gathered it: trc_gather.h) -- no trc_launch_gather then
-bool trc_launch_ans4s_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w,
-                          uint32_t *d_clen, uint8_t *d_payload, uint64_t *d_total, hipStream_t s);
+void trc_launch_ans4s_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
 void trc_launch_ans4s_dec(const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                           const TrcWork &w, uint8_t *d_out, hipStream_t s);
 

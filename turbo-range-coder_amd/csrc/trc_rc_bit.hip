@@ -21,13 +21,7 @@
 //   decoder  the path depends on the decoded bits; both children of the current node are requested before the bit is
 //            resolved, the bit is the borrow of code - cut and everything that depends on it a bit-select under the mask made
 //            from it -- one hand-written block per bit (the compiler turns the C form back into v_cndmask on an SGPR pair).
-// Round 4: the encoder is a model wave + a coder wave per 64 chunks (trc_rcb_enc_mc_kernel, the default).
-// Round 3, ENCODER only: the deepest tree level (nodes 128..255: half of the model) lives in global memory, one 256-byte row per
-// lane, filled by the wave itself at its start -- 16 KiB of model per wave in LDS instead of 32: nine waves per CU where five fit,
-// i.e. more than two per SIMD, which is what fills the issue gaps of a one-wave-per-SIMD kernel (round 2's half-model ablation:
-// 1.4x).  The encoder knows a byte's level-7 node when it has the byte, so the 2-byte load is issued with the LDS reads and is
-// back long before the last bit is coded; the decoder learns that node only from the seventh bit it has just decoded, a memory
-// round trip on its critical path per byte, and keeps the whole model in LDS.  Measured: it buys residency, not throughput (the launch code says when it is used).
+// The encoder is a model wave + a coder wave per 64 chunks (trc_rcb_enc_mc_kernel, round 4).
 #include <stdlib.h>
 #include "trc_rc.h"
 #include "trc_nibmodel.h"
@@ -38,7 +32,6 @@
 #define RCB_MODEL_BYTES (256u * 64u * 2u)                  // [ctx][lane] u16
 #define RCB_AMASK 0x7fffu
 #define RCB_WAVE_LDS    RCB_MODEL_BYTES
-#define RCB_ENC_WAVE_LDS(L7G) ((L7G) ? RCB_MODEL_BYTES / 2u : RCB_MODEL_BYTES)
 
 // (a & m) | (b & ~m) as the one instruction it is (from the C form the compiler builds and / and-or pairs, or compares and selects)
 __device__ __forceinline__ u32 rcb_bfi(u32 m, u32 a, u32 b)
@@ -46,183 +39,6 @@ __device__ __forceinline__ u32 rcb_bfi(u32 m, u32 a, u32 b)
     u32 r;
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
     return r;
-}
-__device__ __forceinline__ u32 rcb_adapt(u32 p, u32 bit) { return (p - (((p - (bit << TRC_PROB_BITS)) >> 5) + bit)) & 0xffffu; }
-
-template <bool L7G>
-__global__ __launch_bounds__(64 * TRC_WPG) void trc_rcb_enc_kernel(
-    const u8 *__restrict__ in, u64 n, u32 chunk, u32 nchunks,
-    u8 *__restrict__ scratch, u32 stride, u8 *__restrict__ level7, u32 *__restrict__ clen, u32 *__restrict__ gsum)
-{
-    TRC_QUAD_PROLOGUE(RCB_ENC_WAVE_LDS(L7G));
-    u16 *mb = (u16 *)smem + lane;                              // mb[ctx * 64]
-    for (u32 i = 0; i < RCB_ENC_WAVE_LDS(L7G) / 128u; i++) mb[i * 64] = (u16)(TRC_PROB_ONE >> 1);
-    u16 *l7 = nullptr;
-    if constexpr (L7G) {
-    // this wave's level-7 rows: 64 lanes x 256 B, contiguous -- filled with coalesced 16-byte stores (lane l: bytes 16 l + 1024 i),
-    // then every lane works on its own row.  The loads below see these stores: same wave, the stores are waited for.
-    u8 *l7w = level7 + (u64)grp_ * (64u * 256u);
-    {
-        const u32 h = (TRC_PROB_ONE >> 1) | (TRC_PROB_ONE >> 1) << 16;
-#pragma unroll
-        for (u32 i = 0; i < 16u; i++) *(uint4 *)(l7w + lane * 16u + i * 1024u) = make_uint4(h, h, h, h);
-        __builtin_amdgcn_s_waitcnt(0x0f70);                    // vmcnt(0) (the compiler does not order the plain stores against the u16 loads of other lanes' bytes)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    }
-    l7 = (u16 *)(l7w + lane * 256u);                           // l7[node - 128]
-    }
-
-    WaveChunks wc;
-    wc.c0 = grp_ * 64u; wc.chunk = chunk; wc.nchunks = nchunks;
-    wc.lastlen = (u32)(n - (u64)(nchunks - 1) * chunk);
-    wc.rows = nchunks - wc.c0 < 64u ? nchunks - wc.c0 : 64u;
-    const bool alive = lane < wc.rows;
-    const u32 c = wc.c0 + lane;
-    const u32 len = alive ? wc.len_of(lane) : 0u;
-    const int lim = trc_rc_limit(len);
-
-    QuadIn qin; qin.base = in + (u64)wc.c0 * chunk;
-    LaneOutDirect so; so.start(scratch + (u64)c * stride);
-    // The coder state of rcbe_ (turborc_.h:417-421) as 32-bit halves: range = rhi:rlo, low = lhi:llo.  The reference finds a
-    // carry by comparing `low` with its value at the last renormalisation; here the carry-out of every `low +=` is ORed
-    // into a lane mask (`cy`, an SGPR pair: SALU work), which is the same event -- between two renormalisations `low`
-    // grows by less than the range it had at the first, so it wraps at most once.
-    u32 rlo = ~0u, rhi = ~0u, llo = 0, lhi = 0;
-    bool cy = false;
-    TrcCarry cw; cw.start();
-    bool ovf = alive && lim <= 0;
-    // `live`: this lane is still coding.  A lane that is not (dead lane, incompressible chunk, past the end of a short
-    // last chunk) keeps running the same arithmetic on its own registers and its own model column -- nothing of it is
-    // observable, because only live lanes emit words -- so the eight steps of a byte carry no per-lane predication at
-    // all.  A lane whose chunk ends before the wave's does (the input's last chunk) flushes at that byte boundary.
-    bool live = alive && !ovf;
-    u32 out_len = alive ? len : 0u;                            // raw until proven otherwise
-
-    // One byte = 4 x (renormalisation point + two bits), unrolled.  With one wave per SIMD (32 KiB of model per wave) the
-    // kernel's time is its instruction count -- scalar mask logic and branches included (profiles/r02_notes.md) -- so:
-    //  * everything that does not depend on the coder state is done for the whole byte up front: the eight nodes of the
-    //    byte's path ((0x100|x) >> (8-k)) are all different, so their probabilities are read in one batch, adapted two at
-    //    a time with packed 16-bit arithmetic (the update p -= ((p - (bit<<15)) >> 5) + bit keeps only 16 bits: in 16-bit
-    //    lanes the logical shift of the 32-bit form is an arithmetic one) and written back where they came from;
-    //  * a bit step is ~12 VALU operations: cut = (range >> 15) * p as alignbit / shift / 32x32->64 mad / 24-bit mad; bit
-    //    selects as and-or under sign masks of the bit (no VCC); low += (bit ? 0 : cut) keeping the carry-out;
-    //    range = bit ? cut : range - cut;
-    //  * a renormalisation point only SHIFTS the state and leaves behind (mask, word, carry) in registers of its own; the
-    //    emit logic (held-back word, carry, store) runs ONCE per byte for the one word a lane has at most -- a lane emits a
-    //    word every ~6 bytes.  Lanes with two or more words in one byte (>= 32 bits of range spent on <= 6 bits) are
-    //    found by one test per byte and served point by point behind a wave-uniform branch.
-    const u32 mcol = trc_lds_addr(smem) + lane * 2u;           // this lane's model column as an LDS byte address
-    auto put_byte = [&](u32 x) {
-        const u32 t = 0x100u | x;
-        u32 ad[8];
-        ad[0] = mcol + 128u;
-#pragma unroll
-        for (int k = 1; k < 8; k++) ad[k] = (((t >> (8 - k)) << 7) & RCB_AMASK) + mcol;
-        u32 pr[8];
-        u16 *g7 = l7 + ((t >> 1) & 127u);                      // (L7G) the byte's level-7 node
-        if constexpr (L7G) pr[7] = *g7; else pr[7] = trc_ldsr16(ad[7]);
-#pragma unroll
-        for (int k = 0; k < 7; k++) pr[k] = trc_ldsr16(ad[k]);
-        u32 P[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            P[j] = pr[2 * j] | pr[2 * j + 1] << 16;
-            const u32 B = __builtin_amdgcn_ubfe(x, 7 - 2 * j, 1) | __builtin_amdgcn_ubfe(x, 6 - 2 * j, 1) << 16;    // the pair's two bits, one per half
-            const trc_s2 pv = trc_as_s2(P[j]), bv = trc_as_s2(B);
-            const trc_s2 np = pv - (((pv - trc_as_s2(B << 15)) >> (trc_s2)5) + bv);
-            const u32 NP = trc_as_u32(np);
-            trc_ldsw16(ad[2 * j], NP);
-            if (L7G && j == 3) *g7 = (u16)(NP >> 16); else trc_ldsw16(ad[2 * j + 1], NP >> 16);
-        }
-        bool rnj[4], cyj[4];
-        u32 pwj[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            {                                                  // renorm before bits 7,5,3,1 only (_RCENORM2)
-                const bool rn = rhi == 0u;
-                rnj[j] = rn; cyj[j] = rn && cy; pwj[j] = lhi;
-                cy = cy && !rn;
-                lhi = rn ? llo : lhi; llo = rn ? 0u : llo;
-                rhi = rn ? rlo : rhi; rlo = rn ? 0u : rlo;
-            }
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int k = 2 * j + h;
-                const u32 prob = h ? P[j] >> 16 : P[j] & 0xffffu;
-                const u32 m = (u32)__builtin_amdgcn_sbfe((int)x, 7 - k, 1);        // bit 1: all ones
-                const u32 slo = __builtin_amdgcn_alignbit(rhi, rlo, TRC_PROB_BITS), shi = rhi >> TRC_PROB_BITS;
-                const u64 c64 = (u64)slo * prob;
-                const u32 clo = (u32)c64, chi = __umul24(shi, prob) + (u32)(c64 >> 32);    // shi < 2^17, prob < 2^16
-                u32 k1, k2;
-                llo = __builtin_addc(llo, rcb_bfi(m, 0u, clo), 0u, &k1);           // low += bit ? 0 : cut
-                lhi = __builtin_addc(lhi, rcb_bfi(m, 0u, chi), k1, &k2);
-                cy = cy || (k2 != 0u);
-                u32 b1, b2;
-                const u32 tlo = __builtin_subc(rlo, clo, 0u, &b1), thi = __builtin_subc(rhi, chi, b1, &b2);
-                rlo = rcb_bfi(m, clo, tlo); rhi = rcb_bfi(m, chi, thi);             // range = bit ? cut : range - cut
-            }
-        }
-        const bool two = (rnj[0] && (rnj[1] || rnj[2] || rnj[3])) || (rnj[1] && (rnj[2] || rnj[3])) || (rnj[2] && rnj[3]);
-        if (__ballot(two && live)) {                           // rare: some lane has several words in this byte
-#pragma unroll
-            for (int j = 0; j < 4; j++) cw.emit_if(so, rnj[j] && live, cyj[j], pwj[j]);
-        } else {
-            const bool pend = rnj[0] || rnj[1] || rnj[2] || rnj[3];
-            const bool pcy = cyj[0] || cyj[1] || cyj[2] || cyj[3];
-            const u32 pw = rnj[3] ? pwj[3] : rnj[2] ? pwj[2] : rnj[1] ? pwj[1] : pwj[0];
-            cw.emit_if(so, pend && live, pcy, pw);
-        }
-    };
-    // rceflush (turborc_.h:118-128) on the same state, then everything still held back
-    auto finish = [&]() {
-        u64 low = ((u64)lhi << 32) | llo;
-        u64 rg = ((u64)rhi << 32) | rlo;
-        bool c0 = cy;
-        if (rg < TRC_TOP32) { cw.emit(so, c0, (u32)(low >> 32)); low <<= 32; rg <<= 32; c0 = false; }
-        if (rg > ((u64)1 << 33)) {
-            const u64 nl = low + TRC_TOP32;
-            cw.emit(so, c0 || nl < low, (u32)(nl >> 32));
-        } else {
-            const u64 nl = low + 1;
-            cw.emit(so, c0 || nl < low, (u32)(nl >> 32));
-            cw.emit(so, false, (u32)nl);
-        }
-        cw.release(so);
-    };
-
-    const u32 S = chunk / TRC_SEG;
-    qin.issue(wc, 0);
-    for (u32 s = 0; s < S; s++) {
-        qin.commit();
-        if (s + 1 < S) qin.issue(wc, (s + 1) * TRC_SEG);
-        uint4 pc0 = qin.read(0), pc1 = qin.read(1), pc2 = qin.read(2), pc3 = qin.read(3);
-#pragma nounroll
-        for (u32 k = 0; k < 4; k++) {
-            uint4 v = pc0; pc0 = pc1; pc1 = pc2; pc2 = pc3;
-            if (!__ballot(live)) continue;
-            const u32 p0 = s * TRC_SEG + k * 16u;
-            const bool ends = __ballot(live && len - p0 < 16u) != 0;     // a short last chunk ends inside this piece (once per grid)
-#pragma nounroll
-            for (u32 d = 0; d < 4; d++) {
-                const u32 w = v.x; v.x = v.y; v.y = v.z; v.z = v.w;
-                const u32 q0 = p0 + d * 4u;
-#pragma nounroll
-                for (u32 i = 0; i < 4; i++) {
-                    if (ends && live && q0 + i == len) {       // decide and flush it at its byte boundary
-                        if ((int)(4u * cw.nwords) < lim) { finish(); out_len = so.wpos; }
-                        live = false;                          // (else: incompressible, out_len stays the raw length)
-                    }
-                    put_byte((w >> (8 * i)) & 255u);
-                }
-                ovf = ovf || (live && (int)(4u * cw.nwords) >= lim);           // OVERFLOW per dword, monotone
-                live = live && !ovf;
-            }
-        }
-    }
-    if (live) { finish(); out_len = so.wpos; }
-    if (alive) clen[c] = out_len;
-    const u32 gs = trc_wave_sum(out_len);
-    if (lane == 0) gsum[wc.c0 >> 6] = gs;
 }
 
 // ---- the encoder as TWO WAVES per 64 chunks (round 4; the scheme of trc_rca_enc_mc_kernel, trc_rc_adaptive.hip) --------
@@ -560,7 +376,7 @@ __global__ __launch_bounds__(64 * TRC_WPG) void trc_rcb_dec_kernel(
                 : [t5] "=&v"(t5), [t6] "=&v"(t6), [r5] "=&v"(r5), [r6] "=&v"(r6), [ch] "=&v"(ch), [tt] "=&v"(tt), [m] "=&v"(m), [np] "=&v"(np),
                   [an] "=&v"(an), [cn] "=&v"(cn), [sb] "=&s"(sb), [rlo] "+v"(rlo), [rhi] "+v"(rhi), [clo] "+v"(clo), [chi] "+v"(chi)
                 : [cl] "v"(cl), [hh] "v"(hh), [shi] "v"(shi), [p] "v"(p), [k5] "s"(0xffff8000u >> 5), [k128] "s"(128u), [c0] "v"(c0), [negm] "v"(negm) : "vcc");
-            trc_ldsw16(RCB_A(a), np);                          // rcb_adapt: p - (t5 + bit), 16 bits kept by the store
+            trc_ldsw16(RCB_A(a), np);                          // adapt: p - (t5 + bit), 16 bits kept by the store
             a = an; c0 = cn;                                   // child 2*ctx + bit (bit 7 of c0 is clear) and its children's row
             p = rcb_bfi(m, pr, pl);
         }
@@ -612,38 +428,12 @@ __global__ __launch_bounds__(64 * TRC_WPG) void trc_rcb_dec_kernel(
     if (!wc.prog) trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)wc.c0 * chunk, chunk, payload);
 }
 
-bool trc_rcb_dec_prog_ok() { return true; }
-bool trc_rcb_enc_gate_ok()
-{
-    const int env = getenv("TRC_RCB_L7G") ? atoi(getenv("TRC_RCB_L7G")) : -1, env_mc = getenv("TRC_RCB_MC") ? atoi(getenv("TRC_RCB_MC")) : -1;
-    return env_mc >= 0 ? env_mc != 0 : (env < 0);              // the model wave + coder wave form (the default) is the one that waits at the gate
-}
+// the model wave + coder wave form: four workgroups per CU
 void trc_launch_rcb_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
-    // Level 7 in global memory buys residency (9 waves per CU instead of 5), not throughput: its two scattered 2-byte accesses
-    // per byte and lane keep the texture-address unit as busy as the second wave per SIMD keeps the ALUs fed (100 MB, chunk 512:
-    // 1.68 -> 1.86-2.0 ms).  It pays where it saves a residency ROUND: more waves than 5 per CU hold, no more than 9 per CU
-    // hold (100 MB at chunk 1024: 1526 waves, 2.12 -> 1.30 ms).  TRC_RCB_L7G=0 / 1 force a form.
-    static const int env = getenv("TRC_RCB_L7G") ? atoi(getenv("TRC_RCB_L7G")) : -1;
-    static const int env_mc = getenv("TRC_RCB_MC") ? atoi(getenv("TRC_RCB_MC")) : -1;
-    const bool l7g = env >= 0 ? env != 0 : (w.ngroups > 5u * 256u && w.ngroups <= 9u * 256u);
-    // the two-wave form (model wave + coder wave): four workgroups per CU
-    const bool mc = env_mc >= 0 ? env_mc != 0 : (env < 0);
-    if (mc) {
-        TRC_RAISE_LDS_ONCE(trc_rcb_enc_mc_kernel, TRC_WPG * RCB_MC_LDS);
-        TRC_LAUNCH_TIMED(trc_rcb_enc_mc_kernel, TRC_QUAD_GRID(w.ngroups), dim3(128 * TRC_WPG), TRC_WPG * RCB_MC_LDS, s,
-                           d_in, (u64)n, chunk, w.nchunks, w.scratch, w.stride, d_clen, w.gsum, trc_gate_tls.flag, trc_gate_tls.part);
-        return;
-    }
-    if (l7g) {
-        TRC_RAISE_LDS_ONCE(trc_rcb_enc_kernel<true>, TRC_WPG * RCB_ENC_WAVE_LDS(true));
-        TRC_LAUNCH_TIMED(trc_rcb_enc_kernel<true>, TRC_QUAD_GRID(w.ngroups), dim3(64 * TRC_WPG), TRC_WPG * (RCB_ENC_WAVE_LDS(true)), s,
-                           d_in, (u64)n, chunk, w.nchunks, w.scratch, w.stride, w.scratch2, d_clen, w.gsum);
-    } else {
-        TRC_RAISE_LDS_ONCE(trc_rcb_enc_kernel<false>, TRC_WPG * RCB_ENC_WAVE_LDS(false));
-        TRC_LAUNCH_TIMED(trc_rcb_enc_kernel<false>, TRC_QUAD_GRID(w.ngroups), dim3(64 * TRC_WPG), TRC_WPG * (RCB_ENC_WAVE_LDS(false)), s,
-                           d_in, (u64)n, chunk, w.nchunks, w.scratch, w.stride, w.scratch2, d_clen, w.gsum);
-    }
+    TRC_RAISE_LDS_ONCE(trc_rcb_enc_mc_kernel, TRC_WPG * RCB_MC_LDS);
+    TRC_LAUNCH_TIMED(trc_rcb_enc_mc_kernel, TRC_QUAD_GRID(w.ngroups), dim3(128 * TRC_WPG), TRC_WPG * RCB_MC_LDS, s,
+                       d_in, (u64)n, chunk, w.nchunks, w.scratch, w.stride, d_clen, w.gsum, trc_gate_tls.flag, trc_gate_tls.part);
 }
 void trc_launch_rcb_dec(const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                         const TrcWork &w, uint8_t *d_out, hipStream_t s)

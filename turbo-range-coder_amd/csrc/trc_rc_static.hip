@@ -21,19 +21,10 @@
 // the segment base, a relocated 0, to every index); the kernels trap at entry if the dynamic segment does not start at 0
 #define RCS_LUT(t) ((u32)*(const trc_lds_u8 *)(uintptr_t)(t))
 
-#ifndef TRC_RCS_EXACT_Q
-#define TRC_RCS_EXACT_Q 0       // 1: every step through the exact quotient (rounds 2-4)
-#endif
 // one symbol of the 64-bit static range decoder against the look-ahead word w: symbol from the estimated quotient, verified against
 // its own bounds (RcDec::probe); the exact quotient only where some lane of the wave fails.  Returns the symbol, `rn` = renormalised.
 __device__ __forceinline__ u32 rcs_step(RcDec &d, const u32 *tab, u32 w, bool &rn)
 {
-#if TRC_RCS_EXACT_Q
-    const u32 x = RCS_LUT(d.quotient15());
-    const u32 t = tab[x];
-    rn = d.consume_w(true, t & 0xffffu, (t & 0xffffu) + (t >> 16), w);
-    return x;
-#else
     u32 x = RCS_LUT(d.estimate15());
     u32 t = tab[x];
     RcDec::Probe q = d.probe(t & 0xffffu, (t & 0xffffu) + (t >> 16));
@@ -44,7 +35,6 @@ __device__ __forceinline__ u32 rcs_step(RcDec &d, const u32 *tab, u32 w, bool &r
     }
     rn = d.commit(q, w);
     return x;
-#endif
 }
 template <int GEO> struct RcGeo;
 template <> struct RcGeo<0> { typedef RcEncV Enc; typedef RcDec Dec; };      // (RcEncV: the state on 32-bit halves with a carry limb, trc_rc.h)
@@ -506,9 +496,19 @@ __global__ __launch_bounds__(896) void trc_rcs2p_dec_kernel(
 }
 
 // ------------------------------------------------------------------------------------- launch ---
-// TRC_RCS2_PAIR=0: the one-lane-per-chunk form of the two-stream coder (rounds 1-2), kept for A/B measurements
-static bool rcs2_pair() { static const bool on = !(getenv("TRC_RCS2_PAIR") && atoi(getenv("TRC_RCS2_PAIR")) == 0); return on; }
-
+// the one-stream coders (GEO 0: RCS, GEO 1: RCSM)
+template <int GEO>
+static void launch_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, const u32 *tab, bool big,
+                       uint32_t *d_clen, hipStream_t s)
+{
+    if (big) {
+        TRC_RAISE_LDS_ONCE((trc_rcs_enc_kernel<1, GEO, 12>), RCS_ENC_FIXED + 12 * RCS_WAVE_LDS(1));
+        TRC_LAUNCH_TIMED((trc_rcs_enc_kernel<1, GEO, 12>), dim3((w.ngroups + 11u) / 12u), dim3(64 * 12), RCS_ENC_FIXED + 12 * RCS_WAVE_LDS(1), s,
+                           d_in, (u64)n, chunk, w.nchunks, tab, w.scratch, w.stride, w.scratch, w.stride, d_clen, w.gsum);
+    } else
+        TRC_LAUNCH_TIMED((trc_rcs_enc_kernel<1, GEO, 1>), dim3(w.ngroups), dim3(64), RCS_ENC_FIXED + RCS_WAVE_LDS(1), s,
+                           d_in, (u64)n, chunk, w.nchunks, tab, w.scratch, w.stride, w.scratch, w.stride, d_clen, w.gsum);
+}
 void trc_launch_rcs_enc(int nstreams, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w,
                         uint32_t *d_clen, hipStream_t s)
 {
@@ -516,19 +516,8 @@ void trc_launch_rcs_enc(int nstreams, const uint8_t *d_in, size_t n, uint32_t ch
     // one residency round (at most twelve waves per CU): workgroups of twelve waves that keep each other's pace (TrcPace)
     static const int env_wpb = getenv("TRC_RCS_ENC_WPB") ? atoi(getenv("TRC_RCS_ENC_WPB")) : 0;      // tuning aid: 1 / 12 force the form
     const bool big = env_wpb ? env_wpb == 12 : (w.ngroups >= 2048u && w.ngroups <= 12u * 256u);
-#define RCS_ENC_LAUNCH(NS, GEO, SB, STB)                                                                                             \
-    do {                                                                                                                             \
-        if (big) {                                                                                                                   \
-            TRC_RAISE_LDS_ONCE((trc_rcs_enc_kernel<NS, GEO, 12>), RCS_ENC_FIXED + 12 * RCS_WAVE_LDS(NS));                            \
-            TRC_LAUNCH_TIMED((trc_rcs_enc_kernel<NS, GEO, 12>), dim3((w.ngroups + 11u) / 12u), dim3(64 * 12), RCS_ENC_FIXED + 12 * RCS_WAVE_LDS(NS), s, \
-                               d_in, (u64)n, chunk, w.nchunks, tab, w.scratch, w.stride, SB, STB, d_clen, w.gsum);                   \
-        } else                                                                                                                       \
-            TRC_LAUNCH_TIMED((trc_rcs_enc_kernel<NS, GEO, 1>), dim3(w.ngroups), dim3(64), RCS_ENC_FIXED + RCS_WAVE_LDS(NS), s,       \
-                               d_in, (u64)n, chunk, w.nchunks, tab, w.scratch, w.stride, SB, STB, d_clen, w.gsum);                   \
-    } while (0)
-    if (nstreams == 1) RCS_ENC_LAUNCH(1, 0, w.scratch, w.stride);
-    else if (nstreams == 2 && rcs2_pair())
-    {
+    if (nstreams == 1) launch_enc<0>(d_in, n, chunk, w, tab, big, d_clen, s);
+    else if (nstreams == 2) {
         // (a group of 64 chunks is two waves here: 2 x ngroups waves in the launch)
         const bool big2 = env_wpb ? env_wpb == 12 : (w.ngroups >= 1024u && w.ngroups <= 6u * 256u);
         if (big2) {
@@ -539,33 +528,28 @@ void trc_launch_rcs_enc(int nstreams, const uint8_t *d_in, size_t n, uint32_t ch
             TRC_LAUNCH_TIMED(trc_rcs2p_enc_kernel<1>, dim3(w.ngroups), dim3(128), 1024 + 128 + 2 * RCS_WAVE_LDS(1), s,
                                d_in, (u64)n, chunk, w.nchunks, tab, w.scratch, w.stride, w.scratch2, w.stride2, d_clen, w.gsum);
     }
-    else if (nstreams == 2) {
-        const bool big2 = false;                               // (two rings per wave: six waves per workgroup would fit; not measured)
-        (void)big2;
-        TRC_LAUNCH_TIMED((trc_rcs_enc_kernel<2, 0, 1>), dim3(w.ngroups), dim3(64), RCS_ENC_FIXED + RCS_WAVE_LDS(2), s,
-                           d_in, (u64)n, chunk, w.nchunks, tab, w.scratch, w.stride, w.scratch2, w.stride2, d_clen, w.gsum);
-    } else RCS_ENC_LAUNCH(1, 1, w.scratch, w.stride);          // nstreams == -1: one stream, 32-bit range / 16-bit words (RCSM)
-#undef RCS_ENC_LAUNCH
+    else launch_enc<1>(d_in, n, chunk, w, tab, big, d_clen, s);          // nstreams == -1: one stream, 32-bit range / 16-bit words (RCSM)
+
 }
 
-template <int NS, int GEO>
+template <int GEO>
 static void launch_dec(const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                        const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    const u32 maxw = NS == 1 ? 14u : 7u;                       // 34 KiB tables + waves x (NS rings) must fit 160 KiB
-    TRC_RAISE_LDS_ONCE((trc_rcs_dec_kernel<NS, GEO>), RCS_DEC_FIXED + maxw * RCS_WAVE_LDS(NS));
+    const u32 maxw = 14u;                                      // 34 KiB tables + waves x one ring must fit 160 KiB
+    TRC_RAISE_LDS_ONCE((trc_rcs_dec_kernel<1, GEO>), RCS_DEC_FIXED + maxw * RCS_WAVE_LDS(1));
     u32 wpb = (w.ngroups + 255u) / 256u;                       // just enough waves per workgroup to give every CU one
     wpb = wpb < 1u ? 1u : wpb > maxw ? maxw : wpb;
-    const size_t sm = RCS_DEC_FIXED + wpb * RCS_WAVE_LDS(NS);
-    TRC_LAUNCH_TIMED((trc_rcs_dec_kernel<NS, GEO>), dim3((w.ngroups + wpb - 1) / wpb), dim3(64 * wpb), sm, s,
+    const size_t sm = RCS_DEC_FIXED + wpb * RCS_WAVE_LDS(1);
+    TRC_LAUNCH_TIMED((trc_rcs_dec_kernel<1, GEO>), dim3((w.ngroups + wpb - 1) / wpb), dim3(64 * wpb), sm, s,
                        d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.tables + TRC_TAB_LUT,
                        (const u32 *)(w.tables + TRC_TAB_DEC), d_out);
 }
 void trc_launch_rcs_dec(int nstreams, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                         const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    if (nstreams == 1)      launch_dec<1, 0>(d_payload, d_clen, n, chunk, w, d_out, s);
-    else if (nstreams == 2 && rcs2_pair()) {
+    if (nstreams == 1)      launch_dec<0>(d_payload, d_clen, n, chunk, w, d_out, s);
+    else if (nstreams == 2) {
         const u32 nwaves = (w.nchunks + 31u) / 32u;
         TRC_RAISE_LDS_ONCE(trc_rcs2p_dec_kernel, RCS_DEC_FIXED + 14u * RCS_WAVE_LDS(1));
         u32 wpb = (nwaves + 255u) / 256u;
@@ -574,6 +558,5 @@ void trc_launch_rcs_dec(int nstreams, const uint8_t *d_payload, const uint32_t *
                            d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, w.tables + TRC_TAB_LUT,
                            (const u32 *)(w.tables + TRC_TAB_DEC), d_out);
     }
-    else if (nstreams == 2) launch_dec<2, 0>(d_payload, d_clen, n, chunk, w, d_out, s);
-    else                    launch_dec<1, 1>(d_payload, d_clen, n, chunk, w, d_out, s);
+    else                    launch_dec<1>(d_payload, d_clen, n, chunk, w, d_out, s);
 }
