@@ -8,8 +8,8 @@
  * The timed calls take HOST pointers, so these numbers include PCIe both ways; the
  * device-resident numbers come from bench.py.
  *
- *   trcbench [-e id[,id..]] [-I runs] [-c chunk] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N)
- * ids: 1 rcs | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
+ *   trcbench [-e id[,id..]] [-I runs] [-c chunk] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)
+ * ids: 1 rcs | 2 rccs | 4 rcxs | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
  */
 #include <math.h>
 #include <stdio.h>
@@ -36,6 +36,20 @@ static unsigned long long sm64(unsigned long long *s)
 static void gen(unsigned char *p, size_t n, int kind)
 {
     unsigned long long s = 12345;
+    if (kind == 5) {                                   /* order-1 source: x = 77 x + perm[Zipf(1.3) rank] mod 256 -- every previous
+                                                          byte has its own skewed distribution, order 0 sees ~uniform bytes */
+        double cum[256], tot = 0;
+        for (int i = 0; i < 256; i++) { tot += 1.0 / pow(i + 1.0, 1.3); cum[i] = tot; }
+        unsigned x = 0;
+        for (size_t k = 0; k < n; k++) {
+            double u = (double)(sm64(&s) >> 11) * (1.0 / 9007199254740992.0) * tot;
+            int lo = 0, hi = 255;
+            while (lo < hi) { int mid = (lo + hi) >> 1; if (cum[mid] <= u) lo = mid + 1; else hi = mid; }
+            x = (77u * x + ((unsigned)lo * 173u + 29u)) & 255u;
+            p[k] = (unsigned char)x;
+        }
+        return;
+    }
     if (kind == 4) {                                   /* slow random walk of 16/32-bit integers (N bytes) */
         unsigned v = 1u << (8 * g_elem - 2);
         for (size_t k = 0; k + g_elem <= n; k += g_elem) {
@@ -98,6 +112,8 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
     }
     if (!e3) switch (id) {
     case 1:  name = "rc o0 (rcsenc/rcsdec)"; e3 = rcsenc; d3 = rcsdec; break;
+    case 2:  name = "rc o1 (rccsenc/rccsdec)"; e3 = rccsenc; d3 = rccsdec; break;
+    case 4:  name = "rc o1 sliding context (rcxsenc/rcxsdec)"; e3 = rcxsenc; d3 = rcxsdec; break;
     case 42: name = "cdfsb (rccdfsenc/rccdfsbdec)"; e5 = rccdfsenc; d5 = rccdfsbdec; break;
     case 43: name = "cdfsv (rccdfsenc/rccdfsvbdec)"; e5 = rccdfsenc; d5 = rccdfsvbdec; break;
     case 44: name = "cdfsm 32-bit range (rccdfsmenc/rccdfsmbdec)"; e5 = rccdfsmenc; d5 = rccdfsmbdec; break;
@@ -159,6 +175,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--nibble") && i + 1 < argc) { kind = 3; n = strtoull(argv[++i], 0, 10); }
         else if (!strcmp(argv[i], "--int16") && i + 1 < argc) { kind = 4; g_elem = 2; n = strtoull(argv[++i], 0, 10) & ~(size_t)1; }
         else if (!strcmp(argv[i], "--int32") && i + 1 < argc) { kind = 4; g_elem = 4; n = strtoull(argv[++i], 0, 10) & ~(size_t)3; }
+        else if (!strcmp(argv[i], "--markov") && i + 1 < argc) { kind = 5; n = strtoull(argv[++i], 0, 10); }
         else file = argv[i];
     }
     if (file) {
@@ -176,7 +193,7 @@ int main(int argc, char **argv)
         for (char *t = strtok_r(s, ",", &sv); t; t = strtok_r(0, ",", &sv)) bad |= bench(in, n, out, cpy, atoi(t), runs);
         return bad;
     }
-    if (kind < 0 || !n) { fprintf(stderr, "usage: trcbench [-e ids] [-I runs] [-c chunk] [--pin] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N)\n"); return 2; }
+    if (kind < 0 || !n) { fprintf(stderr, "usage: trcbench [-e ids] [-I runs] [-c chunk] [--pin] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)\n"); return 2; }
     unsigned char *in = malloc(n * 4 / 3 + 1024), *out = malloc(n * 4 / 3 + 1024), *cpy = malloc(n * 4 / 3 + 1024);
     gen(in, n, kind);
     if (pin && (trc_host_pin(in, n * 4 / 3 + 1024) || trc_host_pin(out, n * 4 / 3 + 1024) || trc_host_pin(cpy, n * 4 / 3 + 1024))) { fprintf(stderr, "--pin: %s\n", trc_last_error()); return 2; }

@@ -7,8 +7,9 @@
  * File = "TRCF" | u8 id | u8 cdfnum-1 | u16 0 | u64 raw length | u64 stored length | [cdf: (cdfnum+1) x u16, static coders]
  *        | stored bytes (the library's TRC1 container, or the raw input when it does not compress: the reference's
  *        "returned length == input length means stored" convention, include/turborc.h:46-59).
- *   trcfile C <in> <out> [bsize]  compress to the REFERENCE's file format (codec 1 = rcsenc per block; see below)
- *   trcfile D <in> <out>          decompress a reference-format file of codec 1 / predictor "s" with blocks <= 65536
+ *   trcfile C <in> <out> [bsize [fc]]  compress to the REFERENCE's file format, file codec fc = 1 (rcsenc per block, the
+ *                                      default), 2 (rccsenc) or 4 (rcxsenc); see below
+ *   trcfile D <in> <out>          decompress a reference-format file of codec 1, 2 or 4 / predictor "s" with blocks <= 65536
  * The reference's own file mode (hd_t / hdb_t, turborc.c:666-733,1044-1167) codes every block as one serial stream; with
  * blocks that are legal chunk sizes a block IS a chunk, and the two tools read each other's files (C / D below). */
 #include <stdint.h>
@@ -24,11 +25,24 @@ typedef size_t (*fn5)(unsigned char *, size_t, unsigned char *, cdf_t *, unsigne
 static size_t e65(unsigned char *i, size_t n, unsigned char *o, cdf_t *c, unsigned m) { (void)m; return anscdf4senc(i, n, o, c); }
 static size_t d65(unsigned char *i, size_t n, unsigned char *o, cdf_t *c, unsigned m) { (void)m; return anscdf4sdec(i, n, o, c); }
 
+/* the reference's file codecs with a GPU coder: 1 rcsenc, 2 rccsenc, 4 rcxsenc (turborc.c:1054-1057) -> container codec, decoder */
+static int file_codec(unsigned fc, fn3 *dec)
+{
+    switch (fc) {
+    case 1: *dec = rcsdec; return TRC_RCB;
+    case 2: *dec = rccsdec; return TRC_RCC1;
+    case 4: *dec = rcxsdec; return TRC_RCX1;
+    }
+    return 0;
+}
+
 static int pick(int id, fn3 *e3, fn3 *d3, fn5 *e5, fn5 *d5)
 {
     *e3 = *d3 = 0; *e5 = *d5 = 0;
     switch (id) {
     case 1:  *e3 = rcsenc; *d3 = rcsdec; return 0;
+    case 2:  *e3 = rccsenc; *d3 = rccsdec; return 0;
+    case 4:  *e3 = rcxsenc; *d3 = rcxsdec; return 0;
     case 46: *e3 = rccdfenc; *d3 = rccdfdec; return 0;
     case 47: *e3 = rccdfienc; *d3 = rccdfidec; return 0;
     case 56: *e3 = anscdfenc; *d3 = anscdfdec; return 0;
@@ -122,8 +136,12 @@ int main(int argc, char **argv)
      * per-chunk payload equals rcsenc(block) bit for bit, so files written by `trcfile C` are read by the reference's
      * `turborc -d`, and `trcfile D` reads what `turborc -1 -b65536B` wrote -- every block of the file coded or decoded by
      * one launch. */
-    if ((argc == 4 || argc == 5) && !strcmp(argv[1], "C")) {
-        const unsigned bsize = argc == 5 ? (unsigned)strtoul(argv[4], 0, 10) : 65536u;
+    if ((argc >= 4 && argc <= 6) && !strcmp(argv[1], "C")) {
+        const unsigned bsize = argc >= 5 ? (unsigned)strtoul(argv[4], 0, 10) : 65536u;
+        const unsigned fc = argc == 6 ? (unsigned)strtoul(argv[5], 0, 10) : 1u;
+        fn3 dec;
+        const int codec = file_codec(fc, &dec);
+        if (!codec) { fprintf(stderr, "file codec %u: only 1 (rcs), 2 (rccs) and 4 (rcxs) are on the GPU path\n", fc); return 2; }
         size_t n;
         if (trc_set_chunk(bsize)) { fprintf(stderr, "block size must be a legal chunk size: %s\n", trc_last_error()); return 2; }
         unsigned char *in = slurp(argv[2], &n);
@@ -133,12 +151,12 @@ int main(int argc, char **argv)
         if (!out) { perror("malloc"); return 2; }
         /* the container is wanted whatever its size: a 70-byte file is one coded block of 60 bytes for the reference, while
          * the reference-named call would hand back "raw" because 32 + 4 + 60 > 70 */
-        size_t l = n ? trc_encode_host(TRC_RCB, in, n, bsize, out, cap, 0, 0) : 0;
+        size_t l = n ? trc_encode_host(codec, in, n, bsize, out, cap, 0, 0) : 0;
         if (n && !l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
         l = n + 1;                                             /* (never the "whole call raw" case below) */
         FILE *f = fopen(argv[3], "wb");
         if (!f) { perror(argv[3]); return 2; }
-        const uint32_t u32 = 1u << 12 | 0x154u | (bsize < 4096u ? bsize << 20 : 0u);
+        const uint32_t u32 = fc << 12 | 0x154u | (bsize < 4096u ? bsize << 20 : 0u);
         const uint16_t u16 = 8u << 10 | 6u << 6 | 5u << 2 | 0u;      /* lev 8, prm2 6, prm1 5 (the reference's defaults), predictor "s" */
         fwrite(&u32, 4, 1, f);
         if (bsize >= 4096u) fwrite(&bsize, 4, 1, f);
@@ -166,7 +184,9 @@ int main(int argc, char **argv)
         if (fl < 6) { fprintf(stderr, "not a TurboRC file\n"); return 2; }
         uint32_t u32; memcpy(&u32, fb, 4);
         size_t pos = 4;
-        if ((u32 & 0xfffu) != 0x154u || ((u32 >> 12) & 0xffu) != 1u) { fprintf(stderr, "not a TurboRC file of codec 1\n"); return 2; }
+        fn3 dec;
+        const int codec = file_codec((u32 >> 12) & 0xffu, &dec);
+        if ((u32 & 0xfffu) != 0x154u || !codec) { fprintf(stderr, "not a TurboRC file of codec 1, 2 or 4\n"); return 2; }
         uint32_t bsize = u32 >> 20;
         if (!bsize) { if (fl < 10) return 2; memcpy(&bsize, fb + 4, 4); pos = 8; }
         uint16_t u16; memcpy(&u16, fb + pos, 2); pos += 2;
@@ -189,7 +209,7 @@ int main(int argc, char **argv)
         unsigned char *cont = malloc(32 + 4 * nblk + paybytes + 1024), *out = malloc(n + 1024);
         if (!cont || !out) { perror("malloc"); return 2; }
         trc_container_hdr hdr; memset(&hdr, 0, sizeof hdr);
-        hdr.magic = TRC_MAGIC; hdr.codec = TRC_RCB; hdr.version = 1; hdr.chunk = bsize; hdr.nchunks = (uint32_t)nblk; hdr.n = n; hdr.payload = paybytes;
+        hdr.magic = TRC_MAGIC; hdr.codec = (uint8_t)codec; hdr.version = 1; hdr.chunk = bsize; hdr.nchunks = (uint32_t)nblk; hdr.n = n; hdr.payload = paybytes;
         memcpy(cont, &hdr, 32);
         unsigned char *dirp = cont + 32, *payp = cont + 32 + 4 * nblk;
         p = pos;
@@ -202,7 +222,7 @@ int main(int argc, char **argv)
         }
         if (n) {
             if (allraw) memcpy(out, cont + 32 + 4 * nblk, n);                 /* nothing coded: stored blocks */
-            else if (trc_container_check(cont, 32 + 4 * nblk + paybytes, TRC_RCB, n) || rcsdec(cont, n, out) != n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            else if (trc_container_check(cont, 32 + 4 * nblk + paybytes, codec, n) || dec(cont, n, out) != n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
         }
         FILE *f = fopen(argv[3], "wb");
         if (!f) { perror(argv[3]); return 2; }
@@ -210,6 +230,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> | trcfile d <in> <out> | trcfile C <in> <out> [bsize] | trcfile D <in> <out>   (C/D: the reference's file format, codec 1)\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> | trcfile d <in> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
     return 2;
 }

@@ -67,7 +67,10 @@ enum trc_codec {
     TRC_VLAV32 = 24,  TRC_VLAVZ32 = 25,  /* anscdfvenc32 / anscdfvzenc32 (+dec) */
     /* "vnibble" coders: a byte becomes 1-3 CDF16 symbols on three adaptive tables (rccdf.c:326-390, rccdf_.h:76-98) */
     TRC_RCV8 = 26,    /* rccdfenc8  / rccdfdec8    one stream    (-e48) */
-    TRC_RCVI8 = 27    /* rccdfienc8 / rccdfidec8   two streams   (-e49) */
+    TRC_RCVI8 = 27,   /* rccdfienc8 / rccdfidec8   two streams   (-e49) */
+    /* bitwise order-1 range coders, "s" predictor (rc_s.c); a model per chunk in the workspace: chunks of 16 KiB and more */
+    TRC_RCC1 = 28,    /* rccsenc    / rccsdec      context = previous byte, 128 KiB model   rc_.c:186-209 (-e2) */
+    TRC_RCX1 = 29     /* rcxsenc    / rcxsdec      sliding 8-bit context, 64 KiB model      rc_.c:372-400 (-e4) */
 };
 
 #define TRC_MAGIC        0x31435254u   /* "TRC1" */
@@ -77,6 +80,7 @@ enum trc_codec {
                                           163 GB/s), 1024 six (449 GB/s), 512 twelve (590 GB/s); payload ratio on text 63.50 / 63.94 /
                                           64.52 %.  Gigabyte inputs fill the chip at 4096 too, so host-pointer calls pick the size from
                                           the input length (trc_auto_chunk) unless the caller fixes it. */
+#define TRC_O1BIT_CHUNK_MIN 16384u     /* TRC_RCC1 / TRC_RCX1: the smallest chunk the automatic rules and the host-pointer calls use */
 #define TRC_ANSB_CHUNK_MAX 8192u       /* TRC_ANSB only: one 8192-byte block of the reference per chunk */
 #define TRC_PAD          256u          /* readable slack the device entry points need after every buffer */
 
@@ -107,7 +111,8 @@ int trc_device_count(void);
  * the adaptive coders, a model that starts from scratch.  100 MB: 4096 for the static and the adaptive byte coders, 2048
  * for the bitwise ones; 1 GB: 16 384 (rccdfenc on drift: 26.9 % stored against 26.7 % for one whole-buffer call of the
  * reference; at chunk 512 it was 38.7 %).  Static coders stop at 4096, the bitwise rANS at one reference block (8192), the
- * order-1 rANS never goes below 4096.  trc_set_chunk(c) or TRC_CHUNK=c in the environment fix it; trc_set_chunk(0)
+ * order-1 rANS never goes below 4096, the bitwise order-1 coders (TRC_RCC1 / TRC_RCX1) never below TRC_O1BIT_CHUNK_MIN:
+ * their model starts cold in every chunk, and below ~16 KiB they store more than the order-0 rcsenc.  trc_set_chunk(c) or TRC_CHUNK=c in the environment fix it; trc_set_chunk(0)
  * returns to automatic.  Decoders take the size from the container. */
 int      trc_set_chunk(uint32_t chunk);
 uint32_t trc_get_chunk(void);

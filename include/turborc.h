@@ -9,6 +9,8 @@
  *   rccdfs2enc / rccdfs{l,b}2dec   include/turborc.h:508-510         (rccdf.c:125-184)
  *   rccdfenc / rccdfdec            include/turborc.h:513-514         (rccdf.c:187-211)
  *   rcsenc / rcsdec                include/turborc.h:62-63           (rc_.c:37-58)
+ *   rccsenc / rccsdec              include/turborc.h:65-66           (rc_.c:186-209)
+ *   rcxsenc / rcxsdec              include/turborc.h:71-72           (rc_.c:372-400)
  *
  * Calling convention (reference include/turborc.h:46-59), unchanged:
  *   encoders: `out` holds at least inlen bytes (+ the harness's usual slack); the return value is
@@ -90,6 +92,13 @@ size_t rccdfienc8(unsigned char *src, size_t srclen, unsigned char *dst);    siz
 /* bitwise order-0 range coder, "s" predictor (reference rc_.c:37-58; `turborc -e1`, file codec 1) */
 size_t rcsenc(unsigned char *src, size_t srclen, unsigned char *dst);
 size_t rcsdec(unsigned char *src, size_t dstlen, unsigned char *dst);
+
+/* bitwise order-1 range coders, "s" predictor: context = the previous byte (reference rc_.c:186-209; `turborc -e2`, file
+ * codec 2) and a sliding 8-bit context (rc_.c:372-400, mb_on.h; `turborc -e4`, file codec 4).  Chunks of 16 KiB and more. */
+size_t rccsenc(unsigned char *src, size_t srclen, unsigned char *dst);
+size_t rccsdec(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcxsenc(unsigned char *src, size_t srclen, unsigned char *dst);
+size_t rcxsdec(unsigned char *src, size_t dstlen, unsigned char *dst);
 
 #ifdef __cplusplus
 }

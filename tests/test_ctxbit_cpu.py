@@ -1,0 +1,170 @@
+"""CPU (no GPU): the bitwise order-1 range coders rccs / rcxs (TRC_RCC1 = 28 / TRC_RCX1 = 29) at the library's boundary --
+exported symbols, ids accepted by the no-device calls, the chunk floor, the committed fixtures against the reference, and the
+plain-C harnesses compiling against the headers."""
+import ctypes
+import hashlib
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import ctxbit_lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "turbo-range-coder_amd", "libturborc_hip.so")
+GOLD = os.path.join(ROOT, "tests", "golden")
+MB, GB = 10**6, 1 << 30
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(LIB):
+        import __graft_entry__ as g
+        g.build()
+    lib = ctypes.CDLL(LIB)
+    lib.trc_work_bytes.restype = ctypes.c_size_t
+    lib.trc_work_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32]
+    lib.trc_auto_chunk_codec.restype = ctypes.c_uint32
+    lib.trc_auto_chunk_codec.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    lib.trc_round_chunk.restype = ctypes.c_uint32
+    lib.trc_round_chunk.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    lib.trc_host_plan.restype = ctypes.c_int
+    lib.trc_host_plan.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
+    return lib
+
+
+def test_symbols_exported(lib):
+    for name in ("rccsenc", "rccsdec", "rcxsenc", "rcxsdec"):
+        assert hasattr(lib, name), name
+    hdr = open(os.path.join(ROOT, "include", "turborc.h")).read()
+    for name in ("rccsenc", "rccsdec", "rcxsenc", "rcxsdec"):
+        assert re.search(r"size_t %s\(unsigned char \*src, size_t \w+, unsigned char \*dst\);" % name, hdr), name
+
+
+def test_codec_ids_in_header():
+    hdr = open(os.path.join(ROOT, "include", "trc_hip.h")).read()
+    assert re.search(r"TRC_RCC1 = 28\b", hdr) and re.search(r"TRC_RCX1 = 29\b", hdr)
+    m = re.search(r"#define TRC_O1BIT_CHUNK_MIN\s+(\d+)u", hdr)
+    assert m and int(m.group(1)) == L.ROUND_CHUNK
+
+
+def test_python_tables():
+    import trc
+    assert (trc.RCC1, trc.RCX1) == (L.RCC1, L.RCX1)
+    assert trc.CODEC_NAMES[trc.RCC1] == "rccs" and trc.CODEC_NAMES[trc.RCX1] == "rcxs"
+    assert trc._HOST_ENC[trc.RCC1] == "rccsenc" and trc._HOST_DEC[trc.RCX1] == "rcxsdec"
+    assert trc.RCC1 in trc.CTXBIT and trc.RCX1 in trc.CTXBIT
+
+
+@pytest.mark.parametrize("codec", [L.RCC1, L.RCX1], ids=lambda c: L.NAMES[c])
+def test_work_bytes_hold_the_models(lib, codec):
+    model = 256 * 17 * 32 if codec == L.RCC1 else 512 * 64 * 2
+    for n, chunk in [(1, 256), (100000, 16384), (100 * MB, 16384), (100 * MB, 65536)]:
+        w = lib.trc_work_bytes(codec, n, chunk)
+        nch = -(-n // chunk)
+        assert w >= nch * model + nch * (chunk + 128), (n, chunk, w)
+        assert w < lib.trc_work_bytes(6, n, chunk) + nch * model + (1 << 20)
+    assert lib.trc_work_bytes(codec, 1000, 100) == 0          # not a legal chunk
+
+
+@pytest.mark.parametrize("codec", [L.RCC1, L.RCX1], ids=lambda c: L.NAMES[c])
+def test_chunk_floor(lib, codec):
+    for n in (1, 4095, 70001, 100 * MB, GB, 8 * GB):
+        assert lib.trc_auto_chunk_codec(codec, n) >= L.ROUND_CHUNK, n
+        c = lib.trc_round_chunk(codec, n)
+        assert c >= L.ROUND_CHUNK and c % 64 == 0 and c <= 65536, n
+    assert lib.trc_round_chunk(codec, 100 * MB) == L.ROUND_CHUNK
+
+
+@pytest.mark.parametrize("codec", [L.RCC1, L.RCX1], ids=lambda c: L.NAMES[c])
+def test_host_plan_accepts_and_caps_models(lib, codec):
+    first = (ctypes.c_size_t * 4096)()
+    part = ctypes.c_uint32(0)
+    model = 256 * 17 * 32 if codec == L.RCC1 else 512 * 64 * 2
+    for n in (1, 16384, 70001, 100 * MB, GB):
+        for chunk in (0, 16384, 65536):
+            for decode in (0, 1):
+                nsl = lib.trc_host_plan(codec, n, chunk, decode, 1, first, 4096, ctypes.byref(part))
+                assert nsl >= 1, (n, chunk, decode)
+                ch = chunk or lib.trc_auto_chunk_codec(codec, n)
+                assert ch >= L.ROUND_CHUNK
+                f = np.array(first[:nsl + 1], dtype=np.int64)
+                assert f[0] == 0 and f[-1] == -(-n // ch) and np.all(np.diff(f) > 0) and np.all(f[:-1] % 64 == 0)
+                assert int(np.diff(f).max()) * model <= GB + 64 * model, "a slice's models stay near 1 GiB"
+                assert part.value == 0                         # no striping for these coders
+
+
+def test_fixture_inputs_regenerate():
+    """the fixtures store no inputs: the seeded generators must give the very bytes they were made from"""
+    z = np.load(os.path.join(GOLD, "ctxbit_vectors.npz"))
+    for e in json.loads(bytes(z["index"]).decode()):
+        d = L.gen(e["kind"], e["n"], e["seed"])
+        assert hashlib.sha256(d.tobytes()).hexdigest() == e["in_sha256"], (e["kind"], e["n"])
+
+
+def test_fixtures_match_reference():
+    if not L.have_ref():
+        pytest.skip("oracle/_ref/libtrc_ref.so absent")
+    z = np.load(os.path.join(GOLD, "ctxbit_vectors.npz"))
+    index = json.loads(bytes(z["index"]).decode())
+    assert {e["chunk"] for e in index} == {256, 1536, 4096, 16384, 65536}
+    assert {e["kind"] for e in index} == {"text", "markov", "runs", "uniform", "const", "binary"}
+    for e in index:
+        k = e["case"]
+        d = L.gen(e["kind"], e["n"], e["seed"])
+        for codec in (L.RCC1, L.RCX1):
+            clen, payload = L.ref_chunked_enc(codec, d, e["chunk"])
+            name = L.NAMES[codec]
+            assert np.array_equal(clen, z["clen_%d_%s" % (k, name)]) and np.array_equal(payload, z["out_%d_%s" % (k, name)]), (name, k)
+            if e["n"] <= 5000:                                 # the reference decodes its own chunks
+                off = 0
+                for i, c in enumerate(clen):
+                    ln = min(e["chunk"], e["n"] - i * e["chunk"])
+                    assert np.array_equal(L.ref_dec(codec, payload[off:off + int(c)], ln), d[i * e["chunk"]:i * e["chunk"] + ln])
+                    off += int(c)
+
+
+def test_large_fixture_one_chunk_sample():
+    """the 100 MB hashes are of the reference's chunked output: re-derive the first chunk's length for every entry"""
+    if not L.have_ref():
+        pytest.skip("oracle/_ref/libtrc_ref.so absent")
+    with open(os.path.join(GOLD, "ctxbit_large.json")) as f:
+        large = json.load(f)
+    assert {(e["codec"], e["kind"]) for e in large} == {(a, b) for a in ("rccs", "rcxs") for b in ("markov", "text")}
+    for e in large:
+        codec = L.RCC1 if e["codec"] == "rccs" else L.RCX1
+        d = L.gen(e["kind"], 4 * e["chunk"], e["seed"])
+        assert e["chunk"] == L.ROUND_CHUNK and e["payload_bytes"] < e["n"]
+        assert L.ref_enc(codec, d[:e["chunk"]]).size < e["chunk"]
+
+
+def test_markov_source_shape():
+    d = L.markov_bytes(1 << 20, 21)
+    h0 = np.bincount(d, minlength=256) / d.size
+    assert h0.max() < 0.01                                     # order 0 sees almost uniform bytes
+    pairs = np.bincount(d[:-1].astype(np.int64) * 256 + d[1:], minlength=65536).reshape(256, 256)
+    top = pairs.max(axis=1) / np.maximum(pairs.sum(axis=1), 1)
+    assert top.mean() > 0.2                                    # order 1 sees a skewed distribution per context
+    # the recurrence, stepped one byte at a time
+    r = L.T.zipf_bytes(4096, 1.3, 256, 21).astype(np.int64)
+    x, ref = 0, []
+    for i in range(4096):
+        x = (L.MK_MUL * x + int(L.MK_PERM[r[i]])) & 255
+        ref.append(x)
+    assert np.array_equal(np.array(ref, np.uint8), d[:4096])
+
+
+@pytest.mark.parametrize("tool", ["trcbench", "trcfile"])
+def test_harness_compiles_against_headers(lib, tool, tmp_path):
+    cc = os.environ.get("CC", "cc")
+    exe = tmp_path / tool
+    libdir = os.path.dirname(LIB)
+    r = subprocess.run([cc, "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "harness", tool + ".c"), "-o", str(exe),
+                        "-L" + libdir, "-lturborc_hip", "-lm", "-Wl,-rpath," + libdir], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    src = open(os.path.join(ROOT, "harness", tool + ".c")).read()
+    assert "rccsenc" in src and "rcxsenc" in src

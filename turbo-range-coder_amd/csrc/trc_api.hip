@@ -67,6 +67,7 @@ extern "C" int trc_device_count(void)
 static uint32_t g_chunk = 0;                                  // 0: not read yet;  ~0u: automatic
 static bool chunk_ok(uint32_t c) { return c >= TRC_CHUNK_MIN && c <= TRC_CHUNK_MAX && (c % 64u) == 0; }
 static inline bool is_static(int codec);
+static inline bool is_o1bit(int codec) { return codec == TRC_RCC1 || codec == TRC_RCX1; }
 // one wave's time per byte of its chunk, ns, the slower of encode and decode (profiles/r05_all_codecs.txt: kernel time at chunk
 // 4096 with the chip a third full / 4096)
 static double trc_wave_ns(int codec)
@@ -77,6 +78,7 @@ static double trc_wave_ns(int codec)
     case TRC_ANSA: return 336;  case TRC_ANSO1: return 884;
     case TRC_RCA4: return 245;  case TRC_RCAI4: return 260; case TRC_ANSA4: return 255;
     case TRC_RCV8: return 746;  case TRC_RCVI8: return 797;
+    case TRC_RCC1: return 2830; case TRC_RCX1: return 3310; // one lane per chunk, models in HBM: chunk 16384, markov (profiles/o1bit_notes.md)
     case TRC_VLCU16: case TRC_VLCV16: case TRC_VLCVZ16: return 391;
     case TRC_VLCU32: case TRC_VLCV32: case TRC_VLCVZ32: return 214;
     case TRC_VLAU16: case TRC_VLAV16: case TRC_VLAVZ16: return 370;
@@ -92,6 +94,7 @@ extern "C" uint32_t trc_auto_chunk_codec(int codec, size_t n)
     const double link_ns = 0.35 * (double)n / 50.0;               // 50 GB/s = 50 bytes per ns
     const double budget_ns = link_ns > 1.7e6 ? link_ns : 1.7e6;
     const uint32_t cap = is_static(codec) ? 4096u : codec == TRC_ANSB ? TRC_ANSB_CHUNK_MAX : TRC_AUTO_CHUNK_MAX;
+    if (is_o1bit(codec)) return TRC_O1BIT_CHUNK_MIN;        // the ratio floor: every larger chunk only waits longer
     const uint32_t lo = codec == TRC_ANSO1 ? 4096u : TRC_CHUNK_AUTO_MIN;
     for (uint32_t c : ladder)
         if (c <= cap && (c <= lo || trc_wave_ns(codec) * c <= budget_ns)) return c;
@@ -121,6 +124,7 @@ static size_t round_chunks(int codec)
 extern "C" uint32_t trc_round_chunk(int codec, size_t n)
 {
     if (codec == TRC_ANSO1) return 4096u;                     // (see trc_auto_chunk_codec)
+    if (is_o1bit(codec)) return TRC_O1BIT_CHUNK_MIN;          // one lane per chunk: the launch's time is one chunk's, so the floor
     const size_t rc = round_chunks(codec);
     const size_t cap = codec == TRC_ANSB ? TRC_ANSB_CHUNK_MAX : TRC_ROUND_CHUNK_MAX;
     for (size_t k = 1;; k++) {
@@ -152,7 +156,7 @@ extern "C" int trc_set_chunk(uint32_t chunk)
 #define TRC_INKERNEL_SCAN_MAX 8192u
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline bool is_static(int codec) { return codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM; }
-static inline bool codec_ok(int codec) { return codec >= TRC_ANS4S && codec <= TRC_RCVI8; }
+static inline bool codec_ok(int codec) { return codec >= TRC_ANS4S && codec <= TRC_RCX1; }
 static inline bool is_vlc(int codec) { return codec >= TRC_VLCU16 && codec <= TRC_VLCVZ32; }
 static inline int vlc_variant(int codec) { return (codec - TRC_VLCU16) >> 1; }      // 0 u, 1 v, 2 vz
 static inline int vlc_elem(int codec) { return ((codec - TRC_VLCU16) & 1) ? 4 : 2; }
@@ -177,6 +181,12 @@ static inline size_t scratch2_bytes(int codec, size_t nchunks, uint32_t chunk)
     return up256(rows * scratch2_stride(codec, chunk) + 256);
 }
 
+// the per-chunk model block of the order-1 coders (w.model)
+static inline size_t model_bytes(int codec)
+{
+    return codec == TRC_ANSO1 || codec == TRC_RCC1 ? TRC_O1_MODEL_BYTES : codec == TRC_RCX1 ? 512u * 64u * 2u : 0;
+}
+
 static uint32_t scratch_stride(int codec, uint32_t chunk)
 {
     (void)codec;
@@ -190,7 +200,7 @@ extern "C" size_t trc_work_bytes(int codec, size_t n, uint32_t chunk)
     const size_t nchunks = (n + chunk - 1) / chunk, ngroups = (nchunks + 63) / 64;
     return up256(TRC_TAB_BYTES) + up256(4 * ngroups) + up256(8 * (ngroups + 1)) +
            up256(nchunks * (size_t)scratch_stride(codec, chunk)) + scratch2_bytes(codec, nchunks, chunk) +
-           (codec == TRC_ANSO1 ? up256(nchunks * (size_t)TRC_O1_MODEL_BYTES) : 0) +
+           up256(nchunks * model_bytes(codec)) +
            ((codec >= TRC_VLCU16 && codec <= TRC_VLAVZ32) ? up256(nchunks * 8) : 0) + 4096;
 }
 
@@ -211,7 +221,7 @@ static int carve(int codec, size_t n, uint32_t chunk, void *d_work, size_t work_
     w.stride2 = (uint32_t)scratch2_stride(codec, chunk);
     w.scratch2 = p + up256(nchunks * (size_t)w.stride);
     w.model = w.scratch2 + scratch2_bytes(codec, nchunks, chunk);
-    w.aux = (uint32_t *)(w.model + (codec == TRC_ANSO1 ? up256(nchunks * (size_t)TRC_O1_MODEL_BYTES) : 0));
+    w.aux = (uint32_t *)(w.model + up256(nchunks * model_bytes(codec)));
     w.nchunks = (uint32_t)nchunks; w.ngroups = (uint32_t)ngroups;
     return TRC_OK;
 }
@@ -400,6 +410,8 @@ extern "C" int trc_encode_dev(int codec, const void *d_in, size_t n, uint32_t ch
     case TRC_ANSB:  trc_launch_ansb_enc((const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 1; break;
     case TRC_RCV8:  trc_launch_rcv_enc(1, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
     case TRC_RCVI8: trc_launch_rcv_enc(2, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 2; break;
+    case TRC_RCC1:  trc_launch_o1bit_enc(0, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
+    case TRC_RCX1:  trc_launch_o1bit_enc(1, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
     default:        if (is_vlc(codec)) { trc_launch_vlc_enc(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 3; }
                     else if (is_vla(codec)) { trc_launch_vla_enc(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 4; }
                     break;
@@ -457,6 +469,8 @@ extern "C" int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_p
     case TRC_ANSB:  trc_launch_ansb_dec((const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     case TRC_RCV8:  trc_launch_rcv_dec(1, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     case TRC_RCVI8: trc_launch_rcv_dec(2, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
+    case TRC_RCC1:  trc_launch_o1bit_dec(0, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
+    case TRC_RCX1:  trc_launch_o1bit_dec(1, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     default:        if (is_vlc(codec)) trc_launch_vlc_dec(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     else if (is_vla(codec)) trc_launch_vla_dec(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     break;
@@ -484,6 +498,7 @@ extern "C" const char *trc_kernel_name(int codec, int decode)
     case TRC_ANSO1: return decode ? "trc_o1_dec_rowsn_kernel" : "trc_o1_sort_kernel";
     case TRC_ANSB: return decode ? "trc_ansb_dec_kernel" : "trc_ansb_model_kernel";
     case TRC_RCV8: case TRC_RCVI8: return decode ? "trc_rcv_dec_kernel" : "trc_rcv_enc_kernel";
+    case TRC_RCC1: case TRC_RCX1: return decode ? "trc_rc_o1bit_dec_kernel" : "trc_rc_o1bit_enc_kernel";
     default: if (is_vlc(codec)) return decode ? "trc_vlc_dec_kernel" : "trc_vlc_enc_kernel";
              if (is_vla(codec)) return decode ? "trc_vla_dec_kernel" : "trc_vla_model_kernel";
     }
@@ -682,6 +697,12 @@ size_t rccdfsb2dec(unsigned char *in, size_t outlen, unsigned char *out, cdf_t *
 // bitwise order-0 range coder, "s" predictor (reference rc_.c:37-58; turborc -e1 / file codec 1)
 size_t rcsenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCB, in, inlen, out, nullptr, 0); }
 size_t rcsdec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(TRC_RCB, in, outlen, out, nullptr, 0); }
+
+// bitwise order-1 range coders, "s" predictor (reference rc_.c:186-209 and :372-400; turborc -e2 / -e4, file codecs 2 / 4)
+size_t rccsenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCC1, in, inlen, out, nullptr, 0); }
+size_t rccsdec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(TRC_RCC1, in, outlen, out, nullptr, 0); }
+size_t rcxsenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCX1, in, inlen, out, nullptr, 0); }
+size_t rcxsdec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(TRC_RCX1, in, outlen, out, nullptr, 0); }
 
 // adaptive-CDF byte range coder (reference rccdf.c:187-211; turborc -e46)
 size_t rccdfenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCA, in, inlen, out, nullptr, 0); }

@@ -489,9 +489,9 @@ size_t slice_plan(int codec, uint32_t chunk, size_t nchunks, int nks, std::vecto
         if (target > ((size_t)256 << 20)) target = (size_t)256 << 20;
     }
     size_t groups = target / ((size_t)chunk * 64);
-    // the order-1 coder keeps 136 KiB of model per chunk of a slice in every workspace: 1 GiB of models = 7 700 chunks = 31 MB
+    // an order-1 coder keeps its model per chunk of a slice in every workspace (136 KiB: anscdf1, rccs; 64 KiB: rcxs): 1 GiB of models = 7 700 chunks = 31 MB
     // slices at chunk 4096 (ADVICE r3: a 65 536-chunk slice would ask for 9 GB)
-    if (codec == TRC_ANSO1 && !forced && groups > ((size_t)1 << 30) / (64u * (size_t)TRC_O1_MODEL_BYTES)) groups = ((size_t)1 << 30) / (64u * (size_t)TRC_O1_MODEL_BYTES);
+    if (model_bytes(codec) && !forced && groups > ((size_t)1 << 30) / (64u * model_bytes(codec))) groups = ((size_t)1 << 30) / (64u * model_bytes(codec));
     if (groups < 1) groups = 1;
     while ((ngroups + groups - 1) / groups > TRC_MAX_SLICES) groups *= 2;              // the totals area holds 4096 slices
     if (equal) {                                                                       // a short last slice would cost its stream a whole wave's time: spread the groups evenly
@@ -983,6 +983,7 @@ static size_t host_encode(int codec, const unsigned char *in, size_t inlen, unsi
     if (!chunk_ok(chunk)) { fail(TRC_E_ARG, "chunk %u: must be a multiple of 64 in [%u,%u]", chunk, TRC_CHUNK_MIN, TRC_CHUNK_MAX); return 0; }
     if (codec == TRC_ANSB && chunk > TRC_ANSB_CHUNK_MAX) chunk = TRC_ANSB_CHUNK_MAX;
     if (codec == TRC_ANSO1 && chunk < 4096u && !chunk_override) chunk = 4096u;    // also under TRC_CHUNK / trc_set_chunk: see trc_auto_chunk_codec
+    if (is_o1bit(codec) && chunk < TRC_O1BIT_CHUNK_MIN && !chunk_override) chunk = TRC_O1BIT_CHUNK_MIN;      // (the same for the bitwise order-1 coders)
     HostJob J;
     J.codec = codec; J.chunk = chunk; J.in = in; J.out = out; J.n = inlen; J.cdf = cdf;
     J.nchunks = (inlen + chunk - 1) / chunk; J.dir = 4 * J.nchunks;

@@ -62,7 +62,7 @@ struct TrcWork {
     uint8_t  *scratch2;  // second region array (RCS2: stream 1)
     uint32_t  stride2;
     uint32_t  nchunks, ngroups;
-    uint8_t  *model;     // ANSO1 only: one 136 KiB order-1 model per chunk
+    uint8_t  *model;     // ANSO1, RCC1, RCX1: one order-1 model per chunk (136 / 136 / 64 KiB)
     uint32_t *aux;       // Turbo-VLC coders: two u32 per chunk (length of the first payload piece; mantissa bits)
 };
 #define TRC_O1_MODEL_BYTES (256u * 17u * 32u)
@@ -102,6 +102,11 @@ void trc_launch_rcs_dec(int nstreams, const uint8_t *d_payload, const uint32_t *
 void trc_launch_rcb_enc(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
 void trc_launch_rcb_dec(const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                         const TrcWork &w, uint8_t *d_out, hipStream_t s);
+
+// RCC1 / RCX1: bitwise order-1 range coders (rccsenc / rccsdec: ctx 0; rcxsenc / rcxsdec: ctx 1), models in w.model
+void trc_launch_o1bit_enc(int ctx, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
+void trc_launch_o1bit_dec(int ctx, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
+                          const TrcWork &w, uint8_t *d_out, hipStream_t s);
 
 // RCA / RCAI: adaptive-CDF byte range coder, 1 stream (rccdfenc / rccdfdec) or hi/lo nibbles on 2 streams (rccdfienc / rccdfidec);
 // nibble != 0: the `turborc -n` coders on values 0..15 (rccdf4enc/dec, rccdf4ienc/idec)
