@@ -9,7 +9,7 @@
  * device-resident numbers come from bench.py.
  *
  *   trcbench [-e id[,id..]] [-I runs] [-c chunk] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)
- * ids: 1 rcs | 2 rccs | 4 rcxs | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
+ * ids: 1 rcs | 2 rccs | 4 rcxs | 26 rcgs | 27 rcgzs | 28 rcrs | 29 rcrzs (8-bit; --int16 / --int32 inputs: the 16 / 32-bit coders) | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
  */
 #include <math.h>
 #include <stdio.h>
@@ -114,6 +114,14 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
     case 1:  name = "rc o0 (rcsenc/rcsdec)"; e3 = rcsenc; d3 = rcsdec; break;
     case 2:  name = "rc o1 (rccsenc/rccsdec)"; e3 = rccsenc; d3 = rccsdec; break;
     case 4:  name = "rc o1 sliding context (rcxsenc/rcxsdec)"; e3 = rcxsenc; d3 = rcxsdec; break;
+    case 26: name = g_elem == 4 ? "gamma 32 (rcgsenc32/rcgsdec32)" : g_elem == 2 ? "gamma 16 (rcgsenc16/rcgsdec16)" : "gamma 8 (rcgsenc8/rcgsdec8)";
+             e3 = g_elem == 4 ? rcgsenc32 : g_elem == 2 ? rcgsenc16 : rcgsenc8; d3 = g_elem == 4 ? rcgsdec32 : g_elem == 2 ? rcgsdec16 : rcgsdec8; break;
+    case 27: name = g_elem == 4 ? "gamma zigzag 32 (rcgzsenc32/rcgzsdec32)" : g_elem == 2 ? "gamma zigzag 16 (rcgzsenc16/rcgzsdec16)" : "gamma zigzag 8 (rcgzsenc8/rcgzsdec8)";
+             e3 = g_elem == 4 ? rcgzsenc32 : g_elem == 2 ? rcgzsenc16 : rcgzsenc8; d3 = g_elem == 4 ? rcgzsdec32 : g_elem == 2 ? rcgzsdec16 : rcgzsdec8; break;
+    case 28: name = g_elem == 4 ? "rice 32 (rcrsenc32/rcrsdec32)" : g_elem == 2 ? "rice 16 (rcrsenc16/rcrsdec16)" : "rice 8 (rcrsenc8/rcrsdec8)";
+             e3 = g_elem == 4 ? rcrsenc32 : g_elem == 2 ? rcrsenc16 : rcrsenc8; d3 = g_elem == 4 ? rcrsdec32 : g_elem == 2 ? rcrsdec16 : rcrsdec8; break;
+    case 29: name = g_elem == 4 ? "rice zigzag 32 (rcrzsenc32/rcrzsdec32)" : g_elem == 2 ? "rice zigzag 16 (rcrzsenc16/rcrzsdec16)" : "rice zigzag 8 (rcrzsenc8/rcrzsdec8)";
+             e3 = g_elem == 4 ? rcrzsenc32 : g_elem == 2 ? rcrzsenc16 : rcrzsenc8; d3 = g_elem == 4 ? rcrzsdec32 : g_elem == 2 ? rcrzsdec16 : rcrzsdec8; break;
     case 42: name = "cdfsb (rccdfsenc/rccdfsbdec)"; e5 = rccdfsenc; d5 = rccdfsbdec; break;
     case 43: name = "cdfsv (rccdfsenc/rccdfsvbdec)"; e5 = rccdfsenc; d5 = rccdfsvbdec; break;
     case 44: name = "cdfsm 32-bit range (rccdfsmenc/rccdfsmbdec)"; e5 = rccdfsmenc; d5 = rccdfsmbdec; break;

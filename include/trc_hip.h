@@ -71,6 +71,14 @@ enum trc_codec {
     /* bitwise order-1 range coders, "s" predictor (rc_s.c); a model per chunk in the workspace: chunks of 16 KiB and more */
     TRC_RCC1 = 28,    /* rccsenc    / rccsdec      context = previous byte, 128 KiB model   rc_.c:186-209 (-e2) */
     TRC_RCX1 = 29     /* rcxsenc    / rcxsdec      sliding 8-bit context, 64 KiB model      rc_.c:372-400 (-e4) */
+    /* integer coders on the bitwise range coder, "s" predictor (rc_.c:464-842; -e26/27/28/29): adaptive gamma and Rice codes of
+       8 / 16 / 32-bit elements, plain or on zigzag deltas.  Parity contract as for every coder (a chunk's payload = the
+       reference function on that chunk), with one exception: a chunk shorter than one element (a final chunk of 1 .. es-1
+       bytes) is stored raw, where the reference returns its tail bytes plus an empty 4-byte flush (len + 4 bytes). */
+    , TRC_RCG8 = 30,  TRC_RCG16 = 31,  TRC_RCG32 = 32,     /* rcgsenc8/16/32   / rcgsdec*    gamma                     (-e26) */
+    TRC_RCGZ8 = 33, TRC_RCGZ16 = 34, TRC_RCGZ32 = 35,      /* rcgzsenc8/16/32  / rcgzsdec*   gamma of zigzag deltas    (-e27) */
+    TRC_RCR8 = 36,  TRC_RCR16 = 37,  TRC_RCR32 = 38,       /* rcrsenc8/16/32   / rcrsdec*    Rice                      (-e28) */
+    TRC_RCRZ8 = 39, TRC_RCRZ16 = 40, TRC_RCRZ32 = 41       /* rcrzsenc8/16/32  / rcrzsdec*   Rice of zigzag deltas     (-e29) */
 };
 
 #define TRC_MAGIC        0x31435254u   /* "TRC1" */

@@ -11,6 +11,7 @@
  *   rcsenc / rcsdec                include/turborc.h:62-63           (rc_.c:37-58)
  *   rccsenc / rccsdec              include/turborc.h:65-66           (rc_.c:186-209)
  *   rcxsenc / rcxsdec              include/turborc.h:71-72           (rc_.c:372-400)
+ *   rcgsenc8/16/32 .. rcrzsdec32   include/turborc.h:128-155         (rc_.c:464-842)
  *
  * Calling convention (reference include/turborc.h:46-59), unchanged:
  *   encoders: `out` holds at least inlen bytes (+ the harness's usual slack); the return value is
@@ -99,6 +100,22 @@ size_t rccsenc(unsigned char *src, size_t srclen, unsigned char *dst);
 size_t rccsdec(unsigned char *src, size_t dstlen, unsigned char *dst);
 size_t rcxsenc(unsigned char *src, size_t srclen, unsigned char *dst);
 size_t rcxsdec(unsigned char *src, size_t dstlen, unsigned char *dst);
+
+/* integer coders on the bitwise range coder, "s" predictor (reference rc_.c:464-842; `turborc -e26/27/28/29`): adaptive gamma
+ * (rcgs*), gamma of zigzag deltas (rcgzs*), length-limited Rice (rcrs*) and Rice of zigzag deltas (rcrzs*) of 8 / 16 / 32-bit
+ * little-endian elements; a length that is not a multiple of the element size keeps its last bytes uncoded */
+size_t rcgsenc8(unsigned char *src, size_t srclen, unsigned char *dst);      size_t rcgsdec8(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcgsenc16(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcgsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcgsenc32(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcgsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcgzsenc8(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcgzsdec8(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcgzsenc16(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcgzsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcgzsenc32(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcgzsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcrsenc8(unsigned char *src, size_t srclen, unsigned char *dst);      size_t rcrsdec8(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcrsenc16(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcrsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcrsenc32(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcrsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcrzsenc8(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcrzsdec8(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcrzsenc16(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcrzsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcrzsenc32(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcrzsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
 
 #ifdef __cplusplus
 }

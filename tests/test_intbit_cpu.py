@@ -1,0 +1,144 @@
+"""CPU (no GPU): the gamma / Rice integer coders (TRC_RCG8 = 30 .. TRC_RCRZ32 = 41) at the library's boundary -- exported and
+declared symbols, ids, the no-device chunk and workspace rules, the committed fixtures against the reference, and the plain-C
+harness compiling against the headers."""
+import ctypes
+import hashlib
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import intbit_lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "turbo-range-coder_amd", "libturborc_hip.so")
+GOLD = os.path.join(ROOT, "tests", "golden")
+MB = 10**6
+ENUM = {30: "TRC_RCG8", 31: "TRC_RCG16", 32: "TRC_RCG32", 33: "TRC_RCGZ8", 34: "TRC_RCGZ16", 35: "TRC_RCGZ32",
+        36: "TRC_RCR8", 37: "TRC_RCR16", 38: "TRC_RCR32", 39: "TRC_RCRZ8", 40: "TRC_RCRZ16", 41: "TRC_RCRZ32"}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(LIB):
+        import __graft_entry__ as g
+        g.build()
+    lib = ctypes.CDLL(LIB)
+    lib.trc_work_bytes.restype = ctypes.c_size_t
+    lib.trc_work_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32]
+    lib.trc_auto_chunk_codec.restype = ctypes.c_uint32
+    lib.trc_auto_chunk_codec.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    lib.trc_round_chunk.restype = ctypes.c_uint32
+    lib.trc_round_chunk.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    lib.trc_host_plan.restype = ctypes.c_int
+    lib.trc_host_plan.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
+    return lib
+
+
+def test_symbols_exported_and_declared(lib):
+    hdr = open(os.path.join(ROOT, "include", "turborc.h")).read()
+    names = [n for c in L.CODECS for n in L.REF_FN[c]]
+    assert len(set(names)) == 24
+    for name in names:
+        assert hasattr(lib, name), name
+        assert re.search(r"size_t %s\(unsigned char \*src, size_t \w+, unsigned char \*dst\);" % name, hdr), name
+
+
+def test_codec_ids_in_header():
+    hdr = open(os.path.join(ROOT, "include", "trc_hip.h")).read()
+    assert re.search(r"TRC_RCX1 = 29\b", hdr)
+    for codec, name in ENUM.items():
+        assert re.search(r"\b%s = %d\b" % (name, codec), hdr), name
+
+
+def test_python_tables():
+    import trc
+    assert [c for c, _ in trc.INTBIT] == L.CODECS
+    assert dict(trc.INTBIT) == L.ES
+    for c in L.CODECS:
+        assert trc.CODEC_NAMES[c] == L.NAMES[c]
+        assert (trc._HOST_ENC[c], trc._HOST_DEC[c]) == L.REF_FN[c]
+        assert c not in trc.AVAILABLE and c not in trc.VLC_CODECS
+        assert getattr(trc, ENUM[c][4:]) == c
+
+
+@pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
+def test_chunk_and_workspace_rules(lib, codec):
+    for n in (1, 3, 1000, 10 * MB, 100 * MB, 1 << 30):
+        c = lib.trc_round_chunk(codec, n)
+        assert c % 64 == 0 and 512 <= c <= 16384, (n, c)
+        a = lib.trc_auto_chunk_codec(codec, n)
+        assert a % 64 == 0 and 512 <= a <= 16384, (n, a)
+        for chunk in (256, 1024, 4096, 16384):
+            assert lib.trc_work_bytes(codec, n, chunk) > n // chunk * chunk
+    assert lib.trc_work_bytes(codec, 1000, 100) == 0                # chunk not a multiple of 64
+    fc = (ctypes.c_size_t * 64)()
+    for n in (1, 3, 777, 3 * MB + 7):
+        ns = lib.trc_host_plan(codec, n, 0, 0, 0, fc, 64, None)
+        assert ns >= 1 and fc[0] == 0
+        chunk = lib.trc_auto_chunk_codec(codec, n)
+        assert fc[min(ns, 63)] == (n + chunk - 1) // chunk or ns >= 63
+    assert lib.trc_host_plan(codec, 0, 0, 0, 0, fc, 64, None) < 0
+
+
+def test_unknown_codec_refused(lib):
+    fc = (ctypes.c_size_t * 4)()
+    assert lib.trc_host_plan(42, 1000, 0, 0, 0, fc, 4, None) < 0
+
+
+def test_fixture_inputs_regenerate():
+    z = np.load(os.path.join(GOLD, "intbit_vectors.npz"))
+    index = json.loads(bytes(z["index"]).decode())
+    assert {e["chunk"] for e in index} == {256, 1024, 4096, 16384}
+    assert {e["kind"] for e in index} == set(L.KINDS)
+    ns = {e["n"] for e in index}
+    assert {1, 2, 3, 63, 64, 65}.issubset(ns)
+    assert any(e["n"] % e["chunk"] == r and e["n"] > e["chunk"] for r in (1, 2, 3) for e in index)
+    for e in index:
+        for c in L.CODECS:
+            d = L.gen(e["kind"], L.ES[c], e["n"], e["seed"])
+            assert hashlib.sha256(d.tobytes()).hexdigest() == e["in_sha256"][L.NAMES[c]], (e["case"], L.NAMES[c])
+
+
+def test_fixtures_equal_the_reference():
+    if not L.have_ref():
+        pytest.skip("oracle/_ref/libtrc_ref.so not built")
+    z = np.load(os.path.join(GOLD, "intbit_vectors.npz"))
+    index = json.loads(bytes(z["index"]).decode())
+    for e in index:
+        for c in L.CODECS:
+            name = L.NAMES[c]
+            d = L.gen(e["kind"], L.ES[c], e["n"], e["seed"])
+            clen, payload = L.ref_chunked_enc(c, d, e["chunk"])
+            assert np.array_equal(clen, z["clen_%d_%s" % (e["case"], name)]), (e["case"], name)
+            assert np.array_equal(payload, z["out_%d_%s" % (e["case"], name)]), (e["case"], name)
+            # and the reference decodes every coded chunk of it back
+            off = 0
+            for i, l in enumerate(clen):
+                piece = d[i * e["chunk"]:(i + 1) * e["chunk"]]
+                if l != piece.size:
+                    assert np.array_equal(L.ref_dec(c, payload[off:off + l], piece.size), piece), (e["case"], name, i)
+                off += int(l)
+
+
+def test_sub_element_chunk_rule():
+    """a chunk shorter than one element: the reference returns len + 4 bytes (tail, empty flush); the library stores it raw"""
+    if not L.have_ref():
+        pytest.skip("oracle/_ref/libtrc_ref.so not built")
+    out = L.ref_enc(L.RCG16, np.array([0xab], np.uint8))
+    assert out.tobytes() == bytes([0xab, 1, 0, 0, 0])
+    assert L.chunk_payload(L.RCG16, np.array([0xab], np.uint8)).tobytes() == b"\xab"
+
+
+def test_trcbench_compiles_against_the_headers(tmp_path):
+    exe = tmp_path / "trcbench"
+    r = subprocess.run(["cc", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "harness", "trcbench.c"),
+                        "-L", os.path.dirname(LIB), "-lturborc_hip", "-lm", "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    src = open(os.path.join(ROOT, "harness", "trcbench.c")).read()
+    for name in (n for c in L.CODECS for n in L.REF_FN[c]):
+        assert name in src, name

@@ -68,6 +68,7 @@ static uint32_t g_chunk = 0;                                  // 0: not read yet
 static bool chunk_ok(uint32_t c) { return c >= TRC_CHUNK_MIN && c <= TRC_CHUNK_MAX && (c % 64u) == 0; }
 static inline bool is_static(int codec);
 static inline bool is_o1bit(int codec) { return codec == TRC_RCC1 || codec == TRC_RCX1; }
+static inline bool is_int(int codec) { return codec >= TRC_RCG8 && codec <= TRC_RCRZ32; }        // gamma / Rice integer coders
 // one wave's time per byte of its chunk, ns, the slower of encode and decode (profiles/r05_all_codecs.txt: kernel time at chunk
 // 4096 with the chip a third full / 4096)
 static double trc_wave_ns(int codec)
@@ -79,6 +80,12 @@ static double trc_wave_ns(int codec)
     case TRC_RCA4: return 245;  case TRC_RCAI4: return 260; case TRC_ANSA4: return 255;
     case TRC_RCV8: return 746;  case TRC_RCVI8: return 797;
     case TRC_RCC1: return 2830; case TRC_RCX1: return 3310; // one lane per chunk, models in HBM: chunk 16384, markov (profiles/o1bit_notes.md)
+    // integer coders, one lane per chunk: the slower of encode / decode per byte of a chunk, 100 MB (chip less than one round full;
+    // rcgs / rcrs at chunk 16384, the zigzag coders at 4096: profiles/intbit/intbit_notes.md)
+    case TRC_RCG8: return 1580;  case TRC_RCG16: return 1490; case TRC_RCG32: return 1160;
+    case TRC_RCGZ8: return 1980; case TRC_RCGZ16: return 650; case TRC_RCGZ32: return 310;
+    case TRC_RCR8: return 2690;  case TRC_RCR16: return 1810; case TRC_RCR32: return 3110;
+    case TRC_RCRZ8: return 1850; case TRC_RCRZ16: return 640; case TRC_RCRZ32: return 770;
     case TRC_VLCU16: case TRC_VLCV16: case TRC_VLCVZ16: return 391;
     case TRC_VLCU32: case TRC_VLCV32: case TRC_VLCVZ32: return 214;
     case TRC_VLAU16: case TRC_VLAV16: case TRC_VLAVZ16: return 370;
@@ -119,6 +126,9 @@ static size_t round_chunks(int codec)
     if (codec == TRC_RCS2) return 98304u;
     if (is_static(codec)) return 196608u;
     if (codec == TRC_RCA || codec == TRC_RCAI || codec == TRC_ANSA || codec == TRC_RCB || codec == TRC_ANSB) return TRC_MODEL_ROUND_CHUNKS;
+    // integer coders: the 8-bit models (9-13 KiB of LDS per wave) leave room for more resident lanes than the 16/32-bit ones
+    // (100 MB: chunk 1024 against 1536, rcgs8 1.9 against 2.6 ms -- profiles/intbit/intbit_notes.md)
+    if (is_int(codec)) return (codec - TRC_RCG8) % 3 == 0 ? 98304u : TRC_MODEL_ROUND_CHUNKS;
     return 327680u;
 }
 extern "C" uint32_t trc_round_chunk(int codec, size_t n)
@@ -156,7 +166,7 @@ extern "C" int trc_set_chunk(uint32_t chunk)
 #define TRC_INKERNEL_SCAN_MAX 8192u
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline bool is_static(int codec) { return codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM; }
-static inline bool codec_ok(int codec) { return codec >= TRC_ANS4S && codec <= TRC_RCX1; }
+static inline bool codec_ok(int codec) { return codec >= TRC_ANS4S && codec <= TRC_RCRZ32; }
 static inline bool is_vlc(int codec) { return codec >= TRC_VLCU16 && codec <= TRC_VLCVZ32; }
 static inline int vlc_variant(int codec) { return (codec - TRC_VLCU16) >> 1; }      // 0 u, 1 v, 2 vz
 static inline int vlc_elem(int codec) { return ((codec - TRC_VLCU16) & 1) ? 4 : 2; }
@@ -189,9 +199,12 @@ static inline size_t model_bytes(int codec)
 
 static uint32_t scratch_stride(int codec, uint32_t chunk)
 {
-    (void)codec;
+    // integer coders: one element may add up to 107 coded bits (~134 B) after the last raw test passed
+    if (is_int(codec)) return chunk + 256;
     return chunk + 128;                // payload + one period of look-ahead, moved in whole 64-B segments (trc_io.h)
 }
+// w.model for the integer coders: per-wave blocks (trc_rc_int.hip)
+static inline size_t int_model_area(int codec, size_t ngroups) { return is_int(codec) ? up256(trc_int_model_bytes(codec - TRC_RCG8, ngroups)) : 0; }
 
 extern "C" size_t trc_work_bytes(int codec, size_t n, uint32_t chunk)
 {
@@ -200,7 +213,7 @@ extern "C" size_t trc_work_bytes(int codec, size_t n, uint32_t chunk)
     const size_t nchunks = (n + chunk - 1) / chunk, ngroups = (nchunks + 63) / 64;
     return up256(TRC_TAB_BYTES) + up256(4 * ngroups) + up256(8 * (ngroups + 1)) +
            up256(nchunks * (size_t)scratch_stride(codec, chunk)) + scratch2_bytes(codec, nchunks, chunk) +
-           up256(nchunks * model_bytes(codec)) +
+           up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) +
            ((codec >= TRC_VLCU16 && codec <= TRC_VLAVZ32) ? up256(nchunks * 8) : 0) + 4096;
 }
 
@@ -221,7 +234,7 @@ static int carve(int codec, size_t n, uint32_t chunk, void *d_work, size_t work_
     w.stride2 = (uint32_t)scratch2_stride(codec, chunk);
     w.scratch2 = p + up256(nchunks * (size_t)w.stride);
     w.model = w.scratch2 + scratch2_bytes(codec, nchunks, chunk);
-    w.aux = (uint32_t *)(w.model + up256(nchunks * model_bytes(codec)));
+    w.aux = (uint32_t *)(w.model + up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups));
     w.nchunks = (uint32_t)nchunks; w.ngroups = (uint32_t)ngroups;
     return TRC_OK;
 }
@@ -412,7 +425,8 @@ extern "C" int trc_encode_dev(int codec, const void *d_in, size_t n, uint32_t ch
     case TRC_RCVI8: trc_launch_rcv_enc(2, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 2; break;
     case TRC_RCC1:  trc_launch_o1bit_enc(0, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
     case TRC_RCX1:  trc_launch_o1bit_enc(1, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
-    default:        if (is_vlc(codec)) { trc_launch_vlc_enc(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 3; }
+    default:        if (is_int(codec)) { trc_launch_int_enc(codec - TRC_RCG8, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; }
+                    else if (is_vlc(codec)) { trc_launch_vlc_enc(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 3; }
                     else if (is_vla(codec)) { trc_launch_vla_enc(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 4; }
                     break;
     case TRC_ANSO1: if (trc_launch_anso1_model((const uint8_t *)d_in, n, chunk, w, s)) trc_launch_ansa_code_planar(n, chunk, w, d_clen, s);
@@ -471,7 +485,8 @@ extern "C" int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_p
     case TRC_RCVI8: trc_launch_rcv_dec(2, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     case TRC_RCC1:  trc_launch_o1bit_dec(0, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     case TRC_RCX1:  trc_launch_o1bit_dec(1, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
-    default:        if (is_vlc(codec)) trc_launch_vlc_dec(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
+    default:        if (is_int(codec)) trc_launch_int_dec(codec - TRC_RCG8, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
+                    else if (is_vlc(codec)) trc_launch_vlc_dec(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     else if (is_vla(codec)) trc_launch_vla_dec(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     break;
     }
@@ -499,7 +514,8 @@ extern "C" const char *trc_kernel_name(int codec, int decode)
     case TRC_ANSB: return decode ? "trc_ansb_dec_kernel" : "trc_ansb_model_kernel";
     case TRC_RCV8: case TRC_RCVI8: return decode ? "trc_rcv_dec_kernel" : "trc_rcv_enc_kernel";
     case TRC_RCC1: case TRC_RCX1: return decode ? "trc_rc_o1bit_dec_kernel" : "trc_rc_o1bit_enc_kernel";
-    default: if (is_vlc(codec)) return decode ? "trc_vlc_dec_kernel" : "trc_vlc_enc_kernel";
+    default: if (is_int(codec)) return decode ? "trc_rc_int_dec_kernel" : "trc_rc_int_enc_kernel";
+             if (is_vlc(codec)) return decode ? "trc_vlc_dec_kernel" : "trc_vlc_enc_kernel";
              if (is_vla(codec)) return decode ? "trc_vla_dec_kernel" : "trc_vla_model_kernel";
     }
     return "";
@@ -703,6 +719,16 @@ size_t rccsenc(unsigned char *in, size_t inlen, unsigned char *out) { return hos
 size_t rccsdec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(TRC_RCC1, in, outlen, out, nullptr, 0); }
 size_t rcxsenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCX1, in, inlen, out, nullptr, 0); }
 size_t rcxsdec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(TRC_RCX1, in, outlen, out, nullptr, 0); }
+
+// gamma / Rice integer coders (reference rc_.c:464-842; turborc -e26 .. -e29)
+#define TRC_INT_HOST(enc, dec, id) \
+    size_t enc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(id, in, inlen, out, nullptr, 0); } \
+    size_t dec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(id, in, outlen, out, nullptr, 0); }
+TRC_INT_HOST(rcgsenc8, rcgsdec8, TRC_RCG8)        TRC_INT_HOST(rcgsenc16, rcgsdec16, TRC_RCG16)     TRC_INT_HOST(rcgsenc32, rcgsdec32, TRC_RCG32)
+TRC_INT_HOST(rcgzsenc8, rcgzsdec8, TRC_RCGZ8)     TRC_INT_HOST(rcgzsenc16, rcgzsdec16, TRC_RCGZ16)  TRC_INT_HOST(rcgzsenc32, rcgzsdec32, TRC_RCGZ32)
+TRC_INT_HOST(rcrsenc8, rcrsdec8, TRC_RCR8)        TRC_INT_HOST(rcrsenc16, rcrsdec16, TRC_RCR16)     TRC_INT_HOST(rcrsenc32, rcrsdec32, TRC_RCR32)
+TRC_INT_HOST(rcrzsenc8, rcrzsdec8, TRC_RCRZ8)     TRC_INT_HOST(rcrzsenc16, rcrzsdec16, TRC_RCRZ16)  TRC_INT_HOST(rcrzsenc32, rcrzsdec32, TRC_RCRZ32)
+#undef TRC_INT_HOST
 
 // adaptive-CDF byte range coder (reference rccdf.c:187-211; turborc -e46)
 size_t rccdfenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCA, in, inlen, out, nullptr, 0); }

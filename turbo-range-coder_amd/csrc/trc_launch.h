@@ -108,6 +108,12 @@ void trc_launch_o1bit_enc(int ctx, const uint8_t *d_in, size_t n, uint32_t chunk
 void trc_launch_o1bit_dec(int ctx, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                           const TrcWork &w, uint8_t *d_out, hipStream_t s);
 
+// RCG8 .. RCRZ32: gamma / Rice integer coders (k = codec - TRC_RCG8); models in LDS, the 32-bit Rice ones in w.model
+void trc_launch_int_enc(int k, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
+void trc_launch_int_dec(int k, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
+                        const TrcWork &w, uint8_t *d_out, hipStream_t s);
+size_t trc_int_model_bytes(int k, size_t ngroups);   // workspace bytes of w.model for ngroups waves (0: the model is in LDS)
+
 // RCA / RCAI: adaptive-CDF byte range coder, 1 stream (rccdfenc / rccdfdec) or hi/lo nibbles on 2 streams (rccdfienc / rccdfidec);
 // nibble != 0: the `turborc -n` coders on values 0..15 (rccdf4enc/dec, rccdf4ienc/idec)
 void trc_launch_rca_enc(int nstreams, int nibble, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
