@@ -9,7 +9,8 @@
  * device-resident numbers come from bench.py.
  *
  *   trcbench [-e id[,id..]] [-I runs] [-c chunk] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)
- * ids: 1 rcs | 2 rccs | 4 rcxs | 26 rcgs | 27 rcgzs | 28 rcrs | 29 rcrzs (8-bit; --int16 / --int32 inputs: the 16 / 32-bit coders) | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
+ * ids: 1 rcs | 2 rccs | 4 rcxs | 26 rcgs | 27 rcgzs | 28 rcrs | 29 rcrzs (8-bit; --int16 / --int32 inputs: the 16 / 32-bit coders) |
+ *      30 rcvs | 33 rcvzs | 35 rcvgs | 36 rcvgzs (16-bit; --int32 input: the 32-bit coders) | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
  */
 #include <math.h>
 #include <stdio.h>
@@ -122,6 +123,14 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
              e3 = g_elem == 4 ? rcrsenc32 : g_elem == 2 ? rcrsenc16 : rcrsenc8; d3 = g_elem == 4 ? rcrsdec32 : g_elem == 2 ? rcrsdec16 : rcrsdec8; break;
     case 29: name = g_elem == 4 ? "rice zigzag 32 (rcrzsenc32/rcrzsdec32)" : g_elem == 2 ? "rice zigzag 16 (rcrzsenc16/rcrzsdec16)" : "rice zigzag 8 (rcrzsenc8/rcrzsdec8)";
              e3 = g_elem == 4 ? rcrzsenc32 : g_elem == 2 ? rcrzsenc16 : rcrzsenc8; d3 = g_elem == 4 ? rcrzsdec32 : g_elem == 2 ? rcrzsdec16 : rcrzsdec8; break;
+    case 30: name = g_elem == 4 ? "Turbo vlc8 32 (rcvsenc32/rcvsdec32)" : "Turbo vlc8 16 (rcvsenc16/rcvsdec16)";
+             e3 = g_elem == 4 ? rcvsenc32 : rcvsenc16; d3 = g_elem == 4 ? rcvsdec32 : rcvsdec16; break;
+    case 33: name = g_elem == 4 ? "Turbo vlc8 zigzag 32 (rcvzsenc32/rcvzsdec32)" : "Turbo vlc8 zigzag 16 (rcvzsenc16/rcvzsdec16)";
+             e3 = g_elem == 4 ? rcvzsenc32 : rcvzsenc16; d3 = g_elem == 4 ? rcvzsdec32 : rcvzsdec16; break;
+    case 35: name = g_elem == 4 ? "Turbo vlc8 gamma 32 (rcvgsenc32/rcvgsdec32)" : "Turbo vlc8 gamma 16 (rcvgsenc16/rcvgsdec16)";
+             e3 = g_elem == 4 ? rcvgsenc32 : rcvgsenc16; d3 = g_elem == 4 ? rcvgsdec32 : rcvgsdec16; break;
+    case 36: name = g_elem == 4 ? "Turbo vlc8 gamma zigzag 32 (rcvgzsenc32/rcvgzsdec32)" : "Turbo vlc8 gamma zigzag 16 (rcvgzsenc16/rcvgzsdec16)";
+             e3 = g_elem == 4 ? rcvgzsenc32 : rcvgzsenc16; d3 = g_elem == 4 ? rcvgzsdec32 : rcvgzsdec16; break;
     case 42: name = "cdfsb (rccdfsenc/rccdfsbdec)"; e5 = rccdfsenc; d5 = rccdfsbdec; break;
     case 43: name = "cdfsv (rccdfsenc/rccdfsvbdec)"; e5 = rccdfsenc; d5 = rccdfsvbdec; break;
     case 44: name = "cdfsm 32-bit range (rccdfsmenc/rccdfsmbdec)"; e5 = rccdfsmenc; d5 = rccdfsmbdec; break;

@@ -79,6 +79,14 @@ enum trc_codec {
     TRC_RCGZ8 = 33, TRC_RCGZ16 = 34, TRC_RCGZ32 = 35,      /* rcgzsenc8/16/32  / rcgzsdec*   gamma of zigzag deltas    (-e27) */
     TRC_RCR8 = 36,  TRC_RCR16 = 37,  TRC_RCR32 = 38,       /* rcrsenc8/16/32   / rcrsdec*    Rice                      (-e28) */
     TRC_RCRZ8 = 39, TRC_RCRZ16 = 40, TRC_RCRZ32 = 41       /* rcrzsenc8/16/32  / rcrzsdec*   Rice of zigzag deltas     (-e29) */
+    /* Turbo-VLC coders on the bitwise range coder, "s" predictor (rc_.c:1012-1336; -e30/33/35/36): 16 / 32-bit elements, an
+       element >= 32 becomes an exponent symbol (mb8enc tree or adaptive gamma) and mantissa bits in a reversed bit string.
+       The tree coders on 16-bit input and rcvzs32 keep 256 trees per chunk in the workspace (72 / 136 KiB): chunks of 16 KiB
+       and more, as for TRC_RCC1.  Id 42 is not assigned. */
+    , TRC_RCBV16 = 43,  TRC_RCBV32 = 44,    /* rcvsenc16/32   / rcvsdec16/32     tree, context prev >> 8 (16) / none (32)   (-e30) */
+    TRC_RCBVZ16 = 45,   TRC_RCBVZ32 = 46,   /* rcvzsenc16/32  / rcvzsdec16/32    tree of zigzag deltas, prev >> 8 / >> 24  (-e33) */
+    TRC_RCBVG16 = 47,   TRC_RCBVG32 = 48,   /* rcvgsenc16/32  / rcvgsdec16/32    gamma exponent                            (-e35) */
+    TRC_RCBVGZ16 = 49,  TRC_RCBVGZ32 = 50   /* rcvgzsenc16/32 / rcvgzsdec16/32   gamma exponent of zigzag deltas           (-e36) */
 };
 
 #define TRC_MAGIC        0x31435254u   /* "TRC1" */
@@ -88,7 +96,7 @@ enum trc_codec {
                                           163 GB/s), 1024 six (449 GB/s), 512 twelve (590 GB/s); payload ratio on text 63.50 / 63.94 /
                                           64.52 %.  Gigabyte inputs fill the chip at 4096 too, so host-pointer calls pick the size from
                                           the input length (trc_auto_chunk) unless the caller fixes it. */
-#define TRC_O1BIT_CHUNK_MIN 16384u     /* TRC_RCC1 / TRC_RCX1: the smallest chunk the automatic rules and the host-pointer calls use */
+#define TRC_O1BIT_CHUNK_MIN 16384u     /* TRC_RCC1 / TRC_RCX1, TRC_RCBV16 / TRC_RCBVZ16 / TRC_RCBVZ32: the smallest chunk the automatic rules and the host-pointer calls use */
 #define TRC_ANSB_CHUNK_MAX 8192u       /* TRC_ANSB only: one 8192-byte block of the reference per chunk */
 #define TRC_PAD          256u          /* readable slack the device entry points need after every buffer */
 

@@ -12,6 +12,7 @@
  *   rccsenc / rccsdec              include/turborc.h:65-66           (rc_.c:186-209)
  *   rcxsenc / rcxsdec              include/turborc.h:71-72           (rc_.c:372-400)
  *   rcgsenc8/16/32 .. rcrzsdec32   include/turborc.h:128-155         (rc_.c:464-842)
+ *   rcvsenc16 .. rcvgzsdec32       include/turborc.h:121-132         (rc_.c:1012-1336)
  *
  * Calling convention (reference include/turborc.h:46-59), unchanged:
  *   encoders: `out` holds at least inlen bytes (+ the harness's usual slack); the return value is
@@ -116,6 +117,19 @@ size_t rcrsenc32(unsigned char *src, size_t srclen, unsigned char *dst);     siz
 size_t rcrzsenc8(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcrzsdec8(unsigned char *src, size_t dstlen, unsigned char *dst);
 size_t rcrzsenc16(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcrzsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
 size_t rcrzsenc32(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcrzsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+
+/* Turbo-VLC coders on the bitwise range coder, "s" predictor (reference rc_.c:1012-1336; `turborc -e30/33/35/36`): 16 / 32-bit
+ * little-endian elements; the exponent of an element >= 32 is coded with an 8-bit tree (rcvs*, rcvzs*: zigzag deltas) or an
+ * adaptive gamma code (rcvgs*, rcvgzs*), its mantissa bits are stored verbatim; a length that is not a multiple of the element
+ * size keeps its last bytes uncoded */
+size_t rcvsenc16(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcvsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcvsenc32(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rcvsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcvzsenc16(unsigned char *src, size_t srclen, unsigned char *dst);   size_t rcvzsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcvzsenc32(unsigned char *src, size_t srclen, unsigned char *dst);   size_t rcvzsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcvgsenc16(unsigned char *src, size_t srclen, unsigned char *dst);   size_t rcvgsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcvgsenc32(unsigned char *src, size_t srclen, unsigned char *dst);   size_t rcvgsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcvgzsenc16(unsigned char *src, size_t srclen, unsigned char *dst);  size_t rcvgzsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcvgzsenc32(unsigned char *src, size_t srclen, unsigned char *dst);  size_t rcvgzsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
 
 #ifdef __cplusplus
 }

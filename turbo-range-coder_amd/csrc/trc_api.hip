@@ -69,6 +69,9 @@ static bool chunk_ok(uint32_t c) { return c >= TRC_CHUNK_MIN && c <= TRC_CHUNK_M
 static inline bool is_static(int codec);
 static inline bool is_o1bit(int codec) { return codec == TRC_RCC1 || codec == TRC_RCX1; }
 static inline bool is_int(int codec) { return codec >= TRC_RCG8 && codec <= TRC_RCRZ32; }        // gamma / Rice integer coders
+static inline bool is_bvlc(int codec) { return codec >= TRC_RCBV16 && codec <= TRC_RCBVGZ32; }    // Turbo-VLC on the bitwise coder
+// ... those of them with 256 trees per chunk in the workspace (rcvs16, rcvzs16, rcvzs32)
+static inline bool is_bvctx(int codec) { return codec == TRC_RCBV16 || codec == TRC_RCBVZ16 || codec == TRC_RCBVZ32; }
 // one wave's time per byte of its chunk, ns, the slower of encode and decode (profiles/r05_all_codecs.txt: kernel time at chunk
 // 4096 with the chip a third full / 4096)
 static double trc_wave_ns(int codec)
@@ -86,6 +89,12 @@ static double trc_wave_ns(int codec)
     case TRC_RCGZ8: return 1980; case TRC_RCGZ16: return 650; case TRC_RCGZ32: return 310;
     case TRC_RCR8: return 2690;  case TRC_RCR16: return 1810; case TRC_RCR32: return 3110;
     case TRC_RCRZ8: return 1850; case TRC_RCRZ16: return 640; case TRC_RCRZ32: return 770;
+    // Turbo-VLC on the bitwise coder, one lane per chunk: the slower of encode / decode per byte of a chunk, 100 MB, about one
+    // round (the context coders at chunk 16384, the others at 1536: profiles/bvlc/bvlc_bench.jsonl)
+    case TRC_RCBV16: return 884;    case TRC_RCBV32: return 392;
+    case TRC_RCBVZ16: return 831;   case TRC_RCBVZ32: return 461;
+    case TRC_RCBVG16: return 1352;  case TRC_RCBVG32: return 728;
+    case TRC_RCBVGZ16: return 1383; case TRC_RCBVGZ32: return 781;
     case TRC_VLCU16: case TRC_VLCV16: case TRC_VLCVZ16: return 391;
     case TRC_VLCU32: case TRC_VLCV32: case TRC_VLCVZ32: return 214;
     case TRC_VLAU16: case TRC_VLAV16: case TRC_VLAVZ16: return 370;
@@ -102,6 +111,9 @@ extern "C" uint32_t trc_auto_chunk_codec(int codec, size_t n)
     const double budget_ns = link_ns > 1.7e6 ? link_ns : 1.7e6;
     const uint32_t cap = is_static(codec) ? 4096u : codec == TRC_ANSB ? TRC_ANSB_CHUNK_MAX : TRC_AUTO_CHUNK_MAX;
     if (is_o1bit(codec)) return TRC_O1BIT_CHUNK_MIN;        // the ratio floor: every larger chunk only waits longer
+    // (the same for the Turbo-VLC coders with 256 trees per chunk: their workspace is 4.5 / 8.5 bytes per input byte at 16384,
+    // four times that at 4096, for 0.4 points of ratio -- profiles/bvlc/bvlc_notes.md)
+    if (is_bvctx(codec)) return TRC_O1BIT_CHUNK_MIN;
     const uint32_t lo = codec == TRC_ANSO1 ? 4096u : TRC_CHUNK_AUTO_MIN;
     for (uint32_t c : ladder)
         if (c <= cap && (c <= lo || trc_wave_ns(codec) * c <= budget_ns)) return c;
@@ -129,12 +141,16 @@ static size_t round_chunks(int codec)
     // integer coders: the 8-bit models (9-13 KiB of LDS per wave) leave room for more resident lanes than the 16/32-bit ones
     // (100 MB: chunk 1024 against 1536, rcgs8 1.9 against 2.6 ms -- profiles/intbit/intbit_notes.md)
     if (is_int(codec)) return (codec - TRC_RCG8) % 3 == 0 ? 98304u : TRC_MODEL_ROUND_CHUNKS;
+    // Turbo-VLC on the bitwise coder (9 / 34 KiB of LDS per wave): 100 MB in one round at 1536 is the sweep's best for every
+    // coder that is not held at the floor (profiles/bvlc/bvlc_bench.jsonl)
+    if (is_bvlc(codec)) return TRC_MODEL_ROUND_CHUNKS;
     return 327680u;
 }
 extern "C" uint32_t trc_round_chunk(int codec, size_t n)
 {
     if (codec == TRC_ANSO1) return 4096u;                     // (see trc_auto_chunk_codec)
     if (is_o1bit(codec)) return TRC_O1BIT_CHUNK_MIN;          // one lane per chunk: the launch's time is one chunk's, so the floor
+    if (is_bvctx(codec)) return TRC_O1BIT_CHUNK_MIN;
     const size_t rc = round_chunks(codec);
     const size_t cap = codec == TRC_ANSB ? TRC_ANSB_CHUNK_MAX : TRC_ROUND_CHUNK_MAX;
     for (size_t k = 1;; k++) {
@@ -166,7 +182,7 @@ extern "C" int trc_set_chunk(uint32_t chunk)
 #define TRC_INKERNEL_SCAN_MAX 8192u
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline bool is_static(int codec) { return codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM; }
-static inline bool codec_ok(int codec) { return codec >= TRC_ANS4S && codec <= TRC_RCRZ32; }
+static inline bool codec_ok(int codec) { return (codec >= TRC_ANS4S && codec <= TRC_RCRZ32) || is_bvlc(codec); }   // 42 unassigned
 static inline bool is_vlc(int codec) { return codec >= TRC_VLCU16 && codec <= TRC_VLCVZ32; }
 static inline int vlc_variant(int codec) { return (codec - TRC_VLCU16) >> 1; }      // 0 u, 1 v, 2 vz
 static inline int vlc_elem(int codec) { return ((codec - TRC_VLCU16) & 1) ? 4 : 2; }
@@ -201,10 +217,14 @@ static uint32_t scratch_stride(int codec, uint32_t chunk)
 {
     // integer coders: one element may add up to 107 coded bits (~134 B) after the last raw test passed
     if (is_int(codec)) return chunk + 256;
+    // Turbo-VLC on the bitwise coder: one element after the last raw test adds at most ~7 words and 4 mantissa bytes
+    if (is_bvlc(codec)) return chunk + 256;
     return chunk + 128;                // payload + one period of look-ahead, moved in whole 64-B segments (trc_io.h)
 }
 // w.model for the integer coders: per-wave blocks (trc_rc_int.hip)
 static inline size_t int_model_area(int codec, size_t ngroups) { return is_int(codec) ? up256(trc_int_model_bytes(codec - TRC_RCG8, ngroups)) : 0; }
+// w.model for the Turbo-VLC coders on the bitwise coder: 256 trees per chunk (trc_rc_bvlc.hip)
+static inline size_t bvlc_model_area(int codec, size_t nchunks) { return is_bvlc(codec) ? up256(trc_bvlc_model_bytes(codec - TRC_RCBV16, nchunks)) : 0; }
 
 extern "C" size_t trc_work_bytes(int codec, size_t n, uint32_t chunk)
 {
@@ -213,8 +233,8 @@ extern "C" size_t trc_work_bytes(int codec, size_t n, uint32_t chunk)
     const size_t nchunks = (n + chunk - 1) / chunk, ngroups = (nchunks + 63) / 64;
     return up256(TRC_TAB_BYTES) + up256(4 * ngroups) + up256(8 * (ngroups + 1)) +
            up256(nchunks * (size_t)scratch_stride(codec, chunk)) + scratch2_bytes(codec, nchunks, chunk) +
-           up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) +
-           ((codec >= TRC_VLCU16 && codec <= TRC_VLAVZ32) ? up256(nchunks * 8) : 0) + 4096;
+           up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) + bvlc_model_area(codec, nchunks) +
+           ((codec >= TRC_VLCU16 && codec <= TRC_VLAVZ32) || is_bvlc(codec) ? up256(nchunks * 8) : 0) + 4096;
 }
 
 static int carve(int codec, size_t n, uint32_t chunk, void *d_work, size_t work_bytes, TrcWork &w)
@@ -234,7 +254,7 @@ static int carve(int codec, size_t n, uint32_t chunk, void *d_work, size_t work_
     w.stride2 = (uint32_t)scratch2_stride(codec, chunk);
     w.scratch2 = p + up256(nchunks * (size_t)w.stride);
     w.model = w.scratch2 + scratch2_bytes(codec, nchunks, chunk);
-    w.aux = (uint32_t *)(w.model + up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups));
+    w.aux = (uint32_t *)(w.model + up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) + bvlc_model_area(codec, nchunks));
     w.nchunks = (uint32_t)nchunks; w.ngroups = (uint32_t)ngroups;
     return TRC_OK;
 }
@@ -426,6 +446,7 @@ extern "C" int trc_encode_dev(int codec, const void *d_in, size_t n, uint32_t ch
     case TRC_RCC1:  trc_launch_o1bit_enc(0, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
     case TRC_RCX1:  trc_launch_o1bit_enc(1, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
     default:        if (is_int(codec)) { trc_launch_int_enc(codec - TRC_RCG8, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; }
+                    else if (is_bvlc(codec)) { trc_launch_bvlc_enc(codec - TRC_RCBV16, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 3; }
                     else if (is_vlc(codec)) { trc_launch_vlc_enc(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 3; }
                     else if (is_vla(codec)) { trc_launch_vla_enc(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 4; }
                     break;
@@ -486,6 +507,7 @@ extern "C" int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_p
     case TRC_RCC1:  trc_launch_o1bit_dec(0, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     case TRC_RCX1:  trc_launch_o1bit_dec(1, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     default:        if (is_int(codec)) trc_launch_int_dec(codec - TRC_RCG8, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
+                    else if (is_bvlc(codec)) trc_launch_bvlc_dec(codec - TRC_RCBV16, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     else if (is_vlc(codec)) trc_launch_vlc_dec(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     else if (is_vla(codec)) trc_launch_vla_dec(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     break;
@@ -515,6 +537,7 @@ extern "C" const char *trc_kernel_name(int codec, int decode)
     case TRC_RCV8: case TRC_RCVI8: return decode ? "trc_rcv_dec_kernel" : "trc_rcv_enc_kernel";
     case TRC_RCC1: case TRC_RCX1: return decode ? "trc_rc_o1bit_dec_kernel" : "trc_rc_o1bit_enc_kernel";
     default: if (is_int(codec)) return decode ? "trc_rc_int_dec_kernel" : "trc_rc_int_enc_kernel";
+             if (is_bvlc(codec)) return decode ? "trc_rc_bvlc_dec_kernel" : "trc_rc_bvlc_enc_kernel";
              if (is_vlc(codec)) return decode ? "trc_vlc_dec_kernel" : "trc_vlc_enc_kernel";
              if (is_vla(codec)) return decode ? "trc_vla_dec_kernel" : "trc_vla_model_kernel";
     }
@@ -729,6 +752,16 @@ TRC_INT_HOST(rcgzsenc8, rcgzsdec8, TRC_RCGZ8)     TRC_INT_HOST(rcgzsenc16, rcgzs
 TRC_INT_HOST(rcrsenc8, rcrsdec8, TRC_RCR8)        TRC_INT_HOST(rcrsenc16, rcrsdec16, TRC_RCR16)     TRC_INT_HOST(rcrsenc32, rcrsdec32, TRC_RCR32)
 TRC_INT_HOST(rcrzsenc8, rcrzsdec8, TRC_RCRZ8)     TRC_INT_HOST(rcrzsenc16, rcrzsdec16, TRC_RCRZ16)  TRC_INT_HOST(rcrzsenc32, rcrzsdec32, TRC_RCRZ32)
 #undef TRC_INT_HOST
+
+// Turbo-VLC coders on the bitwise range coder (reference rc_.c:1012-1336; turborc -e30 / -e33 / -e35 / -e36)
+#define TRC_BVLC_HOST(enc, dec, id) \
+    size_t enc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(id, in, inlen, out, nullptr, 0); } \
+    size_t dec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(id, in, outlen, out, nullptr, 0); }
+TRC_BVLC_HOST(rcvsenc16, rcvsdec16, TRC_RCBV16)       TRC_BVLC_HOST(rcvsenc32, rcvsdec32, TRC_RCBV32)
+TRC_BVLC_HOST(rcvzsenc16, rcvzsdec16, TRC_RCBVZ16)    TRC_BVLC_HOST(rcvzsenc32, rcvzsdec32, TRC_RCBVZ32)
+TRC_BVLC_HOST(rcvgsenc16, rcvgsdec16, TRC_RCBVG16)    TRC_BVLC_HOST(rcvgsenc32, rcvgsdec32, TRC_RCBVG32)
+TRC_BVLC_HOST(rcvgzsenc16, rcvgzsdec16, TRC_RCBVGZ16) TRC_BVLC_HOST(rcvgzsenc32, rcvgzsdec32, TRC_RCBVGZ32)
+#undef TRC_BVLC_HOST
 
 // adaptive-CDF byte range coder (reference rccdf.c:187-211; turborc -e46)
 size_t rccdfenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCA, in, inlen, out, nullptr, 0); }

@@ -984,6 +984,7 @@ static size_t host_encode(int codec, const unsigned char *in, size_t inlen, unsi
     if (codec == TRC_ANSB && chunk > TRC_ANSB_CHUNK_MAX) chunk = TRC_ANSB_CHUNK_MAX;
     if (codec == TRC_ANSO1 && chunk < 4096u && !chunk_override) chunk = 4096u;    // also under TRC_CHUNK / trc_set_chunk: see trc_auto_chunk_codec
     if (is_o1bit(codec) && chunk < TRC_O1BIT_CHUNK_MIN && !chunk_override) chunk = TRC_O1BIT_CHUNK_MIN;      // (the same for the bitwise order-1 coders)
+    if (is_bvctx(codec) && chunk < TRC_O1BIT_CHUNK_MIN && !chunk_override) chunk = TRC_O1BIT_CHUNK_MIN;      // (and the Turbo-VLC ones with 256 trees per chunk)
     HostJob J;
     J.codec = codec; J.chunk = chunk; J.in = in; J.out = out; J.n = inlen; J.cdf = cdf;
     J.nchunks = (inlen + chunk - 1) / chunk; J.dir = 4 * J.nchunks;

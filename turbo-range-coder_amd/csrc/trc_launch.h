@@ -114,6 +114,13 @@ void trc_launch_int_dec(int k, const uint8_t *d_payload, const uint32_t *d_clen,
                         const TrcWork &w, uint8_t *d_out, hipStream_t s);
 size_t trc_int_model_bytes(int k, size_t ngroups);   // workspace bytes of w.model for ngroups waves (0: the model is in LDS)
 
+// RCBV16 .. RCBVGZ32: Turbo-VLC coders on the bitwise range coder (k = codec - TRC_RCBV16); aux[2c] = length of the
+// range-coder piece (gather mode 3); the context-model coders (k = 0, 2, 3) keep 256 trees per chunk in w.model
+void trc_launch_bvlc_enc(int k, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
+void trc_launch_bvlc_dec(int k, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
+                         const TrcWork &w, uint8_t *d_out, hipStream_t s);
+size_t trc_bvlc_model_bytes(int k, size_t nchunks);   // workspace bytes of w.model for nchunks chunks (0: the model is in LDS)
+
 // RCA / RCAI: adaptive-CDF byte range coder, 1 stream (rccdfenc / rccdfdec) or hi/lo nibbles on 2 streams (rccdfienc / rccdfidec);
 // nibble != 0: the `turborc -n` coders on values 0..15 (rccdf4enc/dec, rccdf4ienc/idec)
 void trc_launch_rca_enc(int nstreams, int nibble, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
