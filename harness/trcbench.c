@@ -9,7 +9,7 @@
  * device-resident numbers come from bench.py.
  *
  *   trcbench [-e id[,id..]] [-I runs] [-c chunk] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)
- * ids: 1 rcs | 2 rccs | 4 rcxs | 26 rcgs | 27 rcgzs | 28 rcrs | 29 rcrzs (8-bit; --int16 / --int32 inputs: the 16 / 32-bit coders) |
+ * ids: 1 rcs | 2 rccs | 4 rcxs | 6 rcs16 / rcs32 | 7 rccs32 | 8 rcc2s32 (word coders: --int16 / --int32 input) | 26 rcgs | 27 rcgzs | 28 rcrs | 29 rcrzs (8-bit; --int16 / --int32 inputs: the 16 / 32-bit coders) |
  *      30 rcvs | 33 rcvzs | 35 rcvgs | 36 rcvgzs (16-bit; --int32 input: the 32-bit coders) | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
  */
 #include <math.h>
@@ -123,6 +123,10 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
              e3 = g_elem == 4 ? rcrsenc32 : g_elem == 2 ? rcrsenc16 : rcrsenc8; d3 = g_elem == 4 ? rcrsdec32 : g_elem == 2 ? rcrsdec16 : rcrsdec8; break;
     case 29: name = g_elem == 4 ? "rice zigzag 32 (rcrzsenc32/rcrzsdec32)" : g_elem == 2 ? "rice zigzag 16 (rcrzsenc16/rcrzsdec16)" : "rice zigzag 8 (rcrzsenc8/rcrzsdec8)";
              e3 = g_elem == 4 ? rcrzsenc32 : g_elem == 2 ? rcrzsenc16 : rcrzsenc8; d3 = g_elem == 4 ? rcrzsdec32 : g_elem == 2 ? rcrzsdec16 : rcrzsdec8; break;
+    case 6:  name = g_elem == 4 ? "word o0 32 (rcsenc32/rcsdec32)" : "word o0 16 (rcsenc16/rcsdec16)";
+             e3 = g_elem == 4 ? rcsenc32 : rcsenc16; d3 = g_elem == 4 ? rcsdec32 : rcsdec16; break;
+    case 7:  name = "word o7bs 32 (rccsenc32/rccsdec32)"; e3 = rccsenc32; d3 = rccsdec32; break;
+    case 8:  name = "word o11bs 32 (rcc2senc32/rcc2sdec32)"; e3 = rcc2senc32; d3 = rcc2sdec32; break;
     case 30: name = g_elem == 4 ? "Turbo vlc8 32 (rcvsenc32/rcvsdec32)" : "Turbo vlc8 16 (rcvsenc16/rcvsdec16)";
              e3 = g_elem == 4 ? rcvsenc32 : rcvsenc16; d3 = g_elem == 4 ? rcvsdec32 : rcvsdec16; break;
     case 33: name = g_elem == 4 ? "Turbo vlc8 zigzag 32 (rcvzsenc32/rcvzsdec32)" : "Turbo vlc8 zigzag 16 (rcvzsenc16/rcvzsdec16)";

@@ -87,6 +87,15 @@ enum trc_codec {
     TRC_RCBVZ16 = 45,   TRC_RCBVZ32 = 46,   /* rcvzsenc16/32  / rcvzsdec16/32    tree of zigzag deltas, prev >> 8 / >> 24  (-e33) */
     TRC_RCBVG16 = 47,   TRC_RCBVG32 = 48,   /* rcvgsenc16/32  / rcvgsdec16/32    gamma exponent                            (-e35) */
     TRC_RCBVGZ16 = 49,  TRC_RCBVGZ32 = 50   /* rcvgzsenc16/32 / rcvgzsdec16/32   gamma exponent of zigzag deltas           (-e36) */
+    /* bitwise word coders, "s" predictor (rc_.c:60-138, 248-342; -e6/7/8): every byte of a 16 / 32-bit word coded with an
+       mb8enc tree picked by the bytes above it (and, for -e7/-e8, the top bits of the previous word).  136.5 KiB .. 2.26 MiB of
+       trees per chunk, held in at most TRC_WORD_MODEL_BUDGET bytes of slots that the chunks use in rounds.  Parity contract
+       as for the integer coders (a final chunk shorter than one element is stored raw), plus one exception for rcsenc16,
+       which has no OVERFLOW test: a chunk whose coded length would be >= its length is stored raw.  Id 51 is not assigned. */
+    , TRC_RCW16 = 52,   /* rcsenc16   / rcsdec16     tree 0 for the high byte, 256 for the low byte          (-e6, 16-bit) */
+    TRC_RCW32 = 53,     /* rcsenc32   / rcsdec32     order 0 over the bytes of the word                      (-e6, 32-bit) */
+    TRC_RCCW32 = 54,    /* rccsenc32  / rccsdec32    as rcs32, the top byte's tree by (prev >> 25) & 127      (-e7) */
+    TRC_RCC2W32 = 55    /* rcc2senc32 / rcc2sdec32   as rcs32, the top byte's tree by (prev >> 20) & 0x7ff    (-e8) */
 };
 
 #define TRC_MAGIC        0x31435254u   /* "TRC1" */
@@ -96,7 +105,10 @@ enum trc_codec {
                                           163 GB/s), 1024 six (449 GB/s), 512 twelve (590 GB/s); payload ratio on text 63.50 / 63.94 /
                                           64.52 %.  Gigabyte inputs fill the chip at 4096 too, so host-pointer calls pick the size from
                                           the input length (trc_auto_chunk) unless the caller fixes it. */
-#define TRC_O1BIT_CHUNK_MIN 16384u     /* TRC_RCC1 / TRC_RCX1, TRC_RCBV16 / TRC_RCBVZ16 / TRC_RCBVZ32: the smallest chunk the automatic rules and the host-pointer calls use */
+#define TRC_O1BIT_CHUNK_MIN 16384u     /* TRC_RCC1 / TRC_RCX1, TRC_RCBV16 / TRC_RCBVZ16 / TRC_RCBVZ32, TRC_RCW16 .. TRC_RCC2W32: the smallest chunk the automatic rules and the host-pointer calls use */
+#define TRC_WORD_MODEL_BUDGET 4294967296ull  /* TRC_RCW16 .. TRC_RCC2W32: the most workspace one call spends on models.  A call
+                                          holds min(chunks, budget / model bytes, in whole waves of 64) of them and codes its
+                                          chunks in rounds of that many (profiles/word/word_notes.md) */
 #define TRC_ANSB_CHUNK_MAX 8192u       /* TRC_ANSB only: one 8192-byte block of the reference per chunk */
 #define TRC_PAD          256u          /* readable slack the device entry points need after every buffer */
 

@@ -13,6 +13,7 @@
  *   rcxsenc / rcxsdec              include/turborc.h:71-72           (rc_.c:372-400)
  *   rcgsenc8/16/32 .. rcrzsdec32   include/turborc.h:128-155         (rc_.c:464-842)
  *   rcvsenc16 .. rcvgzsdec32       include/turborc.h:121-132         (rc_.c:1012-1336)
+ *   rcsenc16 .. rcc2sdec32         include/turborc.h:77-90           (rc_.c:60-138, 248-342)
  *
  * Calling convention (reference include/turborc.h:46-59), unchanged:
  *   encoders: `out` holds at least inlen bytes (+ the harness's usual slack); the return value is
@@ -130,6 +131,14 @@ size_t rcvgsenc16(unsigned char *src, size_t srclen, unsigned char *dst);   size
 size_t rcvgsenc32(unsigned char *src, size_t srclen, unsigned char *dst);   size_t rcvgsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
 size_t rcvgzsenc16(unsigned char *src, size_t srclen, unsigned char *dst);  size_t rcvgzsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
 size_t rcvgzsenc32(unsigned char *src, size_t srclen, unsigned char *dst);  size_t rcvgzsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+
+/* bitwise word coders, "s" predictor (reference rc_.c:60-138, 248-342; `turborc -e6/7/8`): 16 / 32-bit little-endian words,
+ * each byte coded with an 8-bit tree picked by the bytes above it (rcc*: and the top bits of the previous word); a length that
+ * is not a multiple of the word size keeps its last bytes uncoded */
+size_t rcsenc16(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcsdec16(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcsenc32(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rccsenc32(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rccsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rcc2senc32(unsigned char *src, size_t srclen, unsigned char *dst);   size_t rcc2sdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,7 @@ static inline bool is_int(int codec) { return codec >= TRC_RCG8 && codec <= TRC_
 static inline bool is_bvlc(int codec) { return codec >= TRC_RCBV16 && codec <= TRC_RCBVGZ32; }    // Turbo-VLC on the bitwise coder
 // ... those of them with 256 trees per chunk in the workspace (rcvs16, rcvzs16, rcvzs32)
 static inline bool is_bvctx(int codec) { return codec == TRC_RCBV16 || codec == TRC_RCBVZ16 || codec == TRC_RCBVZ32; }
+static inline bool is_word(int codec) { return codec >= TRC_RCW16 && codec <= TRC_RCC2W32; }       // bitwise word coders
 // one wave's time per byte of its chunk, ns, the slower of encode and decode (profiles/r05_all_codecs.txt: kernel time at chunk
 // 4096 with the chip a third full / 4096)
 static double trc_wave_ns(int codec)
@@ -95,6 +96,9 @@ static double trc_wave_ns(int codec)
     case TRC_RCBVZ16: return 831;   case TRC_RCBVZ32: return 461;
     case TRC_RCBVG16: return 1352;  case TRC_RCBVG32: return 728;
     case TRC_RCBVGZ16: return 1383; case TRC_RCBVGZ32: return 781;
+    // word coders, one lane per chunk, trees in HBM: the slower of encode / decode per byte of a chunk and round, 100 MB of
+    // `walk` at chunk 16384 (profiles/word/word_notes.md)
+    case TRC_RCW16: return 1340; case TRC_RCW32: return 1430; case TRC_RCCW32: return 1460; case TRC_RCC2W32: return 1440;
     case TRC_VLCU16: case TRC_VLCV16: case TRC_VLCVZ16: return 391;
     case TRC_VLCU32: case TRC_VLCV32: case TRC_VLCVZ32: return 214;
     case TRC_VLAU16: case TRC_VLAV16: case TRC_VLAVZ16: return 370;
@@ -114,6 +118,7 @@ extern "C" uint32_t trc_auto_chunk_codec(int codec, size_t n)
     // (the same for the Turbo-VLC coders with 256 trees per chunk: their workspace is 4.5 / 8.5 bytes per input byte at 16384,
     // four times that at 4096, for 0.4 points of ratio -- profiles/bvlc/bvlc_notes.md)
     if (is_bvctx(codec)) return TRC_O1BIT_CHUNK_MIN;
+    if (is_word(codec)) return TRC_O1BIT_CHUNK_MIN;         // (and the word coders: one lane per chunk, trees in HBM)
     const uint32_t lo = codec == TRC_ANSO1 ? 4096u : TRC_CHUNK_AUTO_MIN;
     for (uint32_t c : ladder)
         if (c <= cap && (c <= lo || trc_wave_ns(codec) * c <= budget_ns)) return c;
@@ -151,6 +156,7 @@ extern "C" uint32_t trc_round_chunk(int codec, size_t n)
     if (codec == TRC_ANSO1) return 4096u;                     // (see trc_auto_chunk_codec)
     if (is_o1bit(codec)) return TRC_O1BIT_CHUNK_MIN;          // one lane per chunk: the launch's time is one chunk's, so the floor
     if (is_bvctx(codec)) return TRC_O1BIT_CHUNK_MIN;
+    if (is_word(codec)) return TRC_O1BIT_CHUNK_MIN;
     const size_t rc = round_chunks(codec);
     const size_t cap = codec == TRC_ANSB ? TRC_ANSB_CHUNK_MAX : TRC_ROUND_CHUNK_MAX;
     for (size_t k = 1;; k++) {
@@ -182,7 +188,7 @@ extern "C" int trc_set_chunk(uint32_t chunk)
 #define TRC_INKERNEL_SCAN_MAX 8192u
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline bool is_static(int codec) { return codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM; }
-static inline bool codec_ok(int codec) { return (codec >= TRC_ANS4S && codec <= TRC_RCRZ32) || is_bvlc(codec); }   // 42 unassigned
+static inline bool codec_ok(int codec) { return (codec >= TRC_ANS4S && codec <= TRC_RCRZ32) || is_bvlc(codec) || is_word(codec); }   // 42, 51 unassigned
 static inline bool is_vlc(int codec) { return codec >= TRC_VLCU16 && codec <= TRC_VLCVZ32; }
 static inline int vlc_variant(int codec) { return (codec - TRC_VLCU16) >> 1; }      // 0 u, 1 v, 2 vz
 static inline int vlc_elem(int codec) { return ((codec - TRC_VLCU16) & 1) ? 4 : 2; }
@@ -219,12 +225,19 @@ static uint32_t scratch_stride(int codec, uint32_t chunk)
     if (is_int(codec)) return chunk + 256;
     // Turbo-VLC on the bitwise coder: one element after the last raw test adds at most ~7 words and 4 mantissa bytes
     if (is_bvlc(codec)) return chunk + 256;
+    // word coders: a 32-bit word after the last raw test adds at most 16 words; rcs16 stops once its output reaches the chunk
+    if (is_word(codec)) return chunk + 256;
     return chunk + 128;                // payload + one period of look-ahead, moved in whole 64-B segments (trc_io.h)
 }
 // w.model for the integer coders: per-wave blocks (trc_rc_int.hip)
 static inline size_t int_model_area(int codec, size_t ngroups) { return is_int(codec) ? up256(trc_int_model_bytes(codec - TRC_RCG8, ngroups)) : 0; }
 // w.model for the Turbo-VLC coders on the bitwise coder: 256 trees per chunk (trc_rc_bvlc.hip)
 static inline size_t bvlc_model_area(int codec, size_t nchunks) { return is_bvlc(codec) ? up256(trc_bvlc_model_bytes(codec - TRC_RCBV16, nchunks)) : 0; }
+// w.model for the word coders: the slots the chunks use in rounds (trc_rc_word.hip), at most TRC_WORD_MODEL_BUDGET bytes
+static inline size_t word_model_area(int codec, size_t nchunks)
+{
+    return is_word(codec) ? up256(trc_word_slots(codec - TRC_RCW16, nchunks) * trc_word_model_bytes(codec - TRC_RCW16)) : 0;
+}
 
 extern "C" size_t trc_work_bytes(int codec, size_t n, uint32_t chunk)
 {
@@ -233,7 +246,7 @@ extern "C" size_t trc_work_bytes(int codec, size_t n, uint32_t chunk)
     const size_t nchunks = (n + chunk - 1) / chunk, ngroups = (nchunks + 63) / 64;
     return up256(TRC_TAB_BYTES) + up256(4 * ngroups) + up256(8 * (ngroups + 1)) +
            up256(nchunks * (size_t)scratch_stride(codec, chunk)) + scratch2_bytes(codec, nchunks, chunk) +
-           up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) + bvlc_model_area(codec, nchunks) +
+           up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) + bvlc_model_area(codec, nchunks) + word_model_area(codec, nchunks) +
            ((codec >= TRC_VLCU16 && codec <= TRC_VLAVZ32) || is_bvlc(codec) ? up256(nchunks * 8) : 0) + 4096;
 }
 
@@ -254,7 +267,8 @@ static int carve(int codec, size_t n, uint32_t chunk, void *d_work, size_t work_
     w.stride2 = (uint32_t)scratch2_stride(codec, chunk);
     w.scratch2 = p + up256(nchunks * (size_t)w.stride);
     w.model = w.scratch2 + scratch2_bytes(codec, nchunks, chunk);
-    w.aux = (uint32_t *)(w.model + up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) + bvlc_model_area(codec, nchunks));
+    w.aux = (uint32_t *)(w.model + up256(nchunks * model_bytes(codec)) + int_model_area(codec, ngroups) + bvlc_model_area(codec, nchunks) +
+                        word_model_area(codec, nchunks));
     w.nchunks = (uint32_t)nchunks; w.ngroups = (uint32_t)ngroups;
     return TRC_OK;
 }
@@ -447,6 +461,7 @@ extern "C" int trc_encode_dev(int codec, const void *d_in, size_t n, uint32_t ch
     case TRC_RCX1:  trc_launch_o1bit_enc(1, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; break;
     default:        if (is_int(codec)) { trc_launch_int_enc(codec - TRC_RCG8, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; }
                     else if (is_bvlc(codec)) { trc_launch_bvlc_enc(codec - TRC_RCBV16, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 3; }
+                    else if (is_word(codec)) { trc_launch_word_enc(codec - TRC_RCW16, (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 0; }
                     else if (is_vlc(codec)) { trc_launch_vlc_enc(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 3; }
                     else if (is_vla(codec)) { trc_launch_vla_enc(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_in, n, chunk, w, d_clen, s); from_end = 4; }
                     break;
@@ -508,6 +523,7 @@ extern "C" int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_p
     case TRC_RCX1:  trc_launch_o1bit_dec(1, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s); break;
     default:        if (is_int(codec)) trc_launch_int_dec(codec - TRC_RCG8, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     else if (is_bvlc(codec)) trc_launch_bvlc_dec(codec - TRC_RCBV16, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
+                    else if (is_word(codec)) trc_launch_word_dec(codec - TRC_RCW16, (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     else if (is_vlc(codec)) trc_launch_vlc_dec(vlc_variant(codec), vlc_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     else if (is_vla(codec)) trc_launch_vla_dec(vla_variant(codec), vla_zz(codec), vla_elem(codec), (const uint8_t *)d_payload, d_clen, n, chunk, w, (uint8_t *)d_out, s);
                     break;
@@ -538,6 +554,7 @@ extern "C" const char *trc_kernel_name(int codec, int decode)
     case TRC_RCC1: case TRC_RCX1: return decode ? "trc_rc_o1bit_dec_kernel" : "trc_rc_o1bit_enc_kernel";
     default: if (is_int(codec)) return decode ? "trc_rc_int_dec_kernel" : "trc_rc_int_enc_kernel";
              if (is_bvlc(codec)) return decode ? "trc_rc_bvlc_dec_kernel" : "trc_rc_bvlc_enc_kernel";
+             if (is_word(codec)) return decode ? "trc_rc_word_dec_kernel" : "trc_rc_word_enc_kernel";
              if (is_vlc(codec)) return decode ? "trc_vlc_dec_kernel" : "trc_vlc_enc_kernel";
              if (is_vla(codec)) return decode ? "trc_vla_dec_kernel" : "trc_vla_model_kernel";
     }
@@ -762,6 +779,14 @@ TRC_BVLC_HOST(rcvzsenc16, rcvzsdec16, TRC_RCBVZ16)    TRC_BVLC_HOST(rcvzsenc32, 
 TRC_BVLC_HOST(rcvgsenc16, rcvgsdec16, TRC_RCBVG16)    TRC_BVLC_HOST(rcvgsenc32, rcvgsdec32, TRC_RCBVG32)
 TRC_BVLC_HOST(rcvgzsenc16, rcvgzsdec16, TRC_RCBVGZ16) TRC_BVLC_HOST(rcvgzsenc32, rcvgzsdec32, TRC_RCBVGZ32)
 #undef TRC_BVLC_HOST
+
+// bitwise word coders (reference rc_.c:60-138, 248-342; turborc -e6 / -e7 / -e8)
+#define TRC_WORD_HOST(enc, dec, id) \
+    size_t enc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(id, in, inlen, out, nullptr, 0); } \
+    size_t dec(unsigned char *in, size_t outlen, unsigned char *out) { return host_decode(id, in, outlen, out, nullptr, 0); }
+TRC_WORD_HOST(rcsenc16, rcsdec16, TRC_RCW16)      TRC_WORD_HOST(rcsenc32, rcsdec32, TRC_RCW32)
+TRC_WORD_HOST(rccsenc32, rccsdec32, TRC_RCCW32)   TRC_WORD_HOST(rcc2senc32, rcc2sdec32, TRC_RCC2W32)
+#undef TRC_WORD_HOST
 
 // adaptive-CDF byte range coder (reference rccdf.c:187-211; turborc -e46)
 size_t rccdfenc(unsigned char *in, size_t inlen, unsigned char *out) { return host_encode(TRC_RCA, in, inlen, out, nullptr, 0); }

@@ -491,7 +491,9 @@ size_t slice_plan(int codec, uint32_t chunk, size_t nchunks, int nks, std::vecto
     size_t groups = target / ((size_t)chunk * 64);
     // an order-1 coder keeps its model per chunk of a slice in every workspace (136 KiB: anscdf1, rccs; 64 KiB: rcxs): 1 GiB of models = 7 700 chunks = 31 MB
     // slices at chunk 4096 (ADVICE r3: a 65 536-chunk slice would ask for 9 GB)
-    if (model_bytes(codec) && !forced && groups > ((size_t)1 << 30) / (64u * model_bytes(codec))) groups = ((size_t)1 << 30) / (64u * model_bytes(codec));
+    // (the word coders: 136.5 KiB .. 2.26 MiB per chunk; 1 GiB of them is 7 groups of rcc2s32, 7.3 MB at chunk 16384)
+    const size_t mpc = is_word(codec) ? trc_word_model_bytes(codec - TRC_RCW16) : model_bytes(codec);
+    if (mpc && !forced && groups > ((size_t)1 << 30) / (64u * mpc)) groups = ((size_t)1 << 30) / (64u * mpc);
     if (groups < 1) groups = 1;
     while ((ngroups + groups - 1) / groups > TRC_MAX_SLICES) groups *= 2;              // the totals area holds 4096 slices
     if (equal) {                                                                       // a short last slice would cost its stream a whole wave's time: spread the groups evenly
@@ -985,6 +987,7 @@ static size_t host_encode(int codec, const unsigned char *in, size_t inlen, unsi
     if (codec == TRC_ANSO1 && chunk < 4096u && !chunk_override) chunk = 4096u;    // also under TRC_CHUNK / trc_set_chunk: see trc_auto_chunk_codec
     if (is_o1bit(codec) && chunk < TRC_O1BIT_CHUNK_MIN && !chunk_override) chunk = TRC_O1BIT_CHUNK_MIN;      // (the same for the bitwise order-1 coders)
     if (is_bvctx(codec) && chunk < TRC_O1BIT_CHUNK_MIN && !chunk_override) chunk = TRC_O1BIT_CHUNK_MIN;      // (and the Turbo-VLC ones with 256 trees per chunk)
+    if (is_word(codec) && chunk < TRC_O1BIT_CHUNK_MIN && !chunk_override) chunk = TRC_O1BIT_CHUNK_MIN;       // (and the word coders)
     HostJob J;
     J.codec = codec; J.chunk = chunk; J.in = in; J.out = out; J.n = inlen; J.cdf = cdf;
     J.nchunks = (inlen + chunk - 1) / chunk; J.dir = 4 * J.nchunks;

@@ -64,6 +64,24 @@ struct LaneOutDirect {
     __device__ __forceinline__ void finish(bool) {}
 };
 
+// The byte sink of the integer and word coders (trc_rc_int.hip, trc_rc_word.hip): the last chunk's tail bytes come first,
+// so its words may be unaligned
+struct IntOut {
+    u8 *dst;
+    u32 wpos;
+    bool un;
+    __device__ __forceinline__ void start(u8 *d, u32 tail) { dst = d; wpos = tail; un = tail != 0u; }
+    __device__ __forceinline__ void put32(u32 v)
+    {
+        u8 *p = dst + wpos;
+        if (un) { p[0] = (u8)v; p[1] = (u8)(v >> 8); p[2] = (u8)(v >> 16); p[3] = (u8)(v >> 24); }
+        else *(u32 *)p = v;
+        wpos += 4u;
+    }
+    __device__ __forceinline__ void put32_slow(u32 v) { put32(v); }
+    __device__ __forceinline__ void put32_if(bool take, u32 v) { if (take) put32(v); }
+};
+
 // UNIT = bytes per consumed unit (4: range coders, 2: rANS)
 template <int UNIT>
 struct LaneIn {

@@ -121,6 +121,15 @@ void trc_launch_bvlc_dec(int k, const uint8_t *d_payload, const uint32_t *d_clen
                          const TrcWork &w, uint8_t *d_out, hipStream_t s);
 size_t trc_bvlc_model_bytes(int k, size_t nchunks);   // workspace bytes of w.model for nchunks chunks (0: the model is in LDS)
 
+// RCW16 .. RCC2W32: bitwise word coders (k = codec - TRC_RCW16); w.model holds trc_word_slots(k, nchunks) models of
+// trc_word_model_bytes(k), used by the chunks in rounds
+void trc_launch_word_enc(int k, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);
+void trc_launch_word_dec(int k, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
+                         const TrcWork &w, uint8_t *d_out, hipStream_t s);
+size_t trc_word_model_bytes(int k);
+size_t trc_word_slots(int k, size_t nchunks);
+void trc_o1bit_fill(uint8_t *model, size_t bytes, hipStream_t s);   // set `bytes` (a multiple of 16) of tree nodes to 0x4000
+
 // RCA / RCAI: adaptive-CDF byte range coder, 1 stream (rccdfenc / rccdfdec) or hi/lo nibbles on 2 streams (rccdfienc / rccdfidec);
 // nibble != 0: the `turborc -n` coders on values 0..15 (rccdf4enc/dec, rccdf4ienc/idec)
 void trc_launch_rca_enc(int nstreams, int nibble, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s);

@@ -83,23 +83,6 @@ __device__ __forceinline__ u32 int_elem(const u8 *p)
     return ES == 1 ? (u32)*p : ES == 2 ? (u32)*(const u16 *)p : *(const u32 *)p;
 }
 
-// The byte sink of the encoder: the last chunk's tail bytes come first, so its words may be unaligned
-struct IntOut {
-    u8 *dst;
-    u32 wpos;
-    bool un;
-    __device__ __forceinline__ void start(u8 *d, u32 tail) { dst = d; wpos = tail; un = tail != 0u; }
-    __device__ __forceinline__ void put32(u32 v)
-    {
-        u8 *p = dst + wpos;
-        if (un) { p[0] = (u8)v; p[1] = (u8)(v >> 8); p[2] = (u8)(v >> 16); p[3] = (u8)(v >> 24); }
-        else *(u32 *)p = v;
-        wpos += 4u;
-    }
-    __device__ __forceinline__ void put32_slow(u32 v) { put32(v); }
-    __device__ __forceinline__ void put32_if(bool take, u32 v) { if (take) put32(v); }
-};
-
 // models: per-wave blocks of E x 64 u16 (LDS: the workgroup's own block); emas: per-wave blocks of 256 x 64 u32 (rcrs32)
 template <int KIND, int ES>
 __global__ __launch_bounds__(64) void trc_rc_int_enc_kernel(

@@ -24,6 +24,7 @@
 #include "trc_rc.h"
 #include "trc_lane_io.h"
 #include "trc_launch.h"
+#include "trc_tree.h"
 
 #define O1B_RCX_MODEL_BYTES (512u * 64u * 2u)
 
@@ -35,17 +36,6 @@ __global__ __launch_bounds__(256) void trc_rc_o1bit_fill_kernel(u8 *__restrict__
     for (u64 i = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * 16u; i < bytes; i += (u64)gridDim.x * blockDim.x * 16u)
         *(uint4 *)(model + i) = v;
 }
-
-// u16 slot j (0..15) of eight packed dwords
-__device__ __forceinline__ u32 o1b_pick(const u32 (&q)[8], u32 j)
-{
-    u32 r = q[0];
-#pragma unroll
-    for (u32 i = 1; i < 8; i++) r = (j >> 1) == i ? q[i] : r;
-    return (j & 1u) ? r >> 16 : r & 0xffffu;
-}
-
-__device__ __forceinline__ u32 o1b_adapt(u32 p, u32 bit) { return (p - (((p - (bit << 15)) >> 5) + bit)) & 0xffffu; }
 
 // u16 offset, inside the lane's model, of node j (1..15) of the nibble tree: RCC1 `row` is the block, RCX1 the 64-node row
 template <int CTX>
@@ -211,6 +201,11 @@ __global__ __launch_bounds__(64) void trc_rc_o1bit_dec_kernel(
             dst[pos] = (u8)(((pos >> 2) == (len >> 2) ? acc : ww[(pos >> 2) & 3u]) >> (8 * (pos & 3u)));
     }
     trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)c0 * chunk, chunk, payload);
+}
+
+void trc_o1bit_fill(uint8_t *model, size_t bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL(trc_rc_o1bit_fill_kernel, dim3(4096), dim3(256), 0, s, model, (u64)bytes);
 }
 
 void trc_launch_o1bit_enc(int ctx, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)

@@ -28,6 +28,8 @@ INTBIT = ((RCG8, 1), (RCG16, 2), (RCG32, 4), (RCGZ8, 1), (RCGZ16, 2), (RCGZ32, 4
 RCBV16, RCBV32, RCBVZ16, RCBVZ32, RCBVG16, RCBVG32, RCBVGZ16, RCBVGZ32 = 43, 44, 45, 46, 47, 48, 49, 50   # Turbo-VLC on the bitwise coder (-e30/33/35/36)
 BVLC = ((RCBV16, 2), (RCBV32, 4), (RCBVZ16, 2), (RCBVZ32, 4),        # (codec, element bytes); kept out of AVAILABLE and VLC_CODECS
         (RCBVG16, 2), (RCBVG32, 4), (RCBVGZ16, 2), (RCBVGZ32, 4))    # for the same reason as CTXBIT
+RCW16, RCW32, RCCW32, RCC2W32 = 52, 53, 54, 55                                  # bitwise word coders (turborc -e6 / -e7 / -e8)
+WORD = ((RCW16, 2), (RCW32, 4), (RCCW32, 4), (RCC2W32, 4))          # (codec, element bytes); kept out of AVAILABLE for the same reason as CTXBIT
 CTXBIT = (RCC1, RCX1)      # HIP kernels too, kept out of AVAILABLE: the suites over AVAILABLE check parity against the oracle/ restatement,
                            # which has no order-1 bitwise coder; tests/test_gpu_ctxbit.py checks them against fixtures made through the reference
 CODEC_NAMES = {ANS4S: "anscdf4s", RCS1: "rccdfs", RCS2: "rccdfs2", RCA: "rccdf", ANSA: "anscdf", RCB: "rcs", RCAI: "rccdfi",
@@ -38,7 +40,8 @@ CODEC_NAMES = {ANS4S: "anscdf4s", RCS1: "rccdfs", RCS2: "rccdfs2", RCA: "rccdf",
                RCG8: "rcgs8", RCG16: "rcgs16", RCG32: "rcgs32", RCGZ8: "rcgzs8", RCGZ16: "rcgzs16", RCGZ32: "rcgzs32",
                RCR8: "rcrs8", RCR16: "rcrs16", RCR32: "rcrs32", RCRZ8: "rcrzs8", RCRZ16: "rcrzs16", RCRZ32: "rcrzs32",
                RCBV16: "rcvs16", RCBV32: "rcvs32", RCBVZ16: "rcvzs16", RCBVZ32: "rcvzs32",
-               RCBVG16: "rcvgs16", RCBVG32: "rcvgs32", RCBVGZ16: "rcvgzs16", RCBVGZ32: "rcvgzs32"}
+               RCBVG16: "rcvgs16", RCBVG32: "rcvgs32", RCBVGZ16: "rcvgzs16", RCBVGZ32: "rcvgzs32",
+               RCW16: "rcs16", RCW32: "rcs32", RCCW32: "rccs32", RCC2W32: "rcc2s32"}
 VLC_CODECS = (VLCU16, VLCU32, VLCV16, VLCV32, VLCVZ16, VLCVZ32, VLAU16, VLAUZ16, VLAV16, VLAVZ16, VLAV32, VLAVZ32)
 VLC_ELEM = {VLCU16: 2, VLCU32: 4, VLCV16: 2, VLCV32: 4, VLCVZ16: 2, VLCVZ32: 4,
             VLAU16: 2, VLAUZ16: 2, VLAV16: 2, VLAVZ16: 2, VLAV32: 4, VLAVZ32: 4}
@@ -233,7 +236,8 @@ _HOST_ENC = {ANS4S: "anscdf4senc", RCS1: "rccdfsenc", RCS2: "rccdfs2enc", RCA: "
              RCG8: "rcgsenc8", RCG16: "rcgsenc16", RCG32: "rcgsenc32", RCGZ8: "rcgzsenc8", RCGZ16: "rcgzsenc16", RCGZ32: "rcgzsenc32",
              RCR8: "rcrsenc8", RCR16: "rcrsenc16", RCR32: "rcrsenc32", RCRZ8: "rcrzsenc8", RCRZ16: "rcrzsenc16", RCRZ32: "rcrzsenc32",
              RCBV16: "rcvsenc16", RCBV32: "rcvsenc32", RCBVZ16: "rcvzsenc16", RCBVZ32: "rcvzsenc32",
-             RCBVG16: "rcvgsenc16", RCBVG32: "rcvgsenc32", RCBVGZ16: "rcvgzsenc16", RCBVGZ32: "rcvgzsenc32"}
+             RCBVG16: "rcvgsenc16", RCBVG32: "rcvgsenc32", RCBVGZ16: "rcvgzsenc16", RCBVGZ32: "rcvgzsenc32",
+             RCW16: "rcsenc16", RCW32: "rcsenc32", RCCW32: "rccsenc32", RCC2W32: "rcc2senc32"}
 _HOST_DEC = {ANS4S: "anscdf4sdec", RCS1: "rccdfsbdec", RCS2: "rccdfsb2dec", RCA: "rccdfdec", ANSA: "anscdfdec", RCB: "rcsdec", RCAI: "rccdfidec",
              RCA4: "rccdf4dec", RCAI4: "rccdf4idec", ANSA4: "anscdf4dec", RCSM: "rccdfsmbdec", ANSO1: "anscdf1dec", ANSB: "ansbd",
              VLCU16: "rccdfudec16", VLCU32: "rccdfudec32", VLCV16: "rccdfvdec16", VLCV32: "rccdfvdec32", VLCVZ16: "rccdfvzdec16", VLCVZ32: "rccdfvzdec32",
@@ -242,7 +246,8 @@ _HOST_DEC = {ANS4S: "anscdf4sdec", RCS1: "rccdfsbdec", RCS2: "rccdfsb2dec", RCA:
              RCG8: "rcgsdec8", RCG16: "rcgsdec16", RCG32: "rcgsdec32", RCGZ8: "rcgzsdec8", RCGZ16: "rcgzsdec16", RCGZ32: "rcgzsdec32",
              RCR8: "rcrsdec8", RCR16: "rcrsdec16", RCR32: "rcrsdec32", RCRZ8: "rcrzsdec8", RCRZ16: "rcrzsdec16", RCRZ32: "rcrzsdec32",
              RCBV16: "rcvsdec16", RCBV32: "rcvsdec32", RCBVZ16: "rcvzsdec16", RCBVZ32: "rcvzsdec32",
-             RCBVG16: "rcvgsdec16", RCBVG32: "rcvgsdec32", RCBVGZ16: "rcvgzsdec16", RCBVGZ32: "rcvgzsdec32"}
+             RCBVG16: "rcvgsdec16", RCBVG32: "rcvgsdec32", RCBVGZ16: "rcvgzsdec16", RCBVGZ32: "rcvgzsdec32",
+             RCW16: "rcsdec16", RCW32: "rcsdec32", RCCW32: "rccsdec32", RCC2W32: "rcc2sdec32"}
 
 
 def _host_fn(name, codec):
