@@ -165,9 +165,12 @@ int trc_host_plan(int codec, size_t n, uint32_t chunk, int decode, int page_lock
 uint32_t trc_round_chunk(int codec, size_t n);
 
 /* ---- device-resident layer --------------------------------------------------------------------
- * All d_* pointers are device pointers on the current HIP device, 16-byte aligned, with TRC_PAD
- * readable/writable bytes of slack behind the stated size.  `stream` is a hipStream_t (NULL =
- * default stream).  Calls only enqueue work; they never synchronise.                            */
+ * All d_* pointers are device pointers on the current HIP device with TRC_PAD readable/writable
+ * bytes of slack behind the stated size.  Alignment, as trc_encode_dev / trc_decode_dev check it:
+ * d_in and d_out 16 bytes, d_work 256, d_total 8, d_clen 4, and d_payload 2 bytes only -- a
+ * payload may sit at any even offset of a container, on the encode and on the decode side
+ * (tests/test_gpu_sweep.py::test_payload_alignment).  `stream` is a hipStream_t (NULL = default
+ * stream).  Calls only enqueue work; they never synchronise.                                    */
 
 /* bytes of device workspace trc_encode_dev / trc_decode_dev need for (codec, n, chunk); 0 for an id that names no coder
  * (42, 51, above 55, negative) or a chunk trc_encode_dev rejects.  codec 0: the 4096 bytes of trc_cdfini_dev. */
