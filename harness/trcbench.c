@@ -10,7 +10,7 @@
  *
  *   trcbench [-e id[,id..]] [-I runs] [-c chunk] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)
  * ids: 1 rcs | 2 rccs | 4 rcxs | 6 rcs16 / rcs32 | 7 rccs32 | 8 rcc2s32 (word coders: --int16 / --int32 input) | 26 rcgs | 27 rcgzs | 28 rcrs | 29 rcrzs (8-bit; --int16 / --int32 inputs: the 16 / 32-bit coders) |
- *      30 rcvs | 33 rcvzs | 35 rcvgs | 36 rcvgzs (16-bit; --int32 input: the 32-bit coders) | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
+ *      17 rcu3s | 30 rcvs | 33 rcvzs | 35 rcvgs | 36 rcvgzs (16-bit; --int32 input: the 32-bit coders) | 40 rc4cs | 41 rc4s (nibble-valued input only) | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
  */
 #include <math.h>
 #include <stdio.h>
@@ -94,6 +94,9 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
     case 56: name = "ans auto nibble (anscdf4enc/anscdf4dec)"; e3 = anscdf4enc; d3 = anscdf4dec; break;
     case 57: name = "ans s nibble (anscdf4encs/anscdf4decs)"; e3 = anscdf4encs; d3 = anscdf4decs; break;
     case 58: name = "ans x nibble (anscdf4encx/anscdf4decx)"; e3 = anscdf4encx; d3 = anscdf4decx; break;
+    /* the bitwise nibble coders exist under the gate only (turborc.c:493-494): on other input ids 40 / 41 print no row */
+    case 40: name = "rc4cs bitwise nibble static (rc4csenc/rc4csdec)"; e3 = rc4csenc; d3 = rc4csdec; break;
+    case 41: name = "rc4s bitwise nibble adaptive (rc4senc/rc4sdec)"; e3 = rc4senc; d3 = rc4sdec; break;
     }
     /* 16/32-bit integer input (`turborc -Os2 / -Os4` style, here: --int16 / --int32): ids 50/52/53 are the Turbo-VLC coders */
     if (!e3 && g_elem) switch (id) {
@@ -115,6 +118,7 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
     case 1:  name = "rc o0 (rcsenc/rcsdec)"; e3 = rcsenc; d3 = rcsdec; break;
     case 2:  name = "rc o1 (rccsenc/rccsdec)"; e3 = rccsenc; d3 = rccsdec; break;
     case 4:  name = "rc o1 sliding context (rcxsenc/rcxsdec)"; e3 = rcxsenc; d3 = rcxsdec; break;
+    case 17: name = "rcu3s varint8 3/5/8 bits (rcu3senc/rcu3sdec)"; e3 = rcu3senc; d3 = rcu3sdec; break;
     case 26: name = g_elem == 4 ? "gamma 32 (rcgsenc32/rcgsdec32)" : g_elem == 2 ? "gamma 16 (rcgsenc16/rcgsdec16)" : "gamma 8 (rcgsenc8/rcgsdec8)";
              e3 = g_elem == 4 ? rcgsenc32 : g_elem == 2 ? rcgsenc16 : rcgsenc8; d3 = g_elem == 4 ? rcgsdec32 : g_elem == 2 ? rcgsdec16 : rcgsdec8; break;
     case 27: name = g_elem == 4 ? "gamma zigzag 32 (rcgzsenc32/rcgzsdec32)" : g_elem == 2 ? "gamma zigzag 16 (rcgzsenc16/rcgzsdec16)" : "gamma zigzag 8 (rcgzsenc8/rcgzsdec8)";
@@ -189,6 +193,9 @@ int main(int argc, char **argv)
         if (!strcmp(argv[i], "-e") && i + 1 < argc) ids = argv[++i];
         else if (!strcmp(argv[i], "-I") && i + 1 < argc) runs = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-c") && i + 1 < argc) { if (trc_set_chunk((unsigned)atoi(argv[++i]))) return 2; }
+        else if (!strncmp(argv[i], "-e", 2) && argv[i][2] >= '0' && argv[i][2] <= '9') ids = argv[i] + 2;    /* -e40,41 / -I1 / -c1024 as one word, the reference tool's style */
+        else if (!strncmp(argv[i], "-I", 2) && argv[i][2] >= '0' && argv[i][2] <= '9') runs = atoi(argv[i] + 2);
+        else if (!strncmp(argv[i], "-c", 2) && argv[i][2] >= '0' && argv[i][2] <= '9') { if (trc_set_chunk((unsigned)atoi(argv[i] + 2))) return 2; }
         else if (!strcmp(argv[i], "--pin")) pin = 1;   /* page-lock in / out / cpy once (what a caller that reuses its buffers would do) */
         else if (!strcmp(argv[i], "--zipf") && i + 1 < argc) { kind = 0; n = strtoull(argv[++i], 0, 10); }
         else if (!strcmp(argv[i], "--text") && i + 1 < argc) { kind = 1; n = strtoull(argv[++i], 0, 10); }

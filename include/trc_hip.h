@@ -96,6 +96,12 @@ enum trc_codec {
     TRC_RCW32 = 53,     /* rcsenc32   / rcsdec32     order 0 over the bytes of the word                      (-e6, 32-bit) */
     TRC_RCCW32 = 54,    /* rccsenc32  / rccsdec32    as rcs32, the top byte's tree by (prev >> 25) & 127      (-e7) */
     TRC_RCC2W32 = 55    /* rcc2senc32 / rcc2sdec32   as rcs32, the top byte's tree by (prev >> 20) & 0x7ff    (-e8) */
+    /* bitwise nibble and varint byte coders, "s" predictor (rc_.c:141-184, 442-462): one lane per chunk, the whole model in
+       LDS, any chunk from TRC_CHUNK_MIN up.  The two nibble coders code in[i] & 15 and their decoders return in[i] & 15, as
+       the reference does: feed them values 0..15 (harness gate m<16, turborc.c:493-494).  Ids 56 and 57 are not assigned. */
+    , TRC_RC4 = 58,     /* rc4senc    / rc4sdec      adaptive 15-node nibble tree                             (-n -e41) */
+    TRC_RC4C = 59,      /* rc4csenc   / rc4csdec     the same walk at probability 1/2: nothing adapts         (-n -e40) */
+    TRC_RCU3 = 60       /* rcu3senc   / rcu3sdec     structured 3/5/8-bit varint of a byte, 3 flags + 3 trees  (-e17) */
 };
 
 #define TRC_MAGIC        0x31435254u   /* "TRC1" */
@@ -173,7 +179,7 @@ uint32_t trc_round_chunk(int codec, size_t n);
  * stream).  Calls only enqueue work; they never synchronise.                                    */
 
 /* bytes of device workspace trc_encode_dev / trc_decode_dev need for (codec, n, chunk); 0 for an id that names no coder
- * (42, 51, above 55, negative) or a chunk trc_encode_dev rejects.  codec 0: the 4096 bytes of trc_cdfini_dev. */
+ * (42, 51, 56, 57, above 60, negative) or a chunk trc_encode_dev rejects.  codec 0: the 4096 bytes of trc_cdfini_dev. */
 size_t trc_work_bytes(int codec, size_t n, uint32_t chunk);
 
 /* cdfini on device (reference: rccdf.c:50-68): byte histogram of d_in[0..n) -> 15-bit CDF

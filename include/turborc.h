@@ -140,6 +140,16 @@ size_t rcsenc32(unsigned char *src, size_t srclen, unsigned char *dst);     size
 size_t rccsenc32(unsigned char *src, size_t srclen, unsigned char *dst);    size_t rccsdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
 size_t rcc2senc32(unsigned char *src, size_t srclen, unsigned char *dst);   size_t rcc2sdec32(unsigned char *src, size_t dstlen, unsigned char *dst);
 
+/* bitwise nibble coders, "s" predictor (reference rc_.c:141-184; `turborc -n -e41 / -e40`): an adaptive 15-node tree (rc4s*)
+ * and the same walk with probabilities that never adapt (rc4cs*).  They code src[i] & 15 and the decoders return src[i] & 15:
+ * input values above 15 lose their high nibble, as in the reference. */
+size_t rc4senc(unsigned char *src, size_t srclen, unsigned char *dst);      size_t rc4sdec(unsigned char *src, size_t dstlen, unsigned char *dst);
+size_t rc4csenc(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rc4csdec(unsigned char *src, size_t dstlen, unsigned char *dst);
+
+/* structured 3/5/8-bit varint of a byte, "s" predictor (reference rc_.c:442-462, mb_vint.h:266-300; `turborc -e17`): 0 is one
+ * flag bit, 1..8 two flags and a 3-bit tree, 9..40 three flags and a 5-bit tree, 41..255 three flags and an 8-bit tree */
+size_t rcu3senc(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcu3sdec(unsigned char *src, size_t dstlen, unsigned char *dst);
+
 #ifdef __cplusplus
 }
 #endif

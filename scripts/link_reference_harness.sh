@@ -9,7 +9,7 @@
 #   1. compile the reference objects as its makefile does (makefile:118,181,195-201,270-275), sources read where
 #      they lie, objects written to $OUT (default /tmp/trc_link);
 #   2. in rccdf.o / rc_s.o / anscdfs.o / anscdfx.o LOCALIZE every global the library exports
-#      (objcopy --localize-symbols): the objects keep their non-hot functions (rc4senc, rccdfenc8, mbc_c, ...),
+#      (objcopy --localize-symbols): the objects keep their non-hot functions (rcc2senc, rcx2senc, mbc_c, ...),
 #      which the harness still needs at link time, but no longer define the hot names;
 #   3. link turborc.o + objects + -lturborc_hip;
 #   4. assert with nm that every hot symbol is UNDEFINED in the executable and (readelf) NEEDED from the library,

@@ -124,6 +124,12 @@ static size_t word_area(const TrcCodec &c, size_t nchunks) { return trc_word_slo
     { .id = i, LAUNCH(word), .k = i - TRC_RCW16, .gather = TRC_GATHER_START, .wave_ns = ns, .round_lanes = 327680u, \
       .auto_max = TRC_AUTO_CHUNK_MAX, .floor = TRC_O1BIT_CHUNK_MIN, .chunk_max = TRC_CHUNK_MAX, .pad = 256, .model_area = word_area, \
       .slice_model = word_model, KERNELS("trc_rc_word_enc_kernel", "trc_rc_word_dec_kernel") }
+// one lane per chunk, the whole model in LDS (rc4s 2 KiB per wave, rcu3s 37.4 KiB, rc4cs none): no floor, any chunk from 256 up.
+// wave_ns from the chunk-16384 runs of the 100 MB sweep in profiles/nibbit/nibbit_notes.md (chip a tenth full); round_lanes from
+// the sweep's best chunk: rc4s 512 (256 is no faster), rc4cs 1024, rcu3s 1536 (four waves per CU, as its LDS allows)
+#define NIBBIT(i, ns, lanes) \
+    { .id = i, LAUNCH(nibbit), .k = i - TRC_RC4, .gather = TRC_GATHER_START, .wave_ns = ns, .round_lanes = lanes, \
+      .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, .pad = 128, KERNELS("trc_rc_nib_enc_kernel", "trc_rc_nib_dec_kernel") }
 // what an id without a coder answers to trc_auto_chunk_codec / trc_round_chunk
 #define NONE(i) { .id = i, .wave_ns = 400, .round_lanes = 327680u, .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, KERNELS("", "") }
 
@@ -160,6 +166,8 @@ static constexpr TrcCodec g_codecs[] = {
     BVLC(TRC_RCBVG16, 0, 1352), BVLC(TRC_RCBVG32, 0, 728), BVLC(TRC_RCBVGZ16, 0, 1383), BVLC(TRC_RCBVGZ32, 0, 781),
     NONE(51),
     WORD(TRC_RCW16, 1340), WORD(TRC_RCW32, 1430), WORD(TRC_RCCW32, 1460), WORD(TRC_RCC2W32, 1440),
+    NONE(56), NONE(57),
+    NIBBIT(TRC_RC4, 570, 196608u), NIBBIT(TRC_RC4C, 320, 98304u), NIBBIT(TRC_RCU3, 1500, TRC_MODEL_ROUND_CHUNKS),
 };
 #undef LAUNCH
 #undef KERNELS
@@ -171,6 +179,7 @@ static constexpr TrcCodec g_codecs[] = {
 #undef INT
 #undef BVLC
 #undef WORD
+#undef NIBBIT
 #undef NONE
 static constexpr int TRC_NCODECS = (int)(sizeof g_codecs / sizeof g_codecs[0]);
 static constexpr bool rows_in_id_order()
@@ -731,6 +740,10 @@ TRC_HOST(rcvgzsenc16, rcvgzsdec16, TRC_RCBVGZ16) TRC_HOST(rcvgzsenc32, rcvgzsdec
 // bitwise word coders (reference rc_.c:60-138, 248-342; turborc -e6 / -e7 / -e8)
 TRC_HOST(rcsenc16, rcsdec16, TRC_RCW16)      TRC_HOST(rcsenc32, rcsdec32, TRC_RCW32)
 TRC_HOST(rccsenc32, rccsdec32, TRC_RCCW32)   TRC_HOST(rcc2senc32, rcc2sdec32, TRC_RCC2W32)
+
+// bitwise nibble coders, adaptive and static (reference rc_.c:141-184; turborc -n -e41 / -e40), and the structured 3/5/8-bit
+// varint byte coder (rc_.c:442-462; turborc -e17)
+TRC_HOST(rc4senc, rc4sdec, TRC_RC4)          TRC_HOST(rc4csenc, rc4csdec, TRC_RC4C)       TRC_HOST(rcu3senc, rcu3sdec, TRC_RCU3)
 
 // adaptive-CDF byte range coder (reference rccdf.c:187-211; turborc -e46)
 TRC_HOST(rccdfenc, rccdfdec, TRC_RCA)

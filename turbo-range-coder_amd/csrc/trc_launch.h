@@ -107,7 +107,7 @@ struct TrcCodec {
     TrcEncFn *enc;             // null: the id is not assigned
     TrcDecFn *dec;
     // the family's parameters
-    int8_t k;                  // index within the family (integer, Turbo-VLC bitwise, word coders); the order-1 bitwise context (0 rccs, 1 rcxs)
+    int8_t k;                  // index within the family (integer, Turbo-VLC bitwise, word, nibble / varint coders); the order-1 bitwise context (0 rccs, 1 rcxs)
     int8_t streams;            // static / adaptive / vnibble range coders: 1 or 2 streams; -1: rccdfsm
     int8_t nibble;             // adaptive coders on values 0..15
     int8_t variant;            // Turbo-VLC: 0 u, 1 v, 2 vz (over rANS: 0 u, 1 v)
@@ -154,6 +154,8 @@ size_t trc_bvlc_model_bytes(int k, size_t nchunks);   // workspace bytes of w.mo
 TrcEncFn trc_launch_word_enc;   TrcDecFn trc_launch_word_dec;
 size_t trc_word_model_bytes(int k);
 size_t trc_word_slots(int k, size_t nchunks);
+// RC4 / RC4C / RCU3: bitwise nibble and varint byte coders (k = codec - TRC_RC4: rc4s, rc4cs, rcu3s); models in LDS, none for rc4cs
+TrcEncFn trc_launch_nibbit_enc; TrcDecFn trc_launch_nibbit_dec;
 void trc_o1bit_fill(uint8_t *model, size_t bytes, hipStream_t s);   // set `bytes` (a multiple of 16) of tree nodes to 0x4000
 // RCA / RCAI: adaptive-CDF byte range coder, 1 stream (rccdfenc / rccdfdec) or hi/lo nibbles on 2 streams (rccdfienc / rccdfidec);
 // nibble != 0: the `turborc -n` coders on values 0..15 (rccdf4enc/dec, rccdf4ienc/idec)

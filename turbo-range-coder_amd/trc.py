@@ -30,6 +30,8 @@ BVLC = ((RCBV16, 2), (RCBV32, 4), (RCBVZ16, 2), (RCBVZ32, 4),        # (codec, e
         (RCBVG16, 2), (RCBVG32, 4), (RCBVGZ16, 2), (RCBVGZ32, 4))    # for the same reason as CTXBIT
 RCW16, RCW32, RCCW32, RCC2W32 = 52, 53, 54, 55                                  # bitwise word coders (turborc -e6 / -e7 / -e8)
 WORD = ((RCW16, 2), (RCW32, 4), (RCCW32, 4), (RCC2W32, 4))          # (codec, element bytes); kept out of AVAILABLE for the same reason as CTXBIT
+RC4, RC4C, RCU3 = 58, 59, 60                                                    # bitwise nibble coders (turborc -n -e41 / -e40), 3/5/8-bit varint (-e17)
+NIBBIT = ((RC4, 1), (RC4C, 1), (RCU3, 1))                           # (codec, element bytes); kept out of AVAILABLE for the same reason as CTXBIT
 CTXBIT = (RCC1, RCX1)      # HIP kernels too, kept out of AVAILABLE: the suites over AVAILABLE check parity against the oracle/ restatement,
                            # which has no order-1 bitwise coder; tests/test_gpu_ctxbit.py checks them against fixtures made through the reference
 CODEC_NAMES = {ANS4S: "anscdf4s", RCS1: "rccdfs", RCS2: "rccdfs2", RCA: "rccdf", ANSA: "anscdf", RCB: "rcs", RCAI: "rccdfi",
@@ -41,7 +43,8 @@ CODEC_NAMES = {ANS4S: "anscdf4s", RCS1: "rccdfs", RCS2: "rccdfs2", RCA: "rccdf",
                RCR8: "rcrs8", RCR16: "rcrs16", RCR32: "rcrs32", RCRZ8: "rcrzs8", RCRZ16: "rcrzs16", RCRZ32: "rcrzs32",
                RCBV16: "rcvs16", RCBV32: "rcvs32", RCBVZ16: "rcvzs16", RCBVZ32: "rcvzs32",
                RCBVG16: "rcvgs16", RCBVG32: "rcvgs32", RCBVGZ16: "rcvgzs16", RCBVGZ32: "rcvgzs32",
-               RCW16: "rcs16", RCW32: "rcs32", RCCW32: "rccs32", RCC2W32: "rcc2s32"}
+               RCW16: "rcs16", RCW32: "rcs32", RCCW32: "rccs32", RCC2W32: "rcc2s32",
+               RC4: "rc4s", RC4C: "rc4cs", RCU3: "rcu3s"}
 VLC_CODECS = (VLCU16, VLCU32, VLCV16, VLCV32, VLCVZ16, VLCVZ32, VLAU16, VLAUZ16, VLAV16, VLAVZ16, VLAV32, VLAVZ32)
 VLC_ELEM = {VLCU16: 2, VLCU32: 4, VLCV16: 2, VLCV32: 4, VLCVZ16: 2, VLCVZ32: 4,
             VLAU16: 2, VLAUZ16: 2, VLAV16: 2, VLAVZ16: 2, VLAV32: 4, VLAVZ32: 4}
@@ -237,7 +240,8 @@ _HOST_ENC = {ANS4S: "anscdf4senc", RCS1: "rccdfsenc", RCS2: "rccdfs2enc", RCA: "
              RCR8: "rcrsenc8", RCR16: "rcrsenc16", RCR32: "rcrsenc32", RCRZ8: "rcrzsenc8", RCRZ16: "rcrzsenc16", RCRZ32: "rcrzsenc32",
              RCBV16: "rcvsenc16", RCBV32: "rcvsenc32", RCBVZ16: "rcvzsenc16", RCBVZ32: "rcvzsenc32",
              RCBVG16: "rcvgsenc16", RCBVG32: "rcvgsenc32", RCBVGZ16: "rcvgzsenc16", RCBVGZ32: "rcvgzsenc32",
-             RCW16: "rcsenc16", RCW32: "rcsenc32", RCCW32: "rccsenc32", RCC2W32: "rcc2senc32"}
+             RCW16: "rcsenc16", RCW32: "rcsenc32", RCCW32: "rccsenc32", RCC2W32: "rcc2senc32",
+             RC4: "rc4senc", RC4C: "rc4csenc", RCU3: "rcu3senc"}
 _HOST_DEC = {ANS4S: "anscdf4sdec", RCS1: "rccdfsbdec", RCS2: "rccdfsb2dec", RCA: "rccdfdec", ANSA: "anscdfdec", RCB: "rcsdec", RCAI: "rccdfidec",
              RCA4: "rccdf4dec", RCAI4: "rccdf4idec", ANSA4: "anscdf4dec", RCSM: "rccdfsmbdec", ANSO1: "anscdf1dec", ANSB: "ansbd",
              VLCU16: "rccdfudec16", VLCU32: "rccdfudec32", VLCV16: "rccdfvdec16", VLCV32: "rccdfvdec32", VLCVZ16: "rccdfvzdec16", VLCVZ32: "rccdfvzdec32",
@@ -247,7 +251,8 @@ _HOST_DEC = {ANS4S: "anscdf4sdec", RCS1: "rccdfsbdec", RCS2: "rccdfsb2dec", RCA:
              RCR8: "rcrsdec8", RCR16: "rcrsdec16", RCR32: "rcrsdec32", RCRZ8: "rcrzsdec8", RCRZ16: "rcrzsdec16", RCRZ32: "rcrzsdec32",
              RCBV16: "rcvsdec16", RCBV32: "rcvsdec32", RCBVZ16: "rcvzsdec16", RCBVZ32: "rcvzsdec32",
              RCBVG16: "rcvgsdec16", RCBVG32: "rcvgsdec32", RCBVGZ16: "rcvgzsdec16", RCBVGZ32: "rcvgzsdec32",
-             RCW16: "rcsdec16", RCW32: "rcsdec32", RCCW32: "rccsdec32", RCC2W32: "rcc2sdec32"}
+             RCW16: "rcsdec16", RCW32: "rcsdec32", RCCW32: "rccsdec32", RCC2W32: "rcc2sdec32",
+             RC4: "rc4sdec", RC4C: "rc4csdec", RCU3: "rcu3sdec"}
 
 
 def _host_fn(name, codec):
