@@ -28,9 +28,10 @@
 // Decoder bounds (a corrupt payload neither leaves the lane's model nor its chunk): the 16-bit tree coders take the high
 // nibble & 7 for the block; the gamma unary walk stops at mgu[7]; the mantissa length is clamped to 28 bits; the header total
 // is clamped to [8, clen] and the mantissa window to the bytes above the chunk's start; range-coder reads stop at clen.
-#include "trc_rc.h"
+#include "trc_rc_lane.h"
 #include "trc_lane_io.h"
 #include "trc_vlc.h"
+#include "trc_tree.h"
 #include "trc_launch.h"
 
 // K: 0 rcvs16, 1 rcvs32, 2 rcvzs16, 3 rcvzs32, 4 rcvgs16, 5 rcvgs32, 6 rcvgzs16, 7 rcvgzs32 (= codec - TRC_RCBV16)
@@ -53,7 +54,6 @@ __global__ __launch_bounds__(256) void trc_rc_bvlc_fill_kernel(u8 *__restrict__ 
         *(uint4 *)(model + i) = v;
 }
 
-__device__ __forceinline__ u32 bv_adapt(u32 p, u32 bit) { return (p - (((p - (bit << 15)) >> 5) + bit)) & 0xffffu; }
 __device__ __forceinline__ u32 bv_bsr(u32 x) { return 31u - (u32)__clz((int)x); }
 template <u32 ES>
 __device__ __forceinline__ u32 bv_zz_enc(u32 d) { return vlc_zigzag_enc(d, ES == 4); }
@@ -64,16 +64,9 @@ __device__ __forceinline__ u32 bv_vb32(u32 mx)
     const u32 f = bv_bsr(mx) - 3u, expo = ((f + 1u) << 3) + ((mx >> f) & 7u);
     return 255u - expo;
 }
-// u16 slot j (0..15) of eight packed dwords
-__device__ __forceinline__ u32 bv_pick(const u32 (&q)[8], u32 j)
-{
-    u32 r = q[0];
-#pragma unroll
-    for (u32 i = 1; i < 8; i++) r = (j >> 1) == i ? q[i] : r;
-    return (j & 1u) ? r >> 16 : r & 0xffffu;
-}
 
-// The byte sink of the encoder: header and tail come first, so the words may be unaligned
+// The byte sink of the encoder: header and tail come first, so the words may be unaligned.  Not IntOut (trc_lane_io.h), which
+// takes any offset but 0 for unaligned: rcvs32's 5-byte header and a 3-byte tail make an aligned start here.
 struct BvOut {
     u8 *dst;
     u32 wpos;
@@ -103,7 +96,7 @@ struct BvTree {
             q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = b.x; q[5] = b.y; q[6] = b.z; q[7] = b.w;
         }
     }
-    __device__ __forceinline__ u32 prob(u32 base, u32 j) const { if constexpr (LDS) return m[(base + j) * 64u]; else return bv_pick(q, j); }
+    __device__ __forceinline__ u32 prob(u32 base, u32 j) const { if constexpr (LDS) return m[(base + j) * 64u]; else return o1b_pick(q, j); }
     __device__ __forceinline__ void store(u32 base, u32 j, u32 v) const { if constexpr (LDS) m[(base + j) * 64u] = (u16)v; else m[base + j] = (u16)v; }
 };
 
@@ -115,6 +108,7 @@ __global__ __launch_bounds__(64) void trc_rc_bvlc_enc_kernel(
     using C = BvCfg<K>;
     constexpr u32 ES = C::ES;
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
+    // (own text: taking this prologue from trc_rc_lane.h changes the generated code, profiles/lanecore_notes.md)
     const u32 lane = trc_lane(), c = blockIdx.x * 64u + lane;
     const bool alive = c < nchunks;
     const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
@@ -123,8 +117,7 @@ __global__ __launch_bounds__(64) void trc_rc_bvlc_enc_kernel(
     u16 *m;
     if constexpr (C::LDS_SLOTS != 0) {
         m = (u16 *)smem + lane;
-        for (u32 i = lane; i < C::LDS_SLOTS * 32u; i += 64u) ((u32 *)smem)[i] = 0x40004000u;
-        __syncthreads();
+        trc_lds_fill<C::LDS_SLOTS>(smem, lane);
     } else m = models + (u64)(alive ? c : 0u) * (256u * C::ROW);
     const u8 *src = in + (u64)c * chunk;
     u8 *const dst = scratch + (u64)c * stride;
@@ -141,11 +134,12 @@ __global__ __launch_bounds__(64) void trc_rc_bvlc_enc_kernel(
     RcEnc e; e.start();
 
     auto bit = [&](u16 *p, u32 b) __attribute__((always_inline)) {     // one decision on *p, no renormalisation
+        // (own text: trc_rcbe of trc_rc_lane.h changes this kernel's generated code)
         const u32 pr = *p;
         const u64 cut = (e.range >> TRC_PROB_BITS) * pr;
         e.low += b ? 0 : cut;
         e.range = b ? cut : e.range - cut;
-        *p = (u16)bv_adapt(pr, b);
+        *p = (u16)trc_bit_adapt(pr, b);
     };
     // the tree: both blocks of the symbol's path loaded before the first decision
     auto code_tree = [&](u32 row, u32 s) __attribute__((always_inline)) {
@@ -159,10 +153,8 @@ __global__ __launch_bounds__(64) void trc_rc_bvlc_enc_kernel(
                 if ((k & 1) == 0) e.renorm(so);                 // before bits 7, 5 (3, 1)
                 const u32 b = (v >> (3 - k)) & 1u;
                 const u32 pr = t.prob(base, j);
-                const u64 cut = (e.range >> TRC_PROB_BITS) * pr;
-                e.low += b ? 0 : cut;
-                e.range = b ? cut : e.range - cut;
-                t.store(base, j, bv_adapt(pr, b));
+                trc_rcbe(e, pr, b);
+                t.store(base, j, trc_bit_adapt(pr, b));
                 j = 2u * j + b;
             }
         };
@@ -222,6 +214,7 @@ __global__ __launch_bounds__(64) void trc_rc_bvlc_dec_kernel(
     using C = BvCfg<K>;
     constexpr u32 ES = C::ES;
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
+    // (own text: taking this prologue from trc_rc_lane.h changes the generated code, profiles/lanecore_notes.md)
     const u32 lane = trc_lane(), c0 = blockIdx.x * 64u, c = c0 + lane;
     const bool alive = c < nchunks;
     const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
@@ -233,6 +226,7 @@ __global__ __launch_bounds__(64) void trc_rc_bvlc_dec_kernel(
     u16 *m;
     if constexpr (C::LDS_SLOTS != 0) {
         m = (u16 *)smem + lane;
+        // (own text: trc_lds_fill of trc_rc_lane.h changes this kernel's generated code)
         for (u32 i = lane; i < C::LDS_SLOTS * 32u; i += 64u) ((u32 *)smem)[i] = 0x40004000u;
         __syncthreads();
     } else m = models + (u64)(alive ? c : 0u) * (256u * C::ROW);
@@ -260,7 +254,7 @@ __global__ __launch_bounds__(64) void trc_rc_bvlc_dec_kernel(
             b = code < cut ? 1u : 0u;
             range = b ? cut : range - cut;
             code = b ? code : code - cut;
-            return bv_adapt(pr, b);
+            return trc_bit_adapt(pr, b);
         };
         auto get_nibble = [&](u32 blk) __attribute__((always_inline)) -> u32 {
             BvTree<C::LDS_SLOTS != 0> t{m};
@@ -357,12 +351,10 @@ static void bv_dispatch(int k, bool dec, const uint8_t *d_src, const uint32_t *d
 
 void trc_launch_bvlc_enc(const TrcCodec &c, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
-    const int k = c.k;
-    bv_dispatch(k, false, d_in, nullptr, n, chunk, w, d_clen, nullptr, s);
+    bv_dispatch(c.k, false, d_in, nullptr, n, chunk, w, d_clen, nullptr, s);
 }
 void trc_launch_bvlc_dec(const TrcCodec &c, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                          const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    const int k = c.k;
-    bv_dispatch(k, true, d_payload, d_clen, n, chunk, w, nullptr, d_out, s);
+    bv_dispatch(c.k, true, d_payload, d_clen, n, chunk, w, nullptr, d_out, s);
 }

@@ -30,7 +30,7 @@
 // Decoder bounds (a corrupt payload neither leaves the lane's model nor spins): the unary walk stops at mgu[U-1] whatever the
 // bit (`unary` below); the escape reads qb-1 <= U-14 bits into row 0 (< C for every variant); the gamma-32 quotient is clamped
 // to 32, the Rice mantissa row to R-1 and k to C; every loop runs at most a fixed count; stream reads stop at the chunk's end.
-#include "trc_rc.h"
+#include "trc_rc_lane.h"
 #include "trc_lane_io.h"
 #include "trc_launch.h"
 
@@ -55,7 +55,6 @@ __global__ __launch_bounds__(256) void trc_rc_int_fill_kernel(u32 *__restrict__ 
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (u64)gridDim.x * blockDim.x) p[i] = v;
 }
 
-__device__ __forceinline__ u32 int_adapt(u32 p, u32 bit) { return (p - (((p - (bit << 15)) >> 5) + bit)) & 0xffffu; }
 __device__ __forceinline__ u32 int_bsr(u32 x) { return 31u - (u32)__clz((int)x); }           // (x == 0: ~0u)
 __device__ __forceinline__ u32 int_ema(u32 n, u32 ema, u32 x)
 {
@@ -91,16 +90,13 @@ __global__ __launch_bounds__(64) void trc_rc_int_enc_kernel(
 {
     using K = IntCfg<KIND, ES>;
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    const u32 lane = trc_lane(), c = blockIdx.x * 64u + lane;
-    const bool alive = c < nchunks;
-    const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
+    const auto [lane, c, c0, alive, len] = trc_lane_enc(n, chunk, nchunks);
     const u32 nel = len / ES, tail = len - nel * ES;
     const int lim = trc_rc_limit(len);
     u16 *m;
     if constexpr (K::LDS) {
         m = (u16 *)smem + lane;
-        for (u32 i = lane; i < K::E * 32u; i += 64u) ((u32 *)smem)[i] = 0x40004000u;
-        __syncthreads();
+        trc_lds_fill<K::E>(smem, lane);
     } else m = models + (u64)blockIdx.x * K::E * 64u + lane;
     u32 *const ema_t = K::CTX ? emas + (u64)blockIdx.x * INT_CTX_EMA * 64u + lane : nullptr;
     const u8 *src = in + (u64)c * chunk;
@@ -112,10 +108,8 @@ __global__ __launch_bounds__(64) void trc_rc_int_enc_kernel(
     auto bit = [&](u32 a, u32 b) __attribute__((always_inline)) {
         e.renorm(so);
         const u32 p = m[a * 64u];
-        const u64 cut = (e.range >> TRC_PROB_BITS) * p;
-        e.low += b ? 0 : cut;
-        e.range = b ? cut : e.range - cut;
-        m[a * 64u] = (u16)int_adapt(p, b);
+        trc_rcbe(e, p, b);
+        m[a * 64u] = (u16)trc_bit_adapt(p, b);
     };
     auto unary = [&](u32 cnt) __attribute__((always_inline)) {     // cnt zeros and a one on mgu[0..cnt]
         for (u32 u = 0; u < cnt; u++) bit(K::MGU + u, 0);
@@ -182,17 +176,14 @@ __global__ __launch_bounds__(64) void trc_rc_int_dec_kernel(
 {
     using K = IntCfg<KIND, ES>;
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    const u32 lane = trc_lane(), c0 = blockIdx.x * 64u, c = c0 + lane;
-    const bool alive = c < nchunks;
-    const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
-    const u32 cl = alive ? trc_min(clen[c], len) : 0u;        // a directory entry above the chunk length (corrupt input) reads as raw
-    const u32 ex = trc_wave_incl_scan(cl) - cl;
-    const u64 off = trc_group_base(goff, gsum, blockIdx.x) + ex;
+    const TrcLaneDec L = trc_lane_dec(n, chunk, nchunks, clen, goff, gsum);
+    const auto [lane, c, c0, alive, len, cl, off] = L;
     const u32 nel = len / ES, tail = len - nel * ES;
     const bool coded = alive && cl != len && cl >= tail;
     u16 *m;
     if constexpr (K::LDS) {
         m = (u16 *)smem + lane;
+        // (own text: trc_lds_fill of trc_rc_lane.h changes this kernel's generated code)
         for (u32 i = lane; i < K::E * 32u; i += 64u) ((u32 *)smem)[i] = 0x40004000u;
         __syncthreads();
     } else m = models + (u64)blockIdx.x * K::E * 64u + lane;
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(64) void trc_rc_int_dec_kernel(
             const u32 b = code < cut ? 1u : 0u;
             range = b ? cut : range - cut;
             code = b ? code : code - cut;
-            m[a * 64u] = (u16)int_adapt(p, b);
+            m[a * 64u] = (u16)trc_bit_adapt(p, b);
             return b;
         };
         auto unary = [&]() __attribute__((always_inline)) -> u32 {   // zeros before the one; stops at mgu[U-1] whatever the bit
@@ -267,7 +258,7 @@ __global__ __launch_bounds__(64) void trc_rc_int_dec_kernel(
         if constexpr (ES < 4)                                   // ragged end (the last chunk only): byte stores, nothing past n
             for (u32 pos = (nel * ES) & ~3u; pos < nel * ES; pos++) dst[pos] = (u8)(acc >> (8u * (pos & 3u)));
     }
-    trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)c0 * chunk, chunk, payload);
+    trc_lane_copy_raw(L, chunk, payload, out);
 }
 
 // codec index k = codec - TRC_RCG8: 0-2 gamma 8/16/32, 3-5 gamma zigzag, 6-8 Rice, 9-11 Rice zigzag
@@ -285,7 +276,6 @@ static void int_launch(bool dec, const uint8_t *d_src, const uint32_t *d_clen_in
                        uint32_t *d_clen, uint8_t *d_out, hipStream_t s)
 {
     using K = IntCfg<KIND, ES>;
-    u16 *models = (u16 *)w.model;
     u32 *emas = nullptr;
     const uint32_t lds = K::LDS ? K::E * 128u : 0u;
     if (!K::LDS) {
@@ -297,9 +287,9 @@ static void int_launch(bool dec, const uint8_t *d_src, const uint32_t *d_clen_in
         }
     }
     if (dec) TRC_LAUNCH_TIMED((trc_rc_int_dec_kernel<KIND, ES>), dim3(w.ngroups), dim3(64), lds, s,
-                              d_src, d_clen_in, w.goff, w.gsum, (u64)n, chunk, w.nchunks, models, emas, d_out);
+                              d_src, d_clen_in, w.goff, w.gsum, (u64)n, chunk, w.nchunks, (u16 *)w.model, emas, d_out);
     else TRC_LAUNCH_TIMED((trc_rc_int_enc_kernel<KIND, ES>), dim3(w.ngroups), dim3(64), lds, s,
-                          d_src, (u64)n, chunk, w.nchunks, models, emas, w.scratch, w.stride, d_clen, w.gsum);
+                          d_src, (u64)n, chunk, w.nchunks, (u16 *)w.model, emas, w.scratch, w.stride, d_clen, w.gsum);
 }
 
 static void int_dispatch(int k, bool dec, const uint8_t *d_src, const uint32_t *d_clen_in, size_t n, uint32_t chunk,
@@ -318,12 +308,10 @@ static void int_dispatch(int k, bool dec, const uint8_t *d_src, const uint32_t *
 
 void trc_launch_int_enc(const TrcCodec &c, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
-    const int k = c.k;
-    int_dispatch(k, false, d_in, nullptr, n, chunk, w, d_clen, nullptr, s);
+    int_dispatch(c.k, false, d_in, nullptr, n, chunk, w, d_clen, nullptr, s);
 }
 void trc_launch_int_dec(const TrcCodec &c, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                         const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    const int k = c.k;
-    int_dispatch(k, true, d_payload, d_clen, n, chunk, w, nullptr, d_out, s);
+    int_dispatch(c.k, true, d_payload, d_clen, n, chunk, w, nullptr, d_out, s);
 }

@@ -22,7 +22,7 @@
 // Decoder bounds (a corrupt payload neither leaves the lane's model nor spins): a tree index is 1 followed by at most nb-1
 // decoded bits (< 2^nb), a flag index is 0 .. 2; every loop runs a fixed count; stream reads stop at the chunk's clen (a
 // directory entry above the chunk length reads as raw), writes at the chunk's length.
-#include "trc_rc.h"
+#include "trc_rc_lane.h"
 #include "trc_lane_io.h"
 #include "trc_launch.h"
 
@@ -34,8 +34,6 @@ struct NibCfg {
     static constexpr u32 E = KIND == 0 ? 16u : KIND == 1 ? 0u : T8 + 256u;          // model entries
 };
 
-__device__ __forceinline__ u32 nib_adapt(u32 p, u32 bit) { return (p - (((p - (bit << 15)) >> 5) + bit)) & 0xffffu; }
-
 template <int KIND>
 __global__ __launch_bounds__(64) void trc_rc_nib_enc_kernel(
     const u8 *__restrict__ in, u64 n, u32 chunk, u32 nchunks, u8 *__restrict__ scratch, u32 stride, u32 *__restrict__ clen,
@@ -43,11 +41,10 @@ __global__ __launch_bounds__(64) void trc_rc_nib_enc_kernel(
 {
     using K = NibCfg<KIND>;
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    const u32 lane = trc_lane(), c = blockIdx.x * 64u + lane;
-    const bool alive = c < nchunks;
-    const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
+    const auto [lane, c, c0, alive, len] = trc_lane_enc(n, chunk, nchunks);
     const int lim = trc_rc_limit(len);
     u16 *const m = (u16 *)smem + lane;
+    // (own text: trc_lds_fill of trc_rc_lane.h changes this kernel's generated code)
     if constexpr (K::E != 0u) {
         for (u32 i = lane; i < K::E * 32u; i += 64u) ((u32 *)smem)[i] = 0x40004000u;
         __syncthreads();
@@ -56,12 +53,12 @@ __global__ __launch_bounds__(64) void trc_rc_nib_enc_kernel(
     LaneOutDirect so; so.start(scratch + (u64)c * stride);
     RcEnc e; e.start();
 
-    auto bit = [&](u32 a, u32 b) __attribute__((always_inline)) {  // rcbe: no renormalisation
+    auto bit = [&](u32 a, u32 b) __attribute__((always_inline)) {  // rcbe: no renormalisation (own text: trc_rcbe changes enc<0>)
         const u32 p = K::ADAPT ? (u32)m[a * 64u] : TRC_PROB_ONE >> 1;
         const u64 cut = (e.range >> TRC_PROB_BITS) * p;
         e.low += b ? 0 : cut;
         e.range = b ? cut : e.range - cut;
-        if constexpr (K::ADAPT) m[a * 64u] = (u16)nib_adapt(p, b);
+        if constexpr (K::ADAPT) m[a * 64u] = (u16)trc_bit_adapt(p, b);
     };
     auto flag = [&](u32 a, u32 b) __attribute__((always_inline)) { e.renorm(so); bit(a, b); };   // rcbenc
 
@@ -110,14 +107,11 @@ __global__ __launch_bounds__(64) void trc_rc_nib_dec_kernel(
 {
     using K = NibCfg<KIND>;
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    const u32 lane = trc_lane(), c0 = blockIdx.x * 64u, c = c0 + lane;
-    const bool alive = c < nchunks;
-    const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
-    const u32 cl = alive ? trc_min(clen[c], len) : 0u;        // a directory entry above the chunk length (corrupt input) reads as raw
-    const u32 ex = trc_wave_incl_scan(cl) - cl;
-    const u64 off = trc_group_base(goff, gsum, blockIdx.x) + ex;
+    const TrcLaneDec L = trc_lane_dec(n, chunk, nchunks, clen, goff, gsum);
+    const auto [lane, c, c0, alive, len, cl, off] = L;
     const bool coded = alive && cl != len;
     u16 *const m = (u16 *)smem + lane;
+    // (own text: trc_lds_fill of trc_rc_lane.h changes this kernel's generated code)
     if constexpr (K::E != 0u) {
         for (u32 i = lane; i < K::E * 32u; i += 64u) ((u32 *)smem)[i] = 0x40004000u;
         __syncthreads();
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(64) void trc_rc_nib_dec_kernel(
             const u32 b = code < cut ? 1u : 0u;
             range = b ? cut : range - cut;
             code = b ? code : code - cut;
-            if constexpr (K::ADAPT) m[a * 64u] = (u16)nib_adapt(p, b);
+            if constexpr (K::ADAPT) m[a * 64u] = (u16)trc_bit_adapt(p, b);
             return b;
         };
         auto flag = [&](u32 a) __attribute__((always_inline)) -> u32 { renorm(); return bit(a); };
@@ -170,7 +164,7 @@ __global__ __launch_bounds__(64) void trc_rc_nib_dec_kernel(
         }
         for (u32 pos = len & ~3u; pos < len; pos++) dst[pos] = (u8)(acc >> (8u * (pos & 3u)));   // ragged end (the last chunk only)
     }
-    trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)c0 * chunk, chunk, payload);
+    trc_lane_copy_raw(L, chunk, payload, out);
 }
 
 // codec index k = codec - TRC_RC4: 0 rc4s, 1 rc4cs, 2 rcu3s
@@ -188,12 +182,12 @@ static void nib_launch(bool dec, const uint8_t *d_src, const uint32_t *d_clen_in
 static void nib_dispatch(int k, bool dec, const uint8_t *d_src, const uint32_t *d_clen_in, size_t n, uint32_t chunk,
                          const TrcWork &w, uint32_t *d_clen, uint8_t *d_out, hipStream_t s)
 {
+#define NIB_CASE(i) case i: nib_launch<i>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
     switch (k) {
-    case 0: nib_launch<0>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
-    case 1: nib_launch<1>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
-    case 2: nib_launch<2>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
+    NIB_CASE(0) NIB_CASE(1) NIB_CASE(2)
     default: break;
     }
+#undef NIB_CASE
 }
 
 void trc_launch_nibbit_enc(const TrcCodec &c, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)

@@ -21,7 +21,7 @@
 // block; RCX1: 15 independent u16 reads, their addresses a function of w4), so a byte costs two dependent rounds of loads
 // instead of eight; the probabilities are picked from registers as the bits are decoded, the adapted ones stored back.
 // The encoder knows every node from the byte; it reads, codes and adapts them one bit after the other.
-#include "trc_rc.h"
+#include "trc_rc_lane.h"
 #include "trc_lane_io.h"
 #include "trc_launch.h"
 #include "trc_tree.h"
@@ -51,6 +51,7 @@ __global__ __launch_bounds__(64) void trc_rc_o1bit_enc_kernel(
     const u8 *__restrict__ in, u64 n, u32 chunk, u32 nchunks, u16 *__restrict__ models, u32 mstride,
     u8 *__restrict__ scratch, u32 stride, u32 *__restrict__ clen, u32 *__restrict__ gsum)
 {
+    // (own text: taking this prologue from trc_rc_lane.h changes the generated code, profiles/lanecore_notes.md)
     const u32 lane = trc_lane(), c = blockIdx.x * 64u + lane;
     const bool alive = c < nchunks;
     const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
@@ -64,10 +65,8 @@ __global__ __launch_bounds__(64) void trc_rc_o1bit_enc_kernel(
 
     auto code_bit = [&](u32 a, u32 bit) __attribute__((always_inline)) {
         const u32 p = m[a];
-        const u64 cut = (e.range >> TRC_PROB_BITS) * p;
-        e.low += bit ? 0 : cut;
-        e.range = bit ? cut : e.range - cut;
-        m[a] = (u16)o1b_adapt(p, bit);
+        trc_rcbe(e, p, bit);
+        m[a] = (u16)trc_bit_adapt(p, bit);
     };
     // one nibble v in its tree (rows and window as the context rule gives them), renormalising before the bits in `rmask`
     auto code_nibble = [&](u32 row, u32 w4, u32 v, u32 rmask) __attribute__((always_inline)) {
@@ -115,12 +114,8 @@ __global__ __launch_bounds__(64) void trc_rc_o1bit_dec_kernel(
     const u8 *__restrict__ payload, const u32 *__restrict__ clen, const u64 *__restrict__ goff, const u32 *__restrict__ gsum,
     u64 n, u32 chunk, u32 nchunks, u16 *__restrict__ models, u32 mstride, u8 *__restrict__ out)
 {
-    const u32 lane = trc_lane(), c0 = blockIdx.x * 64u, c = c0 + lane;
-    const bool alive = c < nchunks;
-    const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
-    const u32 cl = alive ? trc_min(clen[c], len) : 0u;        // a directory entry above the chunk length (corrupt input) reads as raw
-    const u32 ex = trc_wave_incl_scan(cl) - cl;
-    const u64 off = trc_group_base(goff, gsum, blockIdx.x) + ex;
+    const TrcLaneDec L = trc_lane_dec(n, chunk, nchunks, clen, goff, gsum);
+    const auto [lane, c, c0, alive, len, cl, off] = L;
     const bool coded = alive && cl != len;
     u8 *const dst = out + (u64)c * chunk;
 
@@ -148,7 +143,7 @@ __global__ __launch_bounds__(64) void trc_rc_o1bit_dec_kernel(
                 const u32 bit = code < cut ? 1u : 0u;
                 range = bit ? cut : range - cut;
                 code = bit ? code : code - cut;
-                m[o1b_node<CTX>(row, w4, j)] = (u16)o1b_adapt(p, bit);
+                m[o1b_node<CTX>(row, w4, j)] = (u16)trc_bit_adapt(p, bit);
                 j = 2u * j + bit;
             }
             return j - 16u;
@@ -200,7 +195,7 @@ __global__ __launch_bounds__(64) void trc_rc_o1bit_dec_kernel(
         for (u32 pos = len & ~15u; pos < len; pos++)
             dst[pos] = (u8)(((pos >> 2) == (len >> 2) ? acc : ww[(pos >> 2) & 3u]) >> (8 * (pos & 3u)));
     }
-    trc_wave_copy_raw(__ballot(alive && cl == len && len != 0), off, len, out + (u64)c0 * chunk, chunk, payload);
+    trc_lane_copy_raw(L, chunk, payload, out);
 }
 
 void trc_o1bit_fill(uint8_t *model, size_t bytes, hipStream_t s)
@@ -210,10 +205,9 @@ void trc_o1bit_fill(uint8_t *model, size_t bytes, hipStream_t s)
 
 void trc_launch_o1bit_enc(const TrcCodec &c, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
-    const int ctx = c.k;
-    const uint32_t mb = o1b_model_bytes(ctx);
-    hipLaunchKernelGGL(trc_rc_o1bit_fill_kernel, dim3(4096), dim3(256), 0, s, w.model, (u64)w.nchunks * mb);
-    if (ctx) TRC_LAUNCH_TIMED(trc_rc_o1bit_enc_kernel<1>, dim3(w.ngroups), dim3(64), 0, s,
+    const uint32_t mb = o1b_model_bytes(c.k);
+    trc_o1bit_fill(w.model, (size_t)w.nchunks * mb, s);
+    if (c.k) TRC_LAUNCH_TIMED(trc_rc_o1bit_enc_kernel<1>, dim3(w.ngroups), dim3(64), 0, s,
                               d_in, (u64)n, chunk, w.nchunks, (u16 *)w.model, mb / 2u, w.scratch, w.stride, d_clen, w.gsum);
     else TRC_LAUNCH_TIMED(trc_rc_o1bit_enc_kernel<0>, dim3(w.ngroups), dim3(64), 0, s,
                           d_in, (u64)n, chunk, w.nchunks, (u16 *)w.model, mb / 2u, w.scratch, w.stride, d_clen, w.gsum);
@@ -221,10 +215,9 @@ void trc_launch_o1bit_enc(const TrcCodec &c, const uint8_t *d_in, size_t n, uint
 void trc_launch_o1bit_dec(const TrcCodec &c, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                           const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    const int ctx = c.k;
-    const uint32_t mb = o1b_model_bytes(ctx);
-    hipLaunchKernelGGL(trc_rc_o1bit_fill_kernel, dim3(4096), dim3(256), 0, s, w.model, (u64)w.nchunks * mb);
-    if (ctx) TRC_LAUNCH_TIMED(trc_rc_o1bit_dec_kernel<1>, dim3(w.ngroups), dim3(64), 0, s,
+    const uint32_t mb = o1b_model_bytes(c.k);
+    trc_o1bit_fill(w.model, (size_t)w.nchunks * mb, s);
+    if (c.k) TRC_LAUNCH_TIMED(trc_rc_o1bit_dec_kernel<1>, dim3(w.ngroups), dim3(64), 0, s,
                               d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, (u16 *)w.model, mb / 2u, d_out);
     else TRC_LAUNCH_TIMED(trc_rc_o1bit_dec_kernel<0>, dim3(w.ngroups), dim3(64), 0, s,
                           d_payload, d_clen, w.goff, w.gsum, (u64)n, chunk, w.nchunks, (u16 *)w.model, mb / 2u, d_out);

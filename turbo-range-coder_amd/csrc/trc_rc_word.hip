@@ -28,7 +28,7 @@
 // blocks of a word from the word and requests them before it codes its first bit.
 // Decoder bounds: every tree index is a masked byte combination and every nibble is 0..15, so no corrupt payload indexes
 // outside the lane's model; reads are clamped to the chunk's clen, the tail copy to the chunk's length.
-#include "trc_rc.h"
+#include "trc_rc_lane.h"
 #include "trc_lane_io.h"
 #include "trc_launch.h"
 #include "trc_tree.h"
@@ -114,10 +114,8 @@ __global__ __launch_bounds__(64) void trc_rc_word_enc_kernel(
 #pragma unroll
                 for (u32 s2 = 1; s2 < 8; s2++) pw = (j >> 1) == s2 ? q[8 * b + s2] : pw;
                 const u32 p = (j & 1u) ? pw >> 16 : pw & 0xffffu;
-                const u64 cut = (e.range >> TRC_PROB_BITS) * p;
-                e.low += bit ? 0 : cut;
-                e.range = bit ? cut : e.range - cut;
-                blk[b][j] = (u16)o1b_adapt(p, bit);
+                trc_rcbe(e, p, bit);
+                blk[b][j] = (u16)trc_bit_adapt(p, bit);
                 j = 2u * j + bit;
             }
         }
@@ -140,6 +138,7 @@ __global__ __launch_bounds__(64) void trc_rc_word_dec_kernel(
     u64 n, u32 chunk, u32 nchunks, u32 c0, u32 nround, u16 *__restrict__ models, u8 *__restrict__ out)
 {
     using W = WordCfg<K>;
+    // (own text: taking this prologue from trc_rc_lane.h changes the generated code, profiles/lanecore_notes.md)
     const u32 lane = trc_lane(), g = c0 / 64u + blockIdx.x, cw0 = g * 64u, c = cw0 + lane;
     const bool alive = c < nchunks && c < c0 + nround;
     const u32 len = !alive ? 0u : c + 1u < nchunks ? chunk : (u32)(n - (u64)c * chunk);
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(64) void trc_rc_word_dec_kernel(
                 const u32 bit = code < cut ? 1u : 0u;
                 range = bit ? cut : range - cut;
                 code = bit ? code : code - cut;
-                blk[j] = (u16)o1b_adapt(p, bit);
+                blk[j] = (u16)trc_bit_adapt(p, bit);
                 j = 2u * j + bit;
             }
             return j - 16u;
@@ -246,23 +245,20 @@ static void word_launch(bool dec, const uint8_t *d_src, const uint32_t *d_clen_i
 static void word_dispatch(int k, bool dec, const uint8_t *d_src, const uint32_t *d_clen_in, size_t n, uint32_t chunk,
                           const TrcWork &w, uint32_t *d_clen, uint8_t *d_out, hipStream_t s)
 {
+#define WORD_CASE(i) case i: word_launch<i>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
     switch (k) {
-    case 0: word_launch<0>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
-    case 1: word_launch<1>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
-    case 2: word_launch<2>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
-    case 3: word_launch<3>(dec, d_src, d_clen_in, n, chunk, w, d_clen, d_out, s); break;
+    WORD_CASE(0) WORD_CASE(1) WORD_CASE(2) WORD_CASE(3)
     default: break;
     }
+#undef WORD_CASE
 }
 
 void trc_launch_word_enc(const TrcCodec &c, const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, uint32_t *d_clen, hipStream_t s)
 {
-    const int k = c.k;
-    word_dispatch(k, false, d_in, nullptr, n, chunk, w, d_clen, nullptr, s);
+    word_dispatch(c.k, false, d_in, nullptr, n, chunk, w, d_clen, nullptr, s);
 }
 void trc_launch_word_dec(const TrcCodec &c, const uint8_t *d_payload, const uint32_t *d_clen, size_t n, uint32_t chunk,
                          const TrcWork &w, uint8_t *d_out, hipStream_t s)
 {
-    const int k = c.k;
-    word_dispatch(k, true, d_payload, d_clen, n, chunk, w, nullptr, d_out, s);
+    word_dispatch(c.k, true, d_payload, d_clen, n, chunk, w, nullptr, d_out, s);
 }

@@ -11,5 +11,3 @@ __device__ __forceinline__ u32 o1b_pick(const u32 (&q)[8], u32 j)
     for (u32 i = 1; i < 8; i++) r = (j >> 1) == i ? q[i] : r;
     return (j & 1u) ? r >> 16 : r & 0xffffu;
 }
-
-__device__ __forceinline__ u32 o1b_adapt(u32 p, u32 bit) { return (p - (((p - (bit << 15)) >> 5) + bit)) & 0xffffu; }
