@@ -225,6 +225,29 @@ int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_payload, siz
                    const uint16_t *d_cdf, unsigned cdfnum,
                    void *d_out, void *d_work, size_t work_bytes, void *stream);
 
+/* Random access: decode chunks [first_chunk, first_chunk + count) only.  d_clen, d_payload, n and chunk describe the WHOLE
+ * container, exactly as for trc_decode_dev; d_out receives min(n, (first_chunk + count) * chunk) - first_chunk * chunk bytes,
+ * the range's first byte at d_out[0], and nothing is written behind them.  first_chunk may be any chunk (no multiple of 64
+ * needed).  Same alignment rules and error codes as trc_decode_dev; count == 0 returns TRC_OK and launches nothing,
+ * first_chunk + count > nchunks is TRC_E_ARG.  Every coder id decodes ranges.
+ * The workspace is one of its own kind, of trc_range_work_bytes(codec, n, chunk, count) bytes: what a decode of `count` chunks
+ * needs plus 12 bytes per 64 chunks of the whole directory -- it grows with the range, not with n, and holds no encoder
+ * scratch (always <= trc_work_bytes(codec, count * chunk, chunk) + 16 * ceil(nchunks / 64) + 4096).  0 for an id that names
+ * no coder, a chunk trc_encode_dev rejects, count == 0 and count > nchunks; it never shrinks as count grows, so a workspace
+ * sized for the largest range serves every smaller one.  Static coders keep their tables at its start: trc_tables_dev and
+ * TRC_TABLES_READY work as above.
+ * A call indexes the whole directory first (the per-group sums and their scan, O(nchunks)), then builds the range's own group
+ * offsets from that index (O(count)).  `codec | TRC_DIR_READY` skips the first step.  The promise: the previous
+ * trc_decode_range_dev on this workspace was for the same (n, chunk) and d_clen has not changed since -- ANY first_chunk and
+ * ANY count, the index lies where (n, chunk) alone put it.  So the first range of a container costs O(nchunks), every later
+ * one O(count).  The flag does not carry over between the two kinds of workspace: a trc_decode_dev / trc_encode_dev workspace
+ * never serves trc_decode_range_dev and the other way round. */
+size_t trc_range_work_bytes(int codec, size_t n, uint32_t chunk, size_t count);
+int    trc_decode_range_dev(int codec, const uint32_t *d_clen, const void *d_payload, size_t n, uint32_t chunk,
+                            size_t first_chunk, size_t count,
+                            const uint16_t *d_cdf, unsigned cdfnum,
+                            void *d_out, void *d_work, size_t work_bytes, void *stream);
+
 /* ---- multi-GPU: the gather of results over RCCL (xGMI), plain C ------------------------------------------------
  * One process per GPU; every rank codes a contiguous range of whole chunks with the calls above (no data-path
  * collective).  Static coders first agree on one CDF: trc_hist_dev on the shard, trc_hist_allreduce_dev (256 x u64
@@ -275,6 +298,24 @@ int trc_host_unpin(void *p);
  * directory fits, and that the directory's lengths add up to exactly the stated payload, which must end inside
  * buflen.  Host-only (no GPU needed).  Returns TRC_OK or TRC_E_ARG (text in trc_last_error()). */
 int trc_container_check(const void *buf, size_t buflen, int codec, size_t outlen);
+
+/* Random access through host pointers.  trc_container_range (host only, no GPU needed) validates the container as
+ * trc_container_check(buf, buflen, codec, (size_t)-1) does and plans bytes [offset, offset + len) of the original:
+ *   first_chunk, nchunks     the chunks that cover them
+ *   payload_off, payload_len where those chunks' payload lies, from the start of the payload area
+ *                            (buf + 32 + 4 * hdr.nchunks), in bytes
+ *   out_skip                 offset - first_chunk * chunk: the range's first byte within the covering chunks' output
+ *   out_bytes                decoded size of the covering chunks
+ * len == 0 or offset + len > n is TRC_E_ARG.  A caller with its own transport reads clen[first_chunk .. + nchunks) and
+ * those payload_len bytes, nothing else: the two are a container of (out_bytes, chunk) for trc_decode_dev.
+ * trc_decode_range_host does exactly that on the calling thread's current device (device lists are not used): it sends
+ * the covering chunks' directory entries and payload, decodes them, and copies `len` bytes to out.  n is the original
+ * length; inlen == n means "stored raw", as for trc_decode_host, and is a memcpy of the range.  cdf / cdfnum as for
+ * trc_decode_host.  Returns len, 0 on error (text in trc_last_error(); without a device it says so). */
+typedef struct trc_range { uint64_t first_chunk, nchunks, payload_off, payload_len, out_skip, out_bytes; } trc_range;
+int    trc_container_range(const void *buf, size_t buflen, int codec, size_t offset, size_t len, trc_range *r);
+size_t trc_decode_range_host(int codec, const void *in, size_t inlen, size_t n, size_t offset, size_t len, void *out,
+                             const uint16_t *cdf, unsigned cdfnum);
 
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass

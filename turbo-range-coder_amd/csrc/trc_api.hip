@@ -513,6 +513,71 @@ extern "C" int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_p
     return TRC_OK;
 }
 
+// ---- decode of a chunk range ------------------------------------------------------------------------------------
+// Chunks [first_chunk, first_chunk + count) of a container are a container of their own -- the same payload area, the directory
+// from entry first_chunk on -- once their groups' offsets are known: the decoders take ABSOLUTE group offsets (w.goff above).  The
+// range workspace holds the index of the FULL directory (per-group sums and their scan: 12 bytes per 64 chunks, placed by (n, chunk)
+// alone, so that TRC_DIR_READY finds it whatever the last range was), the range's own group sums and offsets
+// (trc_range_dir_kernel, trc_dir.hip), and what a decoder of `count` chunks uses: the tables and the models.  No scratch regions,
+// no record stacks, no aux words: those serve the encoders and the gather only (every TrcDecFn reads w.tables, w.goff, w.gsum,
+// w.model, w.nchunks, w.ngroups and nothing else), and their pointers are null here.
+//   tables | gsum of the full directory | goff of the full directory | gsum of the range | goff of the range | models
+static inline size_t dir_index_bytes(size_t ngroups) { return up256(4 * ngroups) + up256(8 * (ngroups + 1)); }
+extern "C" size_t trc_range_work_bytes(int codec, size_t n, uint32_t chunk, size_t count)
+{
+    const TrcCodec &r = codec_row(codec);
+    if (!r.enc || !chunk_ok(chunk) || chunk > r.chunk_max) return 0;
+    const size_t nchunks = (n + chunk - 1) / chunk;
+    if (!count || count > nchunks || nchunks > 0x7fffffffu) return 0;
+    return up256(TRC_TAB_BYTES) + dir_index_bytes((nchunks + 63) / 64) + dir_index_bytes((count + 63) / 64) + model_area_bytes(r, count);
+}
+
+extern "C" int trc_decode_range_dev(int codec, const uint32_t *d_clen, const void *d_payload, size_t n, uint32_t chunk,
+                                    size_t first_chunk, size_t count,
+                                    const uint16_t *d_cdf, unsigned cdfnum,
+                                    void *d_out, void *d_work, size_t work_bytes, void *stream)
+{
+    const bool tables_ready = codec & TRC_TABLES_READY, dir_ready = codec & TRC_DIR_READY;
+    codec &= ~(TRC_TABLES_READY | TRC_DIR_READY);
+    int rc = check_common(codec, n, chunk, d_cdf, cdfnum);
+    if (rc) return rc;
+    const size_t nchunks = (n + chunk - 1) / chunk, ngroups = (nchunks + 63) / 64;
+    if (first_chunk > nchunks || count > nchunks - first_chunk)
+        return fail(TRC_E_ARG, "decode_range: chunks [%zu, %zu + %zu) of %zu", first_chunk, first_chunk, count, nchunks);
+    if (count == 0) return TRC_OK;
+    if (((uintptr_t)d_out & 15) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_payload & 1))
+        return fail(TRC_E_ARG, "decode_range: d_out must be 16-byte, d_clen 4-byte, d_payload 2-byte aligned");
+    const TrcCodec &r = codec_row(codec);
+    const size_t need = trc_range_work_bytes(codec, n, chunk, count);
+    if (!need || work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
+    if (((uintptr_t)d_work) & 255) return fail(TRC_E_ARG, "workspace must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ngroups_sub = (count + 63) / 64;
+    uint8_t *p = (uint8_t *)d_work;
+    TrcWork w = {};
+    w.tables = p;                        p += up256(TRC_TAB_BYTES);
+    uint32_t *gsum_full = (uint32_t *)p; p += up256(4 * ngroups);
+    uint64_t *goff_full = (uint64_t *)p; p += up256(8 * (ngroups + 1));
+    w.gsum = (uint32_t *)p;              p += up256(4 * ngroups_sub);
+    w.goff = w.goff_area = (uint64_t *)p; p += up256(8 * (ngroups_sub + 1));
+    w.model = p;
+    w.stride = chunk + r.pad;
+    w.stride2 = r.s2_mul * chunk + r.s2_add;
+    w.nchunks = (uint32_t)count; w.ngroups = (uint32_t)ngroups_sub;
+    if (r.cdf && !tables_ready) trc_launch_static_prep(d_cdf, cdfnum, w.tables, s);
+    if (!dir_ready) {                    // O(nchunks), once per container and workspace; everything below is O(count)
+        trc_launch_group_sums(d_clen, (uint32_t)nchunks, n, chunk, gsum_full, s);
+        trc_launch_scan_groups(gsum_full, (uint32_t)ngroups, goff_full, nullptr, s);
+    }
+    trc_launch_range_dir(d_clen, (uint32_t)nchunks, n, chunk, goff_full, (uint32_t)first_chunk, (uint32_t)count, w.gsum, w.goff, s);
+    const size_t b0 = first_chunk * (size_t)chunk, b1 = (first_chunk + count) * (size_t)chunk;
+    tm_begin(1);
+    r.dec(r, (const uint8_t *)d_payload, d_clen + first_chunk, (b1 < n ? b1 : n) - b0, chunk, w, (uint8_t *)d_out, s);
+    tm_end(1);
+    HIPCHK(hipGetLastError());
+    return TRC_OK;
+}
+
 // The kernel that takes the longest in the DEFAULT dispatch of the coder at the bench configurations (100 MB, the library's chunk):
 // what a rocprofv3 --kernel-trace of bench.py lists first for that direction.  Two-pass encoders launch more than one kernel (the
 // timing pairs sum them); forms at other sizes (the order-1 coder's eight-lane decoder and position-order passes) have
@@ -610,6 +675,9 @@ extern "C" int trc_container_check(const void *buf, size_t buflen, int codec, si
     char why[200];
     return container_verdict(buf, buflen, codec, outlen, why, sizeof why) ? fail(TRC_E_ARG, "%s", why) : TRC_OK;
 }
+
+// ---- a byte range of a container: trc_container_range, trc_decode_range_host ------------------------------------
+#include "trc_range.inc"
 
 // ---- exports with the reference's names (include/turborc.h:500, include/anscdf.h:40-96) ----------
 extern "C" {

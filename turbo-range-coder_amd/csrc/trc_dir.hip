@@ -1,5 +1,5 @@
 // trc_dir.hip -- everything around the coders: CDF-derived tables, the chunk directory
-// (per-group sums -> exclusive scan), the payload gather, and cdfini (histogram -> CDF) on device.
+// (per-group sums -> exclusive scan, the directory of a chunk range), the payload gather, and cdfini (histogram -> CDF) on device.
 #include <stdlib.h>
 #include "trc_dev.h"
 #include "trc_launch.h"
@@ -90,6 +90,39 @@ __global__ __launch_bounds__(1024) void trc_scan_groups_kernel(const u32 *__rest
 void trc_launch_scan_groups(const uint32_t *gsum, uint32_t ngroups, uint64_t *goff, uint64_t *d_total, hipStream_t s)
 {
     TRC_LAUNCH_TIMED(trc_scan_groups_kernel, dim3(1), dim3(1024), 0, s, gsum, ngroups, goff, d_total);
+}
+
+// Directory of a chunk range (trc_decode_range_dev): the decoders of chunks [first, first + count) see a directory of their own
+// whose groups start at chunk first + 64 j -- anywhere inside a group of the full directory.  One wave per group j of the range:
+// with b = first + 64 j, its payload offset is the base of b's full-directory group plus the clamped lengths of the b & 63 chunks
+// of that group below b; entry ngroups_sub (b = first + count) is the range's end, as the scan writes it.  gsum_sub[j] = bytes of
+// the range's group j.  goff_full has an entry for group nchunks / 64 too (the scan's total), so b == nchunks reads inside it.
+__global__ __launch_bounds__(256) void trc_range_dir_kernel(const u32 *__restrict__ clen, u32 nchunks, u64 n, u32 chunk,
+                                                            const u64 *__restrict__ goff_full, u32 first, u32 count,
+                                                            u32 *__restrict__ gsum_sub, u64 *__restrict__ goff_sub)
+{
+    const u32 ngroups_sub = (count + 63u) >> 6, end = first + count;
+    const u32 j = blockIdx.x * 4u + (threadIdx.x >> 6), lane = trc_lane();
+    if (j > ngroups_sub) return;
+    const u32 b = trc_min(first + 64u * j, end);
+    auto clamped = [&](u32 c) -> u32 {                          // same clamp as trc_group_sums_kernel and the decoders; c < nchunks
+        const u64 left = n - (u64)c * chunk;
+        return trc_min(clen[c], left < chunk ? (u32)left : chunk);
+    };
+    const u32 below = (b & ~63u) + lane, mine = b + lane;
+    const u32 pre = trc_wave_sum(below < b ? clamped(below) : 0u);
+    const u32 sum = trc_wave_sum(mine < end ? clamped(mine) : 0u);
+    if (lane == 0) {
+        goff_sub[j] = goff_full[b >> 6] + pre;
+        if (j < ngroups_sub) gsum_sub[j] = sum;
+    }
+}
+void trc_launch_range_dir(const uint32_t *d_clen, uint32_t nchunks, size_t n, uint32_t chunk, const uint64_t *goff_full,
+                          uint32_t first, uint32_t count, uint32_t *gsum_sub, uint64_t *goff_sub, hipStream_t s)
+{
+    const uint32_t waves = (count + 63u) / 64u + 1u;
+    hipLaunchKernelGGL(trc_range_dir_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, s, d_clen, nchunks, (u64)n, chunk, goff_full,
+                       first, count, gsum_sub, goff_sub);
 }
 
 // Payload gather: one workgroup per group of 64 chunks moves the group's bytes to payload + base as dst-aligned

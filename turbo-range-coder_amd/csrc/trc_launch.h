@@ -91,6 +91,9 @@ enum TrcGather {
 // directory scan + payload gather
 void trc_launch_group_sums(const uint32_t *d_clen, uint32_t nchunks, size_t n, uint32_t chunk, uint32_t *gsum, hipStream_t s);
 void trc_launch_scan_groups(const uint32_t *gsum, uint32_t ngroups, uint64_t *goff, uint64_t *d_total, hipStream_t s);
+// the directory of chunks [first, first + count): goff_sub[0 .. ceil(count / 64)] and gsum_sub[] from the full directory's goff
+void trc_launch_range_dir(const uint32_t *d_clen, uint32_t nchunks, size_t n, uint32_t chunk, const uint64_t *goff_full,
+                          uint32_t first, uint32_t count, uint32_t *gsum_sub, uint64_t *goff_sub, hipStream_t s);
 void trc_launch_gather(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, TrcGather mode,
                        const uint32_t *d_clen, uint8_t *d_payload, uint64_t *d_total, hipStream_t s);
 

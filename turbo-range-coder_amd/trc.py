@@ -62,6 +62,11 @@ _vp = C.c_void_p
 _sz = C.c_size_t
 
 
+class Range(C.Structure):
+    """struct trc_range (include/trc_hip.h)"""
+    _fields_ = [(f, C.c_uint64) for f in ("first_chunk", "nchunks", "payload_off", "payload_len", "out_skip", "out_bytes")]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into turbo-range-coder_amd/libturborc_hip.so."""
     if force:
@@ -105,6 +110,13 @@ def lib():
         l.trc_tables_dev.argtypes = [_vp, C.c_uint, _vp, _sz, _vp]
         l.trc_decode_dev.restype = C.c_int
         l.trc_decode_dev.argtypes = [C.c_int, _vp, _vp, _sz, C.c_uint32, _vp, C.c_uint, _vp, _vp, _sz, _vp]
+        l.trc_range_work_bytes.restype = _sz; l.trc_range_work_bytes.argtypes = [C.c_int, _sz, C.c_uint32, _sz]
+        l.trc_decode_range_dev.restype = C.c_int
+        l.trc_decode_range_dev.argtypes = [C.c_int, _vp, _vp, _sz, C.c_uint32, _sz, _sz, _vp, C.c_uint, _vp, _vp, _sz, _vp]
+        l.trc_container_range.restype = C.c_int
+        l.trc_container_range.argtypes = [_vp, _sz, C.c_int, _sz, _sz, C.POINTER(Range)]
+        l.trc_decode_range_host.restype = _sz
+        l.trc_decode_range_host.argtypes = [C.c_int, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint]
         l.trc_timing_enable.restype = C.c_int; l.trc_timing_enable.argtypes = [C.c_int]
         l.trc_timing_pause.restype = C.c_int; l.trc_timing_pause.argtypes = [C.c_int]
         l.trc_timing_read.restype = C.c_int
@@ -145,6 +157,11 @@ def nchunks(n, chunk):
     return (n + chunk - 1) // chunk
 
 
+def range_work_bytes(codec, n, chunk, count):
+    """bytes of the workspace trc_decode_range_dev needs for `count` chunks of an (n, chunk) container; 0: bad arguments"""
+    return lib().trc_range_work_bytes(codec, n, chunk, count)
+
+
 # ---------------------------------------------------------------- device-resident layer (torch) ---
 class DeviceCoder:
     """Pre-allocated HBM buffers for repeated encode/decode of up to `n` bytes on the current device."""
@@ -167,6 +184,8 @@ class DeviceCoder:
         self.status = torch.zeros(4, dtype=torch.int32, device=self.dev)
         self.cdfnum = 0
         self.tables_ready = 0                                  # TABLES_READY once trc_tables_dev ran for the current CDF
+        self.range_work, self.range_work_bytes = None, 0       # decode_range's own workspace, made at its first call
+        self.range_tables = 0                                  # ... and TABLES_READY for it
 
     def _stream(self):
         return self.torch.cuda.current_stream(self.dev).cuda_stream
@@ -176,6 +195,7 @@ class DeviceCoder:
         if self.codec in STATIC:
             _chk(lib().trc_tables_dev(self.cdf.data_ptr(), self.cdfnum, self.work.data_ptr(), self.work_bytes, self._stream()))
             self.tables_ready = TABLES_READY
+            self.range_tables = 0
 
     def set_cdf(self, cdf_np, cdfnum):
         t = self.torch.from_numpy(np.ascontiguousarray(cdf_np[:cdfnum + 1]).view(np.int16))
@@ -218,6 +238,27 @@ class DeviceCoder:
         _chk(lib().trc_decode_dev(self.codec | self.tables_ready | (DIR_READY if dir_ready else 0), clen.data_ptr(), payload.data_ptr(), n, self.chunk,
                                   self.cdf.data_ptr() if st else None, self.cdfnum if st else 0,
                                   d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode_range(self, d_out, first, count, n=None, clen=None, payload=None, dir_ready=False):
+        """Enqueue the decode of chunks [first, first + count) of the container (clen, payload, n) to d_out[0:], in a workspace
+        of its own (trc_range_work_bytes; it grows with the largest count seen).  dir_ready: the decode_range before this one
+        was for the same n and an unchanged clen, any first and count (TRC_DIR_READY, include/trc_hip.h); dropped when the
+        workspace has just grown and the index with it."""
+        n = self.n if n is None else n
+        st = self.codec in STATIC
+        clen = self.clen if clen is None else clen
+        payload = self.payload if payload is None else payload
+        need = lib().trc_range_work_bytes(self.codec, n, self.chunk, count)
+        if need > self.range_work_bytes:
+            self.range_work = self.torch.empty(need + PAD, dtype=self.torch.uint8, device=self.dev)
+            self.range_work_bytes, self.range_tables, dir_ready = need, 0, False
+        if st and not self.range_tables and self.range_work is not None:
+            _chk(lib().trc_tables_dev(self.cdf.data_ptr(), self.cdfnum, self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+            self.range_tables = TABLES_READY
+        _chk(lib().trc_decode_range_dev(self.codec | self.range_tables | (DIR_READY if dir_ready else 0), clen.data_ptr(), payload.data_ptr(),
+                                        n, self.chunk, first, count, self.cdf.data_ptr() if st else None, self.cdfnum if st else 0,
+                                        d_out.data_ptr(), self.range_work.data_ptr() if self.range_work is not None else None,
+                                        self.range_work_bytes, self._stream()))
 
     def result(self, n=None):
         """Synchronise and fetch (clen[nchunks] u32, payload bytes) to the host."""
@@ -302,6 +343,26 @@ def host_decode(codec, comp, n, cdf=None, cdfnum=256, name=None):
     if l != n:
         raise TrcError(lib().trc_last_error().decode())
     return out[:n].copy()
+
+
+def container_range(buf, offset, length):
+    """trc_container_range on a container in host memory (needs no device) -> dict of the six trc_range fields"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    r = Range()
+    _chk(lib().trc_container_range(buf.ctypes.data, buf.size, 0, offset, length, C.byref(r)))
+    return {f: int(getattr(r, f)) for f, _ in Range._fields_}
+
+
+def host_decode_range(codec, comp, n, offset, length, cdf=None, cdfnum=256):
+    """bytes [offset, offset + length) of what `comp` (a host-pointer encoder's result for n bytes) holds: trc_decode_range_host"""
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    out = np.full(length + 64, 0xA5, dtype=np.uint8)
+    st = codec in STATIC
+    l = lib().trc_decode_range_host(codec, comp.ctypes.data, comp.size, n, offset, length, out.ctypes.data,
+                                    cdf.ctypes.data if st else None, cdfnum if st else 0)
+    if l != length or not (out[length:] == 0xA5).all():
+        raise TrcError(lib().trc_last_error().decode() if l != length else "trc_decode_range_host wrote past its output")
+    return out[:length].copy()
 
 
 def set_devices(devs):
