@@ -8,9 +8,12 @@
  * The timed calls take HOST pointers, so these numbers include PCIe both ways; the
  * device-resident numbers come from bench.py.
  *
- *   trcbench [-e id[,id..]] [-I runs] [-c chunk] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)
+ *   trcbench [-e id[,id..]] [-I runs] [-c chunk] [-p s|ss] [-r NM] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)
  * ids: 1 rcs | 2 rccs | 4 rcxs | 6 rcs16 / rcs32 | 7 rccs32 | 8 rcc2s32 (word coders: --int16 / --int32 input) | 26 rcgs | 27 rcgzs | 28 rcrs | 29 rcrzs (8-bit; --int16 / --int32 inputs: the 16 / 32-bit coders) |
  *      17 rcu3s | 30 rcvs | 33 rcvzs | 35 rcvgs | 36 rcvgzs (16-bit; --int32 input: the 32-bit coders) | 40 rc4cs | 41 rc4s (nibble-valued input only) | 42 cdfsb | 43 cdfsv | 45 cdfs2 | 46 cdf | 47 cdfi | 56 ans | 57 ans(s) | 58 ans(x) | 65 ans4s | 79 memcpy
+ * -p ss: the dual-rate "ss" predictor builds (the reference tool's -pss): ids 1 rcss | 17 rcu3ss | 40 rc4css | 41 rc4ss (the last two on
+ *      nibble-valued input only) with the two parameters of -r NM (two digits 1..9, as the reference tool reads them; default 56); every
+ *      other id prints no row.  -p s, the default: the rows above.
  */
 #include <math.h>
 #include <stdio.h>
@@ -25,6 +28,8 @@ int trc_host_pin(void *p, size_t len);       /* page-lock a buffer: host-pointer
 const char *trc_last_error(void);
 
 static int g_elem = 0;      /* element bytes of integer input (2 / 4), 0 = bytes */
+static int g_ss = 0;        /* -p ss: the "ss" predictor's rows */
+static unsigned g_prm0 = 5, g_prm1 = 6;   /* -r NM */
 static double now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
 static unsigned long long sm64(unsigned long long *s)
 {
@@ -78,17 +83,27 @@ static size_t memcheck(const unsigned char *a, const unsigned char *b, size_t n)
 typedef size_t (*enc3)(unsigned char *, size_t, unsigned char *);
 typedef size_t (*enc4)(unsigned char *, size_t, unsigned char *, cdf_t *);
 typedef size_t (*enc5)(unsigned char *, size_t, unsigned char *, cdf_t *, unsigned);
+typedef size_t (*encp)(unsigned char *, size_t, unsigned char *, unsigned, unsigned);
 
 static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char *cpy, int id, int runs)
 {
     cdf_t cdf[257];
     unsigned m = 0;
     const char *name = "?";
-    enc3 e3 = 0, d3 = 0; enc4 e4 = 0, d4 = 0; enc5 e5 = 0, d5 = 0;
+    enc3 e3 = 0, d3 = 0; enc4 e4 = 0, d4 = 0; enc5 e5 = 0, d5 = 0; encp ep = 0, dp = 0;
     for (size_t i = 0; i < n; i++) if (in[i] > m) m = in[i];
+    if (g_ss) {                                        /* the "ss" builds of ids 1, 17 and, under the nibble gate, 40 and 41; nothing else */
+        switch (id) {
+        case 1:  name = "rcss o0 (rcssenc/rcssdec)"; ep = rcssenc; dp = rcssdec; break;
+        case 17: name = "rcu3ss varint8 3/5/8 bits (rcu3ssenc/rcu3ssdec)"; ep = rcu3ssenc; dp = rcu3ssdec; break;
+        case 40: if (m < 16) { name = "rc4css bitwise nibble static (rc4cssenc/rc4cssdec)"; ep = rc4cssenc; dp = rc4cssdec; } break;
+        case 41: if (m < 16) { name = "rc4ss bitwise nibble adaptive (rc4ssenc/rc4ssdec)"; ep = rc4ssenc; dp = rc4ssdec; } break;
+        }
+        if (!ep) return 0;
+    }
     /* nibble-valued input (`turborc -n`): ids 46/47/56-58 run the one-table nibble coders, as the reference
      * harness does under its m<16 gate (turborc.c:499-501,514-520) */
-    if (m < 16) switch (id) {
+    if (!ep && m < 16) switch (id) {
     case 46: name = "cdf4 nibble adaptive (rccdf4enc/rccdf4dec)"; e3 = rccdf4enc; d3 = rccdf4dec; break;
     case 47: name = "cdf4i nibble adaptive interleaved (rccdf4ienc/rccdf4idec)"; e3 = rccdf4ienc; d3 = rccdf4idec; break;
     case 56: name = "ans auto nibble (anscdf4enc/anscdf4dec)"; e3 = anscdf4enc; d3 = anscdf4dec; break;
@@ -99,7 +114,7 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
     case 41: name = "rc4s bitwise nibble adaptive (rc4senc/rc4sdec)"; e3 = rc4senc; d3 = rc4sdec; break;
     }
     /* 16/32-bit integer input (`turborc -Os2 / -Os4` style, here: --int16 / --int32): ids 50/52/53 are the Turbo-VLC coders */
-    if (!e3 && g_elem) switch (id) {
+    if (!ep && !e3 && g_elem) switch (id) {
     case 50: name = g_elem == 2 ? "cdf-16 Turbo vlc6 (rccdfuenc16/rccdfudec16)" : "cdf-32 Turbo vlc6 (rccdfuenc32/rccdfudec32)";
              e3 = g_elem == 2 ? rccdfuenc16 : rccdfuenc32; d3 = g_elem == 2 ? rccdfudec16 : rccdfudec32; break;
     case 52: name = g_elem == 2 ? "cdf-16 Turbo vlc7 (rccdfvenc16/rccdfvdec16)" : "cdf-32 Turbo vlc7 (rccdfvenc32/rccdfvdec32)";
@@ -114,7 +129,7 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
     case 63: name = g_elem == 2 ? "anscdf-16 Turbo vlc7 zigzag (anscdfvzenc16/anscdfvzdec16)" : "anscdf-32 Turbo vlc7 zigzag (anscdfvzenc32/anscdfvzdec32)";
              e3 = g_elem == 2 ? anscdfvzenc16 : anscdfvzenc32; d3 = g_elem == 2 ? anscdfvzdec16 : anscdfvzdec32; break;
     }
-    if (!e3) switch (id) {
+    if (!ep && !e3) switch (id) {
     case 1:  name = "rc o0 (rcsenc/rcsdec)"; e3 = rcsenc; d3 = rcsdec; break;
     case 2:  name = "rc o1 (rccsenc/rccsdec)"; e3 = rccsenc; d3 = rccsdec; break;
     case 4:  name = "rc o1 sliding context (rcxsenc/rcxsdec)"; e3 = rcxsenc; d3 = rcxsdec; break;
@@ -164,7 +179,7 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
     double te = 1e30, td = 1e30;
     for (int r = 0; r < runs; r++) {
         double t0 = now();
-        if (e3) l = e3(in, n, out); else if (e4) l = e4(in, n, out, cdf); else if (e5) l = e5(in, n, out, cdf, m + 1);
+        if (ep) l = ep(in, n, out, g_prm0, g_prm1); else if (e3) l = e3(in, n, out); else if (e4) l = e4(in, n, out, cdf); else if (e5) l = e5(in, n, out, cdf, m + 1);
         else { memcpy(out, in, n); l = n; }
         double t1 = now();
         if (t1 - t0 < te) te = t1 - t0;
@@ -174,7 +189,7 @@ static int bench(unsigned char *in, size_t n, unsigned char *out, unsigned char 
         double t0 = now();
         size_t k = n;
         if (l == n) memcpy(cpy, out, n);               /* stored raw: the caller copies (CCPY) */
-        else if (d3) k = d3(out, n, cpy); else if (d4) k = d4(out, n, cpy, cdf); else if (d5) k = d5(out, n, cpy, cdf, m + 1);
+        else if (dp) k = dp(out, n, cpy, g_prm0, g_prm1); else if (d3) k = d3(out, n, cpy); else if (d4) k = d4(out, n, cpy, cdf); else if (d5) k = d5(out, n, cpy, cdf, m + 1);
         double t1 = now();
         if (t1 - t0 < td) td = t1 - t0;
         if (k != n) { printf("%2d: decode failed: %s\n", id, trc_last_error()); return 1; }
@@ -196,6 +211,14 @@ int main(int argc, char **argv)
         else if (!strncmp(argv[i], "-e", 2) && argv[i][2] >= '0' && argv[i][2] <= '9') ids = argv[i] + 2;    /* -e40,41 / -I1 / -c1024 as one word, the reference tool's style */
         else if (!strncmp(argv[i], "-I", 2) && argv[i][2] >= '0' && argv[i][2] <= '9') runs = atoi(argv[i] + 2);
         else if (!strncmp(argv[i], "-c", 2) && argv[i][2] >= '0' && argv[i][2] <= '9') { if (trc_set_chunk((unsigned)atoi(argv[i] + 2))) return 2; }
+        else if (!strcmp(argv[i], "-p") && i + 1 < argc) { const char *v = argv[++i]; if (strcmp(v, "s") && strcmp(v, "ss")) { fprintf(stderr, "-p %s: s or ss\n", v); return 2; } g_ss = !strcmp(v, "ss"); }
+        else if (!strcmp(argv[i], "-pss")) g_ss = 1;
+        else if (!strcmp(argv[i], "-ps")) g_ss = 0;
+        else if ((!strcmp(argv[i], "-r") && i + 1 < argc) || (!strncmp(argv[i], "-r", 2) && argv[i][2])) {     /* two digits, as the reference tool: -r 47 / -r47 */
+            const char *v = argv[i][2] ? argv[i] + 2 : argv[++i];
+            if (v[0] < '1' || v[0] > '9' || v[1] < '1' || v[1] > '9' || v[2]) { fprintf(stderr, "-r %s: two digits 1..9\n", v); return 2; }
+            g_prm0 = (unsigned)(v[0] - '0'); g_prm1 = (unsigned)(v[1] - '0');
+        }
         else if (!strcmp(argv[i], "--pin")) pin = 1;   /* page-lock in / out / cpy once (what a caller that reuses its buffers would do) */
         else if (!strcmp(argv[i], "--zipf") && i + 1 < argc) { kind = 0; n = strtoull(argv[++i], 0, 10); }
         else if (!strcmp(argv[i], "--text") && i + 1 < argc) { kind = 1; n = strtoull(argv[++i], 0, 10); }
@@ -221,7 +244,7 @@ int main(int argc, char **argv)
         for (char *t = strtok_r(s, ",", &sv); t; t = strtok_r(0, ",", &sv)) bad |= bench(in, n, out, cpy, atoi(t), runs);
         return bad;
     }
-    if (kind < 0 || !n) { fprintf(stderr, "usage: trcbench [-e ids] [-I runs] [-c chunk] [--pin] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)\n"); return 2; }
+    if (kind < 0 || !n) { fprintf(stderr, "usage: trcbench [-e ids] [-I runs] [-c chunk] [-p s|ss] [-r NM] [--pin] (file | --zipf N | --text N | --uniform N | --nibble N | --int16 N | --int32 N | --markov N)\n"); return 2; }
     unsigned char *in = malloc(n * 4 / 3 + 1024), *out = malloc(n * 4 / 3 + 1024), *cpy = malloc(n * 4 / 3 + 1024);
     gen(in, n, kind);
     if (pin && (trc_host_pin(in, n * 4 / 3 + 1024) || trc_host_pin(out, n * 4 / 3 + 1024) || trc_host_pin(cpy, n * 4 / 3 + 1024))) { fprintf(stderr, "--pin: %s\n", trc_last_error()); return 2; }

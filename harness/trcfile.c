@@ -2,6 +2,10 @@
  * usable file compressor").  Plain C, links only against libturborc_hip.so.
  *
  *   trcfile c <id> <in> <out>     compress   (id: TurboRC -e numbers 1, 42, 44, 45, 46, 47, 56, 64, 65, 66)
+ *   trcfile c <id> <in> <out> [-r NM]   id 62 .. 65 with -r or without: the library's "ss" predictor coders TRC_RCSS, TRC_RC4SS,
+ *                                 TRC_RC4CSS, TRC_RCU3SS (trc_hip.h) with the parameters N and M (two digits 1..9, default 56);
+ *                                 the container's header records them, so d and x take no option.  Without -r, 64 and 65 are
+ *                                 the TurboRC numbers above
  *   trcfile d <in> <out>          decompress
  *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`: only the chunks
  *                                 that cover them are sent to the GPU and decoded (trc_decode_range_host)
@@ -24,6 +28,18 @@
 
 typedef size_t (*fn3)(unsigned char *, size_t, unsigned char *);
 typedef size_t (*fn5)(unsigned char *, size_t, unsigned char *, cdf_t *, unsigned);
+typedef size_t (*fnp)(unsigned char *, size_t, unsigned char *, unsigned, unsigned);
+/* file id of an "ss" coder = 128 | library id (62 and 63 are free TurboRC numbers here, 64 and 65 are not) */
+static fnp pick_ss(int codec)
+{
+    switch (codec) {
+    case TRC_RCSS: return rcssenc;
+    case TRC_RC4SS: return rc4ssenc;
+    case TRC_RC4CSS: return rc4cssenc;
+    case TRC_RCU3SS: return rcu3ssenc;
+    }
+    return 0;
+}
 static size_t e65(unsigned char *i, size_t n, unsigned char *o, cdf_t *c, unsigned m) { (void)m; return anscdf4senc(i, n, o, c); }
 static size_t d65(unsigned char *i, size_t n, unsigned char *o, cdf_t *c, unsigned m) { (void)m; return anscdf4sdec(i, n, o, c); }
 
@@ -71,6 +87,35 @@ static unsigned char *slurp(const char *path, size_t *n)
 int main(int argc, char **argv)
 {
     fn3 e3, d3; fn5 e5, d5;
+    /* c <id> <in> <out> [-r NM]: ids 62 .. 65 as "ss" coders (64 and 65 only with -r: they are TurboRC numbers too) */
+    unsigned prm0 = 5, prm1 = 6;
+    int with_r = 0;
+    if ((argc == 7 && !strcmp(argv[1], "c") && !strcmp(argv[5], "-r")) || (argc == 6 && !strcmp(argv[1], "c") && !strncmp(argv[5], "-r", 2) && argv[5][2])) {
+        const char *v = argc == 7 ? argv[6] : argv[5] + 2;
+        if (v[0] < '1' || v[0] > '9' || v[1] < '1' || v[1] > '9' || v[2]) { fprintf(stderr, "-r %s: two digits 1..9\n", v); return 2; }
+        prm0 = (unsigned)(v[0] - '0'); prm1 = (unsigned)(v[1] - '0');
+        with_r = 1; argc = 5;
+    }
+    if (argc == 5 && !strcmp(argv[1], "c") && pick_ss(atoi(argv[2])) && (with_r || atoi(argv[2]) < 64)) {
+        const int codec = atoi(argv[2]);
+        size_t n;
+        unsigned char *in = slurp(argv[3], &n);
+        if (!in) return 2;
+        unsigned char *out = malloc(n + n / 3 + 1024);
+        if (!out) { perror("malloc"); return 2; }
+        size_t l = n;
+        if (n && !(l = pick_ss(codec)(in, n, out, prm0, prm1))) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        FILE *f = fopen(argv[4], "wb");
+        if (!f) { perror(argv[4]); return 2; }
+        const uint8_t hdr[8] = { 'T', 'R', 'C', 'F', (uint8_t)(128 | codec), 0, 0, 0 };
+        const uint64_t raw = n, stored = l;
+        fwrite(hdr, 1, 8, f); fwrite(&raw, 8, 1, f); fwrite(&stored, 8, 1, f);
+        fwrite(l == n ? in : out, 1, l, f);
+        fclose(f);
+        printf("%zu -> %zu bytes (%.2f%%)%s\n", n, l, n ? 100.0 * l / n : 0.0, l == n ? "  stored" : "");
+        return 0;
+    }
+    if (with_r) { fprintf(stderr, "-r goes with ids 62 .. 65\n"); return 2; }
     if (argc == 5 && !strcmp(argv[1], "c")) {
         const int id = atoi(argv[2]);
         size_t n;
@@ -110,7 +155,9 @@ int main(int argc, char **argv)
         const unsigned m = fb[5];
         uint64_t raw, stored;
         memcpy(&raw, fb + 8, 8); memcpy(&stored, fb + 16, 8);
-        if (pick(id, &e3, &d3, &e5, &d5)) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        const int ss = id >= 128 && pick_ss(id & 127);                   /* an "ss" coder: the parameters are in the container's header */
+        if (ss) { e3 = d3 = 0; e5 = d5 = 0; }
+        else if (pick(id, &e3, &d3, &e5, &d5)) { fprintf(stderr, "unknown id %d\n", id); return 2; }
         size_t pos = 24;
         cdf_t cdf[257];
         if (d5) {
@@ -123,7 +170,7 @@ int main(int argc, char **argv)
         unsigned char *out = malloc(raw + 1024);
         if (!out) { perror("malloc"); return 2; }
         if (stored == raw) memcpy(out, fb + pos, raw);                    /* stored: the caller copies (CCPY) */
-        else if ((d3 ? d3(fb + pos, raw, out) : d5(fb + pos, raw, out, cdf, m + 1)) != raw) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+        else if ((ss ? trc_decode_host(id & 127, fb + pos, (size_t)stored, out, (size_t)raw, 0, 0) : d3 ? d3(fb + pos, raw, out) : d5(fb + pos, raw, out, cdf, m + 1)) != raw) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
         FILE *f = fopen(argv[3], "wb");
         if (!f) { perror(argv[3]); return 2; }
         fwrite(out, 1, raw, f);
@@ -140,7 +187,8 @@ int main(int argc, char **argv)
         const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
         uint64_t raw, stored;
         memcpy(&raw, fb + 8, 8); memcpy(&stored, fb + 16, 8);
-        if (pick(id, &e3, &d3, &e5, &d5)) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (id >= 128 && pick_ss(id & 127)) { e3 = d3 = 0; e5 = d5 = 0; }       /* an "ss" coder: no CDF, cdfnum 0 = the header's parameters */
+        else if (pick(id, &e3, &d3, &e5, &d5)) { fprintf(stderr, "unknown id %d\n", id); return 2; }
         size_t pos = 24;
         cdf_t cdf[257];
         if (d5) {
@@ -270,6 +318,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
     return 2;
 }

@@ -102,7 +102,20 @@ enum trc_codec {
     , TRC_RC4 = 58,     /* rc4senc    / rc4sdec      adaptive 15-node nibble tree                             (-n -e41) */
     TRC_RC4C = 59,      /* rc4csenc   / rc4csdec     the same walk at probability 1/2: nothing adapts         (-n -e40) */
     TRC_RCU3 = 60       /* rcu3senc   / rcu3sdec     structured 3/5/8-bit varint of a byte, 3 flags + 3 trees  (-e17) */
+    /* the byte-level bitwise coders on the dual-rate "ss" predictor (rc_ss.c; `turborc -pss -rNM`): two 16-bit counters per
+       context, adapted with the shifts prm0 and prm1, a bit coded at their mean.  One lane per chunk, the whole model in LDS,
+       any chunk from TRC_CHUNK_MIN up.  They take no CDF: `cdfnum` of the device and host calls carries TRC_SS_PRM(prm0, prm1),
+       and so does the container header.  The id after TRC_RCU3 is not assigned. */
+    , TRC_RCSS = 62,    /* rcssenc    / rcssdec      order-0 byte, one 255-node tree                          (-pss -e1) */
+    TRC_RC4SS = 63,     /* rc4ssenc   / rc4ssdec     adaptive 15-node nibble tree                             (-pss -n -e41) */
+    TRC_RC4CSS = 64,    /* rc4cssenc  / rc4cssdec    the same walk at probability 1/2: nothing adapts         (-pss -n -e40) */
+    TRC_RCU3SS = 65     /* rcu3ssenc  / rcu3ssdec    structured 3/5/8-bit varint of a byte                    (-pss -e17) */
 };
+
+/* the two shift parameters of the "ss" coders as one `cdfnum` value: each in 1 .. 15 (0 would drive a probability to zero, and
+ * the reference's file header has 4 bits per parameter); anything else is TRC_E_ARG */
+#define TRC_SS_PRM(p0, p1) ((p0) | (p1) << 8)
+#define TRC_SS_PRM_DEFAULT TRC_SS_PRM(5, 6)      /* the reference's defaults (turborc.c:91) */
 
 #define TRC_MAGIC        0x31435254u   /* "TRC1" */
 #define TRC_CHUNK_MIN    256u
@@ -122,7 +135,7 @@ typedef struct trc_container_hdr {
     uint32_t magic;      /* TRC_MAGIC */
     uint8_t  codec;      /* enum trc_codec */
     uint8_t  version;    /* 1 */
-    uint16_t cdfnum;     /* static coders: alphabet size the CDF was built for, else 0 */
+    uint16_t cdfnum;     /* static coders: alphabet size; ss coders: TRC_SS_PRM; else 0 */
     uint32_t chunk;      /* chunk size in bytes */
     uint32_t nchunks;    /* ceil(n / chunk) */
     uint64_t n;          /* original length */
@@ -179,7 +192,7 @@ uint32_t trc_round_chunk(int codec, size_t n);
  * stream).  Calls only enqueue work; they never synchronise.                                    */
 
 /* bytes of device workspace trc_encode_dev / trc_decode_dev need for (codec, n, chunk); 0 for an id that names no coder
- * (42, 51, 56, 57, above 60, negative) or a chunk trc_encode_dev rejects.  codec 0: the 4096 bytes of trc_cdfini_dev. */
+ * (42, 51, 56, 57, 61, above 65, negative) or a chunk trc_encode_dev rejects.  codec 0: the 4096 bytes of trc_cdfini_dev. */
 size_t trc_work_bytes(int codec, size_t n, uint32_t chunk);
 
 /* cdfini on device (reference: rccdf.c:50-68): byte histogram of d_in[0..n) -> 15-bit CDF
@@ -204,7 +217,8 @@ int trc_cdf_from_hist_dev(const uint64_t *d_hist, size_t n_total, uint16_t *d_cd
 int trc_tables_dev(const uint16_t *d_cdf, unsigned cdfnum, void *d_work, size_t work_bytes, void *stream);
 
 /* Encode n bytes at d_in with `codec`.
- *   d_cdf/cdfnum : static coders only (uint16[cdfnum+1], cdf[cdfnum] == 32768), else NULL/0
+ *   d_cdf/cdfnum : static coders only (uint16[cdfnum+1], cdf[cdfnum] == 32768), else NULL/0; the "ss" coders (TRC_RCSS ..
+ *                  TRC_RCU3SS) take NULL and cdfnum = TRC_SS_PRM(prm0, prm1), here and in every decode call below
  *   d_clen       : uint32[nchunks]  <- per-chunk compressed length (== chunk length: raw)
  *   d_payload    : >= n bytes       <- concatenated payloads
  *   d_total      : uint64           <- sum of clen[]
@@ -277,11 +291,13 @@ int trc_hist_allreduce_dev(void *nccl_comm, uint64_t *d_hist, void *stream);
  * error.  Decode with the reference-named decoder of the codec, or trc_decode_dev. */
 size_t trc_container_bound(size_t n, uint32_t chunk);
 size_t trc_encode_host(int codec, const void *in, size_t n, uint32_t chunk, void *out, size_t outcap,
-                       const uint16_t *cdf, unsigned cdfnum);
+                       const uint16_t *cdf, unsigned cdfnum);       /* "ss" coders: cdf = NULL, cdfnum = TRC_SS_PRM(prm0, prm1) */
 
 /* Bounded decode for untrusted input: the reference-named decoders carry no input length, this one does -- the container is
  * validated against `inlen` (trc_container_check) before anything is read; inlen == outlen means "stored raw" and is copied.
- * cdf / cdfnum: static coders only (cdfnum 0: derived from the CDF's terminating 32768).  Returns outlen, 0 on error. */
+ * cdf / cdfnum: static coders only (cdfnum 0: derived from the CDF's terminating 32768).  The "ss" coders take cdf = NULL and
+ * cdfnum = 0 (the parameters are read from the header) or TRC_SS_PRM(..), which must then equal the header's: otherwise 0 is
+ * returned.  Returns outlen, 0 on error. */
 size_t trc_decode_host(int codec, const void *in, size_t inlen, void *out, size_t outlen,
                        const uint16_t *cdf, unsigned cdfnum);
 
@@ -296,7 +312,8 @@ int trc_host_unpin(void *p);
  * carry no input length, so a caller reading untrusted files must check that everything the decoder will touch lies
  * inside its buffer.  Checks header fields, codec (0 = any), the original length (outlen, (size_t)-1 = any), that the
  * directory fits, and that the directory's lengths add up to exactly the stated payload, which must end inside
- * buflen.  Host-only (no GPU needed).  Returns TRC_OK or TRC_E_ARG (text in trc_last_error()). */
+ * buflen; a container of an "ss" coder must hold two parameters in 1 .. 15 in its cdfnum field.  Host-only (no GPU needed).
+ * Returns TRC_OK or TRC_E_ARG (text in trc_last_error()). */
 int trc_container_check(const void *buf, size_t buflen, int codec, size_t outlen);
 
 /* Random access through host pointers.  trc_container_range (host only, no GPU needed) validates the container as

@@ -150,6 +150,20 @@ size_t rc4csenc(unsigned char *src, size_t srclen, unsigned char *dst);     size
  * flag bit, 1..8 two flags and a 3-bit tree, 9..40 three flags and a 5-bit tree, 41..255 three flags and an 8-bit tree */
 size_t rcu3senc(unsigned char *src, size_t srclen, unsigned char *dst);     size_t rcu3sdec(unsigned char *src, size_t dstlen, unsigned char *dst);
 
+/* the same four byte-level coders on the dual-rate "ss" predictor (reference rc_ss.c; `turborc -pss -rNM` with -e1, -n -e41,
+ * -n -e40, -e17): every context holds two 16-bit counters that adapt with the shifts prm0 and prm1, a bit is coded at their
+ * mean.  prm0, prm1: 1 .. 15 each (the reference's defaults: 5, 6; TRC_SS_PRM_DEFAULT in trc_hip.h), anything else returns 0.
+ * The container's header records them; a decoder uses its arguments and returns 0 where the header holds other ones.
+ * rc4css* codes every bit at probability 1/2 whatever the parameters. */
+size_t rcssenc(unsigned char *src, size_t srclen, unsigned char *dst, unsigned prm0, unsigned prm1);
+size_t rcssdec(unsigned char *src, size_t dstlen, unsigned char *dst, unsigned prm0, unsigned prm1);
+size_t rc4ssenc(unsigned char *src, size_t srclen, unsigned char *dst, unsigned prm0, unsigned prm1);
+size_t rc4ssdec(unsigned char *src, size_t dstlen, unsigned char *dst, unsigned prm0, unsigned prm1);
+size_t rc4cssenc(unsigned char *src, size_t srclen, unsigned char *dst, unsigned prm0, unsigned prm1);
+size_t rc4cssdec(unsigned char *src, size_t dstlen, unsigned char *dst, unsigned prm0, unsigned prm1);
+size_t rcu3ssenc(unsigned char *src, size_t srclen, unsigned char *dst, unsigned prm0, unsigned prm1);
+size_t rcu3ssdec(unsigned char *src, size_t dstlen, unsigned char *dst, unsigned prm0, unsigned prm1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@
 # Recipe (what a reference maintainer would put behind `make HIP=1`):
 #   1. compile the reference objects as its makefile does (makefile:118,181,195-201,270-275), sources read where
 #      they lie, objects written to $OUT (default /tmp/trc_link);
-#   2. in rccdf.o / rc_s.o / anscdfs.o / anscdfx.o LOCALIZE every global the library exports
+#   2. in rccdf.o / rc_s.o / rc_ss.o / anscdfs.o / anscdfx.o LOCALIZE every global the library exports
 #      (objcopy --localize-symbols): the objects keep their non-hot functions (rcc2senc, rcx2senc, mbc_c, ...),
 #      which the harness still needs at link time, but no longer define the hot names;
 #   3. link turborc.o + objects + -lturborc_hip;
@@ -45,7 +45,7 @@ gcc $OBJS0 -lrt -lpthread -lm -o turborc_ref
 # ---- 2. hot symbols = (globals the four hot-path objects define) x (what the library exports) ----------------
 nm -D --defined-only "$LIBDIR/libturborc_hip.so" | awk '$2 ~ /^[TDB]$/ {print $3}' | sort -u > lib_exports.txt
 : > hot.txt
-for o in rccdf.o rc_s.o anscdfs.o anscdfx.o; do
+for o in rccdf.o rc_s.o rc_ss.o anscdfs.o anscdfx.o; do
     nm --defined-only "$o" | awk '$2 ~ /^[TDBR]$/ {print $3}' | sort -u > "$o.defs"
     comm -12 "$o.defs" lib_exports.txt > "$o.hot"
     objcopy --localize-symbols="$o.hot" "$o"
@@ -65,7 +65,8 @@ MUST="cdfini rccdfsenc rccdfsbdec rccdfsldec rccdfsvbdec rccdfsvldec rccdfsmenc 
 rccdfenc rccdfdec rccdfienc rccdfidec rccdf4enc rccdf4dec rccdf4ienc rccdf4idec rccdfenc8 rccdfdec8 rccdfienc8 rccdfidec8 rcsenc rcsdec
 rccdfuenc16 rccdfudec16 rccdfvenc16 rccdfvdec16 rccdfvzenc16 rccdfvzdec16 rccdfuenc32 rccdfvenc32 rccdfvzenc32
 anscdfenc anscdfdec anscdfencs anscdfdecs anscdfencx anscdfdecx anscdf4enc anscdf4dec anscdf1enc anscdf1dec anscdf4senc anscdf4sdec
-anscdfuenc16 anscdfuzenc16 anscdfvenc16 anscdfvzenc16 anscdfvenc32 anscdfvzenc32 ansbc ansbd"
+anscdfuenc16 anscdfuzenc16 anscdfvenc16 anscdfvzenc16 anscdfvenc32 anscdfvzenc32 ansbc ansbd
+rcssenc rcssdec rcu3ssenc rcu3ssdec"
 nm turborc_hip > exe.nm
 for s in $MUST; do
     t=$(awk -v s="$s" '$NF == s {print $(NF-1)}' exe.nm | sort -u | tr -d '\n')

@@ -1,0 +1,256 @@
+"""CPU (no GPU): the byte-level bitwise coders on the dual-rate "ss" predictor (TRC_RCSS = 62, TRC_RC4SS = 63, TRC_RC4CSS = 64,
+TRC_RCU3SS = 65) at the library's boundary -- exported and declared symbols, ids and TRC_SS_PRM, the Python tables, the
+no-device chunk and workspace rules, the parameter rule of trc_container_check, the committed fixtures against the
+reference, and the plain-C harness compiling against the headers."""
+import ctypes
+import hashlib
+import json
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import ssbit_lib as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "turbo-range-coder_amd", "libturborc_hip.so")
+GOLD = os.path.join(ROOT, "tests", "golden")
+MB = 10**6
+ENUM = {62: "TRC_RCSS", 63: "TRC_RC4SS", 64: "TRC_RC4CSS", 65: "TRC_RCU3SS"}
+TRC_E_ARG = -1
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(LIB):
+        import __graft_entry__ as g
+        g.build()
+    lib = ctypes.CDLL(LIB)
+    lib.trc_work_bytes.restype = ctypes.c_size_t
+    lib.trc_work_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32]
+    lib.trc_range_work_bytes.restype = ctypes.c_size_t
+    lib.trc_range_work_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t]
+    lib.trc_auto_chunk_codec.restype = ctypes.c_uint32
+    lib.trc_auto_chunk_codec.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    lib.trc_round_chunk.restype = ctypes.c_uint32
+    lib.trc_round_chunk.argtypes = [ctypes.c_int, ctypes.c_size_t]
+    lib.trc_host_plan.restype = ctypes.c_int
+    lib.trc_host_plan.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
+    lib.trc_kernel_name.restype = ctypes.c_char_p
+    lib.trc_kernel_name.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.trc_container_check.restype = ctypes.c_int
+    lib.trc_container_check.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t]
+    return lib
+
+
+@pytest.fixture(scope="module")
+def vectors():
+    return L.load_fixtures(os.path.join(GOLD, "ssbit_vectors.npz"))
+
+
+def test_symbols_exported_and_declared(lib):
+    hdr = open(os.path.join(ROOT, "include", "turborc.h")).read()
+    names = [n for c in L.CODECS for n in L.REF_FN[c]]
+    assert sorted(names) == ["rc4cssdec", "rc4cssenc", "rc4ssdec", "rc4ssenc", "rcssdec", "rcssenc", "rcu3ssdec", "rcu3ssenc"]
+    for name in names:
+        assert hasattr(lib, name), name
+        assert re.search(r"size_t %s\(unsigned char \*src, size_t \w+, unsigned char \*dst, unsigned prm0, unsigned prm1\);" % name, hdr), name
+
+
+def test_codec_ids_in_header(lib):
+    hdr = open(os.path.join(ROOT, "include", "trc_hip.h")).read()
+    assert re.search(r"TRC_RCU3 = 60\b", hdr)
+    for codec, name in ENUM.items():
+        assert re.search(r"\b%s = %d\b" % (name, codec), hdr), name
+        assert lib.trc_kernel_name(codec, 0) == b"trc_rc_ss_enc_kernel" and lib.trc_kernel_name(codec, 1) == b"trc_rc_ss_dec_kernel"
+    assert not re.search(r"= 61\b", hdr)                              # 61 stays unassigned
+    assert lib.trc_kernel_name(61, 0) == b"" and lib.trc_kernel_name(61, 1) == b""
+    assert re.search(r"#define TRC_SS_PRM\(p0, p1\) \(\(p0\) \| \(p1\) << 8\)", hdr)
+    assert re.search(r"#define TRC_SS_PRM_DEFAULT\s+TRC_SS_PRM\(5, 6\)", hdr)
+    assert "static coders: alphabet size; ss coders: TRC_SS_PRM; else 0" in hdr
+    assert hdr.count("(42, 51, 56, 57, 61, above 65, negative)") == 1
+
+
+def test_python_tables():
+    import trc
+    assert list(trc.SSBIT) == L.CODECS
+    assert (trc.RCSS, trc.RC4SS, trc.RC4CSS, trc.RCU3SS) == (62, 63, 64, 65)
+    for c in L.CODECS:
+        assert trc.CODEC_NAMES[c] == L.NAMES[c]
+        assert (trc._HOST_ENC[c], trc._HOST_DEC[c]) == L.REF_FN[c]
+        assert c not in trc.AVAILABLE and c not in trc.VLC_CODECS and c not in trc.NIBBLE_CODECS
+        assert c not in [x for x, _ in trc.NIBBIT]
+        assert getattr(trc, ENUM[c][4:]) == c
+    assert trc.ss_prm((5, 6)) == 5 | 6 << 8
+    import inspect
+    for f in (trc.DeviceCoder.encode, trc.DeviceCoder.decode, trc.DeviceCoder.decode_range, trc.host_encode, trc.host_decode):
+        assert inspect.signature(f).parameters["prm"].default == (5, 6), f
+    assert "prm" in inspect.signature(trc.host_decode_range).parameters
+
+
+@pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
+def test_chunk_and_workspace_rules(lib, codec):
+    for n in (1, 3, 1000, 10 * MB, 100 * MB, 1 << 30):
+        c = lib.trc_round_chunk(codec, n)
+        assert c % 64 == 0 and 512 <= c <= 16384, (n, c)
+        a = lib.trc_auto_chunk_codec(codec, n)
+        assert a % 64 == 0 and 512 <= a <= 16384, (n, a)
+        for chunk in (256, 1024, 4096, 16384):
+            wb = lib.trc_work_bytes(codec, n, chunk)
+            assert wb > n // chunk * chunk
+            # no model area: the workspace is that of the "s" coder of the same shape (rc4s: tables, directory, scratch)
+            assert wb == lib.trc_work_bytes(58, n, chunk)
+            nch = -(-n // chunk)
+            assert 0 < lib.trc_range_work_bytes(codec, n, chunk, nch) == lib.trc_range_work_bytes(58, n, chunk, nch)
+    assert lib.trc_work_bytes(codec, 1000, 100) == 0                # chunk not a multiple of 64
+    assert lib.trc_range_work_bytes(codec, 1000, 100, 1) == 0
+    fc = (ctypes.c_size_t * 64)()
+    for n in (1, 3, 777, 3 * MB + 7):
+        ns = lib.trc_host_plan(codec, n, 0, 0, 0, fc, 64, None)
+        assert ns >= 1 and fc[0] == 0
+        chunk = lib.trc_auto_chunk_codec(codec, n)
+        assert fc[min(ns, 63)] == (n + chunk - 1) // chunk or ns >= 63
+    assert lib.trc_host_plan(codec, 0, 0, 0, 0, fc, 64, None) < 0
+    pb = ctypes.c_uint32(7)
+    assert lib.trc_host_plan(codec, 100 * MB, 0, 0, 1, fc, 64, ctypes.byref(pb)) >= 1 and pb.value == 0     # no gate, no streaming
+    assert lib.trc_host_plan(codec, 100 * MB, 0, 1, 1, fc, 64, ctypes.byref(pb)) >= 1 and pb.value == 0
+
+
+def test_id_61_and_ids_above_65_stay_unassigned(lib):
+    fc = (ctypes.c_size_t * 4)()
+    for codec in (61, 66, 67, 100):
+        for n in (1, 1000, 100 * MB):
+            for chunk in (256, 1024, 4096, 16384):
+                assert lib.trc_work_bytes(codec, n, chunk) == 0
+                assert lib.trc_range_work_bytes(codec, n, chunk, 1) == 0
+        assert lib.trc_host_plan(codec, 1000, 0, 0, 0, fc, 4, None) < 0
+        assert lib.trc_kernel_name(codec, 0) == b""
+
+
+def container(codec, field, n=5 * 256 + 7, chunk=256, clen=(256, 10, 256, 33, 1, 7)):
+    """a hand-built container: header with `field` in the cdfnum place, directory, filler payload"""
+    clen = np.array(clen, dtype=np.uint32)
+    lens = np.minimum(chunk, n - np.arange(0, n, chunk))
+    pay = int(np.minimum(clen, lens).sum())
+    hdr = struct.pack("<IBBHIIQQ", 0x31435254, codec, 1, field, chunk, len(clen), n, pay)
+    return np.frombuffer(hdr + clen.astype("<u4").tobytes() + bytes(pay), dtype=np.uint8).copy(), n
+
+
+@pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
+def test_container_check_parameter_rule(lib, codec):
+    def verdict(field, named=codec):
+        buf, n = container(codec, field)
+        return lib.trc_container_check(buf.ctypes.data, buf.size, named, n)
+    assert verdict(5 | 6 << 8) == 0 and verdict(5 | 6 << 8, 0) == 0
+    assert verdict(1 | 1 << 8) == 0 and verdict(15 | 15 << 8) == 0
+    for p0, p1 in ((0, 6), (5, 16), (5, 0), (16, 6), (0, 0)):
+        assert verdict(p0 | p1 << 8) == TRC_E_ARG, (p0, p1)
+        assert verdict(p0 | p1 << 8, 0) == TRC_E_ARG, (p0, p1)
+    assert verdict(5 | 6 << 8 | 0x1000) == TRC_E_ARG               # bits above a parameter's four
+    # ... and trc_container_range, which validates in the same way
+    import trc
+    buf, n = container(codec, 0 | 6 << 8)
+    r = trc.Range()
+    l = trc.lib()
+    assert l.trc_container_range(buf.ctypes.data, buf.size, codec, 0, 10, ctypes.byref(r)) == TRC_E_ARG
+    buf, n = container(codec, 5 | 6 << 8)
+    assert l.trc_container_range(buf.ctypes.data, buf.size, codec, 0, 10, ctypes.byref(r)) == 0
+
+
+def test_other_ids_ignore_the_field(lib):
+    """an id-4 container is judged as before whatever its cdfnum field holds"""
+    for field in (0, 256, 0x0605, 0x1000, 0xffff):
+        buf, n = container(4, field)
+        assert lib.trc_container_check(buf.ctypes.data, buf.size, 4, n) == 0, field
+        assert lib.trc_container_check(buf.ctypes.data, buf.size, 0, n) == 0, field
+        assert lib.trc_container_check(buf.ctypes.data, buf.size - 1, 4, n) == TRC_E_ARG
+
+
+def test_fixture_inputs_regenerate(vectors):
+    z, index = vectors
+    assert {e["chunk"] for e in index} == {256, 1024, 4096, 65536}
+    assert {e["kind"] for e in index} == set(L.KINDS)
+    ns = {e["n"] for e in index if e["chunk"] == 256}
+    assert {1, 2, 3, 8, 9, 10, 63, 64, 65, 255, 256, 257, 256 + 9, 3 * 256 + 10, 64 * 256 + 1, 65 * 256}.issubset(ns)
+    for chunk in (1024, 4096):
+        assert any(e["n"] > chunk for e in index if e["chunk"] == chunk)
+    assert len({e["kind"] for e in index if e["chunk"] == 65536 and e["n"] > 65536}) == 2
+    for e in index:
+        d = L.gen(e["kind"], e["n"], e["seed"], e["chunk"])
+        assert hashlib.sha256(d.tobytes()).hexdigest() == e["in_sha256"], e["case"]
+        prms = [tuple(p) for p in e["prms"]]
+        assert L.DEFAULT in prms
+        if e["chunk"] == 256 and e["kind"] in ("mixed", "nib_skew"):
+            assert prms == L.PRMS and {(4, 7), (1, 1), (1, 9), (15, 15)}.issubset(prms)
+    with open(os.path.join(GOLD, "ssbit_large.json")) as f:
+        large = json.load(f)
+    assert [e["codec"] for e in large] == [L.NAMES[c] for c in L.CODECS]
+    for e in large:
+        assert (e["n"], e["chunk"], e["kind"], tuple(e["prm"])) == (4 << 20, 1024, "mixed", (5, 6))
+    e = large[0]
+    assert hashlib.sha256(L.gen(e["kind"], e["n"], e["seed"], e["chunk"]).tobytes()).hexdigest() == e["in_sha256"]
+    assert os.path.getsize(os.path.join(GOLD, "ssbit_vectors.npz")) < 512 * 1024
+
+
+def test_fixture_properties(vectors):
+    """what the generator asserted, read back off the committed file (needs no reference)"""
+    z, index = vectors
+    raw = {c: 0 for c in L.CODECS}
+    coded = {c: 0 for c in L.CODECS}
+    differs = 0
+    for e in index:
+        n, chunk = e["n"], e["chunk"]
+        lens = np.minimum(chunk, n - np.arange(0, n, chunk))
+        for c in L.CODECS:
+            for prm in e["prms"]:
+                clen, payload = L.fixture(z, e, c, prm)
+                assert clen.size == lens.size and int(clen.sum()) == payload.size
+                israw = clen == lens
+                assert israw[lens <= 9].all()                       # the raw rule: 9 bytes and fewer are always raw
+                raw[c] += int(israw.sum()); coded[c] += int((~israw).sum())
+                if c == L.RC4CSS:                                    # 4 bits per nibble whatever the data and the parameters, and a 4-byte flush
+                    full = ~israw & np.isin(lens, (256, 1024, 4096, 65536))
+                    assert (clen[full] == lens[full] // 2 + 4).all()
+                if tuple(prm) == (4, 7):
+                    differs += not np.array_equal(payload, L.fixture(z, e, c, L.DEFAULT)[1])
+    for c in L.CODECS:
+        assert raw[c] >= 1 and coded[c] >= 40, (L.NAMES[c], raw[c], coded[c])
+    assert differs >= 1
+
+
+def test_fixtures_equal_the_reference(vectors, tmp_path):
+    if not L.have_ref_sources():
+        pytest.skip("the reference sources are not here")
+    R = L.Ref(tmp_path)
+    z, index = vectors
+    for e in index:
+        d = L.gen(e["kind"], e["n"], e["seed"], e["chunk"])
+        for c in L.CODECS:
+            for prm in e["prms"]:
+                tag = (e["case"], L.NAMES[c], prm)
+                eclen, epay = L.fixture(z, e, c, prm)
+                clen, payload = R.chunked_enc(c, d, e["chunk"], prm)
+                assert np.array_equal(clen, eclen), tag
+                assert np.array_equal(payload, epay), tag
+                # and the reference decodes every coded chunk of it back (the nibble coders: to the low nibbles)
+                want = L.expected(c, d, clen, e["chunk"])
+                off = 0
+                for i, l in enumerate(clen):
+                    piece = want[i * e["chunk"]:(i + 1) * e["chunk"]]
+                    if l != piece.size:
+                        assert np.array_equal(R.dec(c, payload[off:off + l], piece.size, prm), piece), tag + (i,)
+                    off += int(l)
+
+
+def test_trcbench_compiles_against_the_headers(tmp_path):
+    exe = tmp_path / "trcbench"
+    r = subprocess.run(["cc", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "harness", "trcbench.c"),
+                        "-L", os.path.dirname(LIB), "-lturborc_hip", "-lm", "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    src = open(os.path.join(ROOT, "harness", "trcbench.c")).read()
+    for name in (n for c in L.CODECS for n in L.REF_FN[c]):
+        assert name in src, name

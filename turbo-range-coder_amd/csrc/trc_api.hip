@@ -130,6 +130,12 @@ static size_t word_area(const TrcCodec &c, size_t nchunks) { return trc_word_slo
 #define NIBBIT(i, ns, lanes) \
     { .id = i, LAUNCH(nibbit), .k = i - TRC_RC4, .gather = TRC_GATHER_START, .wave_ns = ns, .round_lanes = lanes, \
       .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, .pad = 128, KERNELS("trc_rc_nib_enc_kernel", "trc_rc_nib_dec_kernel") }
+// the same shape on the dual-rate "ss" predictor (trc_rc_ss.hip: rc4ss 4 KiB of LDS per wave, rcss 64 KiB, rcu3ss 74.75 KiB, rc4css
+// none); the call's two shift parameters travel in `cdfnum` (TRC_SS_PRM).  wave_ns and round_lanes are those of the "s" counterparts (rcs, rc4s, rc4cs, rcu3s) until the sweep of
+// profiles/ssbit/ssbit_notes.md has been run: not measured
+#define SSBIT(i, kk, ns, lanes) \
+    { .id = i, LAUNCH(ssbit), .k = kk, .gather = TRC_GATHER_START, .ss = true, .wave_ns = ns, .round_lanes = lanes, \
+      .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, .pad = 128, KERNELS("trc_rc_ss_enc_kernel", "trc_rc_ss_dec_kernel") }
 // what an id without a coder answers to trc_auto_chunk_codec / trc_round_chunk
 #define NONE(i) { .id = i, .wave_ns = 400, .round_lanes = 327680u, .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, KERNELS("", "") }
 
@@ -168,6 +174,9 @@ static constexpr TrcCodec g_codecs[] = {
     WORD(TRC_RCW16, 1340), WORD(TRC_RCW32, 1430), WORD(TRC_RCCW32, 1460), WORD(TRC_RCC2W32, 1440),
     NONE(56), NONE(57),
     NIBBIT(TRC_RC4, 570, 196608u), NIBBIT(TRC_RC4C, 320, 98304u), NIBBIT(TRC_RCU3, 1500, TRC_MODEL_ROUND_CHUNKS),
+    NONE(61),
+    SSBIT(TRC_RCSS, 3, 592, TRC_MODEL_ROUND_CHUNKS), SSBIT(TRC_RC4SS, 0, 570, 196608u), SSBIT(TRC_RC4CSS, 1, 320, 98304u),
+    SSBIT(TRC_RCU3SS, 2, 1500, TRC_MODEL_ROUND_CHUNKS),
 };
 #undef LAUNCH
 #undef KERNELS
@@ -180,6 +189,7 @@ static constexpr TrcCodec g_codecs[] = {
 #undef BVLC
 #undef WORD
 #undef NIBBIT
+#undef SSBIT
 #undef NONE
 static constexpr int TRC_NCODECS = (int)(sizeof g_codecs / sizeof g_codecs[0]);
 static constexpr bool rows_in_id_order()
@@ -191,6 +201,8 @@ static_assert(rows_in_id_order(), "g_codecs[i] must be the row of id i");
 // the row of an id; ids without a coder get a row without launchers
 static const TrcCodec &codec_row(int codec) { return g_codecs[codec > 0 && codec < TRC_NCODECS ? codec : 0]; }
 static bool codec_ok(int codec) { return codec_row(codec).enc != nullptr; }
+// the two shift parameters of an "ss" coder as `cdfnum` carries them (TRC_SS_PRM): each in 1 .. 15, nothing above them
+static bool ss_prm_ok(unsigned v) { return !(v & ~0x0f0fu) && (v & 0x0fu) && (v & 0x0f00u); }
 
 // ------------------------------------------------------------------------------------ config ---
 // The chunk is the parallel unit AND the price of the format: every chunk costs 8 bytes of coder state and 4 bytes of
@@ -317,6 +329,8 @@ static int check_common(int codec, size_t n, uint32_t chunk, const uint16_t *d_c
     if ((n + chunk - 1) / chunk > 0x7fffffffu) return fail(TRC_E_ARG, "too many chunks");
     if (chunk > r.chunk_max) return fail(TRC_E_ARG, "codec %d: chunk %u exceeds %u", r.id, chunk, r.chunk_max);
     if (r.cdf && (!d_cdf || cdfnum < 1 || cdfnum > 256)) return fail(TRC_E_CDF, "static coder needs a CDF with 1..256 symbols");
+    if (r.ss && (d_cdf || !ss_prm_ok(cdfnum)))
+        return fail(TRC_E_ARG, "codec %d takes no CDF and cdfnum = TRC_SS_PRM(prm0, prm1) with both in 1..15 (got %s, 0x%x)", r.id, d_cdf ? "a CDF" : "none", cdfnum);
     return TRC_OK;
 }
 
@@ -469,6 +483,7 @@ extern "C" int trc_encode_dev(int codec, const void *d_in, size_t n, uint32_t ch
     const TrcCodec &r = codec_row(codec);
     TrcWork w;
     if ((rc = carve(r, n, chunk, d_work, work_bytes, w))) return rc;
+    w.ss_prm = r.ss ? cdfnum : 0u;
     if (r.cdf && !tables_ready) trc_launch_static_prep(d_cdf, cdfnum, w.tables, s);
     tm_begin(0);
     r.enc(r, (const uint8_t *)d_in, n, chunk, w, d_clen, s);
@@ -496,6 +511,7 @@ extern "C" int trc_decode_dev(int codec, const uint32_t *d_clen, const void *d_p
     const TrcCodec &r = codec_row(codec);
     TrcWork w;
     if ((rc = carve(r, n, chunk, d_work, work_bytes, w))) return rc;
+    w.ss_prm = r.ss ? cdfnum : 0u;
     if (r.cdf && !tables_ready) trc_launch_static_prep(d_cdf, cdfnum, w.tables, s);
     // TRC_DIR_READY promises that the last encode OR DECODE on this workspace was of this directory (include/trc_hip.h), so both must
     // leave every group's base in goff_area: an encode's gather does (trc_launch.h); a decode derives the sums from clen[] and scans
@@ -564,6 +580,7 @@ extern "C" int trc_decode_range_dev(int codec, const uint32_t *d_clen, const voi
     w.stride = chunk + r.pad;
     w.stride2 = r.s2_mul * chunk + r.s2_add;
     w.nchunks = (uint32_t)count; w.ngroups = (uint32_t)ngroups_sub;
+    w.ss_prm = r.ss ? cdfnum : 0u;
     if (r.cdf && !tables_ready) trc_launch_static_prep(d_cdf, cdfnum, w.tables, s);
     if (!dir_ready) {                    // O(nchunks), once per container and workspace; everything below is O(count)
         trc_launch_group_sums(d_clen, (uint32_t)nchunks, n, chunk, gsum_full, s);
@@ -653,6 +670,7 @@ static int container_verdict(const void *buf, size_t buflen, int codec, size_t o
     memcpy(&h, buf, sizeof h);
     if (h.magic != TRC_MAGIC || h.version != 1) BAD("container: bad magic/version");
     if (!codec_ok(h.codec) || (codec && h.codec != codec)) BAD("container: codec %u (expected %d)", h.codec, codec);
+    if (codec_row(h.codec).ss && !ss_prm_ok(h.cdfnum)) BAD("container: codec %u with parameters 0x%x (each must be 1..15)", h.codec, h.cdfnum);
     if (!chunk_ok(h.chunk)) BAD("container: chunk %u", h.chunk);
     if (outlen != (size_t)-1 && h.n != outlen) BAD("container: holds %llu bytes, caller expects %zu", (unsigned long long)h.n, outlen);
     if (h.n == 0 || (h.n + h.chunk - 1) / h.chunk != h.nchunks) BAD("container: nchunks %u does not match n/chunk", h.nchunks);
@@ -680,6 +698,12 @@ extern "C" int trc_container_check(const void *buf, size_t buflen, int codec, si
 #include "trc_range.inc"
 
 // ---- exports with the reference's names (include/turborc.h:500, include/anscdf.h:40-96) ----------
+static bool ss_args_ok(const char *who, unsigned prm0, unsigned prm1)
+{
+    if (prm0 >= 1 && prm0 <= 15 && prm1 >= 1 && prm1 <= 15) return true;
+    fail(TRC_E_ARG, "%s: parameters (%u, %u) must both be in 1..15", who, prm0, prm1);
+    return false;
+}
 extern "C" {
 
 // cdfini: reference rccdf.c:50-68.  Returns (int)inlen; -1 where the reference would die().
@@ -812,6 +836,17 @@ TRC_HOST(rccsenc32, rccsdec32, TRC_RCCW32)   TRC_HOST(rcc2senc32, rcc2sdec32, TR
 // bitwise nibble coders, adaptive and static (reference rc_.c:141-184; turborc -n -e41 / -e40), and the structured 3/5/8-bit
 // varint byte coder (rc_.c:442-462; turborc -e17)
 TRC_HOST(rc4senc, rc4sdec, TRC_RC4)          TRC_HOST(rc4csenc, rc4csdec, TRC_RC4C)       TRC_HOST(rcu3senc, rcu3sdec, TRC_RCU3)
+
+// the same byte-level coders on the dual-rate "ss" predictor (reference rc_ss.c; turborc -pss -rNM): the two shift parameters
+// are arguments; a decoder uses its own and fails where the container's header holds other ones
+#define TRC_HOST_SS(enc, dec, id) \
+    size_t enc(unsigned char *in, size_t inlen, unsigned char *out, unsigned prm0, unsigned prm1) \
+    { return ss_args_ok(#enc, prm0, prm1) ? host_encode(id, in, inlen, out, nullptr, (int)TRC_SS_PRM(prm0, prm1)) : 0; } \
+    size_t dec(unsigned char *in, size_t outlen, unsigned char *out, unsigned prm0, unsigned prm1) \
+    { return ss_args_ok(#dec, prm0, prm1) ? host_decode(id, in, outlen, out, nullptr, (int)TRC_SS_PRM(prm0, prm1)) : 0; }
+TRC_HOST_SS(rcssenc, rcssdec, TRC_RCSS)          TRC_HOST_SS(rc4ssenc, rc4ssdec, TRC_RC4SS)
+TRC_HOST_SS(rc4cssenc, rc4cssdec, TRC_RC4CSS)    TRC_HOST_SS(rcu3ssenc, rcu3ssdec, TRC_RCU3SS)
+#undef TRC_HOST_SS
 
 // adaptive-CDF byte range coder (reference rccdf.c:187-211; turborc -e46)
 TRC_HOST(rccdfenc, rccdfdec, TRC_RCA)

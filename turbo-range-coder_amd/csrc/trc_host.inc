@@ -617,6 +617,7 @@ void shard_plan(size_t nchunks, int ndev, std::vector<size_t> &first)
 // What the shards of one call share.  Errors of a worker thread travel through `err` (trc_last_error is per thread).
 struct HostJob {
     int codec = 0; uint32_t chunk = 0; int cdfnum = 0; const cdf_t *cdf = nullptr;
+    unsigned prm = 0;                     // "ss" coders: TRC_SS_PRM of the call (they have no CDF: cdfnum stays 0), else 0
     const uint8_t *in = nullptr; uint8_t *out = nullptr;
     size_t n = 0;                         // plain bytes (encode: inlen, decode: outlen)
     size_t nchunks = 0, dir = 0, hdrsz = sizeof(trc_container_hdr);
@@ -713,7 +714,7 @@ bool encode_shard(HostCtx &c, HostJob &J, int s)
         else if (!push_in(c, J, c.d_in + o, J.in + b0 + o, l)) return false;
         SCHK(hipEventRecord(c.ev_h[j], c.s_in));
         SCHK(hipStreamWaitEvent(c.s_k[ks], c.ev_h[j], 0));
-        if (trc_encode_dev(codec | flags, c.d_in + o, l, chunk, cdfnum ? d_cdf : nullptr, (unsigned)cdfnum, d_clen + sc[j], slice_pay(j),
+        if (trc_encode_dev(codec | flags, c.d_in + o, l, chunk, cdfnum ? d_cdf : nullptr, cdfnum ? (unsigned)cdfnum : J.prm, d_clen + sc[j], slice_pay(j),
                            d_tot + j, c.d_work[ks], c.cap_work[ks], c.s_k[ks])) SFAIL(trc_last_error());
         SCHK(hipMemcpyAsync(c.pin_tot + j, d_tot + j, 8, hipMemcpyDeviceToHost, c.s_k[ks]));
         SCHK(hipEventRecord(c.ev_k[j], c.s_k[ks]));
@@ -732,7 +733,7 @@ bool encode_shard(HostCtx &c, HostJob &J, int s)
         auto launch = [&]() -> bool {
             SCHK(hipStreamWaitEvent(c.s_k[ks], c.ev_h[0], 0));                         // behind the gates' reset, not behind the input
             trc_gate_tls = { gates + j, (uint32_t)part };
-            const int rc = trc_encode_dev(codec | flags, c.d_in + o, l, chunk, cdfnum ? d_cdf : nullptr, (unsigned)cdfnum, d_clen + sc[j], slice_pay(j),
+            const int rc = trc_encode_dev(codec | flags, c.d_in + o, l, chunk, cdfnum ? d_cdf : nullptr, cdfnum ? (unsigned)cdfnum : J.prm, d_clen + sc[j], slice_pay(j),
                                           d_tot + j, c.d_work[ks], c.cap_work[ks], c.s_k[ks]);
             trc_gate_tls = { nullptr, 0 };
             if (rc) SFAIL(trc_last_error());
@@ -878,7 +879,7 @@ bool decode_shard(HostCtx &c, HostJob &J, int s)
             for (size_t k = 0; k < 16; k++) pflags[k] = 0;
             SCHK(hipMemsetAsync(counters, 0, 64, c.s_k[ks]));
             trc_prog_tls = { counters, c.pin_prog + 16 * i, (uint32_t)part };
-            const int rc = trc_decode_dev(codec | flags, d_clen + c0, slice_pay(i), l, chunk, cdfnum ? d_cdf : nullptr, (unsigned)cdfnum,
+            const int rc = trc_decode_dev(codec | flags, d_clen + c0, slice_pay(i), l, chunk, cdfnum ? d_cdf : nullptr, cdfnum ? (unsigned)cdfnum : J.prm,
                                           c.d_in + o, c.d_work[ks], c.cap_work[ks], c.s_k[ks]);
             trc_prog_tls = { nullptr, nullptr, 0 };
             if (rc) SFAIL(trc_last_error());
@@ -894,7 +895,7 @@ bool decode_shard(HostCtx &c, HostJob &J, int s)
             }
             continue;
         }
-        if (trc_decode_dev(codec | flags, d_clen + c0, slice_pay(i), l, chunk, cdfnum ? d_cdf : nullptr, (unsigned)cdfnum,
+        if (trc_decode_dev(codec | flags, d_clen + c0, slice_pay(i), l, chunk, cdfnum ? d_cdf : nullptr, cdfnum ? (unsigned)cdfnum : J.prm,
                            c.d_in + o, c.d_work[ks], c.cap_work[ks], c.s_k[ks])) SFAIL(trc_last_error());
         SCHK(hipEventRecord(c.ev_k[i], c.s_k[ks]));
         if (J.out_direct) {
@@ -994,6 +995,9 @@ static size_t host_encode(int codec, const unsigned char *in, size_t inlen, unsi
     if (r.cdf) {
         if (cdfnum <= 0) cdfnum = host_cdfnum(cdf);
         if (cdfnum <= 0 || cdfnum > 256) { fail(TRC_E_CDF, "bad CDF (need cdf[0]=0 < ... < cdf[cdfnum]=32768)"); return 0; }
+    } else if (r.ss) {
+        if (cdf || !ss_prm_ok((unsigned)cdfnum)) { fail(TRC_E_ARG, "codec %d takes no CDF and cdfnum = TRC_SS_PRM(prm0, prm1) with both in 1..15 (got 0x%x)", codec, (unsigned)cdfnum); return 0; }
+        J.prm = (unsigned)cdfnum; cdfnum = 0;
     } else cdfnum = 0;
     J.cdfnum = cdfnum;
     J.lim = outcap ? (size_t)-1 : inlen > J.hdrsz + J.dir ? inlen - J.hdrsz - J.dir : 0;      // payload bytes above which the call returns raw
@@ -1020,7 +1024,7 @@ static size_t host_encode(int codec, const unsigned char *in, size_t inlen, unsi
     for (int s = 0; s < nshard; s++) ppos += (size_t)J.total[s];
     trc_container_hdr h;
     memset(&h, 0, sizeof h);
-    h.magic = TRC_MAGIC; h.codec = (uint8_t)codec; h.version = 1; h.cdfnum = (uint16_t)cdfnum;
+    h.magic = TRC_MAGIC; h.codec = (uint8_t)codec; h.version = 1; h.cdfnum = (uint16_t)(cdfnum ? (unsigned)cdfnum : J.prm);
     h.chunk = chunk; h.nchunks = (uint32_t)J.nchunks; h.n = inlen; h.payload = ppos;
     memcpy(out, &h, J.hdrsz);
     return J.hdrsz + J.dir + ppos;
@@ -1051,6 +1055,10 @@ static size_t host_decode(int codec, const unsigned char *in, size_t outlen, uns
     if (codec_row(codec).cdf) {
         if (cdfnum <= 0) cdfnum = host_cdfnum(cdf);
         if (cdfnum <= 0 || cdfnum > 256) { fail(TRC_E_CDF, "bad CDF"); return 0; }
+    } else if (codec_row(codec).ss) {
+        // the header's parameters (validated by trc_container_check above); a caller that states its own must state the same
+        if (cdfnum && (unsigned)cdfnum != h.cdfnum) { fail(TRC_E_ARG, "codec %d: the container was coded with parameters 0x%x, the caller states 0x%x", codec, h.cdfnum, (unsigned)cdfnum); return 0; }
+        J.prm = h.cdfnum; cdfnum = 0;
     } else cdfnum = 0;
     J.cdfnum = cdfnum;
     // payload offset of every group of 64 chunks, from the directory (the decoders clamp an entry above the chunk length to "raw")

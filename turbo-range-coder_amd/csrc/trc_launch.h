@@ -65,6 +65,7 @@ struct TrcWork {
     uint8_t  *model;     // models in HBM (TrcCodec::model_area): ANSO1, RCC1, RCX1 one order-1 model per chunk (136 / 136 / 64 KiB); trees
                          // of the 32-bit Rice, Turbo-VLC context and word coders
     uint32_t *aux;       // Turbo-VLC coders: two u32 per chunk (length of the first payload piece; mantissa bits)
+    uint32_t  ss_prm;    // "ss" predictor coders: the call's two shift parameters, prm0 | prm1 << 8 (TRC_SS_PRM), else 0
 };
 #define TRC_O1_MODEL_BYTES (256u * 17u * 32u)
 
@@ -118,6 +119,7 @@ struct TrcCodec {
     int8_t elem;               // Turbo-VLC: element bytes (2 or 4)
     TrcGather gather;
     bool cdf;                  // static coder: needs a CDF, derives its tables from it
+    bool ss;                   // "ss" predictor coder: no CDF, `cdfnum` carries the two shift parameters (TRC_SS_PRM)
     bool aux;                  // two u32 per chunk in the workspace (TrcWork::aux)
     bool gate;                 // the encoder waits at the arrival gate (WaveChunks::gate)
     bool prog;                 // the decoder reports its progress (WaveChunks::prog)
@@ -159,6 +161,9 @@ size_t trc_word_model_bytes(int k);
 size_t trc_word_slots(int k, size_t nchunks);
 // RC4 / RC4C / RCU3: bitwise nibble and varint byte coders (k = codec - TRC_RC4: rc4s, rc4cs, rcu3s); models in LDS, none for rc4cs
 TrcEncFn trc_launch_nibbit_enc; TrcDecFn trc_launch_nibbit_dec;
+// RC4SS / RC4CSS / RCU3SS / RCSS: the byte-level bitwise coders on the dual-rate "ss" predictor (k = 0 rc4ss, 1 rc4css, 2 rcu3ss,
+// 3 rcss); models in LDS, none for rc4css; the two shift parameters in w.ss_prm
+TrcEncFn trc_launch_ssbit_enc;  TrcDecFn trc_launch_ssbit_dec;
 void trc_o1bit_fill(uint8_t *model, size_t bytes, hipStream_t s);   // set `bytes` (a multiple of 16) of tree nodes to 0x4000
 // RCA / RCAI: adaptive-CDF byte range coder, 1 stream (rccdfenc / rccdfdec) or hi/lo nibbles on 2 streams (rccdfienc / rccdfidec);
 // nibble != 0: the `turborc -n` coders on values 0..15 (rccdf4enc/dec, rccdf4ienc/idec)

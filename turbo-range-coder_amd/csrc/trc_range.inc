@@ -35,7 +35,7 @@ extern "C" int trc_container_range(const void *buf, size_t buflen, int codec, si
 // one plain trc_decode_dev of (out_bytes, chunk) runs on the caller's current device (its context of the host-pointer calls: its
 // buffers, its first coder stream), `len` bytes come back.  One copy each way and one launch: no slices, no staging threads.
 static size_t host_decode_range(int codec, const uint8_t *in, const trc_container_hdr &h, const trc_range &R, size_t len, uint8_t *out,
-                                const cdf_t *cdf, int cdfnum)
+                                const cdf_t *cdf, int cdfnum, unsigned prm)
 {
     HostCtx *cp = nullptr;
     int dev = 0;
@@ -57,7 +57,7 @@ static size_t host_decode_range(int codec, const uint8_t *in, const trc_containe
     if (cdfnum) RCHK(hipMemcpyAsync(d_cdf, cdf, (cdfnum + 1) * sizeof(cdf_t), hipMemcpyHostToDevice, s));
     RCHK(hipMemcpyAsync(d_clen, dir + 4 * (size_t)R.first_chunk, 4 * (size_t)R.nchunks, hipMemcpyHostToDevice, s));
     if (R.payload_len) RCHK(hipMemcpyAsync(d_payload, pay + R.payload_off, (size_t)R.payload_len, hipMemcpyHostToDevice, s));
-    if (trc_decode_dev(codec, d_clen, d_payload, (size_t)R.out_bytes, h.chunk, cdfnum ? d_cdf : nullptr, (unsigned)cdfnum,
+    if (trc_decode_dev(codec, d_clen, d_payload, (size_t)R.out_bytes, h.chunk, cdfnum ? d_cdf : nullptr, cdfnum ? (unsigned)cdfnum : prm,
                        c.d_in, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
     RCHK(hipMemcpyAsync(out, c.d_in + R.out_skip, len, hipMemcpyDeviceToHost, s));
     RCHK(hipStreamSynchronize(s));
@@ -82,7 +82,12 @@ extern "C" size_t trc_decode_range_host(int codec, const void *in, size_t inlen,
         ncdf = (int)cdfnum > 0 ? (int)cdfnum : host_cdfnum((const cdf_t *)cdf);
         if (!cdf || ncdf <= 0 || ncdf > 256) { fail(TRC_E_CDF, "bad CDF"); return 0; }
     }
+    unsigned prm = 0;
+    if (codec_row(codec).ss) {                                  // the header's parameters; a caller that states its own must state the same
+        if (cdfnum && cdfnum != h.cdfnum) { fail(TRC_E_ARG, "codec %d: the container was coded with parameters 0x%x, the caller states 0x%x", codec, h.cdfnum, cdfnum); return 0; }
+        prm = h.cdfnum;
+    }
     trc_range R;
     range_plan((const uint8_t *)in, h, offset, len, &R);
-    return host_decode_range(codec, (const uint8_t *)in, h, R, len, (uint8_t *)out, (const cdf_t *)cdf, ncdf);
+    return host_decode_range(codec, (const uint8_t *)in, h, R, len, (uint8_t *)out, (const cdf_t *)cdf, ncdf, prm);
 }

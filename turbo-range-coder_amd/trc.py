@@ -32,6 +32,8 @@ RCW16, RCW32, RCCW32, RCC2W32 = 52, 53, 54, 55                                  
 WORD = ((RCW16, 2), (RCW32, 4), (RCCW32, 4), (RCC2W32, 4))          # (codec, element bytes); kept out of AVAILABLE for the same reason as CTXBIT
 RC4, RC4C, RCU3 = 58, 59, 60                                                    # bitwise nibble coders (turborc -n -e41 / -e40), 3/5/8-bit varint (-e17)
 NIBBIT = ((RC4, 1), (RC4C, 1), (RCU3, 1))                           # (codec, element bytes); kept out of AVAILABLE for the same reason as CTXBIT
+RCSS, RC4SS, RC4CSS, RCU3SS = 62, 63, 64, 65                                    # the same on the dual-rate "ss" predictor (turborc -pss -e1 / -n -e41 / -n -e40 / -e17)
+SSBIT = (RCSS, RC4SS, RC4CSS, RCU3SS)                               # kept out of AVAILABLE for the same reason as CTXBIT; they take prm=(prm0, prm1)
 CTXBIT = (RCC1, RCX1)      # HIP kernels too, kept out of AVAILABLE: the suites over AVAILABLE check parity against the oracle/ restatement,
                            # which has no order-1 bitwise coder; tests/test_gpu_ctxbit.py checks them against fixtures made through the reference
 CODEC_NAMES = {ANS4S: "anscdf4s", RCS1: "rccdfs", RCS2: "rccdfs2", RCA: "rccdf", ANSA: "anscdf", RCB: "rcs", RCAI: "rccdfi",
@@ -44,7 +46,7 @@ CODEC_NAMES = {ANS4S: "anscdf4s", RCS1: "rccdfs", RCS2: "rccdfs2", RCA: "rccdf",
                RCBV16: "rcvs16", RCBV32: "rcvs32", RCBVZ16: "rcvzs16", RCBVZ32: "rcvzs32",
                RCBVG16: "rcvgs16", RCBVG32: "rcvgs32", RCBVGZ16: "rcvgzs16", RCBVGZ32: "rcvgzs32",
                RCW16: "rcs16", RCW32: "rcs32", RCCW32: "rccs32", RCC2W32: "rcc2s32",
-               RC4: "rc4s", RC4C: "rc4cs", RCU3: "rcu3s"}
+               RC4: "rc4s", RC4C: "rc4cs", RCU3: "rcu3s", RCSS: "rcss", RC4SS: "rc4ss", RC4CSS: "rc4css", RCU3SS: "rcu3ss"}
 VLC_CODECS = (VLCU16, VLCU32, VLCV16, VLCV32, VLCVZ16, VLCVZ32, VLAU16, VLAUZ16, VLAV16, VLAVZ16, VLAV32, VLAVZ32)
 VLC_ELEM = {VLCU16: 2, VLCU32: 4, VLCV16: 2, VLCV32: 4, VLCVZ16: 2, VLCVZ32: 4,
             VLAU16: 2, VLAUZ16: 2, VLAV16: 2, VLAVZ16: 2, VLAV32: 4, VLAVZ32: 4}
@@ -153,6 +155,16 @@ def timing_read(decode):
     return ms.value, cnt.value
 
 
+def ss_prm(prm):
+    """TRC_SS_PRM(prm0, prm1) of include/trc_hip.h: the `cdfnum` of an "ss" coder's call"""
+    return int(prm[0]) | int(prm[1]) << 8
+
+
+def _cdfnum(codec, cdfnum, prm):
+    """what a call passes as cdfnum: the alphabet size (static coders), the two parameters (ss coders), else 0"""
+    return cdfnum if codec in STATIC else ss_prm(prm) if codec in SSBIT else 0
+
+
 def nchunks(n, chunk):
     return (n + chunk - 1) // chunk
 
@@ -219,16 +231,17 @@ class DeviceCoder:
         self.cdfnum = cdfnum
         self._tables()
 
-    def encode(self, d_in, n=None):
-        """Enqueue encode of d_in[:n]; results in self.clen / self.payload / self.total (device)."""
+    def encode(self, d_in, n=None, prm=(5, 6)):
+        """Enqueue encode of d_in[:n]; results in self.clen / self.payload / self.total (device).  prm: the two shift
+        parameters of an "ss" coder (SSBIT), unused by every other one."""
         n = self.n if n is None else n
         st = self.codec in STATIC
         _chk(lib().trc_encode_dev(self.codec | self.tables_ready, d_in.data_ptr(), n, self.chunk,
-                                  self.cdf.data_ptr() if st else None, self.cdfnum if st else 0,
+                                  self.cdf.data_ptr() if st else None, _cdfnum(self.codec, self.cdfnum, prm),
                                   self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(),
                                   self.work.data_ptr(), self.work_bytes, self._stream()))
 
-    def decode(self, d_out, n=None, clen=None, payload=None, dir_ready=False):
+    def decode(self, d_out, n=None, clen=None, payload=None, dir_ready=False, prm=(5, 6)):
         """dir_ready: the workspace still holds the group sums of `clen` (the encode or decode just before this call
         was for the same directory): TRC_DIR_READY, include/trc_hip.h"""
         n = self.n if n is None else n
@@ -236,10 +249,10 @@ class DeviceCoder:
         clen = self.clen if clen is None else clen
         payload = self.payload if payload is None else payload
         _chk(lib().trc_decode_dev(self.codec | self.tables_ready | (DIR_READY if dir_ready else 0), clen.data_ptr(), payload.data_ptr(), n, self.chunk,
-                                  self.cdf.data_ptr() if st else None, self.cdfnum if st else 0,
+                                  self.cdf.data_ptr() if st else None, _cdfnum(self.codec, self.cdfnum, prm),
                                   d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
 
-    def decode_range(self, d_out, first, count, n=None, clen=None, payload=None, dir_ready=False):
+    def decode_range(self, d_out, first, count, n=None, clen=None, payload=None, dir_ready=False, prm=(5, 6)):
         """Enqueue the decode of chunks [first, first + count) of the container (clen, payload, n) to d_out[0:], in a workspace
         of its own (trc_range_work_bytes; it grows with the largest count seen).  dir_ready: the decode_range before this one
         was for the same n and an unchanged clen, any first and count (TRC_DIR_READY, include/trc_hip.h); dropped when the
@@ -256,7 +269,7 @@ class DeviceCoder:
             _chk(lib().trc_tables_dev(self.cdf.data_ptr(), self.cdfnum, self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
             self.range_tables = TABLES_READY
         _chk(lib().trc_decode_range_dev(self.codec | self.range_tables | (DIR_READY if dir_ready else 0), clen.data_ptr(), payload.data_ptr(),
-                                        n, self.chunk, first, count, self.cdf.data_ptr() if st else None, self.cdfnum if st else 0,
+                                        n, self.chunk, first, count, self.cdf.data_ptr() if st else None, _cdfnum(self.codec, self.cdfnum, prm),
                                         d_out.data_ptr(), self.range_work.data_ptr() if self.range_work is not None else None,
                                         self.range_work_bytes, self._stream()))
 
@@ -282,7 +295,8 @@ _HOST_ENC = {ANS4S: "anscdf4senc", RCS1: "rccdfsenc", RCS2: "rccdfs2enc", RCA: "
              RCBV16: "rcvsenc16", RCBV32: "rcvsenc32", RCBVZ16: "rcvzsenc16", RCBVZ32: "rcvzsenc32",
              RCBVG16: "rcvgsenc16", RCBVG32: "rcvgsenc32", RCBVGZ16: "rcvgzsenc16", RCBVGZ32: "rcvgzsenc32",
              RCW16: "rcsenc16", RCW32: "rcsenc32", RCCW32: "rccsenc32", RCC2W32: "rcc2senc32",
-             RC4: "rc4senc", RC4C: "rc4csenc", RCU3: "rcu3senc"}
+             RC4: "rc4senc", RC4C: "rc4csenc", RCU3: "rcu3senc",
+             RCSS: "rcssenc", RC4SS: "rc4ssenc", RC4CSS: "rc4cssenc", RCU3SS: "rcu3ssenc"}
 _HOST_DEC = {ANS4S: "anscdf4sdec", RCS1: "rccdfsbdec", RCS2: "rccdfsb2dec", RCA: "rccdfdec", ANSA: "anscdfdec", RCB: "rcsdec", RCAI: "rccdfidec",
              RCA4: "rccdf4dec", RCAI4: "rccdf4idec", ANSA4: "anscdf4dec", RCSM: "rccdfsmbdec", ANSO1: "anscdf1dec", ANSB: "ansbd",
              VLCU16: "rccdfudec16", VLCU32: "rccdfudec32", VLCV16: "rccdfvdec16", VLCV32: "rccdfvdec32", VLCVZ16: "rccdfvzdec16", VLCVZ32: "rccdfvzdec32",
@@ -293,7 +307,8 @@ _HOST_DEC = {ANS4S: "anscdf4sdec", RCS1: "rccdfsbdec", RCS2: "rccdfsb2dec", RCA:
              RCBV16: "rcvsdec16", RCBV32: "rcvsdec32", RCBVZ16: "rcvzsdec16", RCBVZ32: "rcvzsdec32",
              RCBVG16: "rcvgsdec16", RCBVG32: "rcvgsdec32", RCBVGZ16: "rcvgzsdec16", RCBVGZ32: "rcvgzsdec32",
              RCW16: "rcsdec16", RCW32: "rcsdec32", RCCW32: "rccsdec32", RCC2W32: "rcc2sdec32",
-             RC4: "rc4sdec", RC4C: "rc4csdec", RCU3: "rcu3sdec"}
+             RC4: "rc4sdec", RC4C: "rc4csdec", RCU3: "rcu3sdec",
+             RCSS: "rcssdec", RC4SS: "rc4ssdec", RC4CSS: "rc4cssdec", RCU3SS: "rcu3ssdec"}
 
 
 def _host_fn(name, codec):
@@ -303,12 +318,14 @@ def _host_fn(name, codec):
         f.argtypes = [_u8p, _sz, _u8p, _u16p]
     elif codec in (RCS1, RCS2, RCSM):
         f.argtypes = [_u8p, _sz, _u8p, _u16p, C.c_uint]
+    elif codec in SSBIT:
+        f.argtypes = [_u8p, _sz, _u8p, C.c_uint, C.c_uint]
     else:
         f.argtypes = [_u8p, _sz, _u8p]
     return f
 
 
-def host_encode(codec, data, cdf=None, cdfnum=256, name=None):
+def host_encode(codec, data, cdf=None, cdfnum=256, name=None, prm=(5, 6)):
     """Call the reference-named encoder with host pointers -> np.uint8 array of the returned length."""
     data = np.ascontiguousarray(data, dtype=np.uint8)
     n = data.size
@@ -319,6 +336,8 @@ def host_encode(codec, data, cdf=None, cdfnum=256, name=None):
         l = f(pin, n, pout, cdf.ctypes.data_as(_u16p))
     elif codec in (RCS1, RCS2, RCSM):
         l = f(pin, n, pout, cdf.ctypes.data_as(_u16p), cdfnum)
+    elif codec in SSBIT:
+        l = f(pin, n, pout, prm[0], prm[1])
     else:
         l = f(pin, n, pout)
     if l == 0 and n != 0:
@@ -326,7 +345,7 @@ def host_encode(codec, data, cdf=None, cdfnum=256, name=None):
     return out[:l].copy()
 
 
-def host_decode(codec, comp, n, cdf=None, cdfnum=256, name=None):
+def host_decode(codec, comp, n, cdf=None, cdfnum=256, name=None, prm=(5, 6)):
     comp = np.ascontiguousarray(comp, dtype=np.uint8)
     if comp.size == n:
         return comp.copy()                                      # CCPY rule (turborc.c:434)
@@ -338,6 +357,8 @@ def host_decode(codec, comp, n, cdf=None, cdfnum=256, name=None):
         l = f(pin, n, pout, cdf.ctypes.data_as(_u16p))
     elif codec in (RCS1, RCS2, RCSM):
         l = f(pin, n, pout, cdf.ctypes.data_as(_u16p), cdfnum)
+    elif codec in SSBIT:
+        l = f(pin, n, pout, prm[0], prm[1])
     else:
         l = f(pin, n, pout)
     if l != n:
@@ -353,13 +374,14 @@ def container_range(buf, offset, length):
     return {f: int(getattr(r, f)) for f, _ in Range._fields_}
 
 
-def host_decode_range(codec, comp, n, offset, length, cdf=None, cdfnum=256):
-    """bytes [offset, offset + length) of what `comp` (a host-pointer encoder's result for n bytes) holds: trc_decode_range_host"""
+def host_decode_range(codec, comp, n, offset, length, cdf=None, cdfnum=256, prm=None):
+    """bytes [offset, offset + length) of what `comp` (a host-pointer encoder's result for n bytes) holds: trc_decode_range_host.
+    prm: an "ss" coder's parameters, None = those of the container's header"""
     comp = np.ascontiguousarray(comp, dtype=np.uint8)
     out = np.full(length + 64, 0xA5, dtype=np.uint8)
     st = codec in STATIC
     l = lib().trc_decode_range_host(codec, comp.ctypes.data, comp.size, n, offset, length, out.ctypes.data,
-                                    cdf.ctypes.data if st else None, cdfnum if st else 0)
+                                    cdf.ctypes.data if st else None, _cdfnum(codec, cdfnum, prm) if prm or st else 0)
     if l != length or not (out[length:] == 0xA5).all():
         raise TrcError(lib().trc_last_error().decode() if l != length else "trc_decode_range_host wrote past its output")
     return out[:length].copy()
