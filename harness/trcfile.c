@@ -6,6 +6,9 @@
  *                                 TRC_RC4CSS, TRC_RCU3SS (trc_hip.h) with the parameters N and M (two digits 1..9, default 56);
  *                                 the container's header records them, so d and x take no option.  Without -r, 64 and 65 are
  *                                 the TurboRC numbers above
+ *   trcfile p <id> <esize> <in> <out>   compress the BYTE PLANES of esize-byte elements (2, 4 or 8: bf16 / fp16, fp32, fp64 and wide
+ *                                 integers), each plane with coder <id>: the file is the library's TRCP container (trc_hip.h), which
+ *                                 records everything d and x need; static coders (42, 44, 45, 65) get a CDF per plane
  *   trcfile d <in> <out>          decompress
  *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`: only the chunks
  *                                 that cover them are sent to the GPU and decoded (trc_decode_range_host)
@@ -72,6 +75,34 @@ static int pick(int id, fn3 *e3, fn3 *d3, fn5 *e5, fn5 *d5)
     case 65: *e5 = e65; *d5 = d65; return 0;
     }
     return -1;
+}
+/* TurboRC id -> the library's coder id, for the calls that take one (trcfile p) */
+static int lib_codec(int id)
+{
+    switch (id) {
+    case 1:  return TRC_RCB;
+    case 2:  return TRC_RCC1;
+    case 4:  return TRC_RCX1;
+    case 42: return TRC_RCS1;
+    case 44: return TRC_RCSM;
+    case 45: return TRC_RCS2;
+    case 46: return TRC_RCA;
+    case 47: return TRC_RCAI;
+    case 56: return TRC_ANSA;
+    case 64: return TRC_ANSO1;
+    case 65: return TRC_ANS4S;
+    case 66: return TRC_ANSB;
+    }
+    return 0;
+}
+static int is_planes(const unsigned char *fb, size_t fl) { return fl >= 4 && !memcmp(fb, "TRCP", 4); }
+static int write_file(const char *path, const unsigned char *p, size_t n)
+{
+    FILE *f = fopen(path, "wb");
+    if (!f) { perror(path); return 2; }
+    if (fwrite(p, 1, n, f) != n) { perror("write"); fclose(f); return 2; }
+    fclose(f);
+    return 0;
 }
 static unsigned char *slurp(const char *path, size_t *n)
 {
@@ -146,10 +177,37 @@ int main(int argc, char **argv)
         printf("%zu -> %zu bytes (%.2f%%)%s\n", n, l, n ? 100.0 * l / n : 0.0, l == n ? "  stored" : "");
         return 0;
     }
+    if (argc == 6 && !strcmp(argv[1], "p")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        size_t n;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        unsigned char *in = slurp(argv[4], &n);
+        if (!in) return 2;
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_planes_bound(n, esize, 0, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u with %zu bytes: esize is 2, 4 or 8 and the file holds at least one element\n", esize, n); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        const size_t l = trc_encode_planes_host(codec, in, n, esize, 0, out, cap, cdfnum);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[5], out, l)) return 2;
+        printf("%zu -> %zu bytes (%.2f%%)  %u planes\n", n, l, 100.0 * l / n, esize);
+        return 0;
+    }
     if (argc == 4 && !strcmp(argv[1], "d")) {
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        if (is_planes(fb, fl)) {                                          /* a file of `trcfile p`: untrusted, so checked against what was read */
+            trc_planes_hdr ph;
+            if (trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            memcpy(&ph, fb, sizeof ph);
+            unsigned char *out = malloc((size_t)ph.n + 1024);
+            if (!out) { perror("malloc"); return 2; }
+            if (trc_decode_planes_host(fb, fl, out, (size_t)ph.n) != ph.n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            return write_file(argv[3], out, (size_t)ph.n);
+        }
         if (fl < 24 || memcmp(fb, "TRCF", 4)) { fprintf(stderr, "not a TRCF file\n"); return 2; }
         const int id = fb[4];
         const unsigned m = fb[5];
@@ -181,6 +239,17 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        if (is_planes(fb, fl)) {
+            const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
+            trc_planes_hdr ph;
+            if (trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            memcpy(&ph, fb, sizeof ph);
+            if (!len || off > ph.n || len > ph.n - off) { fprintf(stderr, "range outside the file's %llu bytes\n", (unsigned long long)ph.n); return 2; }
+            unsigned char *out = malloc((size_t)len + 1024);
+            if (!out) { perror("malloc"); return 2; }
+            if (trc_decode_planes_range_host(fb, fl, (size_t)off, (size_t)len, out) != len) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            return write_file(argv[5], out, (size_t)len);
+        }
         if (fl < 24 || memcmp(fb, "TRCF", 4)) { fprintf(stderr, "not a TRCF file\n"); return 2; }
         const int id = fb[4];
         const unsigned m = fb[5];
@@ -318,6 +387,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
     return 2;
 }

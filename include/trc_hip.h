@@ -334,6 +334,87 @@ int    trc_container_range(const void *buf, size_t buflen, int codec, size_t off
 size_t trc_decode_range_host(int codec, const void *in, size_t inlen, size_t n, size_t offset, size_t len, void *out,
                              const uint16_t *cdf, unsigned cdfnum);
 
+/* ---- byte planes of 16 / 32 / 64-bit elements ---------------------------------------------------------------------
+ * A byte coder run flat over bf16 / fp16 / fp32 / fp64 or wide-integer data mixes near-uniform mantissa bytes with highly
+ * skewed sign / exponent bytes.  These calls code the BYTE PLANES separately, on the device, without touching the coders:
+ *        esize in {2, 4, 8};   m = n / esize whole elements;   t = n % esize tail bytes;   plane k = the m bytes in[i * esize + k]
+ * (the plain definition: the reference's tpenc, transpose_.c:110-123, gives exactly this where n % (32 esize) < esize and an
+ * ISA-dependent layout elsewhere -- DESIGN.md).  Any other esize and m == 0 are TRC_E_ARG.
+ *
+ * The two kernels.  Planes lie `pitch` bytes apart: a multiple of 256, at least m; trc_planes_pitch(n, esize) = m + TRC_PAD
+ * rounded up to 256 is the pitch of the coded calls below (0 for a bad esize or m == 0).  d_in / d_out 16-byte, d_planes 256-byte
+ * aligned; d_tail: 8 bytes on the device that receive / supply the t tail bytes, may be NULL when t == 0.  Nothing is written
+ * outside [0, m) of each plane, [0, t) of the tail and [0, n) of d_out; the calls only enqueue work. */
+size_t trc_planes_pitch(size_t n, unsigned esize);
+int trc_planes_split_dev(const void *d_in, size_t n, unsigned esize, void *d_planes, size_t pitch, void *d_tail, void *stream);
+int trc_planes_join_dev(const void *d_planes, size_t pitch, const void *d_tail, size_t n, unsigned esize, void *d_out, void *stream);
+
+/* Coded planes, device-resident: split into the workspace, then one trc_encode_dev(codec, plane k, m, chunk, ...) per plane on
+ * the caller's stream -- plane k's (clen, payload, total) is exactly what trc_encode_dev returns for the m bytes of plane k.
+ * With nc = ceil(m / chunk) and pitch = trc_planes_pitch(n, esize):
+ *   d_clen    : uint32[esize * nc]      plane k's directory at d_clen + k * nc
+ *   d_payload : esize * pitch bytes     plane k's payload at (char *)d_payload + k * pitch
+ *   d_total   : uint64[esize]           plane k's payload bytes
+ *   d_tail    : 8 bytes                 the t tail bytes (may be NULL when t == 0)
+ * Static coders: every plane gets its OWN CDF, built over the plane as trc_cdfini_dev builds it, at d_cdf + k *
+ * TRC_PLANES_CDF_STRIDE (uint16[esize * 264]; cdfnum = the alphabet size), its status at d_status[k] -- on encode d_cdf is an
+ * OUTPUT, on decode an input.  Every other coder takes d_cdf = d_status = NULL; the "ss" coders pass cdfnum = TRC_SS_PRM(..)
+ * through to every plane.  Decode and range decode run trc_decode_dev / trc_decode_range_dev per plane and join.  The range
+ * call returns ELEMENTS [first_chunk * chunk, min(m, (first_chunk + count) * chunk)), esize times as many bytes, the first
+ * element at d_out[0], never tail bytes.  Argument errors are those of the per-plane calls; TRC_TABLES_READY and TRC_DIR_READY
+ * are TRC_E_ARG in all three (the planes share nothing a caller could promise about).
+ * Workspace: trc_planes_work_bytes (encode and decode) / trc_planes_range_work_bytes bytes, 256-byte aligned: every plane has a
+ * slice of its own, the plane buffer followed by what the per-plane call needs.  Both return 0 for what the calls reject. */
+#define TRC_PLANES_CDF_STRIDE 264
+size_t trc_planes_work_bytes(int codec, size_t n, unsigned esize, uint32_t chunk);
+int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                          uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                          uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                          void *d_work, size_t work_bytes, void *stream);
+int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                          size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                          void *d_out, void *d_work, size_t work_bytes, void *stream);
+size_t trc_planes_range_work_bytes(int codec, size_t n, unsigned esize, uint32_t chunk, size_t count);
+int trc_decode_planes_range_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                const uint16_t *d_cdf, unsigned cdfnum,
+                                void *d_out, void *d_work, size_t work_bytes, void *stream);
+
+/* Coded planes through host pointers: the TRCP container, little endian.
+ *   trc_planes_hdr (32 B) | uint64 off[esize] | section 0 .. esize - 1 | tail bytes
+ *   off[k]     offset of section k from the container's start, a multiple of 8
+ *   section k  static coders only: uint16 cdf[cdfnum + 1], zero-padded to a multiple of 8; then the TRC1 container of plane k,
+ *              byte-identical to trc_encode_host(codec, plane k, m, chunk, ..) with the plane's own CDF -- so the
+ *              reference-named decoders, trc_container_check and trc_container_range work on a section as they stand
+ *   tail       `tail` bytes, the last bytes of the container
+ * trc_encode_planes_host: chunk 0 = trc_auto_chunk_codec(codec, m); cdfnum = the alphabet size (static coders), TRC_SS_PRM (ss
+ * coders), else 0; out must hold the container (trc_planes_bound is always enough; its chunk 0 = any chunk).  Decoders read
+ * everything from the header.  trc_decode_planes_range_host returns bytes [offset, offset + len) of the original: it sends only
+ * the covering chunks of every plane and takes tail bytes straight from the container.  All return the size, 0 on error (text
+ * in trc_last_error()).  These calls are plain: the caller's current device, one copy each way, no device list, no striping.
+ * trc_planes_check (host only, no GPU needed; outlen (size_t)-1 = any) validates magic, version, esize, tail == n % esize,
+ * size <= buflen, the offsets (increasing, multiples of 8, inside size), every section with trc_container_check(section, its
+ * extent, codec, m), a static coder's CDFs (strictly increasing, ending at 32768) and an ss coder's parameters; both decoders
+ * call it before they read anything else. */
+#define TRC_PLANES_MAGIC 0x50435254u   /* "TRCP" */
+typedef struct trc_planes_hdr {
+    uint32_t magic;      /* TRC_PLANES_MAGIC */
+    uint8_t  codec;      /* enum trc_codec */
+    uint8_t  version;    /* 1 */
+    uint8_t  esize;      /* 2, 4 or 8 */
+    uint8_t  tail;       /* n % esize */
+    uint32_t chunk;      /* chunk size of every plane, in bytes */
+    uint32_t cdfnum;     /* static coders: alphabet size; ss coders: TRC_SS_PRM; else 0 */
+    uint64_t n;          /* original length */
+    uint64_t size;       /* the whole container, bytes */
+} trc_planes_hdr;        /* 32 bytes, little endian */
+size_t trc_planes_bound(size_t n, unsigned esize, uint32_t chunk, unsigned cdfnum);
+size_t trc_encode_planes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                              void *out, size_t outcap, unsigned cdfnum);
+size_t trc_decode_planes_host(const void *in, size_t inlen, void *out, size_t outlen);
+size_t trc_decode_planes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
+int    trc_planes_check(const void *buf, size_t buflen, size_t outlen);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

@@ -119,6 +119,24 @@ def lib():
         l.trc_container_range.argtypes = [_vp, _sz, C.c_int, _sz, _sz, C.POINTER(Range)]
         l.trc_decode_range_host.restype = _sz
         l.trc_decode_range_host.argtypes = [C.c_int, _vp, _sz, _sz, _sz, _sz, _vp, _vp, C.c_uint]
+        l.trc_planes_pitch.restype = _sz; l.trc_planes_pitch.argtypes = [_sz, C.c_uint]
+        l.trc_planes_split_dev.restype = C.c_int; l.trc_planes_split_dev.argtypes = [_vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]
+        l.trc_planes_join_dev.restype = C.c_int; l.trc_planes_join_dev.argtypes = [_vp, _sz, _vp, _sz, C.c_uint, _vp, _vp]
+        l.trc_planes_work_bytes.restype = _sz; l.trc_planes_work_bytes.argtypes = [C.c_int, _sz, C.c_uint, C.c_uint32]
+        l.trc_planes_range_work_bytes.restype = _sz; l.trc_planes_range_work_bytes.argtypes = [C.c_int, _sz, C.c_uint, C.c_uint32, _sz]
+        l.trc_encode_planes_dev.restype = C.c_int
+        l.trc_encode_planes_dev.argtypes = [C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        l.trc_decode_planes_dev.restype = C.c_int
+        l.trc_decode_planes_dev.argtypes = [C.c_int, _vp, _vp, _vp, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _sz, _vp]
+        l.trc_decode_planes_range_dev.restype = C.c_int
+        l.trc_decode_planes_range_dev.argtypes = [C.c_int, _vp, _vp, _sz, C.c_uint, C.c_uint32, _sz, _sz, _vp, C.c_uint, _vp, _vp, _sz, _vp]
+        l.trc_planes_bound.restype = _sz; l.trc_planes_bound.argtypes = [_sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_encode_planes_host.restype = _sz; l.trc_encode_planes_host.argtypes = [C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint]
+        l.trc_decode_planes_host.restype = _sz; l.trc_decode_planes_host.argtypes = [_vp, _sz, _vp, _sz]
+        l.trc_decode_planes_range_host.restype = _sz; l.trc_decode_planes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
+        l.trc_planes_check.restype = C.c_int; l.trc_planes_check.argtypes = [_vp, _sz, _sz]
+        l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
+        l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
         l.trc_timing_enable.restype = C.c_int; l.trc_timing_enable.argtypes = [C.c_int]
         l.trc_timing_pause.restype = C.c_int; l.trc_timing_pause.argtypes = [C.c_int]
         l.trc_timing_read.restype = C.c_int
@@ -284,6 +302,119 @@ class DeviceCoder:
         return clen, payload
 
 
+# ------------------------------------------------------------------- byte planes (include/trc_hip.h) ---
+PLANES_MAGIC = 0x50435254                                      # "TRCP"
+PLANES_CDF_STRIDE = 264
+PLANES_HDR = 32
+
+
+def planes_pitch(n, esize):
+    """bytes from plane k to plane k + 1 in the coded planar calls: n // esize + PAD rounded up to 256; 0: bad arguments"""
+    return lib().trc_planes_pitch(n, esize)
+
+
+def _cur_stream(t):
+    import torch
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def planes_split(d_in, n, esize, d_planes, pitch, d_tail=None):
+    """enqueue trc_planes_split_dev: d_in[:n] (uint8 tensor) -> plane k at d_planes[k * pitch:], the n % esize tail bytes to d_tail"""
+    _chk(lib().trc_planes_split_dev(d_in.data_ptr(), n, esize, d_planes.data_ptr(), pitch,
+                                    d_tail.data_ptr() if d_tail is not None else None, _cur_stream(d_in)))
+
+
+def planes_join(d_planes, pitch, d_tail, n, esize, d_out):
+    """enqueue trc_planes_join_dev, the inverse of planes_split"""
+    _chk(lib().trc_planes_join_dev(d_planes.data_ptr(), pitch, d_tail.data_ptr() if d_tail is not None else None, n, esize,
+                                   d_out.data_ptr(), _cur_stream(d_out)))
+
+
+class PlanesCoder:
+    """Pre-allocated HBM buffers for the planar calls on up to n bytes of esize-byte elements: plane k's directory at
+    self.clen[k * nch:], its payload at self.payload[k * pitch:], its size in self.total[k], its CDF (static coders, built by
+    encode) at self.cdf[k * PLANES_CDF_STRIDE:], the tail bytes in self.tail."""
+
+    def __init__(self, codec, n, esize, chunk=4096, device="cuda", cdfnum=256, prm=(5, 6), guard=0):
+        """guard: that many bytes of 0xA5 behind every buffer and its TRC_PAD slack; guards_ok() tells whether they survived"""
+        import torch
+        self.torch = torch
+        self.codec, self.n, self.esize, self.chunk = codec, n, esize, chunk
+        self.m = n // esize
+        self.nch = nchunks(self.m, chunk)
+        self.pitch = planes_pitch(n, esize)
+        self.dev = torch.device(device)
+        self.cdfnum = _cdfnum(codec, cdfnum, prm)
+        self.work_bytes = lib().trc_planes_work_bytes(codec, n, esize, chunk)
+        if self.work_bytes == 0:
+            raise TrcError("bad (codec, n, esize, chunk)")
+        self.guard, self._guards = guard, []
+        self.work = self._buf(self.work_bytes)
+        self.clen = self._buf(4 * esize * self.nch)
+        self.payload = self._buf(esize * self.pitch)
+        self.total = self._buf(8 * esize)
+        self.tail = self._buf(8)
+        self.cdf = self._buf(2 * esize * PLANES_CDF_STRIDE)
+        self.status = self._buf(4 * esize)
+        self.range_work, self.range_work_bytes = None, 0
+
+    def _buf(self, nbytes):
+        """nbytes + PAD zero bytes on the device (uint8), followed by the guard"""
+        t = self.torch.zeros(nbytes + PAD + self.guard, dtype=self.torch.uint8, device=self.dev)
+        if self.guard:
+            t[nbytes + PAD:] = 0xA5
+            self._guards.append(t[nbytes + PAD:])
+        return t
+
+    def guards_ok(self):
+        self.torch.cuda.synchronize(self.dev)
+        return all(bool((g == 0xA5).all().item()) for g in self._guards)
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def encode(self, d_in, n=None, flags=0):
+        n = self.n if n is None else n
+        st = self.codec in STATIC
+        _chk(lib().trc_encode_planes_dev(self.codec | flags, d_in.data_ptr(), n, self.esize, self.chunk,
+                                         self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                                         self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.tail.data_ptr(),
+                                         self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode(self, d_out, n=None, flags=0):
+        n = self.n if n is None else n
+        _chk(lib().trc_decode_planes_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), self.tail.data_ptr(),
+                                         n, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                         d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode_range(self, d_out, first, count, n=None, flags=0):
+        """elements [first * chunk, min(m, (first + count) * chunk)) to d_out[0:], in a workspace of its own that grows with count"""
+        n = self.n if n is None else n
+        need = lib().trc_planes_range_work_bytes(self.codec, n, self.esize, self.chunk, count)
+        if need > self.range_work_bytes:
+            self.range_work, self.range_work_bytes = self._buf(need), need
+        if self.range_work is None:                            # nothing to size a workspace by: the call rejects these arguments itself
+            self.range_work = self._buf(0)
+        _chk(lib().trc_decode_planes_range_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), n, self.esize, self.chunk,
+                                               first, count, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                               d_out.data_ptr(), self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+
+    def cdf_of(self, k):
+        """Synchronise and fetch plane k's CDF (uint16[cdfnum + 1]) and cdfini status, as encode left them (static coders)"""
+        self.torch.cuda.synchronize(self.dev)
+        cdf = self.cdf[:2 * self.esize * PLANES_CDF_STRIDE].cpu().numpy().view("<u2")
+        status = self.status[:4 * self.esize].cpu().numpy().view("<i4")
+        return cdf[k * PLANES_CDF_STRIDE:k * PLANES_CDF_STRIDE + self.cdfnum + 1].copy(), int(status[k])
+
+    def result(self, k):
+        """Synchronise and fetch plane k's (clen[nch] u32, payload bytes, total) to the host."""
+        self.torch.cuda.synchronize(self.dev)
+        tot = int(self.total[:8 * self.esize].cpu().numpy().view("<u8")[k])
+        clen = self.clen[4 * k * self.nch:4 * (k + 1) * self.nch].cpu().numpy().view(np.uint32).copy()
+        payload = self.payload[k * self.pitch:k * self.pitch + tot].cpu().numpy().copy()
+        return clen, payload, tot
+
+
 # ------------------------------------------------------ reference-signature layer (host pointers) ---
 _HOST_ENC = {ANS4S: "anscdf4senc", RCS1: "rccdfsenc", RCS2: "rccdfs2enc", RCA: "rccdfenc", ANSA: "anscdfenc", RCB: "rcsenc", RCAI: "rccdfienc",
              RCA4: "rccdf4enc", RCAI4: "rccdf4ienc", ANSA4: "anscdf4enc", RCSM: "rccdfsmenc", ANSO1: "anscdf1enc", ANSB: "ansbc",
@@ -413,3 +544,73 @@ def parse_container(buf):
     payload = buf[HDR + 4 * int(nch):HDR + 4 * int(nch) + int(pay)].copy()
     return dict(magic=int(magic), codec=int(codec), version=int(ver), cdfnum=int(cdfnum), chunk=int(chunk),
                 nchunks=int(nch), n=int(n), payload=int(pay)), clen, payload
+
+
+def planes_bound(n, esize, chunk=0, cdfnum=0):
+    return lib().trc_planes_bound(n, esize, chunk, cdfnum)
+
+
+def host_encode_planes(codec, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
+    """trc_encode_planes_host -> the TRCP container (np.uint8); chunk 0 = automatic"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(planes_bound(data.size, esize, chunk, cn), 64), dtype=np.uint8)
+    l = lib().trc_encode_planes_host(codec, data.ctypes.data, data.size, esize, chunk, out.ctypes.data, out.size, cn)
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy()
+
+
+def host_decode_planes(comp, n):
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    out = np.full(n + 64, 0xA5, dtype=np.uint8)
+    l = lib().trc_decode_planes_host(comp.ctypes.data, comp.size, out.ctypes.data, n)
+    if l != n or not (out[n:] == 0xA5).all():
+        raise TrcError(lib().trc_last_error().decode() if l != n else "trc_decode_planes_host wrote past its output")
+    return out[:n].copy()
+
+
+def host_decode_planes_range(comp, offset, length):
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    out = np.full(length + 64, 0xA5, dtype=np.uint8)
+    l = lib().trc_decode_planes_range_host(comp.ctypes.data, comp.size, offset, length, out.ctypes.data)
+    if l != length or not (out[length:] == 0xA5).all():
+        raise TrcError(lib().trc_last_error().decode() if l != length else "trc_decode_planes_range_host wrote past its output")
+    return out[:length].copy()
+
+
+def planes_check(buf, outlen=None):
+    """trc_planes_check on a TRCP container in host memory (needs no device); raises TrcError with the library's reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_planes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
+
+
+def parse_planes(buf):
+    """-> dict(hdr fields, off=[...]), sections: per plane (cdf u16 array or None, the TRC1 container of the plane as u8 array), tail"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    magic, codec, ver, esize, tail, chunk, cdfnum = np.frombuffer(buf[:16].tobytes(), dtype="<u4,u1,u1,u1,u1,<u4,<u4")[0]
+    n, size = (int(x) for x in np.frombuffer(buf[16:32].tobytes(), dtype="<u8"))
+    esize, tail, cdfnum, codec = int(esize), int(tail), int(cdfnum), int(codec)
+    off = [int(x) for x in np.frombuffer(buf[PLANES_HDR:PLANES_HDR + 8 * esize].tobytes(), dtype="<u8")]
+    cdfb = (2 * (cdfnum + 1) + 7) & ~7 if codec in STATIC else 0
+    sections = []
+    for k in range(esize):
+        sec = buf[off[k]:(off[k + 1] if k + 1 < esize else size - tail)]
+        hdr, _, _ = parse_container(sec[cdfb:])
+        used = HDR + 4 * hdr["nchunks"] + hdr["payload"]
+        sections.append((sec[:2 * (cdfnum + 1)].view("<u2").copy() if cdfb else None, sec[cdfb:cdfb + used].copy()))
+    return dict(magic=int(magic), codec=codec, version=int(ver), esize=esize, tail=tail, chunk=int(chunk), cdfnum=cdfnum,
+                n=n, size=size, off=off), sections, buf[size - tail:size].copy()
+
+
+def encode_host_container(codec, data, chunk, cdf=None, cdfnum=256, prm=(5, 6)):
+    """trc_encode_host: the TRC1 container of `data` at an explicit chunk, whatever its size"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    cap = lib().trc_container_bound(data.size, chunk) + 64
+    out = np.zeros(cap, dtype=np.uint8)
+    st = codec in STATIC
+    l = lib().trc_encode_host(codec, data.ctypes.data, data.size, chunk, out.ctypes.data, cap,
+                              np.ascontiguousarray(cdf, dtype=np.uint16).ctypes.data if st else None, _cdfnum(codec, cdfnum, prm))
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy()
