@@ -115,10 +115,13 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
     wc.rows = nchunks - wc.c0 < 64u ? nchunks - wc.c0 : 64u;
 
     const bool alive = lane < wc.rows;
+    const u64 amask = trc_ballot(alive);
     const u32 c = wc.c0 + lane;
     const u32 len = alive ? wc.len_of(lane) : 0u;
     QuadIn tin; tin.base = in + (u64)wc.c0 * chunk;
-    StreamOut<true, false, false, true> so;                   // (write-through drains: trc_io.h)
+    // write-through drains, full rounds only (trc_io.h).  G = 32: between two drain calls a lane codes one 16-byte piece, at most one
+    // 2-byte unit per symbol; the ragged tail (up to 63 symbols = 126 bytes) goes into a ring that is still empty
+    StreamOut<true, false, false, true, 32u> so;
     so.rings = wbase;
     so.scratch = scratch; so.stride = stride; so.c0 = wc.c0; so.wpos = 0; so.nfl = 0;
     const u32 rbase = (u32)(uintptr_t)(so.rings - smem) + trc_raddr(lane, 0);    // this lane's ring, as an LDS byte address
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the ring writes above are not in the compiler's books
             if (k == 0 && s > 0) take(s - 1u);                  // (this segment's last piece has been read)
-            so.drain(false, alive);                             // <= 32 new bytes per lane since the last drain
+            so.drain(false, alive, amask);                      // <= 32 new bytes per lane since the last drain
             ovf = ovf || (alive && so.wpos + 8u >= len);        // already incompressible: stop coding this chunk
             act = act && !ovf;
         }
@@ -392,6 +395,7 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec_kernel(
     const u32 rbase = (u32)(uintptr_t)(si.rings - smem) + AnsStreamIn::ra(lane, 0);    // this lane's ring, as an LDS byte address
     u32 sel_lo = 0x05040100u, sel_hi = 0x05040302u;            // byte selectors of the pair step's permutes (VGPR operands: VCC takes the one constant-bus slot)
     asm volatile("" : "+v"(sel_lo), "+v"(sel_hi));
+    const u64 cmask = trc_ballot(coded);
     PROF_T(pt2);
     for (u32 s = 0; s < S; s++) {
 #pragma unroll
@@ -402,7 +406,7 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec_kernel(
             if (k == 0) pace.step(s * 4u + 1u);
             // period boundary: land the round requested 16 symbols ago, request the next one
             PROF_T(qa);
-            si.period(coded && p0 < len, k & 1);
+            si.period(coded && p0 < len, cmask & trc_ballot(p0 < len), k & 1);      // (the mask of the same lanes, term by term: trc_io.h)
             PROF_T(qb); PROF_ACC(acc_p, qa, qb);
             if (k == 0 && s > 0) tout.flush(wc, (s - 1u) * TRC_SEG);   // the segment before: behind this period's commit (header comment)
             PROF_T(qc); PROF_ACC(acc_f, qb, qc);

@@ -10,7 +10,7 @@
 //              registers instead of through an LDS tile
 //   StreamOut  variable-rate output (coded bytes at encode): 128-B ring per lane; lanes whose ring
 //              holds a full segment are ranked (ballot + mbcnt) and 16 of them are drained per
-//              round, each by one quad
+//              round, each by one quad (static rANS encoder: full rounds only, StreamOut's G)
 //   StreamIn   variable-rate input (coded bytes at decode):  128-B ring per lane, refilled the same
 //              way one period ahead of use
 //
@@ -39,6 +39,17 @@ __device__ __forceinline__ u32 trc_mbcnt(u64 mask)   // number of set bits of ma
 {
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
 }
+
+// A wave mask from a lane predicate.  Give it ONE comparison: `v_cmp` then writes the SGPR pair that is the mask.  Of a conjunction
+// (`alive && x < y`) the compiler keeps each term as an SGPR pair, ANDs them -- and, not knowing what the terms hold in lanes that
+// are switched off, turns the result into a 0/1 VGPR and compares that with zero to form the ballot: two vector instructions per
+// ballot for nothing.  The protocols below ballot every term by itself and AND the masks as scalars.
+__device__ __forceinline__ u64 trc_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// bits set in a wave mask, as a 32-bit scalar the compiler cannot widen again (it compares the 64-bit count of __popcll with a
+// vector instruction: there is no scalar 64-bit `less than`)
+__device__ __forceinline__ u32 trc_popc(u64 m) { u32 c; asm("s_bcnt1_i32_b64 %0, %1" : "=s"(c) : "s"(m) : "scc"); return c; }
+// v += 1 in the lanes of a wave mask: one v_addc with the mask as the carry (a 0/1 VGPR made of the mask and an add: two)
+__device__ __forceinline__ void trc_inc_in(u32 &v, u64 m) { u64 cy; asm("v_addc_co_u32_e64 %0, %1, 0, %0, %2" : "+v"(v), "=&s"(cy) : "s"(m)); }
 
 // Round 6, the ARRIVAL GATE of an input that is still on its way (host-pointer encodes, trc_host.inc): the host delivers the input in
 // K passes -- pass k = bytes [k * part, (k + 1) * part) of EVERY chunk, one 2-D DMA copy -- and sets *gate = k + 1 behind each pass (a
@@ -303,8 +314,20 @@ struct QuadOut {
 // inline asm, outside the compiler's vmcnt accounting, so neither a later access nor a release at the kernel's end would wait for it
 // on the compiler's say-so.  A coder that patches a header behind a drain (the two-stream range coders) must keep WT = false; code that
 // READS drained bytes in the same kernel must put its own `s_waitcnt vmcnt(0)` + barrier in between.
-template <bool DOWN, bool PAIR = false, bool QUAD = false, bool WT = false>
+// G (the static rANS encoder: 32) turns on the FULL-ROUND rule of the non-final drain.  A round costs the wave the same ~35 vector
+// instructions whether 1 or 16 of its helper quads have a segment to move, and on text about 10 lanes of 64 fill a segment per
+// 16-symbol piece: under the plain rule (G = 0: a round whenever ANY lane holds 64 bytes) a round ran behind almost every piece with
+// a third of its quads idle.  With G > 0 a non-final call runs a round only while (a) at least 16 lanes are ready -- the round is
+// full -- or (b) some lane is URGENT: it could not take the G bytes its caller may append before the next call,
+//     pending() + G > TRC_SRING - 2      (the ring minus the slot of the next speculative unit, which must stay free)
+// and otherwise returns; the ready lanes wait for the next call.  INVARIANT: pending() <= TRC_SRING - 2 = 126 at every call -- a
+// non-final call ends only when no lane is urgent, i.e. with pending() <= 126 - G everywhere (an urgent lane is a ready lane, and
+// every round serves the 16 lowest ready lanes, so the loop reaches all of them), and the caller adds at most G before it calls
+// again.  G is the CALLER's bound and is stated where StreamOut is instantiated; the bytes and their places in the region do not
+// depend on when a segment leaves, so the payload is the same under either rule.  (QUAD streams keep the plain rule.)
+template <bool DOWN, bool PAIR = false, bool QUAD = false, bool WT = false, u32 G = 0u>
 struct StreamOut {
+    static_assert(G == 0u || (!QUAD && G + TRC_SEG <= TRC_SRING - 2u), "full-round drains: one lane per ring, and a ready lane must not be urgent by itself");
     u8 *rings;           // this wave's ring array (LDS)
     u8 *scratch;         // global scratch, region of chunk c is [c*stride, (c+1)*stride)
     u32 stride;
@@ -373,16 +396,26 @@ struct StreamOut {
     // array (relative to the wave's first region) to the leader of helper quad `rank` with two ds_permute_b32 (lanes not
     // picked push to lane 1, which leads no quad), and the quad takes them from its leader by DPP -- one cross-lane round
     // trip per round where round 2 made two (rank -> lane table written to and read back from LDS, then a shuffle).
-    __device__ __forceinline__ void drain(bool final, bool alive)
+    __device__ __forceinline__ void drain(bool final, bool alive) { drain(final, alive, trc_ballot(alive)); }
+    // the same for a caller that keeps trc_ballot(alive) at hand (a loop around the call: the mask of a predicate that is not one
+    // comparison costs two vector instructions every time it is formed)
+    __device__ __forceinline__ void drain(bool final, bool alive, u64 alive_mask)
     {
         const u32 lane = trc_lane();
         const u32 rw = trc_lds_addr(rings);
-        bool ready = alive && (final ? pending() > 0 : pending() >= TRC_SEG) && (!QUAD || (lane & 3u) == 0u);
-        u64 mask = __ballot(ready);
+        // the lanes that may drain at all, as a wave mask (trc_ballot: one comparison per ballot)
+        const bool able = alive && (!QUAD || (lane & 3u) == 0u);
+        const u64 amask = alive_mask & (QUAD ? 0x1111111111111111ull : ~0ull);
+        auto full = [&]() { return final ? wpos > TRC_SEG * nfl : pending() >= TRC_SEG; };      // (`final` is a literal at every call)
+        u64 mask = amask & trc_ballot(full());
         while (mask) {
+            const u32 cnt = G != 0u ? trc_popc(mask) : (u32)__popcll(mask);
+            if (G != 0u && !final && cnt < 16u) {               // not a full round: only for an urgent lane (header comment)
+                if (!(amask & trc_ballot(pending() > TRC_SRING - 2u - G))) break;
+            }
             const u32 rank = trc_mbcnt(mask);
-            const bool pick = ready && rank < 16u;
-            const u32 cnt = (u32)__popcll(mask);
+            const u64 pmask = mask & trc_ballot(rank < 16u);
+            const bool pick = able && full() && rank < 16u;     // (the lanes of pmask)
             const u32 ro = DOWN ? ((0u - TRC_SEG * (nfl + 1u)) & (TRC_SRING - 1)) : ((TRC_SEG * nfl) & (TRC_SRING - 1));
             const u32 from = rw + trc_raddr(ring_row(), ro);
             // place in the scratch array relative to the wave's first region (63 regions of at most 64 KiB + slack: 32 bits; offsets
@@ -406,8 +439,8 @@ if constexpr (WT) {                                // (an asm store is not in th
                 } else
                     *(uint4 *)(base + (to_q & ~1u) + part) = make_uint4(s0, s1, s2, s3);
             }
-            if (pick) { nfl++; ready = final ? (wpos > TRC_SEG * nfl) : pending() >= TRC_SEG; }
-            mask = __ballot(ready);
+            trc_inc_in(nfl, pmask);
+            mask = amask & trc_ballot(full());
         }
         if (QUAD) nfl = (u32)__builtin_amdgcn_update_dpp(0, (int)nfl, 0x00, 0xf, 0xf, false);       // the quad follows its first lane
     }
@@ -441,7 +474,7 @@ struct StreamInT {
     u32 lbytes;          // bytes committed to the ring
     u32 infl;            // segments requested for this lane and not yet committed (0..2)
     u32 rw;              // (set by prime) LDS byte address of this wave's ring array
-    bool mineA, mineB;   // ... and in which register set they travel
+    u64 mineA, mineB;    // ... and in which register set they travel: wave masks of the lanes that own a segment of the set
     // helper side: this lane moves one 16-byte piece of some lane's segment, per register set
     uint4 hvA, hvB; u32 hdA, hdB; bool hokA, hokB;
 
@@ -467,7 +500,7 @@ struct StreamInT {
     // start of every decoder wave (ablation in profiles/r03_notes.md).  Eight loads in flight, one round trip.
     __device__ __forceinline__ void prime(bool alive)
     {
-        rpos = 0; lbytes = 0; infl = 0; mineA = mineB = false; hokA = hokB = false;
+        rpos = 0; lbytes = 0; infl = 0; mineA = mineB = 0; hokA = hokB = false;
         rw = trc_lds_addr(rings);
         {
             const u32 blo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)soff), bhi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(soff >> 32));
@@ -506,7 +539,7 @@ struct StreamInT {
     struct Prime { uint4 v[8]; u32 at[4]; };
     __device__ __forceinline__ void prime_issue(bool alive, Prime &P)
     {
-        rpos = 0; lbytes = 0; infl = 0; mineA = mineB = false; hokA = hokB = false;
+        rpos = 0; lbytes = 0; infl = 0; mineA = mineB = 0; hokA = hokB = false;
         rw = trc_lds_addr(rings);
         {
             const u32 blo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)soff), bhi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(soff >> 32));
@@ -564,26 +597,37 @@ struct StreamInT {
         }
         if (hd & 1u) *(lds_u32 *)(uintptr_t)(a + GUARD_OFF) = v.x;   // guard: a reader may take what lies at ring offset p and just behind it from one address
     }
+    // the lanes of wave mask m: one segment more in the ring, one fewer in flight (select, v_subb on the mask, add)
+    __device__ __forceinline__ void landed(u64 m)
+    {
+        u32 t; u64 cy;
+        asm("v_cndmask_b32_e64 %[t], 0, 64, %[m]\n\t"
+            "v_subb_co_u32_e64 %[fl], %[cy], %[fl], 0, %[m]\n\t"
+            "v_add_u32_e32 %[lb], %[lb], %[t]"
+            : [t] "=&v"(t), [fl] "+v"(infl), [lb] "+v"(lbytes), [cy] "=&s"(cy) : [m] "s"(m));
+    }
     // land the round that travels in set `par` (requested two periods ago)
     __device__ __forceinline__ void commit(int par)
     {
         if (par == 0) {
             if (hokA) { put_piece(hdA, hvA); hokA = false; }
-            if (mineA) { lbytes += TRC_SEG; infl--; mineA = false; }
+            landed(mineA); mineA = 0;
         } else {
             if (hokB) { put_piece(hdB, hvB); hokB = false; }
-            if (mineB) { lbytes += TRC_SEG; infl--; mineB = false; }
+            landed(mineB); mineB = 0;
         }
     }
-    // request one more segment for up to 16 lanes whose ring has room, into register set `par`
-    __device__ __forceinline__ void refill(bool alive, int par)
+    // request one more segment for up to 16 lanes whose ring has room, into register set `par`.  amask = trc_ballot(alive), from
+    // the caller, who knows the terms of `alive` (trc_ballot's comment); what only the picked lanes need comes behind the early out
+    __device__ __forceinline__ void refill(bool alive, u64 amask, int par)
     {
         const u32 lane = trc_lane();
-        const bool needy = alive && avail() + TRC_SEG * infl <= TRC_SEG;
-        const u64 mask = __ballot(needy);
+        const bool room = avail() + TRC_SEG * infl <= TRC_SEG;
+        const u64 mask = amask & trc_ballot(room);
         if (!mask) return;
         const u32 rank = trc_mbcnt(mask);
-        const bool pick = needy && rank < 16u;
+        const u64 pmask = mask & trc_ballot(rank < 16u);
+        const bool pick = alive && room && rank < 16u;         // (the lanes of pmask)
         const u32 cnt = (u32)__popcll(mask);
         const u32 nx = lbytes + TRC_SEG * infl;                 // stream offset of this lane's next segment
         const u32 ro = nx & (TRC_SRING - 1);                    // its ring offset: 0 or 64
@@ -599,26 +643,26 @@ struct StreamInT {
             const u32 dd = ((slot_q & ~1u) + part * PIECE_STEP) | (part == 0u ? slot_q & 1u : 0u);
             if (par == 0) { hvA = v; hdA = dd; hokA = true; } else { hvB = v; hdB = dd; hokB = true; }
         }
-        if (pick) { infl++; if (par == 0) mineA = true; else mineB = true; }
+        trc_inc_in(infl, pmask);
+        if (par == 0) mineA = pmask; else mineB = pmask;
     }
     // emergency: some lane is about to run dry.  Land everything in flight (older set first: at this
     // point only set !par can still be in flight), then fill every ring synchronously.
-    __device__ __forceinline__ void sync_refill(bool alive, int par)
+    __device__ __forceinline__ void sync_refill(bool alive, u64 amask, int par)
     {
         commit(par ^ 1);
-        for (;;) {
-            const bool needy = alive && avail() <= TRC_SEG;
-            if (!__ballot(needy)) break;
-            refill(alive, 0);
+        while (amask & trc_ballot(avail() <= TRC_SEG)) {
+            refill(alive, amask, 0);
             commit(0);
         }
     }
     // the per-period protocol every decoder runs at a uniform point (<= 32 bytes consumed per period)
-    __device__ __forceinline__ void period(bool alive, int par)
+    __device__ __forceinline__ void period(bool alive, u64 amask, int par)
     {
         commit(par);
-        if (__ballot(alive && avail() < 36u)) sync_refill(alive, par);
-        refill(alive, par);
+        if (amask & trc_ballot(avail() < 36u)) sync_refill(alive, amask, par);
+        refill(alive, amask, par);
     }
+    __device__ __forceinline__ void period(bool alive, int par) { period(alive, trc_ballot(alive), par); }
 };
 typedef StreamInT<false> StreamIn;
