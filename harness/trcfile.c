@@ -9,9 +9,13 @@
  *   trcfile p <id> <esize> <in> <out>   compress the BYTE PLANES of esize-byte elements (2, 4 or 8: bf16 / fp16, fp32, fp64 and wide
  *                                 integers), each plane with coder <id>: the file is the library's TRCP container (trc_hip.h), which
  *                                 records everything d and x need; static coders (42, 44, 45, 65) get a CDF per plane
- *   trcfile d <in> <out>          decompress
- *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`: only the chunks
- *                                 that cover them are sent to the GPU and decoded (trc_decode_range_host)
+ *   trcfile f <id> <esize> <z|x> <in> <out>   as p, with a filter ahead of the planes: z = zigzag delta, x = xor against the
+ *                                 previous element, restarted at every chunk -- for integer columns and smooth series (sorted ids,
+ *                                 timestamps, sampled signals).  The file is the library's filtered planes container: 16 bytes
+ *                                 "TRCF" | u8 filter | u8 1 | u16 0 | u64 size, then the TRCP container of the filtered data
+ *   trcfile d <in> <out>          decompress (files of c, p and f)
+ *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p or f: only the
+ *                                 chunks that cover them are sent to the GPU and decoded (trc_decode_range_host)
  *
  * File = "TRCF" | u8 id | u8 cdfnum-1 | u16 0 | u64 raw length | u64 stored length | [cdf: (cdfnum+1) x u16, static coders]
  *        | stored bytes (the library's TRC1 container, or the raw input when it does not compress: the reference's
@@ -96,6 +100,9 @@ static int lib_codec(int id)
     return 0;
 }
 static int is_planes(const unsigned char *fb, size_t fl) { return fl >= 4 && !memcmp(fb, "TRCP", 4); }
+/* a file of `trcfile f`.  `trcfile c` opens its files with the same four letters; there byte 5 is 0 for the coders without a CDF
+ * and bytes 16 .. 19 belong to a length, here byte 5 is the version 1 and a TRCP container starts at byte 16 */
+static int is_fplanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCF", 4) && fb[5] == 1 && !memcmp(fb + 16, "TRCP", 4); }
 static int write_file(const char *path, const unsigned char *p, size_t n)
 {
     FILE *f = fopen(path, "wb");
@@ -195,10 +202,39 @@ int main(int argc, char **argv)
         printf("%zu -> %zu bytes (%.2f%%)  %u planes\n", n, l, 100.0 * l / n, esize);
         return 0;
     }
+    if (argc == 7 && !strcmp(argv[1], "f")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        const int filter = !strcmp(argv[4], "z") ? TRC_FILTER_ZDELTA : !strcmp(argv[4], "x") ? TRC_FILTER_XOR : TRC_FILTER_NONE;
+        size_t n;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (filter == TRC_FILTER_NONE) { fprintf(stderr, "filter %s: z (zigzag delta) or x (xor)\n", argv[4]); return 2; }
+        unsigned char *in = slurp(argv[5], &n);
+        if (!in) return 2;
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_fplanes_bound(n, esize, 0, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u with %zu bytes: esize is 2, 4 or 8 and the file holds at least one element\n", esize, n); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        const size_t l = trc_encode_fplanes_host(codec, filter, in, n, esize, 0, out, cap, cdfnum);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[6], out, l)) return 2;
+        printf("%zu -> %zu bytes (%.2f%%)  %u planes, filter %s\n", n, l, 100.0 * l / n, esize, argv[4]);
+        return 0;
+    }
     if (argc == 4 && !strcmp(argv[1], "d")) {
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        if (is_fplanes(fb, fl)) {                                         /* a file of `trcfile f`: checked like one of p */
+            trc_planes_hdr ph;
+            if (trc_fplanes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            memcpy(&ph, fb + sizeof(trc_fplanes_hdr), sizeof ph);
+            unsigned char *out = malloc((size_t)ph.n + 1024);
+            if (!out) { perror("malloc"); return 2; }
+            if (trc_decode_fplanes_host(fb, fl, out, (size_t)ph.n) != ph.n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            return write_file(argv[3], out, (size_t)ph.n);
+        }
         if (is_planes(fb, fl)) {                                          /* a file of `trcfile p`: untrusted, so checked against what was read */
             trc_planes_hdr ph;
             if (trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
@@ -239,6 +275,17 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        if (is_fplanes(fb, fl)) {
+            const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
+            trc_planes_hdr ph;
+            if (trc_fplanes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            memcpy(&ph, fb + sizeof(trc_fplanes_hdr), sizeof ph);
+            if (!len || off > ph.n || len > ph.n - off) { fprintf(stderr, "range outside the file's %llu bytes\n", (unsigned long long)ph.n); return 2; }
+            unsigned char *out = malloc((size_t)len + 1024);
+            if (!out) { perror("malloc"); return 2; }
+            if (trc_decode_fplanes_range_host(fb, fl, (size_t)off, (size_t)len, out) != len) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            return write_file(argv[5], out, (size_t)len);
+        }
         if (is_planes(fb, fl)) {
             const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
             trc_planes_hdr ph;
@@ -387,6 +434,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
     return 2;
 }

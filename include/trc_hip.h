@@ -415,6 +415,65 @@ size_t trc_decode_planes_host(const void *in, size_t inlen, void *out, size_t ou
 size_t trc_decode_planes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
 int    trc_planes_check(const void *buf, size_t buflen, size_t outlen);
 
+/* ---- byte planes behind a predictor filter -----------------------------------------------------------------------------
+ * The low byte planes of sorted ids, timestamps, offsets or sampled signals are near-uniform: their structure lies between
+ * neighbouring elements.  A filter replaces every element by its difference to the one before it, ahead of the split:
+ *        x[i] = the m elements as little-endian unsigned words of w = 8 * esize bits;   p[i] = 0 where i % seg == 0, else x[i - 1]
+ *        TRC_FILTER_ZDELTA   d = x[i] - p[i] mod 2^w;   y[i] = (d << 1) ^ (0 - (d >> (w - 1)))      (zigzag of d read as signed)
+ *                            inverse: d = (y >> 1) ^ (0 - (y & 1));   x[i] = p[i] + d mod 2^w
+ *        TRC_FILTER_XOR      y[i] = x[i] ^ p[i];   inverse: x[i] = y[i] ^ p[i]
+ * F(filter, seg, esize, in) = the y's followed by the t untouched tail bytes.  The predictor RESTARTS every seg elements (a multiple
+ * of 64 in [TRC_CHUNK_MIN, TRC_CHUNK_MAX], the chunk rule; anything else is TRC_E_ARG), and the coded calls use seg = chunk, so a
+ * restart segment is a coded chunk of every plane: the inverse is a scan within one segment, and a chunk range still decodes
+ * from its own bytes alone.  A filter is an option, never a default: it helps integer columns and smooth series and does nothing
+ * for weights.
+ *
+ * The whole contract:  fplanes(filter, ..., in)  ==  planes(..., F(filter, chunk, esize, in))  byte for byte -- directory, payload,
+ * totals, per-plane CDFs, tail, the host container's body.  Every argument, alignment, flag and workspace rule is the one of the
+ * unfiltered call (trc_planes_work_bytes / trc_planes_range_work_bytes serve unchanged: the filter lives inside split and join).
+ * filter = TRC_FILTER_NONE makes a device call its unfiltered counterpart, launching the same kernels; any other value outside
+ * {1, 2} is TRC_E_ARG before anything else is looked at.  The range call returns elements [first_chunk * chunk,
+ * min(m, (first_chunk + count) * chunk)): its scan starts at a restart. */
+enum { TRC_FILTER_NONE = 0, TRC_FILTER_ZDELTA = 1, TRC_FILTER_XOR = 2 };
+int trc_planes_split_filter_dev(int filter, const void *d_in, size_t n, unsigned esize, uint32_t seg,
+                                void *d_planes, size_t pitch, void *d_tail, void *stream);
+int trc_planes_join_filter_dev(int filter, const void *d_planes, size_t pitch, const void *d_tail,
+                               size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream);
+int trc_encode_fplanes_dev(int codec, int filter, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                           uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                           uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                           void *d_work, size_t work_bytes, void *stream);
+int trc_decode_fplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                           size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                           void *d_out, void *d_work, size_t work_bytes, void *stream);
+int trc_decode_fplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload,
+                                 size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                 const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_out, void *d_work, size_t work_bytes, void *stream);
+
+/* Filtered planes through host pointers: the TRCF container = a 16-byte prefix in front of an ordinary TRCP container of
+ * F(filter, chunk, esize, in).  Bytes [16, size) are byte-identical to trc_encode_planes_host(codec, F(in), ...) at the same
+ * resolved chunk, so trc_planes_check, trc_container_check and trc_container_range work on the inner part as they stand.
+ * trc_encode_fplanes_host takes filter 1 or 2 (TRC_FILTER_NONE returns 0: trc_encode_planes_host writes that content, one
+ * container per content); out must hold trc_fplanes_bound = trc_planes_bound + 16 bytes.  The decoders read everything from the
+ * two headers; the range decoder fetches the covering chunks of every plane, which are whole segments.  All return the size,
+ * 0 on error (text in trc_last_error()).  trc_fplanes_check (host only, no GPU needed) validates magic, version 1, filter 1 or 2,
+ * zero == 0, 16 < size <= buflen, then trc_planes_check(buf + 16, size - 16, outlen); both decoders call it first. */
+#define TRC_FPLANES_MAGIC 0x46435254u   /* "TRCF" */
+typedef struct trc_fplanes_hdr {
+    uint32_t magic;      /* TRC_FPLANES_MAGIC */
+    uint8_t  filter;     /* TRC_FILTER_ZDELTA or TRC_FILTER_XOR */
+    uint8_t  version;    /* 1 */
+    uint16_t zero;
+    uint64_t size;       /* 16 + the inner TRCP container's size */
+} trc_fplanes_hdr;       /* 16 bytes, little endian */
+size_t trc_fplanes_bound(size_t n, unsigned esize, uint32_t chunk, unsigned cdfnum);
+size_t trc_encode_fplanes_host(int codec, int filter, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                               void *out, size_t outcap, unsigned cdfnum);
+size_t trc_decode_fplanes_host(const void *in, size_t inlen, void *out, size_t outlen);
+size_t trc_decode_fplanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
+int    trc_fplanes_check(const void *buf, size_t buflen, size_t outlen);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

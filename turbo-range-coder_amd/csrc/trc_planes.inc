@@ -55,13 +55,23 @@ static int planes_common(const char *who, int codec, size_t n, unsigned esize, c
     return TRC_OK;
 }
 
-extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
-                                     uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
-                                     uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
-                                     void *d_work, size_t work_bytes, void *stream)
+// The three calls with a filter (trc_fplanes.hip) between the elements and the planes; with TRC_FILTER_NONE the filter forms of split
+// and join are the plain ones.  The restart length is the chunk, which check_common has vetted by the time split or join see it.
+static int filter_common(const char *who, int filter)
 {
-    int rc = planes_common("encode_planes", codec, n, esize, d_work);
+    if (filter != TRC_FILTER_NONE && filter != TRC_FILTER_ZDELTA && filter != TRC_FILTER_XOR)
+        return fail(TRC_E_ARG, "%s: filter %d (0 none, 1 zigzag delta, 2 xor)", who, filter);
+    return TRC_OK;
+}
+
+extern "C" int trc_encode_fplanes_dev(int codec, int filter, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                                      uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                      uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                                      void *d_work, size_t work_bytes, void *stream)
+{
+    int rc = filter_common("encode_planes", filter);
     if (rc) return rc;
+    if ((rc = planes_common("encode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
     const TrcCodec &r = codec_row(codec);
@@ -72,7 +82,7 @@ extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsi
     if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
         return fail(TRC_E_ARG, "encode_planes: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned");
     uint8_t *w = (uint8_t *)d_work;
-    if ((rc = trc_planes_split_dev(d_in, n, esize, w, P.slice, d_tail, stream))) return rc;
+    if ((rc = trc_planes_split_filter_dev(filter, d_in, n, esize, chunk, w, P.slice, d_tail, stream))) return rc;
     for (unsigned k = 0; k < esize; k++) {
         uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
         uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
@@ -83,12 +93,22 @@ extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsi
     return TRC_OK;
 }
 
-extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
-                                     size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
-                                     void *d_out, void *d_work, size_t work_bytes, void *stream)
+extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                                     uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                     uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                                     void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = planes_common("decode_planes", codec, n, esize, d_work);
+    return trc_encode_fplanes_dev(codec, TRC_FILTER_NONE, d_in, n, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total, d_tail,
+                                  d_work, work_bytes, stream);
+}
+
+extern "C" int trc_decode_fplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                                      size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                      void *d_out, void *d_work, size_t work_bytes, void *stream)
+{
+    int rc = filter_common("decode_planes", filter);
     if (rc) return rc;
+    if ((rc = planes_common("decode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
     if (!planes_map(codec, n, esize, chunk, P)) return fail(TRC_E_ARG, "decode_planes: bad (codec, n, esize, chunk)");
@@ -102,16 +122,23 @@ extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const vo
         if ((rc = trc_decode_dev(codec, d_clen + k * P.nc, (const uint8_t *)d_payload + k * P.buf, P.m, chunk,
                                  r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return trc_planes_join_dev(w, P.slice, d_tail, n, esize, d_out, stream);
+    return trc_planes_join_filter_dev(filter, w, P.slice, d_tail, n, esize, chunk, d_out, stream);
+}
+extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                                     size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                     void *d_out, void *d_work, size_t work_bytes, void *stream)
+{
+    return trc_decode_fplanes_dev(codec, TRC_FILTER_NONE, d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 
-extern "C" int trc_decode_planes_range_dev(int codec, const uint32_t *d_clen, const void *d_payload,
-                                           size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
-                                           const uint16_t *d_cdf, unsigned cdfnum,
-                                           void *d_out, void *d_work, size_t work_bytes, void *stream)
+extern "C" int trc_decode_fplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload,
+                                            size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                            const uint16_t *d_cdf, unsigned cdfnum,
+                                            void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = planes_common("decode_planes_range", codec, n, esize, d_work);
+    int rc = filter_common("decode_planes_range", filter);
     if (rc) return rc;
+    if ((rc = planes_common("decode_planes_range", codec, n, esize, d_work))) return rc;
     const size_t m = n / esize;
     if ((rc = check_common(codec, m, chunk, d_cdf, cdfnum))) return rc;
     const size_t nc = (m + chunk - 1) / chunk;
@@ -132,7 +159,15 @@ extern "C" int trc_decode_planes_range_dev(int codec, const uint32_t *d_clen, co
         if ((rc = trc_decode_range_dev(codec, d_clen + k * nc, (const uint8_t *)d_payload + k * pitch, m, chunk, first_chunk, count,
                                        r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return trc_planes_join_dev(w, P.slice, nullptr, elems * esize, esize, d_out, stream);
+    return trc_planes_join_filter_dev(filter, w, P.slice, nullptr, elems * esize, esize, chunk, d_out, stream);       // (the range opens a segment)
+}
+extern "C" int trc_decode_planes_range_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                           size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                           const uint16_t *d_cdf, unsigned cdfnum,
+                                           void *d_out, void *d_work, size_t work_bytes, void *stream)
+{
+    return trc_decode_fplanes_range_dev(codec, TRC_FILTER_NONE, d_clen, d_payload, n, esize, chunk, first_chunk, count, d_cdf, cdfnum,
+                                        d_out, d_work, work_bytes, stream);
 }
 
 // ---- the TRCP container ----------------------------------------------------------------------------------------------------------
@@ -219,8 +254,9 @@ static int planes_ctx(HostCtx *&cp, std::unique_lock<std::mutex> &lk)
     return ctx_init(*cp, dev);
 }
 
-extern "C" size_t trc_encode_planes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
-                                         void *out, size_t outcap, unsigned cdfnum)
+// the TRCP container of F(filter, chunk, esize, in) -- of `in` itself with TRC_FILTER_NONE
+static size_t planes_host_encode(int codec, int filter, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                                 void *out, size_t outcap, unsigned cdfnum)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
     if (!in || !out || !planes_esize_ok(esize) || n < esize) { fail(TRC_E_ARG, "encode_planes_host: bad arguments (esize %u, %zu bytes)", esize, n); return 0; }
@@ -247,7 +283,7 @@ extern "C" size_t trc_encode_planes_host(int codec, const void *in, size_t n, un
     int32_t *d_status = (int32_t *)(c.d_small + PLANES_SMALL_STATUS);
     uint8_t *d_tail = c.d_small + PLANES_SMALL_TAIL;
     PCHK(hipMemcpyAsync(c.d_in, in, n, hipMemcpyHostToDevice, s));
-    if (trc_encode_planes_dev(codec, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+    if (trc_encode_fplanes_dev(codec, filter, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                               d_clen, d_payload, d_total, d_tail, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
     uint64_t total[8];
     int32_t status[8];
@@ -296,6 +332,11 @@ extern "C" size_t trc_encode_planes_host(int codec, const void *in, size_t n, un
     PCHK(hipStreamSynchronize(s));
     return size;
 }
+extern "C" size_t trc_encode_planes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                                         void *out, size_t outcap, unsigned cdfnum)
+{
+    return planes_host_encode(codec, TRC_FILTER_NONE, in, n, esize, chunk, out, outcap, cdfnum);
+}
 
 // sections of a container that planes_verdict has accepted: where plane k's CDF and TRC1 container lie and how far the latter may reach
 struct PlanesSec { const uint8_t *cdf, *cont; size_t ext; };
@@ -311,7 +352,7 @@ static void planes_sections(const uint8_t *b, const trc_planes_hdr &h, PlanesSec
 }
 
 // elements [first_chunk * chunk, ...) of `count` chunks -- or, whole = true, everything with the tail -- decoded to c.d_in
-static size_t planes_host_decode(HostCtx &c, const uint8_t *b, const trc_planes_hdr &h, bool whole, size_t first_chunk, size_t count, size_t elems)
+static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const trc_planes_hdr &h, bool whole, size_t first_chunk, size_t count, size_t elems)
 {
     const TrcCodec &r = codec_row(h.codec);
     const unsigned esize = h.esize;
@@ -339,14 +380,14 @@ static size_t planes_host_decode(HostCtx &c, const uint8_t *b, const trc_planes_
         if (R.payload_len) PCHK(hipMemcpyAsync(d_payload + k * P.buf, pay + R.payload_off, (size_t)R.payload_len, hipMemcpyHostToDevice, s));
     }
     if (whole && h.tail) PCHK(hipMemcpyAsync(d_tail, b + h.size - h.tail, h.tail, hipMemcpyHostToDevice, s));
-    if (trc_decode_planes_dev(h.codec, d_clen, d_payload, d_tail, nsub, esize, h.chunk, r.cdf ? d_cdf : nullptr, h.cdfnum,
+    if (trc_decode_fplanes_dev(h.codec, filter, d_clen, d_payload, d_tail, nsub, esize, h.chunk, r.cdf ? d_cdf : nullptr, h.cdfnum,
                               c.d_in, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
     return nsub;
 }
 
-extern "C" size_t trc_decode_planes_host(const void *in, size_t inlen, void *out, size_t outlen)
+// the two decoders of a TRCP container whose content is F(filter, chunk, esize, original)
+static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, void *out, size_t outlen)
 {
-    if (!in || !out) { fail(TRC_E_ARG, "decode_planes_host: bad arguments"); return 0; }
     if (trc_planes_check(in, inlen, outlen)) return 0;
     trc_planes_hdr h;
     memcpy(&h, in, sizeof h);
@@ -354,16 +395,21 @@ extern "C" size_t trc_decode_planes_host(const void *in, size_t inlen, void *out
     std::unique_lock<std::mutex> lk;
     if (planes_ctx(cp, lk)) return 0;
     const size_t m = (size_t)(h.n / h.esize);
-    if (!planes_host_decode(*cp, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m)) return 0;
+    if (!planes_host_decode(*cp, filter, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m)) return 0;
     hipStream_t s = cp->s_k[0];
     PCHK(hipMemcpyAsync(out, cp->d_in, (size_t)h.n, hipMemcpyDeviceToHost, s));
     PCHK(hipStreamSynchronize(s));
     return (size_t)h.n;
 }
 
-extern "C" size_t trc_decode_planes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out)
+extern "C" size_t trc_decode_planes_host(const void *in, size_t inlen, void *out, size_t outlen)
 {
-    if (!in || !out) { fail(TRC_E_ARG, "decode_planes_range_host: bad arguments"); return 0; }
+    if (!in || !out) { fail(TRC_E_ARG, "decode_planes_host: bad arguments"); return 0; }
+    return planes_host_decode_all(TRC_FILTER_NONE, in, inlen, out, outlen);
+}
+
+static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen, size_t offset, size_t len, void *out)
+{
     if (trc_planes_check(in, inlen, (size_t)-1)) return 0;
     trc_planes_hdr h;
     memcpy(&h, in, sizeof h);
@@ -378,7 +424,7 @@ extern "C" size_t trc_decode_planes_range_host(const void *in, size_t inlen, siz
         HostCtx *cp = nullptr;
         std::unique_lock<std::mutex> lk;
         if (planes_ctx(cp, lk)) return 0;
-        if (!planes_host_decode(*cp, b, h, false, c0, c1 - c0 + 1, elems)) return 0;
+        if (!planes_host_decode(*cp, filter, b, h, false, c0, c1 - c0 + 1, elems)) return 0;
         hipStream_t s = cp->s_k[0];
         PCHK(hipMemcpyAsync(out, cp->d_in + (offset - c0 * (size_t)h.chunk * h.esize), lb, hipMemcpyDeviceToHost, s));
         PCHK(hipStreamSynchronize(s));
@@ -386,4 +432,69 @@ extern "C" size_t trc_decode_planes_range_host(const void *in, size_t inlen, siz
     if (lb < len) memcpy((uint8_t *)out + lb, b + h.size - h.tail + (offset + lb - body), len - lb);
     return len;
 }
+extern "C" size_t trc_decode_planes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out)
+{
+    if (!in || !out) { fail(TRC_E_ARG, "decode_planes_range_host: bad arguments"); return 0; }
+    return planes_host_decode_bytes(TRC_FILTER_NONE, in, inlen, offset, len, out);
+}
 #undef PCHK
+
+// ---- the TRCF container: trc_fplanes_hdr (16 B) | the TRCP container of the filtered data ------------------------------------------
+extern "C" size_t trc_fplanes_bound(size_t n, unsigned esize, uint32_t chunk, unsigned cdfnum)
+{
+    const size_t b = trc_planes_bound(n, esize, chunk, cdfnum);
+    return b ? b + sizeof(trc_fplanes_hdr) : 0;
+}
+
+// the prefix alone: 0 and the header, or TRC_E_ARG with the reason set
+static int fplanes_prefix(const void *buf, size_t buflen, trc_fplanes_hdr &h)
+{
+    if (!buf || buflen < sizeof h) return fail(TRC_E_ARG, "filtered planes container: %zu bytes is shorter than the header", buflen);
+    memcpy(&h, buf, sizeof h);
+    if (h.magic != TRC_FPLANES_MAGIC || h.version != 1) return fail(TRC_E_ARG, "filtered planes container: bad magic/version");
+    if (h.filter != TRC_FILTER_ZDELTA && h.filter != TRC_FILTER_XOR) return fail(TRC_E_ARG, "filtered planes container: filter %u (1 zigzag delta, 2 xor)", h.filter);
+    if (h.zero) return fail(TRC_E_ARG, "filtered planes container: reserved field is 0x%x, must be 0", h.zero);
+    if (h.size > buflen) return fail(TRC_E_ARG, "filtered planes container: states %llu bytes, the buffer holds %zu", (unsigned long long)h.size, buflen);
+    if (h.size <= sizeof h) return fail(TRC_E_ARG, "filtered planes container: size %llu leaves no room behind the header", (unsigned long long)h.size);
+    return TRC_OK;
+}
+extern "C" int trc_fplanes_check(const void *buf, size_t buflen, size_t outlen)
+{
+    trc_fplanes_hdr h;
+    const int rc = fplanes_prefix(buf, buflen, h);
+    return rc ? rc : trc_planes_check((const uint8_t *)buf + sizeof h, (size_t)h.size - sizeof h, outlen);
+}
+
+extern "C" size_t trc_encode_fplanes_host(int codec, int filter, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                                          void *out, size_t outcap, unsigned cdfnum)
+{
+    if (filter != TRC_FILTER_ZDELTA && filter != TRC_FILTER_XOR) {
+        fail(TRC_E_ARG, "encode_fplanes_host: filter %d (1 zigzag delta, 2 xor; unfiltered data goes through trc_encode_planes_host)", filter);
+        return 0;
+    }
+    if (!out || outcap <= sizeof(trc_fplanes_hdr)) { fail(TRC_E_ARG, "encode_fplanes_host: out holds %zu bytes (trc_fplanes_bound)", outcap); return 0; }
+    const size_t inner = planes_host_encode(codec, filter, in, n, esize, chunk, (uint8_t *)out + sizeof(trc_fplanes_hdr), outcap - sizeof(trc_fplanes_hdr), cdfnum);
+    if (!inner) return 0;
+    trc_fplanes_hdr h;
+    memset(&h, 0, sizeof h);
+    h.magic = TRC_FPLANES_MAGIC; h.filter = (uint8_t)filter; h.version = 1; h.size = sizeof h + inner;
+    memcpy(out, &h, sizeof h);
+    return (size_t)h.size;
+}
+
+// (the prefix is checked here, the inner container by the planes decoders: together trc_fplanes_check, ahead of anything else)
+extern "C" size_t trc_decode_fplanes_host(const void *in, size_t inlen, void *out, size_t outlen)
+{
+    trc_fplanes_hdr h;
+    if (!in || !out) { fail(TRC_E_ARG, "decode_fplanes_host: bad arguments"); return 0; }
+    if (fplanes_prefix(in, inlen, h)) return 0;
+    return planes_host_decode_all(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, out, outlen);
+}
+
+extern "C" size_t trc_decode_fplanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out)
+{
+    trc_fplanes_hdr h;
+    if (!in || !out) { fail(TRC_E_ARG, "decode_fplanes_range_host: bad arguments"); return 0; }
+    if (fplanes_prefix(in, inlen, h)) return 0;
+    return planes_host_decode_bytes(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out);
+}

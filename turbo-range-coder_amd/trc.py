@@ -135,6 +135,19 @@ def lib():
         l.trc_decode_planes_host.restype = _sz; l.trc_decode_planes_host.argtypes = [_vp, _sz, _vp, _sz]
         l.trc_decode_planes_range_host.restype = _sz; l.trc_decode_planes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
         l.trc_planes_check.restype = C.c_int; l.trc_planes_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_split_filter_dev.restype = C.c_int
+        l.trc_planes_split_filter_dev.argtypes = [C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, _vp, _vp]
+        l.trc_planes_join_filter_dev.restype = C.c_int
+        l.trc_planes_join_filter_dev.argtypes = [C.c_int, _vp, _sz, _vp, _sz, C.c_uint, C.c_uint32, _vp, _vp]
+        l.trc_encode_fplanes_dev.restype = C.c_int; l.trc_encode_fplanes_dev.argtypes = [C.c_int, C.c_int] + l.trc_encode_planes_dev.argtypes[1:]
+        l.trc_decode_fplanes_dev.restype = C.c_int; l.trc_decode_fplanes_dev.argtypes = [C.c_int, C.c_int] + l.trc_decode_planes_dev.argtypes[1:]
+        l.trc_decode_fplanes_range_dev.restype = C.c_int
+        l.trc_decode_fplanes_range_dev.argtypes = [C.c_int, C.c_int] + l.trc_decode_planes_range_dev.argtypes[1:]
+        l.trc_fplanes_bound.restype = _sz; l.trc_fplanes_bound.argtypes = [_sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_encode_fplanes_host.restype = _sz; l.trc_encode_fplanes_host.argtypes = [C.c_int, C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint]
+        l.trc_decode_fplanes_host.restype = _sz; l.trc_decode_fplanes_host.argtypes = [_vp, _sz, _vp, _sz]
+        l.trc_decode_fplanes_range_host.restype = _sz; l.trc_decode_fplanes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
+        l.trc_fplanes_check.restype = C.c_int; l.trc_fplanes_check.argtypes = [_vp, _sz, _sz]
         l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
         l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
         l.trc_timing_enable.restype = C.c_int; l.trc_timing_enable.argtypes = [C.c_int]
@@ -601,6 +614,97 @@ def parse_planes(buf):
         sections.append((sec[:2 * (cdfnum + 1)].view("<u2").copy() if cdfb else None, sec[cdfb:cdfb + used].copy()))
     return dict(magic=int(magic), codec=codec, version=int(ver), esize=esize, tail=tail, chunk=int(chunk), cdfnum=cdfnum,
                 n=n, size=size, off=off), sections, buf[size - tail:size].copy()
+
+
+# ------------------------------------------------------------ byte planes behind a filter (include/trc_hip.h) ---
+FILTER_NONE, FILTER_ZDELTA, FILTER_XOR = 0, 1, 2
+FPLANES_MAGIC = 0x46435254                                     # "TRCF"
+FPLANES_HDR = 16
+
+
+def planes_split_filter(filt, d_in, n, esize, seg, d_planes, pitch, d_tail=None):
+    """enqueue trc_planes_split_filter_dev: planes_split of the zigzag-delta / xor filtered elements, restarting every seg elements"""
+    _chk(lib().trc_planes_split_filter_dev(filt, d_in.data_ptr(), n, esize, seg, d_planes.data_ptr(), pitch,
+                                           d_tail.data_ptr() if d_tail is not None else None, _cur_stream(d_in)))
+
+
+def planes_join_filter(filt, d_planes, pitch, d_tail, n, esize, seg, d_out):
+    """enqueue trc_planes_join_filter_dev, the inverse of planes_split_filter"""
+    _chk(lib().trc_planes_join_filter_dev(filt, d_planes.data_ptr(), pitch, d_tail.data_ptr() if d_tail is not None else None, n, esize,
+                                          seg, d_out.data_ptr(), _cur_stream(d_out)))
+
+
+class FilteredPlanesCoder(PlanesCoder):
+    """PlanesCoder through the trc_*_fplanes_dev calls: the same buffers and results, of the filtered elements (restart = chunk).
+    filter=FILTER_NONE is the unfiltered coder."""
+
+    def __init__(self, codec, n, esize, chunk=4096, device="cuda", cdfnum=256, prm=(5, 6), guard=0, filter=FILTER_NONE):
+        super().__init__(codec, n, esize, chunk, device, cdfnum=cdfnum, prm=prm, guard=guard)
+        self.filter = filter
+
+    def encode(self, d_in, n=None, flags=0):
+        n = self.n if n is None else n
+        st = self.codec in STATIC
+        _chk(lib().trc_encode_fplanes_dev(self.codec | flags, self.filter, d_in.data_ptr(), n, self.esize, self.chunk,
+                                          self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                                          self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.tail.data_ptr(),
+                                          self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode(self, d_out, n=None, flags=0):
+        n = self.n if n is None else n
+        _chk(lib().trc_decode_fplanes_dev(self.codec | flags, self.filter, self.clen.data_ptr(), self.payload.data_ptr(), self.tail.data_ptr(),
+                                          n, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                          d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode_range(self, d_out, first, count, n=None, flags=0):
+        n = self.n if n is None else n
+        need = lib().trc_planes_range_work_bytes(self.codec, n, self.esize, self.chunk, count)
+        if need > self.range_work_bytes:
+            self.range_work, self.range_work_bytes = self._buf(need), need
+        if self.range_work is None:
+            self.range_work = self._buf(0)
+        _chk(lib().trc_decode_fplanes_range_dev(self.codec | flags, self.filter, self.clen.data_ptr(), self.payload.data_ptr(), n, self.esize,
+                                                self.chunk, first, count, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                                d_out.data_ptr(), self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+
+
+def fplanes_bound(n, esize, chunk=0, cdfnum=0):
+    return lib().trc_fplanes_bound(n, esize, chunk, cdfnum)
+
+
+def host_encode_fplanes(codec, filt, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
+    """trc_encode_fplanes_host -> the TRCF container (np.uint8): 16 bytes, then the TRCP container of the filtered data"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(fplanes_bound(data.size, esize, chunk, cn), 64), dtype=np.uint8)
+    l = lib().trc_encode_fplanes_host(codec, filt, data.ctypes.data, data.size, esize, chunk, out.ctypes.data, out.size, cn)
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy()
+
+
+def host_decode_fplanes(comp, n):
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    out = np.full(n + 64, 0xA5, dtype=np.uint8)
+    l = lib().trc_decode_fplanes_host(comp.ctypes.data, comp.size, out.ctypes.data, n)
+    if l != n or not (out[n:] == 0xA5).all():
+        raise TrcError(lib().trc_last_error().decode() if l != n else "trc_decode_fplanes_host wrote past its output")
+    return out[:n].copy()
+
+
+def host_decode_fplanes_range(comp, offset, length):
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    out = np.full(length + 64, 0xA5, dtype=np.uint8)
+    l = lib().trc_decode_fplanes_range_host(comp.ctypes.data, comp.size, offset, length, out.ctypes.data)
+    if l != length or not (out[length:] == 0xA5).all():
+        raise TrcError(lib().trc_last_error().decode() if l != length else "trc_decode_fplanes_range_host wrote past its output")
+    return out[:length].copy()
+
+
+def fplanes_check(buf, outlen=None):
+    """trc_fplanes_check on a TRCF container in host memory (needs no device); raises TrcError with the library's reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_fplanes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
 
 
 def encode_host_container(codec, data, chunk, cdf=None, cdfnum=256, prm=(5, 6)):
