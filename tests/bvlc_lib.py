@@ -9,9 +9,6 @@ gen(kind, es, n, seed): n bytes of little-endian es-byte elements (the last elem
   uniform  uniform bytes (every chunk raw)
   max<v>   v (masked to the width) at every 16th element, 0 elsewhere: the chunk maxima that pin rcvsenc32's vb (VB32)
 """
-import ctypes as C
-import os
-
 import numpy as np
 
 import trc_testlib as T
@@ -27,7 +24,6 @@ CONSTS = {"max0": 0, "max7": 7, "max8": 8, "max15": 15, "max16": 16, "max1000": 
 # vb byte of rcvsenc32 (payload offset 4) against the chunk's maximum, measured on the reference
 VB32 = {0: 255, 7: 255, 8: 247, 15: 240, 16: 239, 1000: 192, 1 << 31: 23}
 KINDS = ["geo", "walk", "mixed", "allmax", "uniform"] + list(CONSTS)
-_INV = {}
 
 
 def gen(kind, es, n, seed):
@@ -55,36 +51,6 @@ def gen(kind, es, n, seed):
     return np.ascontiguousarray(v.astype(np.uint64).astype(dt)).view(np.uint8)[:n].copy()
 
 
-def have_ref():
-    return os.path.exists(T.REF_SO)
-
-
-def _ref_lib():
-    lib = C.CDLL(T.REF_SO)
-    for codec in REF_FN:
-        for name in REF_FN[codec]:
-            f = getattr(lib, name)
-            f.restype = C.c_size_t
-            f.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8)]
-    return lib
-
-
-def ref_enc(codec, data):
-    """one call of the reference encoder on `data`; `out` has 2n+64 writable bytes in front of it (trc_testlib._arena): on
-    short inputs the reference's reversed bit writer stores 8 bytes at out + n - 8"""
-    lib = _INV.get("lib") or _INV.setdefault("lib", _ref_lib())
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    n = data.size
-    buf, io, oo = T._arena(n)
-    buf[io:io + n] = data
-    base = buf.ctypes.data
-    l = getattr(lib, REF_FN[codec][0])(C.cast(base + io, C.POINTER(C.c_uint8)), n, C.cast(base + oo, C.POINTER(C.c_uint8)))
-    return buf[oo:oo + l].copy()
-
-
-def ref_chunked_enc(codec, data, chunk):
-    """-> (clen u32 array, payload u8 array): the reference called once per chunk"""
-    outs = [ref_enc(codec, data[i:i + chunk]) for i in range(0, data.size, chunk)]
-    clen = np.array([o.size for o in outs], dtype=np.uint32)
-    payload = np.concatenate(outs) if outs else np.zeros(0, np.uint8)
-    return clen, payload
+# (on short inputs the reference's reversed bit writer stores 8 bytes at out + n - 8: the arena's 2n+64 bytes in front of `out`)
+_REF = T.RefCalls(REF_FN, T.REF_SO)
+have_ref, ref_enc, ref_chunked_enc = _REF.have, _REF.enc, _REF.chunked_enc

@@ -5,9 +5,6 @@ distribution over a permuted alphabet: x_i = (MK_MUL * x_{i-1} + MK_PERM[r_i]) m
 puts rank r on symbol MK_MUL * s + MK_PERM[r].  The recurrence is affine in x, which makes it vectorisable
 (x_i = A^i * (x_0 + sum_{j <= i} A^-j t_j)); harness/trcbench.c --markov generates the same bytes in C.
 """
-import ctypes as C
-import os
-
 import numpy as np
 
 import trc_testlib as T
@@ -18,7 +15,6 @@ REF_FN = {RCC1: ("rccsenc", "rccsdec"), RCX1: ("rcxsenc", "rcxsdec")}
 ROUND_CHUNK = 16384                                            # TRC_O1BIT_CHUNK_MIN (include/trc_hip.h)
 MK_MUL = 77                                                    # odd: a bijection of the state for every rank
 MK_PERM = (np.arange(256, dtype=np.int64) * 173 + 29) & 255   # rank -> symbol offset (a permutation)
-_INV = {}
 
 
 def markov_bytes(n, seed=21, alpha=1.3):
@@ -50,46 +46,5 @@ def gen(kind, n, seed):
     raise ValueError(kind)
 
 
-def have_ref():
-    return os.path.exists(T.REF_SO)
-
-
-def _ref_lib():
-    lib = C.CDLL(T.REF_SO)
-    for codec in REF_FN:
-        for name in REF_FN[codec]:
-            f = getattr(lib, name)
-            f.restype = C.c_size_t
-            f.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8)]
-    return lib
-
-
-def ref_enc(codec, data):
-    """one call of the reference encoder on `data`, `in` below `out` in one arena (trc_testlib._arena)"""
-    lib = _INV.get("lib") or _INV.setdefault("lib", _ref_lib())
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    n = data.size
-    buf, io, oo = T._arena(n)
-    buf[io:io + n] = data
-    base = buf.ctypes.data
-    l = getattr(lib, REF_FN[codec][0])(C.cast(base + io, C.POINTER(C.c_uint8)), n, C.cast(base + oo, C.POINTER(C.c_uint8)))
-    return buf[oo:oo + l].copy()
-
-
-def ref_chunked_enc(codec, data, chunk):
-    """-> (clen u32 array, payload u8 array): the reference called once per chunk"""
-    outs = [ref_enc(codec, data[i:i + chunk]) for i in range(0, data.size, chunk)]
-    clen = np.array([o.size for o in outs], dtype=np.uint32)
-    payload = np.concatenate(outs) if outs else np.zeros(0, np.uint8)
-    return clen, payload
-
-
-def ref_dec(codec, comp, n):
-    lib = _INV.get("lib") or _INV.setdefault("lib", _ref_lib())
-    comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    if comp.size == n:
-        return comp.copy()
-    src = np.zeros(comp.size + 1024, dtype=np.uint8); src[:comp.size] = comp
-    out = np.zeros(n + 64, dtype=np.uint8)
-    getattr(lib, REF_FN[codec][1])(src.ctypes.data_as(C.POINTER(C.c_uint8)), n, out.ctypes.data_as(C.POINTER(C.c_uint8)))
-    return out[:n].copy()
+_REF = T.RefCalls(REF_FN, T.REF_SO)
+have_ref, ref_enc, ref_chunked_enc, ref_dec = _REF.have, _REF.enc, _REF.chunked_enc, _REF.dec

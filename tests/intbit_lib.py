@@ -9,9 +9,6 @@ gen(kind, es, n, seed): n bytes of little-endian es-byte elements (the last elem
   const    every element 5
   uniform  uniform bytes (every chunk raw)
 """
-import ctypes as C
-import os
-
 import numpy as np
 
 import trc_testlib as T
@@ -25,7 +22,6 @@ NAMES = {c: FAMILY[30 + 3 * ((c - 30) // 3)] + str(8 * ES[c]) for c in CODECS}
 REF_FN = {c: (FAMILY[30 + 3 * ((c - 30) // 3)] + "enc" + str(8 * ES[c]), FAMILY[30 + 3 * ((c - 30) // 3)] + "dec" + str(8 * ES[c]))
           for c in CODECS}
 KINDS = ["geo", "walk", "mixed", "allmax", "const", "uniform"]
-_INV = {}
 
 
 def gen(kind, es, n, seed):
@@ -52,32 +48,6 @@ def gen(kind, es, n, seed):
     return np.ascontiguousarray(v.astype(np.uint64).astype(dt)).view(np.uint8)[:n].copy()
 
 
-def have_ref():
-    return os.path.exists(T.REF_SO)
-
-
-def _ref_lib():
-    lib = C.CDLL(T.REF_SO)
-    for codec in REF_FN:
-        for name in REF_FN[codec]:
-            f = getattr(lib, name)
-            f.restype = C.c_size_t
-            f.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8)]
-    return lib
-
-
-def ref_enc(codec, data):
-    """one call of the reference encoder on `data`, `in` below `out` in one arena (trc_testlib._arena)"""
-    lib = _INV.get("lib") or _INV.setdefault("lib", _ref_lib())
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    n = data.size
-    buf, io, oo = T._arena(n)
-    buf[io:io + n] = data
-    base = buf.ctypes.data
-    l = getattr(lib, REF_FN[codec][0])(C.cast(base + io, C.POINTER(C.c_uint8)), n, C.cast(base + oo, C.POINTER(C.c_uint8)))
-    return buf[oo:oo + l].copy()
-
-
 def chunk_payload(codec, piece):
     """the library's payload of one chunk: the reference's bytes, except that a chunk shorter than one element is stored raw
     (the reference returns its tail bytes plus an empty 4-byte flush there, include/trc_hip.h)"""
@@ -86,20 +56,5 @@ def chunk_payload(codec, piece):
     return ref_enc(codec, piece)
 
 
-def ref_chunked_enc(codec, data, chunk):
-    """-> (clen u32 array, payload u8 array): the reference called once per chunk"""
-    outs = [chunk_payload(codec, data[i:i + chunk]) for i in range(0, data.size, chunk)]
-    clen = np.array([o.size for o in outs], dtype=np.uint32)
-    payload = np.concatenate(outs) if outs else np.zeros(0, np.uint8)
-    return clen, payload
-
-
-def ref_dec(codec, comp, n):
-    lib = _INV.get("lib") or _INV.setdefault("lib", _ref_lib())
-    comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    if comp.size == n:
-        return comp.copy()
-    src = np.zeros(comp.size + 1024, dtype=np.uint8); src[:comp.size] = comp
-    out = np.zeros(n + 64, dtype=np.uint8)
-    getattr(lib, REF_FN[codec][1])(src.ctypes.data_as(C.POINTER(C.c_uint8)), n, out.ctypes.data_as(C.POINTER(C.c_uint8)))
-    return out[:n].copy()
+_REF = T.RefCalls(REF_FN, T.REF_SO, chunk_hook=chunk_payload)
+have_ref, ref_enc, ref_chunked_enc, ref_dec = _REF.have, _REF.enc, _REF.chunked_enc, _REF.dec

@@ -60,43 +60,19 @@ def have_ref_sources():
 
 
 class Ref:
-    """the reference's eight functions, compiled into `outdir`"""
+    """the reference's eight functions, compiled into `outdir`; every call takes prm=(prm0, prm1) behind its own arguments"""
 
     def __init__(self, outdir):
         so = os.path.join(str(outdir), "libtrc_ref_ss.so")
         flags = ["-O3", "-w", "-fPIC", "-DNDEBUG", "-D_NCPUISA", "-mavx", "-mpopcnt", "-I" + REF_DIR]
         subprocess.check_call(["gcc"] + flags + ["-shared", os.path.join(REF_DIR, "rc_ss.c"), os.path.join(REF_DIR, "rc_s.c"), "-o", so])
-        self.lib = C.CDLL(so)
-        for codec in REF_FN:
-            for name in REF_FN[codec]:
-                f = getattr(self.lib, name)
-                f.restype = C.c_size_t
-                f.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_uint, C.c_uint]
+        self.calls = T.RefCalls(REF_FN, so, extra=(C.c_uint, C.c_uint))
 
     def enc(self, codec, data, prm=DEFAULT):
-        """one call of the reference encoder on `data`, `in` below `out` in one arena (trc_testlib._arena)"""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        n = data.size
-        buf, io, oo = T._arena(n)
-        buf[io:io + n] = data
-        base = buf.ctypes.data
-        l = getattr(self.lib, REF_FN[codec][0])(C.cast(base + io, C.POINTER(C.c_uint8)), n, C.cast(base + oo, C.POINTER(C.c_uint8)),
-                                                prm[0], prm[1])
-        return buf[oo:oo + l].copy()
+        return self.calls.enc(codec, data, *prm)
 
     def chunked_enc(self, codec, data, chunk, prm=DEFAULT):
-        """-> (clen u32 array, payload u8 array): the reference called once per chunk"""
-        outs = [self.enc(codec, data[i:i + chunk], prm) for i in range(0, data.size, chunk)]
-        clen = np.array([o.size for o in outs], dtype=np.uint32)
-        payload = np.concatenate(outs) if outs else np.zeros(0, np.uint8)
-        return clen, payload
+        return self.calls.chunked_enc(codec, data, chunk, *prm)
 
     def dec(self, codec, comp, n, prm=DEFAULT):
-        comp = np.ascontiguousarray(comp, dtype=np.uint8)
-        if comp.size == n:
-            return comp.copy()
-        src = np.zeros(comp.size + 1024, dtype=np.uint8); src[:comp.size] = comp
-        out = np.zeros(n + 64, dtype=np.uint8)
-        getattr(self.lib, REF_FN[codec][1])(src.ctypes.data_as(C.POINTER(C.c_uint8)), n, out.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                            prm[0], prm[1])
-        return out[:n].copy()
+        return self.calls.dec(codec, comp, n, *prm)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import bvlc_lib as L
+import trc_testlib as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "turbo-range-coder_amd", "libturborc_hip.so")
@@ -23,22 +24,7 @@ ENUM = {43: "TRC_RCBV16", 44: "TRC_RCBV32", 45: "TRC_RCBVZ16", 46: "TRC_RCBVZ32"
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(LIB)
-    lib.trc_work_bytes.restype = ctypes.c_size_t
-    lib.trc_work_bytes.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32]
-    lib.trc_auto_chunk_codec.restype = ctypes.c_uint32
-    lib.trc_auto_chunk_codec.argtypes = [ctypes.c_int, ctypes.c_size_t]
-    lib.trc_round_chunk.restype = ctypes.c_uint32
-    lib.trc_round_chunk.argtypes = [ctypes.c_int, ctypes.c_size_t]
-    lib.trc_kernel_name.restype = ctypes.c_char_p
-    lib.trc_kernel_name.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.trc_host_plan.restype = ctypes.c_int
-    lib.trc_host_plan.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
-                                  ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
-    return lib
+    return T.product_lib()
 
 
 def test_symbols_exported_and_declared(lib):

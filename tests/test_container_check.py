@@ -3,7 +3,6 @@
 The reference prototypes carry no input length, so a caller handed a file must be able to check that everything a
 decoder will read lies inside its buffer (round-1 advisor finding: a crafted/truncated container made the host layer
 read past the file buffer)."""
-import ctypes as C
 import struct
 
 import numpy as np
@@ -23,8 +22,6 @@ def make(codec=1, chunk=1024, n=5000, clens=None, payload=None, magic=0x31435254
 @pytest.fixture(scope="module")
 def check():
     f = trc.lib().trc_container_check
-    f.restype = C.c_int
-    f.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_size_t]
     return lambda b, blen=None, codec=0, outlen=2**64 - 1: f(b, len(b) if blen is None else blen, codec, outlen)
 
 

@@ -14,20 +14,13 @@ import pytest
 import trc
 import bytesweep_lib as B
 import gpu_contracts as G
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 SHIFTS = [0, 2, 6, 30, 62, 64, 66, 126]
 GUARD = 512
 LEAK_PRMS = [(15, 15), (1, 1), (5, 6), (1, 9), (4, 7), (5, 6)]
 by_name = pytest.mark.parametrize("codec", B.CODECS, ids=lambda c: B.NAMES[c])
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 @pytest.fixture(scope="module")

@@ -150,10 +150,7 @@ import sys
 sys.path.insert(0, "tests"); sys.path.insert(0, "turbo-range-coder_amd")
 import numpy as np, trc, trc_testlib as T
 from golden.make_golden import gen
-import ctypes
 lib = trc.lib()
-lib.trc_host_pin.restype = ctypes.c_int; lib.trc_host_pin.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-lib.trc_host_unpin.restype = ctypes.c_int; lib.trc_host_unpin.argtypes = [ctypes.c_void_p]
 rng = np.random.default_rng(5)
 n_calls = 0
 for codec in (trc.RCA, trc.RCAI, trc.ANSA, trc.RCB):
@@ -203,9 +200,7 @@ import sys, time
 sys.path.insert(0, "tests"); sys.path.insert(0, "turbo-range-coder_amd")
 import numpy as np, trc, trc_testlib as T
 from golden.make_golden import gen
-import ctypes
 d = gen("text", 3000001, 5)
-trc.lib().trc_host_pin.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
 assert trc.lib().trc_host_pin(d.ctypes.data, d.nbytes) == 0
 t0 = time.time(); a = trc.host_encode(trc.RCA, d); t1 = time.time(); b = trc.host_encode(trc.RCA, d); t2 = time.time()
 hdr, clen, payload = trc.parse_container(a)

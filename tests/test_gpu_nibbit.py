@@ -1,7 +1,6 @@
 """Bitwise nibble and varint byte coders on the MI355X (rc4s, rc4cs, rcu3s: TRC_RC4, TRC_RC4C, TRC_RCU3): device-resident
 encode bit-exact to the fixtures generated through the reference (tests/golden/make_nibbit_golden.py), the decoder on the
 fixtures' payloads, the 4 MiB hashes, a payload at an odd-word offset, the host-pointer layer, argument errors and trcbench."""
-import ctypes
 import hashlib
 import json
 import os
@@ -12,25 +11,15 @@ import pytest
 
 import trc
 import nibbit_lib as L
+import gpu_contracts as G
+from gpu_contracts import GOLD, ROOT, to_dev, torch_cuda  # noqa: F401 (torch_cuda: the fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-GUARD = 512
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 @pytest.fixture(scope="module")
 def vectors():
-    z = np.load(os.path.join(GOLD, "nibbit_vectors.npz"))
-    return z, json.loads(bytes(z["index"]).decode())
+    return G.vectors("nibbit")
 
 
 @pytest.fixture(scope="module")
@@ -43,10 +32,6 @@ def large():
     assert hashlib.sha256(d.tobytes()).hexdigest() == e["in_sha256"]
     d.setflags(write=False)
     return d, rec
-
-
-def to_dev(torch, a, pad=GUARD):
-    return torch.from_numpy(np.concatenate([a, np.zeros(pad, np.uint8)])).to("cuda:0")
 
 
 @pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
@@ -65,16 +50,8 @@ def test_fixtures_encode_and_decode(torch_cuda, vectors, codec):
         tag = (name, ent["kind"], n, chunk)
         assert np.array_equal(clen, eclen), tag
         assert np.array_equal(payload, epay), tag
-        # the decoder from the FIXTURE's directory and payload, in a fresh workspace
-        rx = trc.DeviceCoder(codec, n, chunk, "cuda:0")
-        d_clen = torch.from_numpy(np.concatenate([eclen, np.zeros(64, np.uint32)]).view(np.int32)).to("cuda:0")
-        d_pay = to_dev(torch, epay)
-        d_out = torch.full((n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-        rx.decode(d_out, n, clen=d_clen, payload=d_pay)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        assert np.array_equal(out[:n], L.expected(codec, d, eclen, chunk)), tag
-        assert (out[n:] == 0xA5).all(), tag
+        out, guards = G.decode_fixture(torch, codec, n, chunk, eclen, epay)   # the FIXTURE's directory and payload
+        assert np.array_equal(out, L.expected(codec, d, eclen, chunk)) and guards, tag
         lens = np.minimum(chunk, n - np.arange(0, n, chunk))
         raw = int((eclen == lens).sum())
         raw_seen += raw
@@ -90,19 +67,7 @@ def test_large_hashes(torch_cuda, large, codec):
     d, rec = large
     e = rec[L.NAMES[codec]]
     n, chunk = e["n"], e["chunk"]
-    d_in = to_dev(torch, d)
-    dc = trc.DeviceCoder(codec, n, chunk, "cuda:0")
-    dc.encode(d_in, n)
-    clen, payload = dc.result(n)
-    assert payload.size == e["payload_bytes"] and int((clen == chunk).sum()) == e["raw_chunks"]
-    assert hashlib.sha256(clen.astype("<u4").tobytes()).hexdigest() == e["clen_sha256"]
-    assert hashlib.sha256(payload.tobytes()).hexdigest() == e["payload_sha256"]
-    d_out = torch.full((n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-    dc.decode(d_out, n)
-    torch.cuda.synchronize()
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:n], L.expected(codec, d, clen, chunk))
-    assert (out[n:] == 0xA5).all()
+    dc, d_in, clen, payload = G.large_roundtrip(torch, codec, d, e, raw_chunks=True, expected=L.expected, fill=0xA5)
     # payload at offset 6 of a 256-byte aligned buffer: encode into it, decode from it
     buf = torch.zeros(n + trc.PAD + 64 + 256, dtype=torch.uint8, device="cuda:0")
     base = (buf.data_ptr() + 255) & ~255
@@ -112,11 +77,7 @@ def test_large_hashes(torch_cuda, large, codec):
     dc.encode(d_in, n)
     clen2, payload2 = dc.result(n)
     assert np.array_equal(clen2, clen) and np.array_equal(payload2, payload)
-    d_out.fill_(0xA5)
-    dc.decode(d_out, n)
-    torch.cuda.synchronize()
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:n], L.expected(codec, d, clen, chunk)) and (out[n:] == 0xA5).all()
+    G.decode_checked(torch, dc, L.expected(codec, d, clen, chunk), n, 0xA5, "payload at offset 6")
 
 
 @pytest.mark.parametrize("chunk", [0, 256], ids=["auto", "chunk256"])
@@ -124,8 +85,6 @@ def test_large_hashes(torch_cuda, large, codec):
 def test_host_pointer_round_trip(torch_cuda, codec, chunk):
     """rc4senc / rc4sdec, rc4csenc / rc4csdec, rcu3senc / rcu3sdec on 1 MB + 7 bytes, automatic chunk and 256"""
     lib = trc.lib()
-    lib.trc_container_check.restype = ctypes.c_int
-    lib.trc_container_check.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t]
     n = 10**6 + 7
     prev = lib.trc_get_chunk()
     assert lib.trc_set_chunk(chunk) == 0
@@ -179,13 +138,7 @@ def test_trcbench_rows(torch_cuda):
 
 def test_reference_harness_no_mismatch(torch_cuda, tmp_path):
     """the reference's own harness linked against the library: -e17 on a byte file, -n -e40,41 on a nibble file"""
-    exe = os.path.join(ROOT, "oracle", "_ref", "turborc_hip")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/turborc_hip not built")
     for kind, args, rows in (("bytes_small", ["-e17"], ("17:rcu3",)), ("nib_skew", ["-n", "-e40,41"], ("40:rc4cs", "41:rc4s"))):
         src = tmp_path / (kind + ".bin")
         src.write_bytes(L.gen(kind, 10**6 + 11, 4).tobytes())
-        r = subprocess.run([exe, "-I1", "-J1"] + args + [str(src)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and "ERROR" not in r.stdout and "ERROR" not in r.stderr, r.stdout[-3000:] + r.stderr[-2000:]
-        for row in rows:
-            assert row in r.stdout, r.stdout[-3000:]
+        G.reference_harness(args, src, rows, 300)

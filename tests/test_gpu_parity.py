@@ -505,8 +505,6 @@ def test_bounded_host_decoder(torch_cuda):
     before anything is decoded (the reference-named decoders cannot know: their prototypes carry no input length)."""
     import ctypes as C
     L = trc.lib()
-    L.trc_decode_host.restype = C.c_size_t
-    L.trc_decode_host.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint]
     for codec in (trc.ANS4S, trc.RCS2, trc.RCA, trc.RCB):
         d = gen("text", 300001, 91)
         _, cdf, cdfnum = T.orc_cdfini(d)

@@ -12,6 +12,7 @@ import trc
 import trc_testlib as T
 import nibbit_lib as NL
 import sweep_lib as S
+from gpu_contracts import to_dev, torch_cuda  # noqa: F401 (torch_cuda: the fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,18 +47,6 @@ def make_input(codec):
         skew, uni = T.nibble_bytes(n, 5, "geo"), T.uniform_bytes(n, 6)
     d = np.where((np.arange(n) // chunk) % 2 == 0, uni[:n], skew[:n]).astype(np.uint8)
     return n, chunk, d
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-def to_dev(torch, a, pad=GUARD):
-    return torch.from_numpy(np.concatenate([a, np.zeros(pad, np.uint8)])).to("cuda:0")
 
 
 def encoded(torch, codec, n, chunk, d):

@@ -2,7 +2,6 @@
 TRC_RC4SS, TRC_RC4CSS, TRC_RCU3SS): device-resident encode bit-exact to the fixtures generated through the reference
 (tests/golden/make_ssbit_golden.py) for every parameter pair, the decoder and the range decoder on the fixtures' payloads, the
 4 MiB hashes, the host-pointer layer and its parameter rules, argument errors, trcbench and the reference's harness."""
-import ctypes
 import hashlib
 import json
 import os
@@ -13,20 +12,11 @@ import pytest
 
 import trc
 import ssbit_lib as L
+import gpu_contracts as G
+from gpu_contracts import GOLD, ROOT, to_dev, torch_cuda  # noqa: F401 (torch_cuda: the fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-GUARD = 512
 TRC_E_ARG, TRC_E_WORK = -1, -3
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -46,10 +36,6 @@ def large():
     return d, rec
 
 
-def to_dev(torch, a, pad=GUARD):
-    return torch.from_numpy(np.concatenate([a, np.zeros(pad, np.uint8)])).to("cuda:0")
-
-
 @pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
 def test_fixtures_encode_and_decode(torch_cuda, vectors, codec):
     """every case and parameter pair: the encoder gives the fixture's directory and payload; the decoder, from the FIXTURE's
@@ -63,7 +49,7 @@ def test_fixtures_encode_and_decode(torch_cuda, vectors, codec):
         d = L.gen(ent["kind"], n, ent["seed"], chunk)          # (inputs are regenerated, not stored)
         d_in = to_dev(torch, d)
         dc = trc.DeviceCoder(codec, n, chunk, "cuda:0")
-        rx = trc.DeviceCoder(codec, n, chunk, "cuda:0")        # the decoders' own workspace, never encoded in
+        rx = trc.DeviceCoder(codec, n, chunk, "cuda:0")        # the range decoder's own workspace, never encoded in
         for prm in ent["prms"]:
             eclen, epay = L.fixture(z, ent, codec, prm)
             dc.encode(d_in, n, prm=prm)
@@ -71,20 +57,15 @@ def test_fixtures_encode_and_decode(torch_cuda, vectors, codec):
             tag = (name, ent["kind"], n, chunk, prm)
             assert np.array_equal(clen, eclen), tag
             assert np.array_equal(payload, epay), tag
-            d_clen = torch.from_numpy(np.concatenate([eclen, np.zeros(64, np.uint32)]).view(np.int32)).to("cuda:0")
-            d_pay = to_dev(torch, epay)
-            d_out = torch.full((n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-            rx.decode(d_out, n, clen=d_clen, payload=d_pay, prm=prm)
-            torch.cuda.synchronize()
-            out = d_out.cpu().numpy()
             want = L.expected(codec, d, eclen, chunk)
-            assert np.array_equal(out[:n], want), tag
-            assert (out[n:] == 0xA5).all(), tag
+            out, guards = G.decode_fixture(torch, codec, n, chunk, eclen, epay, prm=prm)
+            assert np.array_equal(out, want) and guards, tag
             nch = eclen.size
             if nch >= 3:                                        # a range that starts and ends inside the container
                 first, count = 1, nch - 2
                 b0, b1 = first * chunk, min(n, (first + count) * chunk)
-                d_out.fill_(0xA5)
+                d_clen, d_pay = G.fixture_to_dev(torch, eclen, epay)
+                d_out = torch.full((n + 512,), 0xA5, dtype=torch.uint8, device="cuda:0")
                 rx.decode_range(d_out, first, count, n, clen=d_clen, payload=d_pay, prm=prm)
                 torch.cuda.synchronize()
                 out = d_out.cpu().numpy()
@@ -101,23 +82,9 @@ def test_fixtures_encode_and_decode(torch_cuda, vectors, codec):
 @pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
 def test_large_hashes(torch_cuda, large, codec):
     """4 MiB of `mixed` at chunk 1024, parameters (5, 6): 4096 chunks, 64 waves, raw and coded chunks side by side"""
-    torch = torch_cuda
     d, rec = large
     e = rec[L.NAMES[codec]]
-    n, chunk = e["n"], e["chunk"]
-    d_in = to_dev(torch, d)
-    dc = trc.DeviceCoder(codec, n, chunk, "cuda:0")
-    dc.encode(d_in, n, prm=tuple(e["prm"]))
-    clen, payload = dc.result(n)
-    assert payload.size == e["payload_bytes"] and int((clen == chunk).sum()) == e["raw_chunks"]
-    assert hashlib.sha256(clen.astype("<u4").tobytes()).hexdigest() == e["clen_sha256"]
-    assert hashlib.sha256(payload.tobytes()).hexdigest() == e["payload_sha256"]
-    d_out = torch.full((n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
-    dc.decode(d_out, n, prm=tuple(e["prm"]))
-    torch.cuda.synchronize()
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:n], L.expected(codec, d, clen, chunk))
-    assert (out[n:] == 0xA5).all()
+    G.large_roundtrip(torch_cuda, codec, d, e, prm=e["prm"], raw_chunks=True, expected=L.expected, fill=0xA5)
 
 
 @pytest.mark.parametrize("prm", [(5, 6), (1, 9)], ids=["5_6", "1_9"])
@@ -127,8 +94,6 @@ def test_host_pointer_round_trip(torch_cuda, codec, chunk, prm):
     """the eight reference-named functions on 10^6 + 11 bytes, automatic chunk and 256; the header records the parameters, and a
     decoder that states other ones returns 0"""
     lib = trc.lib()
-    lib.trc_container_check.restype = ctypes.c_int
-    lib.trc_container_check.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t]
     n = 10**6 + 11
     prev = lib.trc_get_chunk()
     assert lib.trc_set_chunk(chunk) == 0
@@ -157,12 +122,6 @@ def test_host_layer_parameter_rules(torch_cuda):
     """trc_encode_host / trc_decode_host: NULL CDF and TRC_SS_PRM; cdfnum 0 on decode = the header's parameters; a header whose
     parameters were altered fails against an explicit cdfnum that now disagrees, and decodes to something else without one"""
     lib = trc.lib()
-    lib.trc_encode_host.restype = ctypes.c_size_t
-    lib.trc_encode_host.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint]
-    lib.trc_decode_host.restype = ctypes.c_size_t
-    lib.trc_decode_host.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint]
-    lib.trc_container_bound.restype = ctypes.c_size_t
-    lib.trc_container_bound.argtypes = [ctypes.c_size_t, ctypes.c_uint32]
     n, chunk, codec = 100003, 1024, trc.RCSS
     d = L.gen("bytes_small", n, 5)
     cap = lib.trc_container_bound(n, chunk)
@@ -236,11 +195,6 @@ def test_trcbench_rows(torch_cuda):
 
 def test_reference_harness_no_error(torch_cuda, tmp_path):
     """the reference's own harness linked against the library, started with -pss: ids 1 and 17 on a 1 MB file"""
-    exe = os.path.join(ROOT, "oracle", "_ref", "turborc_hip")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/turborc_hip not built")
     src = tmp_path / "bytes_small.bin"
     src.write_bytes(L.gen("bytes_small", 10**6 + 11, 4).tobytes())
-    r = subprocess.run([exe, "-I1", "-J1", "-e1,17", "-pss", str(src)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ERROR" not in r.stdout and "ERROR" not in r.stderr, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "1:rc" in r.stdout and "17:rcu3" in r.stdout, r.stdout[-3000:]
+    G.reference_harness(["-e1,17", "-pss"], src, ("1:rc", "17:rcu3"), 300)

@@ -13,6 +13,7 @@ import pytest
 
 import trc
 import gpu_contracts as G
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
 import sweep_lib as S
 
 pytestmark = pytest.mark.gpu
@@ -21,14 +22,6 @@ CONTRACT_MAX_N = 300000                                        # sweep cases abo
 SHIFTS = [0, 2, 6, 30, 62, 64, 66, 126]
 SOAK_SEEDS = int(os.environ.get("TRC_SWEEP_SEEDS", "0"))
 by_name = pytest.mark.parametrize("codec", S.CODECS, ids=lambda c: S.NAMES[c])
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 @pytest.fixture(scope="module")

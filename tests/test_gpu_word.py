@@ -6,47 +6,21 @@ import ctypes
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import trc
 import word_lib as L
+import gpu_contracts as G
+from gpu_contracts import GOLD, to_dev, torch_cuda  # noqa: F401 (torch_cuda: the fixture)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 @pytest.fixture(scope="module")
 def vectors():
-    z = np.load(os.path.join(GOLD, "word_vectors.npz"))
-    return z, json.loads(bytes(z["index"]).decode())
-
-
-def to_dev(torch, a, pad=512):
-    return torch.from_numpy(np.concatenate([a, np.zeros(pad, np.uint8)])).to("cuda:0")
-
-
-def decode_into(torch, codec, n, chunk, clen, payload, guard=512):
-    """decode (clen, payload) into an output with 0xA5 sentinels on both sides -> (decoded bytes, sentinels intact)"""
-    rx = trc.DeviceCoder(codec, n, chunk, "cuda:0")
-    d_clen = torch.from_numpy(np.concatenate([clen, np.zeros(64, np.uint32)]).view(np.int32)).to("cuda:0")
-    d_pay = to_dev(torch, payload)
-    buf = torch.full((guard + n + guard,), 0xA5, dtype=torch.uint8, device="cuda:0")
-    rx.decode(buf[guard:], n, clen=d_clen, payload=d_pay)
-    torch.cuda.synchronize()
-    out = buf.cpu().numpy()
-    return out[guard:guard + n], bool((out[:guard] == 0xA5).all() and (out[guard + n:] == 0xA5).all())
+    return G.vectors("word")
 
 
 @pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
@@ -71,7 +45,7 @@ def test_fixtures_encode_and_decode(torch_cuda, vectors, codec):
         tag = (name, ent["kind"], n, chunk)
         assert np.array_equal(clen, eclen), tag
         assert np.array_equal(payload, epay), tag
-        out, guards = decode_into(torch, codec, n, chunk, eclen, epay)
+        out, guards = G.decode_fixture(torch, codec, n, chunk, eclen, epay, front=512)
         assert np.array_equal(out, d) and guards, tag
         raw = int((eclen == lens).sum())
         raw_seen += raw
@@ -81,22 +55,9 @@ def test_fixtures_encode_and_decode(torch_cuda, vectors, codec):
 
 
 def _large(torch, e, codec):
-    n, chunk = e["n"], e["chunk"]
-    d = L.gen(e["kind"], L.ES[codec], n, e["seed"])
+    d = L.gen(e["kind"], L.ES[codec], e["n"], e["seed"])
     assert hashlib.sha256(d.tobytes()).hexdigest() == e["in_sha256"]
-    d_in = to_dev(torch, d)
-    dc = trc.DeviceCoder(codec, n, chunk, "cuda:0")
-    dc.encode(d_in, n)
-    clen, payload = dc.result(n)
-    assert clen.size == e["nchunks"]
-    assert payload.size == e["payload_bytes"]
-    assert hashlib.sha256(clen.astype("<u4").tobytes()).hexdigest() == e["clen_sha256"]
-    assert hashlib.sha256(payload.tobytes()).hexdigest() == e["payload_sha256"]
-    d_out = torch.zeros(n + 512, dtype=torch.uint8, device="cuda:0")
-    dc.decode(d_out, n)
-    torch.cuda.synchronize()
-    assert torch.equal(d_out[:n], d_in[:n])
-    del d_in, d_out, dc
+    G.large_roundtrip(torch, codec, d, e, nchunks=True)
 
 
 @pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
@@ -167,42 +128,7 @@ def test_host_pointer_layer(torch_cuda, codec):
 @pytest.mark.parametrize("codec", L.CODECS, ids=lambda c: L.NAMES[c])
 def test_malformed_arguments_like_rcs(torch_cuda, codec):
     """every bad call is refused with the code TRC_RCB's is refused with"""
-    torch = torch_cuda
-    lib = trc.lib()
-    f = lib.trc_encode_dev
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint,
-                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    g = lib.trc_decode_dev
-    g.restype = ctypes.c_int
-    g.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint,
-                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    n = 100000
-    buf = torch.zeros(4 * n + (1 << 20), dtype=torch.uint8, device="cuda:0")
-    p = buf.data_ptr()
-    wb = max(lib.trc_work_bytes(codec, n, 4096), lib.trc_work_bytes(trc.RCB, n, 4096))
-    work = torch.zeros(wb + 4096, dtype=torch.uint8, device="cuda:0")
-    w = (work.data_ptr() + 255) & ~255
-    calls = [
-        lambda c: f(c, p, n, 100, None, 0, p + 2 * n, p + 3 * n, p + 4 * n, w, wb, None),           # chunk not a multiple of 64
-        lambda c: f(c, p, n, 1 << 20, None, 0, p + 2 * n, p + 3 * n, p + 4 * n, w, wb, None),       # chunk too large
-        lambda c: f(c, p + 1, n, 4096, None, 0, p + 2 * n, p + 3 * n, p + 4 * n, w, wb, None),      # misaligned input
-        lambda c: f(c, p, n, 4096, None, 0, p + 2 * n, p + 3 * n, p + 4 * n, w, 1024, None),       # workspace too small
-        lambda c: f(c, p, n, 4096, None, 0, p + 2 * n, p + 3 * n, p + 4 * n, w + 16, wb, None),    # misaligned workspace
-        lambda c: g(c, p + 2 * n, p + 3 * n, n, 4096, None, 0, p + 1, w, wb, None),                 # misaligned output
-        lambda c: g(c, p + 2 * n, p + 3 * n, n, 4096, None, 0, p, w, 1024, None),                   # workspace too small
-    ]
-    for i, call in enumerate(calls):
-        want = call(trc.RCB)
-        assert want < 0 and call(codec) == want, i
-    for bad in (42, 51):
-        assert f(bad, p, n, 4096, None, 0, p + 2 * n, p + 3 * n, p + 4 * n, w, wb, None) < 0
-    torch.cuda.synchronize()
-    d = L.gen("geo", 2, 50000, 1)
-    comp = trc.host_encode(trc.RCB, d)
-    assert comp.size < d.size
-    with pytest.raises(trc.TrcError):
-        trc.host_decode(codec, comp, d.size)
+    G.refused_like_rcb(torch_cuda, codec, 4096, L.gen("geo", 2, 50000, 1), unknown=(42, 51))
 
 
 def test_corrupt_payloads_stay_inside_the_output(torch_cuda):
@@ -223,20 +149,13 @@ def test_corrupt_payloads_stay_inside_the_output(torch_cuda):
         c3 = np.minimum(clen, 2).astype(np.uint32)             # shorter than the tail (3 bytes on the 32-bit coders)
         variants.append((c3, rng.integers(0, 256, int(c3.sum()), dtype=np.uint8)))
         for i, (cl, pay) in enumerate(variants):
-            _, guards = decode_into(torch, codec, n, chunk, cl, pay)
+            _, guards = G.decode_fixture(torch, codec, n, chunk, cl, pay, front=512)
             assert guards, (L.NAMES[codec], i)
 
 
 def test_reference_harness_no_mismatch(torch_cuda, tmp_path):
     """the reference's own harness linked against the library: -e6,7,8 on a 16-bit file (-Os) and a 32-bit file (-Ou)"""
-    exe = os.path.join(ROOT, "oracle", "_ref", "turborc_hip")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/turborc_hip not built")
     for es, rows in ((2, ("6:rc-16",)), (4, ("6:rc-32", "7:rcc-32", "8:rcc2-32"))):
         src = tmp_path / ("walk%d.bin" % (8 * es))
         src.write_bytes(L.gen("walk", es, 3 * 10**6 + 2 * es, 4).tobytes())
-        r = subprocess.run([exe, "-I1", "-J1", "-e6,7,8", "-Os" if es == 2 else "-Ou", str(src)],
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0 and "ERROR" not in r.stdout and "ERROR" not in r.stderr, r.stdout[-3000:] + r.stderr[-2000:]
-        for row in rows:
-            assert row in r.stdout, r.stdout[-3000:]
+        G.reference_harness(["-e6,7,8", "-Os" if es == 2 else "-Ou"], src, rows, 600)

@@ -5,6 +5,8 @@
   development container, the compiled reference (oracle/_ref/libtrc_ref.so)
 * `ref_*` wrappers that respect the reference's calling quirks: `out` is placed at a
   HIGHER address than `in` with slack below it, and a decoder is never called on a raw stream.
+* RefCalls: the same calls for a coder family's (in, n, out[, ...]) functions, which the <family>_lib modules build on
+* product_lib(): the product library through trc.lib(), the one place that declares its prototypes
 """
 import ctypes as C
 import os
@@ -459,6 +461,74 @@ def _arena(n):
     gap = 2 * n + 64
     buf = np.zeros(n + gap + n + n // 2 + 1024, dtype=np.uint8)
     return buf, 0, n + gap
+
+
+class RefCalls:
+    """The reference calls of one coder family: ref_fn maps a codec to its (encoder, decoder) names in the shared object `so`,
+    every one a (u8 *in, size_t n, u8 *out) function followed by arguments of the types in `extra`; the calls take those
+    arguments' values behind their own.  The shared object is opened at the first call.
+    guard: the encoder's arena is filled with 0xA5, and that many bytes in front of `out` and behind what the encoder returns
+    must still hold it (0: the arena stays zero, nothing is asserted).
+    chunk_hook(codec, piece, *extra) -> the payload of one chunk, where chunked_enc is not to call enc on every piece."""
+
+    def __init__(self, ref_fn, so, extra=(), guard=0, chunk_hook=None):
+        self.ref_fn, self.so, self.extra, self.guard, self.chunk_hook = ref_fn, so, list(extra), guard, chunk_hook
+        self._lib = None
+
+    def have(self):
+        return os.path.exists(self.so)
+
+    def _fn(self, name):
+        if self._lib is None:
+            lib = C.CDLL(self.so)
+            for pair in self.ref_fn.values():
+                for f in (getattr(lib, n) for n in pair):
+                    f.restype = C.c_size_t
+                    f.argtypes = [_u8p, C.c_size_t, _u8p] + self.extra
+            self._lib = lib
+        return getattr(self._lib, name)
+
+    def enc(self, codec, data, *extra):
+        """one call of the reference encoder on `data`, `in` below `out` in one arena (_arena)"""
+        name = self.ref_fn[codec][0]
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        n = data.size
+        buf, io, oo = _arena(n)
+        if self.guard:
+            buf[:] = 0xA5
+        buf[io:io + n] = data
+        base = buf.ctypes.data
+        l = self._fn(name)(C.cast(base + io, _u8p), n, C.cast(base + oo, _u8p), *extra)
+        if self.guard:
+            assert (buf[oo - self.guard:oo] == 0xA5).all() and (buf[oo + l:oo + l + self.guard] == 0xA5).all(), (name, n)
+        return buf[oo:oo + l].copy()
+
+    def chunked_enc(self, codec, data, chunk, *extra):
+        """-> (clen u32 array, payload u8 array): the reference called once per chunk"""
+        one = self.chunk_hook or self.enc
+        outs = [one(codec, data[i:i + chunk], *extra) for i in range(0, data.size, chunk)]
+        clen = np.array([o.size for o in outs], dtype=np.uint32)
+        payload = np.concatenate(outs) if outs else np.zeros(0, np.uint8)
+        return clen, payload
+
+    def dec(self, codec, comp, n, *extra):
+        """the reference decoder on one coded chunk; a raw one (comp.size == n) is the output itself"""
+        comp = np.ascontiguousarray(comp, dtype=np.uint8)
+        if comp.size == n:
+            return comp.copy()
+        src = np.zeros(comp.size + 1024, dtype=np.uint8); src[:comp.size] = comp
+        out = np.zeros(n + 64, dtype=np.uint8)
+        self._fn(self.ref_fn[codec][1])(_p8(src), n, _p8(out), *extra)
+        return out[:n].copy()
+
+
+def product_lib():
+    """trc.lib(), the product library with every prototype the tests call declared; built first where it is missing"""
+    import trc
+    if not os.path.exists(trc.LIB):
+        import __graft_entry__ as g
+        g.build()
+    return trc.lib()
 
 
 def ref_enc(codec, data, cdf=None, cdfnum=256, variant=""):

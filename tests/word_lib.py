@@ -10,7 +10,6 @@ gen(kind, es, n, seed): n bytes of little-endian es-byte words (the last word cu
   const    one random value repeated
   uniform  uniform bytes (the 32-bit coders store every chunk raw; rcs16 codes it to more than its length: raw)
 """
-import ctypes as C
 import os
 import re
 
@@ -28,7 +27,6 @@ TREES = {RCW16: 257, RCW32: 2305, RCCW32: 2432, RCC2W32: 4352}
 MODEL_BYTES = {c: t * 544 for c, t in TREES.items()}          # 17 blocks of 32 B per tree
 KINDS = ["walk", "sine", "stamps", "geo", "allmax", "const", "uniform"]
 GUARD = 64
-_INV = {}
 
 
 def budget():
@@ -71,42 +69,11 @@ def gen(kind, es, n, seed):
     return np.ascontiguousarray(np.asarray(v).astype(np.uint64).astype(dt)).view(np.uint8)[:n].copy()
 
 
-def have_ref():
-    return os.path.exists(T.REF_SO)
-
-
-def _ref_lib():
-    lib = C.CDLL(T.REF_SO)
-    for codec in REF_FN:
-        for name in REF_FN[codec]:
-            f = getattr(lib, name)
-            f.restype = C.c_size_t
-            f.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8)]
-    return lib
-
-
-def ref_enc(codec, data):
-    """one call of the reference encoder on `data`; `out` sits in a 0xA5-filled arena, and the GUARD bytes in front of it
-    and behind what it returns must be intact"""
-    lib = _INV.get("lib") or _INV.setdefault("lib", _ref_lib())
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    n = data.size
-    buf, io, oo = T._arena(n)
-    buf[:] = 0xA5
-    buf[io:io + n] = data
-    base = buf.ctypes.data
-    l = getattr(lib, REF_FN[codec][0])(C.cast(base + io, C.POINTER(C.c_uint8)), n, C.cast(base + oo, C.POINTER(C.c_uint8)))
-    assert (buf[oo - GUARD:oo] == 0xA5).all() and (buf[oo + l:oo + l + GUARD] == 0xA5).all(), (NAMES[codec], n)
-    return buf[oo:oo + l].copy()
-
-
-def ref_chunked_enc(codec, data, chunk):
-    """-> (clen u32 array, payload u8 array): the reference called once per chunk, as it returns it (rcs16 and sub-word
-    chunks may return more bytes than the chunk: see expected())"""
-    outs = [ref_enc(codec, data[i:i + chunk]) for i in range(0, data.size, chunk)]
-    clen = np.array([o.size for o in outs], dtype=np.uint32)
-    payload = np.concatenate(outs) if outs else np.zeros(0, np.uint8)
-    return clen, payload
+# `out` sits in a 0xA5-filled arena, and the GUARD bytes in front of it and behind what the encoder returns must be intact;
+# ref_chunked_enc gives the chunks as the reference returns them (rcs16 and sub-word chunks may return more bytes than the
+# chunk: see expected())
+_REF = T.RefCalls(REF_FN, T.REF_SO, guard=GUARD)
+have_ref, ref_enc, ref_chunked_enc = _REF.have, _REF.enc, _REF.chunked_enc
 
 
 def expected(codec, data, chunk, clen, payload):

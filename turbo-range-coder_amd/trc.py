@@ -149,7 +149,13 @@ def lib():
         l.trc_decode_fplanes_range_host.restype = _sz; l.trc_decode_fplanes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
         l.trc_fplanes_check.restype = C.c_int; l.trc_fplanes_check.argtypes = [_vp, _sz, _sz]
         l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
+        l.trc_decode_host.restype = _sz; l.trc_decode_host.argtypes = [C.c_int, _vp, _sz, _vp, _sz, _vp, C.c_uint]
         l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
+        l.trc_container_check.restype = C.c_int; l.trc_container_check.argtypes = [_vp, _sz, C.c_int, _sz]
+        l.trc_host_plan.restype = C.c_int
+        l.trc_host_plan.argtypes = [C.c_int, _sz, C.c_uint32, C.c_int, C.c_int, C.POINTER(_sz), C.c_int, C.POINTER(C.c_uint32)]
+        l.trc_host_pin.restype = C.c_int; l.trc_host_pin.argtypes = [_vp, _sz]
+        l.trc_host_unpin.restype = C.c_int; l.trc_host_unpin.argtypes = [_vp]
         l.trc_timing_enable.restype = C.c_int; l.trc_timing_enable.argtypes = [C.c_int]
         l.trc_timing_pause.restype = C.c_int; l.trc_timing_pause.argtypes = [C.c_int]
         l.trc_timing_read.restype = C.c_int
@@ -347,6 +353,7 @@ class PlanesCoder:
     """Pre-allocated HBM buffers for the planar calls on up to n bytes of esize-byte elements: plane k's directory at
     self.clen[k * nch:], its payload at self.payload[k * pitch:], its size in self.total[k], its CDF (static coders, built by
     encode) at self.cdf[k * PLANES_CDF_STRIDE:], the tail bytes in self.tail."""
+    _ENC, _DEC, _DEC_RANGE = "trc_encode_planes_dev", "trc_decode_planes_dev", "trc_decode_planes_range_dev"
 
     def __init__(self, codec, n, esize, chunk=4096, device="cuda", cdfnum=256, prm=(5, 6), guard=0):
         """guard: that many bytes of 0xA5 behind every buffer and its TRC_PAD slack; guards_ok() tells whether they survived"""
@@ -371,6 +378,10 @@ class PlanesCoder:
         self.status = self._buf(4 * esize)
         self.range_work, self.range_work_bytes = None, 0
 
+    def _lead(self):
+        """what the calls take between the codec and the first pointer"""
+        return ()
+
     def _buf(self, nbytes):
         """nbytes + PAD zero bytes on the device (uint8), followed by the guard"""
         t = self.torch.zeros(nbytes + PAD + self.guard, dtype=self.torch.uint8, device=self.dev)
@@ -389,16 +400,16 @@ class PlanesCoder:
     def encode(self, d_in, n=None, flags=0):
         n = self.n if n is None else n
         st = self.codec in STATIC
-        _chk(lib().trc_encode_planes_dev(self.codec | flags, d_in.data_ptr(), n, self.esize, self.chunk,
-                                         self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
-                                         self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.tail.data_ptr(),
-                                         self.work.data_ptr(), self.work_bytes, self._stream()))
+        _chk(getattr(lib(), self._ENC)(self.codec | flags, *self._lead(), d_in.data_ptr(), n, self.esize, self.chunk,
+                                       self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                                       self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.tail.data_ptr(),
+                                       self.work.data_ptr(), self.work_bytes, self._stream()))
 
     def decode(self, d_out, n=None, flags=0):
         n = self.n if n is None else n
-        _chk(lib().trc_decode_planes_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), self.tail.data_ptr(),
-                                         n, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
-                                         d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
+        _chk(getattr(lib(), self._DEC)(self.codec | flags, *self._lead(), self.clen.data_ptr(), self.payload.data_ptr(), self.tail.data_ptr(),
+                                       n, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                       d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
 
     def decode_range(self, d_out, first, count, n=None, flags=0):
         """elements [first * chunk, min(m, (first + count) * chunk)) to d_out[0:], in a workspace of its own that grows with count"""
@@ -408,9 +419,9 @@ class PlanesCoder:
             self.range_work, self.range_work_bytes = self._buf(need), need
         if self.range_work is None:                            # nothing to size a workspace by: the call rejects these arguments itself
             self.range_work = self._buf(0)
-        _chk(lib().trc_decode_planes_range_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), n, self.esize, self.chunk,
-                                               first, count, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
-                                               d_out.data_ptr(), self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+        _chk(getattr(lib(), self._DEC_RANGE)(self.codec | flags, *self._lead(), self.clen.data_ptr(), self.payload.data_ptr(), n, self.esize,
+                                             self.chunk, first, count, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                             d_out.data_ptr(), self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
 
     def cdf_of(self, k):
         """Synchronise and fetch plane k's CDF (uint16[cdfnum + 1]) and cdfini status, as encode left them (static coders)"""
@@ -469,21 +480,24 @@ def _host_fn(name, codec):
     return f
 
 
+def _host_args(codec, cdf, cdfnum, prm):
+    """what a reference-named call takes behind (in, n, out): the values for the prototype _host_fn sets"""
+    if codec == ANS4S:
+        return (cdf.ctypes.data_as(_u16p),)
+    if codec in (RCS1, RCS2, RCSM):
+        return (cdf.ctypes.data_as(_u16p), cdfnum)
+    if codec in SSBIT:
+        return (prm[0], prm[1])
+    return ()
+
+
 def host_encode(codec, data, cdf=None, cdfnum=256, name=None, prm=(5, 6)):
     """Call the reference-named encoder with host pointers -> np.uint8 array of the returned length."""
     data = np.ascontiguousarray(data, dtype=np.uint8)
     n = data.size
     out = np.zeros(n + n // 3 + 1024, dtype=np.uint8)          # the harness's OSIZE (turborc.c:418)
     f = _host_fn(name or _HOST_ENC[codec], codec)
-    pin, pout = data.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p)
-    if codec == ANS4S:
-        l = f(pin, n, pout, cdf.ctypes.data_as(_u16p))
-    elif codec in (RCS1, RCS2, RCSM):
-        l = f(pin, n, pout, cdf.ctypes.data_as(_u16p), cdfnum)
-    elif codec in SSBIT:
-        l = f(pin, n, pout, prm[0], prm[1])
-    else:
-        l = f(pin, n, pout)
+    l = f(data.ctypes.data_as(_u8p), n, out.ctypes.data_as(_u8p), *_host_args(codec, cdf, cdfnum, prm))
     if l == 0 and n != 0:
         raise TrcError(lib().trc_last_error().decode())
     return out[:l].copy()
@@ -496,15 +510,7 @@ def host_decode(codec, comp, n, cdf=None, cdfnum=256, name=None, prm=(5, 6)):
     src = np.zeros(comp.size + 1024, dtype=np.uint8); src[:comp.size] = comp
     out = np.full(n + 64, 0xA5, dtype=np.uint8)
     f = _host_fn(name or _HOST_DEC[codec], codec)
-    pin, pout = src.ctypes.data_as(_u8p), out.ctypes.data_as(_u8p)
-    if codec == ANS4S:
-        l = f(pin, n, pout, cdf.ctypes.data_as(_u16p))
-    elif codec in (RCS1, RCS2, RCSM):
-        l = f(pin, n, pout, cdf.ctypes.data_as(_u16p), cdfnum)
-    elif codec in SSBIT:
-        l = f(pin, n, pout, prm[0], prm[1])
-    else:
-        l = f(pin, n, pout)
+    l = f(src.ctypes.data_as(_u8p), n, out.ctypes.data_as(_u8p), *_host_args(codec, cdf, cdfnum, prm))
     if l != n:
         raise TrcError(lib().trc_last_error().decode())
     return out[:n].copy()
@@ -574,22 +580,27 @@ def host_encode_planes(codec, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
     return out[:l].copy()
 
 
-def host_decode_planes(comp, n):
+def _host_decode_guarded(name, comp, length, offset=None):
+    """the host call `name` for `length` bytes (of the whole container, or from `offset` where given) into an output with 64 bytes
+    of 0xA5 behind it, which must survive"""
     comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    out = np.full(n + 64, 0xA5, dtype=np.uint8)
-    l = lib().trc_decode_planes_host(comp.ctypes.data, comp.size, out.ctypes.data, n)
-    if l != n or not (out[n:] == 0xA5).all():
-        raise TrcError(lib().trc_last_error().decode() if l != n else "trc_decode_planes_host wrote past its output")
-    return out[:n].copy()
+    out = np.full(length + 64, 0xA5, dtype=np.uint8)
+    f = getattr(lib(), name)
+    if offset is None:
+        l = f(comp.ctypes.data, comp.size, out.ctypes.data, length)
+    else:
+        l = f(comp.ctypes.data, comp.size, offset, length, out.ctypes.data)
+    if l != length or not (out[length:] == 0xA5).all():
+        raise TrcError(lib().trc_last_error().decode() if l != length else name + " wrote past its output")
+    return out[:length].copy()
+
+
+def host_decode_planes(comp, n):
+    return _host_decode_guarded("trc_decode_planes_host", comp, n)
 
 
 def host_decode_planes_range(comp, offset, length):
-    comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    out = np.full(length + 64, 0xA5, dtype=np.uint8)
-    l = lib().trc_decode_planes_range_host(comp.ctypes.data, comp.size, offset, length, out.ctypes.data)
-    if l != length or not (out[length:] == 0xA5).all():
-        raise TrcError(lib().trc_last_error().decode() if l != length else "trc_decode_planes_range_host wrote past its output")
-    return out[:length].copy()
+    return _host_decode_guarded("trc_decode_planes_range_host", comp, length, offset)
 
 
 def planes_check(buf, outlen=None):
@@ -637,35 +648,14 @@ def planes_join_filter(filt, d_planes, pitch, d_tail, n, esize, seg, d_out):
 class FilteredPlanesCoder(PlanesCoder):
     """PlanesCoder through the trc_*_fplanes_dev calls: the same buffers and results, of the filtered elements (restart = chunk).
     filter=FILTER_NONE is the unfiltered coder."""
+    _ENC, _DEC, _DEC_RANGE = "trc_encode_fplanes_dev", "trc_decode_fplanes_dev", "trc_decode_fplanes_range_dev"
 
     def __init__(self, codec, n, esize, chunk=4096, device="cuda", cdfnum=256, prm=(5, 6), guard=0, filter=FILTER_NONE):
         super().__init__(codec, n, esize, chunk, device, cdfnum=cdfnum, prm=prm, guard=guard)
         self.filter = filter
 
-    def encode(self, d_in, n=None, flags=0):
-        n = self.n if n is None else n
-        st = self.codec in STATIC
-        _chk(lib().trc_encode_fplanes_dev(self.codec | flags, self.filter, d_in.data_ptr(), n, self.esize, self.chunk,
-                                          self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
-                                          self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.tail.data_ptr(),
-                                          self.work.data_ptr(), self.work_bytes, self._stream()))
-
-    def decode(self, d_out, n=None, flags=0):
-        n = self.n if n is None else n
-        _chk(lib().trc_decode_fplanes_dev(self.codec | flags, self.filter, self.clen.data_ptr(), self.payload.data_ptr(), self.tail.data_ptr(),
-                                          n, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
-                                          d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
-
-    def decode_range(self, d_out, first, count, n=None, flags=0):
-        n = self.n if n is None else n
-        need = lib().trc_planes_range_work_bytes(self.codec, n, self.esize, self.chunk, count)
-        if need > self.range_work_bytes:
-            self.range_work, self.range_work_bytes = self._buf(need), need
-        if self.range_work is None:
-            self.range_work = self._buf(0)
-        _chk(lib().trc_decode_fplanes_range_dev(self.codec | flags, self.filter, self.clen.data_ptr(), self.payload.data_ptr(), n, self.esize,
-                                                self.chunk, first, count, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
-                                                d_out.data_ptr(), self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+    def _lead(self):
+        return (self.filter,)
 
 
 def fplanes_bound(n, esize, chunk=0, cdfnum=0):
@@ -684,21 +674,11 @@ def host_encode_fplanes(codec, filt, data, esize, chunk=0, cdfnum=256, prm=(5, 6
 
 
 def host_decode_fplanes(comp, n):
-    comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    out = np.full(n + 64, 0xA5, dtype=np.uint8)
-    l = lib().trc_decode_fplanes_host(comp.ctypes.data, comp.size, out.ctypes.data, n)
-    if l != n or not (out[n:] == 0xA5).all():
-        raise TrcError(lib().trc_last_error().decode() if l != n else "trc_decode_fplanes_host wrote past its output")
-    return out[:n].copy()
+    return _host_decode_guarded("trc_decode_fplanes_host", comp, n)
 
 
 def host_decode_fplanes_range(comp, offset, length):
-    comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    out = np.full(length + 64, 0xA5, dtype=np.uint8)
-    l = lib().trc_decode_fplanes_range_host(comp.ctypes.data, comp.size, offset, length, out.ctypes.data)
-    if l != length or not (out[length:] == 0xA5).all():
-        raise TrcError(lib().trc_last_error().decode() if l != length else "trc_decode_fplanes_range_host wrote past its output")
-    return out[:length].copy()
+    return _host_decode_guarded("trc_decode_fplanes_range_host", comp, length, offset)
 
 
 def fplanes_check(buf, outlen=None):
