@@ -13,7 +13,10 @@
  *                                 previous element, restarted at every chunk -- for integer columns and smooth series (sorted ids,
  *                                 timestamps, sampled signals).  The file is the library's filtered planes container: 16 bytes
  *                                 "TRCF" | u8 filter | u8 1 | u16 0 | u64 size, then the TRCP container of the filtered data
- *   trcfile d <in> <out>          decompress (files of c, p and f)
+ *   trcfile a <id> <esize> <in> <out>   as p or f, whichever the library's planes advisor chooses from the order-0 histograms of the
+ *                                 planes under no filter, z and x (trc_encode_aplanes_host): the file is what p or f would have
+ *                                 written; prints the three estimates and the choice (n, z or x)
+ *   trcfile d <in> <out>          decompress (files of c, p, f and a)
  *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p or f: only the
  *                                 chunks that cover them are sent to the GPU and decoded (trc_decode_range_host)
  *
@@ -222,26 +225,40 @@ int main(int argc, char **argv)
         printf("%zu -> %zu bytes (%.2f%%)  %u planes, filter %s\n", n, l, 100.0 * l / n, esize, argv[4]);
         return 0;
     }
+    if (argc == 6 && !strcmp(argv[1], "a")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        size_t n;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        unsigned char *in = slurp(argv[4], &n);
+        if (!in) return 2;
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_fplanes_bound(n, esize, 0, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u with %zu bytes: esize is 2, 4 or 8 and the file holds at least one element\n", esize, n); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        trc_planes_advice adv;
+        const size_t l = trc_encode_aplanes_host(codec, in, n, esize, 0, out, cap, cdfnum, &adv);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[5], out, l)) return 2;
+        printf("%zu -> %zu bytes (%.2f%%)  %u planes, order-0 estimate n %.0f z %.0f x %.0f bytes, choice %c\n", n, l, 100.0 * l / n, esize,
+               adv.total_bits[0] / 8, adv.total_bits[1] / 8, adv.total_bits[2] / 8, "nzx"[adv.filter]);
+        return 0;
+    }
     if (argc == 4 && !strcmp(argv[1], "d")) {
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
-        if (is_fplanes(fb, fl)) {                                         /* a file of `trcfile f`: checked like one of p */
+        /* a file of `trcfile p`, f or a: untrusted, so checked against what was read; the library looks at the magic itself
+         * (trc_decode_xplanes_host = trc_decode_planes_host or trc_decode_fplanes_host) */
+        if (is_fplanes(fb, fl) || is_planes(fb, fl)) {
+            const size_t lead = is_planes(fb, fl) ? 0 : sizeof(trc_fplanes_hdr);
             trc_planes_hdr ph;
-            if (trc_fplanes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
-            memcpy(&ph, fb + sizeof(trc_fplanes_hdr), sizeof ph);
+            if (lead ? trc_fplanes_check(fb, fl, (size_t)-1) : trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            memcpy(&ph, fb + lead, sizeof ph);
             unsigned char *out = malloc((size_t)ph.n + 1024);
             if (!out) { perror("malloc"); return 2; }
-            if (trc_decode_fplanes_host(fb, fl, out, (size_t)ph.n) != ph.n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
-            return write_file(argv[3], out, (size_t)ph.n);
-        }
-        if (is_planes(fb, fl)) {                                          /* a file of `trcfile p`: untrusted, so checked against what was read */
-            trc_planes_hdr ph;
-            if (trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
-            memcpy(&ph, fb, sizeof ph);
-            unsigned char *out = malloc((size_t)ph.n + 1024);
-            if (!out) { perror("malloc"); return 2; }
-            if (trc_decode_planes_host(fb, fl, out, (size_t)ph.n) != ph.n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            if (trc_decode_xplanes_host(fb, fl, out, (size_t)ph.n) != ph.n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
             return write_file(argv[3], out, (size_t)ph.n);
         }
         if (fl < 24 || memcmp(fb, "TRCF", 4)) { fprintf(stderr, "not a TRCF file\n"); return 2; }
@@ -434,6 +451,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
     return 2;
 }

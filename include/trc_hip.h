@@ -474,6 +474,50 @@ size_t trc_decode_fplanes_host(const void *in, size_t inlen, void *out, size_t o
 size_t trc_decode_fplanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
 int    trc_fplanes_check(const void *buf, size_t buflen, size_t outlen);
 
+/* ---- the planes advisor: which filter for this buffer? -------------------------------------------------------------------
+ * A filter is an option, never a default, so somebody has to choose; what decides the choice is the order-0 byte histogram of
+ * every plane under every filter, and all of them come from ONE read of the input at about the cost of a split, writing nothing
+ * but counters.
+ *
+ * trc_planes_hist_dev(filters, d_in, n, esize, seg, d_hist, stream): filters is a bit set, bit f requests filter id f (1 = none,
+ * 2 = zigzag delta, 4 = xor; 1 .. 7, anything else is TRC_E_ARG).  d_hist[(f * esize + k) * 256 + b] = the number of the m =
+ * n / esize elements whose byte k under filter f (restarted every seg elements) equals b.  The call zeroes all
+ * trc_planes_hist_bytes(esize) = 3 * esize * 256 * 8 bytes first, on the stream: rows of filters not requested stay zero, nothing
+ * behind them is written.  The tail bytes are in no plane and are not counted.  Arguments as for trc_planes_split_filter_dev
+ * (esize 2, 4 or 8; n >= esize; seg by the chunk rule; d_in 16-byte aligned), d_hist 8-byte aligned.  Only enqueues work.
+ * TRC_PLANES_GRID caps its grid as it does the split's; TRC_PLANES_HIST_ROUND_VECS (test aid) = vectors per thread between two
+ * flushes of a workgroup's 32-bit counters.
+ *
+ * trc_planes_advise (host only, no GPU needed) turns such histograms into estimates and a choice:
+ *     bits[f][k] = sum over b of c * log2(m / c), c = hist[(f * esize + k) * 256 + b]      (0 for rows not requested)
+ *     total_bits[f] = sum over the planes
+ *     filter = the requested filter with the smallest total, ties to the lower id -- but TRC_FILTER_NONE where it was requested
+ *              and the winner saves less than 1/64 of TRC_FILTER_NONE's total.
+ * The 1/64 is policy, not a measurement: on uniform data the three totals differ by noise only (0.01 - 0.03 % on 65 539 random
+ * elements) and an argmin would pick a filter by coin toss; a filter has to earn its place.  Every requested row must sum to m:
+ * a row that does not, esize outside {2, 4, 8}, filters outside 1 .. 7, m == 0 or a NULL pointer is TRC_E_ARG.
+ *
+ * trc_encode_aplanes_host: upload once, trc_planes_hist_dev(7, ..., seg = the resolved chunk), trc_planes_advise, then the coded
+ * call on the bytes already on the device.  The output is byte for byte what the explicit call writes at the same resolved chunk:
+ * trc_encode_planes_host (a TRCP container) where the choice is TRC_FILTER_NONE, trc_encode_fplanes_host(..., choice, ...) (a TRCF
+ * container) otherwise; out must hold trc_fplanes_bound bytes; *advice (may be NULL) receives what decided.
+ * trc_decode_xplanes_host reads either container: it looks at the magic and calls trc_decode_planes_host or
+ * trc_decode_fplanes_host; any other magic returns 0 with the reason in trc_last_error(). */
+typedef struct trc_planes_advice {
+    int      filter;             /* the choice: TRC_FILTER_NONE, TRC_FILTER_ZDELTA or TRC_FILTER_XOR */
+    unsigned esize, filters;     /* as given */
+    uint64_t m;
+    double   bits[3][8];         /* order-0 estimate of plane k under filter f, in bits */
+    double   total_bits[3];      /* sum over the planes */
+} trc_planes_advice;
+size_t trc_planes_hist_bytes(unsigned esize);
+int    trc_planes_hist_dev(unsigned filters, const void *d_in, size_t n, unsigned esize, uint32_t seg,
+                           uint64_t *d_hist, void *stream);
+int    trc_planes_advise(const uint64_t *hist, unsigned filters, unsigned esize, size_t m, trc_planes_advice *a);
+size_t trc_encode_aplanes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                               void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice);
+size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *out, size_t outlen);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

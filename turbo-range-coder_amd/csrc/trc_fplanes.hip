@@ -20,40 +20,6 @@
 
 #define TRC_FPLANES_TILE (64 * TRC_PLANES_VEC)      // elements a wave handles per step of the join
 
-template <int ESIZE> struct Elem { typedef u32 T; typedef u32 M; };          // T: the register type of an element, M: its type in memory
-template <> struct Elem<2> { typedef u32 T; typedef uint16_t M; };           // (16-bit elements are computed in 32 bits and truncated when packed)
-template <> struct Elem<8> { typedef uint64_t T; typedef uint64_t M; };
-
-// the 8 elements of a vector from / to its 2 * ESIZE words
-template <int ESIZE> __device__ __forceinline__ void unpack(const u32 *w, typename Elem<ESIZE>::T *e)
-{
-#pragma unroll
-    for (int j = 0; j < TRC_PLANES_VEC; j++) {
-        if constexpr (ESIZE == 2) e[j] = j & 1 ? w[j / 2] >> 16 : w[j / 2] & 0xffffu;
-        else if constexpr (ESIZE == 4) e[j] = w[j];
-        else e[j] = (uint64_t)w[2 * j] | (uint64_t)w[2 * j + 1] << 32;
-    }
-}
-template <int ESIZE> __device__ __forceinline__ void pack(const typename Elem<ESIZE>::T *e, u32 *w)
-{
-#pragma unroll
-    for (int j = 0; j < TRC_PLANES_VEC; j++) {
-        if constexpr (ESIZE == 2) { if (j & 1) w[j / 2] = (e[j - 1] & 0xffffu) | e[j] << 16; }
-        else if constexpr (ESIZE == 4) w[j] = e[j];
-        else { w[2 * j] = (u32)e[j]; w[2 * j + 1] = (u32)(e[j] >> 32); }
-    }
-}
-
-// y of x and its predecessor: clean in the element's width
-template <int ESIZE, int FILTER> __device__ __forceinline__ typename Elem<ESIZE>::T fwd(typename Elem<ESIZE>::T x, typename Elem<ESIZE>::T p)
-{
-    typedef typename Elem<ESIZE>::T T;
-    constexpr int W = 8 * ESIZE;
-    constexpr T MASK = (T)~(T)0 >> (8 * sizeof(T) - W);
-    if constexpr (FILTER == TRC_FILTER_XOR) return x ^ p;
-    const T d = (x - p) & MASK;
-    return ((d << 1) ^ ((T)0 - (d >> (W - 1)))) & MASK;
-}
 // the scan's operand of y (bits above a 16-bit element's width are junk from here on; pack drops them) and the scan's operation
 template <int ESIZE, int FILTER> __device__ __forceinline__ typename Elem<ESIZE>::T operand(typename Elem<ESIZE>::T y)
 {

@@ -4,6 +4,7 @@
 //
 // Nothing here knows a coder: plane k's (clen, payload, total) is what trc_encode_dev returns for the m bytes of plane k, so every
 // contract of the per-plane calls (chunk parity, raw fallback, random access) holds for each plane as it stands.
+#include <math.h>
 
 // ---- workspace -------------------------------------------------------------------------------------------------------------------
 // esize slices, `slice` bytes apart (a multiple of 256, so the slices are the planes of the split / join kernels with pitch = slice):
@@ -254,9 +255,47 @@ static int planes_ctx(HostCtx *&cp, std::unique_lock<std::mutex> &lk)
     return ctx_init(*cp, dev);
 }
 
-// the TRCP container of F(filter, chunk, esize, in) -- of `in` itself with TRC_FILTER_NONE
+// ---- the advisor's host half: estimates and a choice from the histograms of trc_planes_hist_dev (no device involved) ----------------
+extern "C" int trc_planes_advise(const uint64_t *hist, unsigned filters, unsigned esize, size_t m, trc_planes_advice *a)
+{
+    if (!hist || !a) return fail(TRC_E_ARG, "planes_advise: null histogram or advice");
+    if (filters < 1 || filters > 7) return fail(TRC_E_ARG, "planes_advise: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", filters);
+    if (!planes_esize_ok(esize)) return fail(TRC_E_ARG, "planes_advise: esize %u (2, 4 or 8)", esize);
+    if (!m) return fail(TRC_E_ARG, "planes_advise: no element");
+    memset(a, 0, sizeof *a);
+    a->esize = esize; a->filters = filters; a->m = m;
+    int best = -1;
+    for (unsigned f = 0; f < 3; f++) {
+        if (!(filters >> f & 1)) continue;
+        for (unsigned k = 0; k < esize; k++) {
+            const uint64_t *row = hist + ((size_t)f * esize + k) * 256;
+            uint64_t sum = 0;
+            double bits = 0;
+            for (unsigned b = 0; b < 256; b++) {
+                const uint64_t c = row[b];
+                if (c > m - sum) return fail(TRC_E_ARG, "planes_advise: filter %u plane %u counts more than the %zu elements", f, k, m);
+                sum += c;
+                if (c) bits += (double)c * log2((double)m / (double)c);
+            }
+            if (sum != m) return fail(TRC_E_ARG, "planes_advise: filter %u plane %u counts %llu elements of %zu", f, k, (unsigned long long)sum, m);
+            a->bits[f][k] = bits;
+            a->total_bits[f] += bits;
+        }
+        if (best < 0 || a->total_bits[f] < a->total_bits[best]) best = (int)f;       // (ties: the lower id)
+    }
+    // a filter is never a default: it has to save 1/64 of the unfiltered total to be chosen over no filter
+    if ((filters & 1) && best != TRC_FILTER_NONE && a->total_bits[TRC_FILTER_NONE] - a->total_bits[best] < a->total_bits[TRC_FILTER_NONE] / 64)
+        best = TRC_FILTER_NONE;
+    a->filter = best;
+    return TRC_OK;
+}
+
+// the TRCP container of F(filter, chunk, esize, in) -- of `in` itself with TRC_FILTER_NONE.  filter = PLANES_FILTER_AUTO: the advisor
+// chooses from the bytes on the device (*advice, where given, says how), and `out` receives what the explicit host call writes for
+// that choice: the TRCP container, behind the 16-byte TRCF prefix where the choice is a filter.
+#define PLANES_FILTER_AUTO (-1)
 static size_t planes_host_encode(int codec, int filter, const void *in, size_t n, unsigned esize, uint32_t chunk,
-                                 void *out, size_t outcap, unsigned cdfnum)
+                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice = nullptr)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
     if (!in || !out || !planes_esize_ok(esize) || n < esize) { fail(TRC_E_ARG, "encode_planes_host: bad arguments (esize %u, %zu bytes)", esize, n); return 0; }
@@ -273,8 +312,9 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
     if (planes_ctx(cp, lk)) return 0;
     HostCtx &c = *cp;
     const size_t dirsz = up256(4 * P.nc + 256);
+    const size_t histb = filter == PLANES_FILTER_AUTO ? trc_planes_hist_bytes(esize) : 0;        // (in the workspace, ahead of the encode)
     if (grow(&c.d_in, &c.cap_in, n) || grow(&c.d_cont, &c.cap_cont, esize * (dirsz + P.buf)) ||
-        grow(&c.d_work[0], &c.cap_work[0], esize * P.slice)) return 0;
+        grow(&c.d_work[0], &c.cap_work[0], esize * P.slice > histb ? esize * P.slice : histb)) return 0;
     hipStream_t s = c.s_k[0];
     uint32_t *d_clen = (uint32_t *)c.d_cont;
     uint8_t *d_payload = c.d_cont + up256(esize * 4 * P.nc + 256);
@@ -283,6 +323,22 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
     int32_t *d_status = (int32_t *)(c.d_small + PLANES_SMALL_STATUS);
     uint8_t *d_tail = c.d_small + PLANES_SMALL_TAIL;
     PCHK(hipMemcpyAsync(c.d_in, in, n, hipMemcpyHostToDevice, s));
+    size_t lead = 0;                                                     // bytes of TRCF prefix in front of the container
+    if (filter == PLANES_FILTER_AUTO) {
+        std::vector<uint64_t> hist(histb / sizeof(uint64_t));
+        trc_planes_advice adv;
+        if (trc_planes_hist_dev(7, c.d_in, n, esize, chunk, (uint64_t *)c.d_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
+        PCHK(hipMemcpyAsync(hist.data(), c.d_work[0], histb, hipMemcpyDeviceToHost, s));
+        PCHK(hipStreamSynchronize(s));
+        if (trc_planes_advise(hist.data(), 7, esize, m, &adv)) return 0;
+        if (advice) *advice = adv;
+        filter = adv.filter;
+        if (filter != TRC_FILTER_NONE) {
+            lead = sizeof(trc_fplanes_hdr);
+            if (outcap <= lead) { fail(TRC_E_ARG, "encode_aplanes_host: out holds %zu bytes (trc_fplanes_bound)", outcap); return 0; }
+            out = (uint8_t *)out + lead; outcap -= lead;
+        }
+    }
     if (trc_encode_fplanes_dev(codec, filter, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                               d_clen, d_payload, d_total, d_tail, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
     uint64_t total[8];
@@ -330,7 +386,13 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
     }
     if (t) PCHK(hipMemcpyAsync(o + pos, d_tail, t, hipMemcpyDeviceToHost, s));
     PCHK(hipStreamSynchronize(s));
-    return size;
+    if (lead) {
+        trc_fplanes_hdr fh;
+        memset(&fh, 0, sizeof fh);
+        fh.magic = TRC_FPLANES_MAGIC; fh.filter = (uint8_t)filter; fh.version = 1; fh.size = lead + size;
+        memcpy(o - lead, &fh, sizeof fh);
+    }
+    return lead + size;
 }
 extern "C" size_t trc_encode_planes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
                                          void *out, size_t outcap, unsigned cdfnum)
@@ -497,4 +559,22 @@ extern "C" size_t trc_decode_fplanes_range_host(const void *in, size_t inlen, si
     if (!in || !out) { fail(TRC_E_ARG, "decode_fplanes_range_host: bad arguments"); return 0; }
     if (fplanes_prefix(in, inlen, h)) return 0;
     return planes_host_decode_bytes(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out);
+}
+
+// ---- either container, and the encoder that chooses between them ------------------------------------------------------------------
+extern "C" size_t trc_encode_aplanes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                                          void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice)
+{
+    return planes_host_encode(codec, PLANES_FILTER_AUTO, in, n, esize, chunk, out, outcap, cdfnum, advice);
+}
+
+extern "C" size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *out, size_t outlen)
+{
+    uint32_t magic = 0;
+    if (!in || !out) { fail(TRC_E_ARG, "decode_xplanes_host: bad arguments"); return 0; }
+    if (inlen >= sizeof magic) memcpy(&magic, in, sizeof magic);
+    if (magic == TRC_PLANES_MAGIC) return trc_decode_planes_host(in, inlen, out, outlen);
+    if (magic == TRC_FPLANES_MAGIC) return trc_decode_fplanes_host(in, inlen, out, outlen);
+    fail(TRC_E_ARG, "decode_xplanes_host: neither a planes (TRCP) nor a filtered planes (TRCF) container");
+    return 0;
 }

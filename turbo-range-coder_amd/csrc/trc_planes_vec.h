@@ -1,5 +1,6 @@
 // trc_planes_vec.h -- what the plane kernels share (trc_planes.hip: split / join; trc_fplanes.hip: the same with a zigzag-delta
-// or xor filter): the byte separation of one thread's vector of 8 elements in registers, the launch shape and the argument rules.
+// or xor filter; trc_planes_hist.hip: the histograms of the filtered planes): the byte separation of one thread's vector of 8
+// elements in registers, the filters' forward step, the launch shape and the argument rules.
 #ifndef TRC_PLANES_VEC_H
 #define TRC_PLANES_VEC_H
 #include <hip/hip_runtime.h>
@@ -58,6 +59,42 @@ template <int ESIZE> __device__ __forceinline__ void vec_join(const uint2 *p, u3
         tr4(p[0].y, p[1].y, p[2].y, p[3].y, w[8], w[10], w[12], w[14]);
         tr4(p[4].y, p[5].y, p[6].y, p[7].y, w[9], w[11], w[13], w[15]);
     }
+}
+
+// ---- what the filter kernels share (trc_fplanes.hip: split / join; trc_planes_hist.hip: the advisor's histograms)
+template <int ESIZE> struct Elem { typedef u32 T; typedef u32 M; };          // T: the register type of an element, M: its type in memory
+template <> struct Elem<2> { typedef u32 T; typedef uint16_t M; };           // (16-bit elements are computed in 32 bits and truncated when packed)
+template <> struct Elem<8> { typedef uint64_t T; typedef uint64_t M; };
+
+// the 8 elements of a vector from / to its 2 * ESIZE words
+template <int ESIZE> __device__ __forceinline__ void unpack(const u32 *w, typename Elem<ESIZE>::T *e)
+{
+#pragma unroll
+    for (int j = 0; j < TRC_PLANES_VEC; j++) {
+        if constexpr (ESIZE == 2) e[j] = j & 1 ? w[j / 2] >> 16 : w[j / 2] & 0xffffu;
+        else if constexpr (ESIZE == 4) e[j] = w[j];
+        else e[j] = (uint64_t)w[2 * j] | (uint64_t)w[2 * j + 1] << 32;
+    }
+}
+template <int ESIZE> __device__ __forceinline__ void pack(const typename Elem<ESIZE>::T *e, u32 *w)
+{
+#pragma unroll
+    for (int j = 0; j < TRC_PLANES_VEC; j++) {
+        if constexpr (ESIZE == 2) { if (j & 1) w[j / 2] = (e[j - 1] & 0xffffu) | e[j] << 16; }
+        else if constexpr (ESIZE == 4) w[j] = e[j];
+        else { w[2 * j] = (u32)e[j]; w[2 * j + 1] = (u32)(e[j] >> 32); }
+    }
+}
+
+// y of x and its predecessor: clean in the element's width
+template <int ESIZE, int FILTER> __device__ __forceinline__ typename Elem<ESIZE>::T fwd(typename Elem<ESIZE>::T x, typename Elem<ESIZE>::T p)
+{
+    typedef typename Elem<ESIZE>::T T;
+    constexpr int W = 8 * ESIZE;
+    constexpr T MASK = (T)~(T)0 >> (8 * sizeof(T) - W);
+    if constexpr (FILTER == TRC_FILTER_XOR) return x ^ p;
+    const T d = (x - p) & MASK;
+    return ((d << 1) ^ ((T)0 - (d >> (W - 1)))) & MASK;
 }
 
 // workgroups of a launch over m elements; TRC_PLANES_GRID in the environment lowers the cap (tuning aid, and how the tests make

@@ -69,6 +69,12 @@ class Range(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("first_chunk", "nchunks", "payload_off", "payload_len", "out_skip", "out_bytes")]
 
 
+class PlanesAdvice(C.Structure):
+    """struct trc_planes_advice (include/trc_hip.h)"""
+    _fields_ = [("filter", C.c_int), ("esize", C.c_uint), ("filters", C.c_uint), ("m", C.c_uint64),
+                ("bits", C.c_double * 8 * 3), ("total_bits", C.c_double * 3)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into turbo-range-coder_amd/libturborc_hip.so."""
     if force:
@@ -148,6 +154,12 @@ def lib():
         l.trc_decode_fplanes_host.restype = _sz; l.trc_decode_fplanes_host.argtypes = [_vp, _sz, _vp, _sz]
         l.trc_decode_fplanes_range_host.restype = _sz; l.trc_decode_fplanes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
         l.trc_fplanes_check.restype = C.c_int; l.trc_fplanes_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_hist_bytes.restype = _sz; l.trc_planes_hist_bytes.argtypes = [C.c_uint]
+        l.trc_planes_hist_dev.restype = C.c_int; l.trc_planes_hist_dev.argtypes = [C.c_uint, _vp, _sz, C.c_uint, C.c_uint32, _vp, _vp]
+        l.trc_planes_advise.restype = C.c_int; l.trc_planes_advise.argtypes = [_vp, C.c_uint, C.c_uint, _sz, C.POINTER(PlanesAdvice)]
+        l.trc_encode_aplanes_host.restype = _sz
+        l.trc_encode_aplanes_host.argtypes = [C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint, C.POINTER(PlanesAdvice)]
+        l.trc_decode_xplanes_host.restype = _sz; l.trc_decode_xplanes_host.argtypes = [_vp, _sz, _vp, _sz]
         l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
         l.trc_decode_host.restype = _sz; l.trc_decode_host.argtypes = [C.c_int, _vp, _sz, _vp, _sz, _vp, C.c_uint]
         l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
@@ -685,6 +697,48 @@ def fplanes_check(buf, outlen=None):
     """trc_fplanes_check on a TRCF container in host memory (needs no device); raises TrcError with the library's reason"""
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
     _chk(lib().trc_fplanes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
+
+
+# ------------------------------------------------------------------- the planes advisor (include/trc_hip.h) ---
+def planes_hist_bytes(esize):
+    return lib().trc_planes_hist_bytes(esize)
+
+
+def planes_hist(filters, d_in, n, esize, seg, d_hist):
+    """enqueue trc_planes_hist_dev: the byte histograms of the planes of d_in[:n] under every filter of the bit set `filters`,
+    into d_hist (3 * esize * 256 uint64 as a device tensor; zeroed by the call)"""
+    _chk(lib().trc_planes_hist_dev(filters, d_in.data_ptr(), n, esize, seg, d_hist.data_ptr(), _cur_stream(d_in)))
+
+
+def _advice_dict(a):
+    return dict(filter=int(a.filter), esize=int(a.esize), filters=int(a.filters), m=int(a.m),
+                bits=np.array([list(r) for r in a.bits], dtype=np.float64), total_bits=np.array(list(a.total_bits), dtype=np.float64))
+
+
+def planes_advise(hist, filters, esize, m):
+    """trc_planes_advise on histograms in host memory (uint64 [3 * esize * 256]; needs no device) -> dict of the advice's fields"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    if hist.size < 3 * esize * 256:                                # (a bad esize is the library's to refuse: give it something to read)
+        hist = np.concatenate([hist.reshape(-1), np.zeros(3 * 8 * 256, dtype=np.uint64)])
+    a = PlanesAdvice()
+    _chk(lib().trc_planes_advise(hist.ctypes.data, filters, esize, m, C.byref(a)))
+    return _advice_dict(a)
+
+
+def encode_aplanes_host(codec, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
+    """trc_encode_aplanes_host -> (the TRCP or TRCF container the advisor chose (np.uint8), dict of the advice's fields)"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(fplanes_bound(data.size, esize, chunk, cn), 64), dtype=np.uint8)
+    a = PlanesAdvice()
+    l = lib().trc_encode_aplanes_host(codec, data.ctypes.data, data.size, esize, chunk, out.ctypes.data, out.size, cn, C.byref(a))
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy(), _advice_dict(a)
+
+
+def host_decode_xplanes(comp, n):
+    return _host_decode_guarded("trc_decode_xplanes_host", comp, n)
 
 
 def encode_host_container(codec, data, chunk, cdf=None, cdfnum=256, prm=(5, 6)):
