@@ -364,7 +364,9 @@ int trc_planes_join_dev(const void *d_planes, size_t pitch, const void *d_tail, 
  * element at d_out[0], never tail bytes.  Argument errors are those of the per-plane calls; TRC_TABLES_READY and TRC_DIR_READY
  * are TRC_E_ARG in all three (the planes share nothing a caller could promise about).
  * Workspace: trc_planes_work_bytes (encode and decode) / trc_planes_range_work_bytes bytes, 256-byte aligned: every plane has a
- * slice of its own, the plane buffer followed by what the per-plane call needs.  Both return 0 for what the calls reject. */
+ * slice of its own, the plane buffer followed by what the per-plane call needs.  Both return 0 for what the calls reject.
+ * The seven coders that keep only the low four bits of a byte (TRC_RCA4, TRC_RCAI4, TRC_ANSA4, TRC_RC4, TRC_RC4C, TRC_RC4SS,
+ * TRC_RC4CSS) are refused by every coded planes call, filtered, host-pointer and container checks included: TRC_E_ARG / 0. */
 #define TRC_PLANES_CDF_STRIDE 264
 size_t trc_planes_work_bytes(int codec, size_t n, unsigned esize, uint32_t chunk);
 int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsigned esize, uint32_t chunk,

@@ -11,6 +11,7 @@ import pytest
 import advise_lib as AL
 import fplanes_lib as FL
 import trc
+from planes_matrix_lib import LOW4, LOW4_TEXT
 
 SEG = 256
 MS = (4105, 65539)
@@ -122,6 +123,22 @@ def test_argument_errors():
         trc.planes_advise(huge, 7, esize, m)
     with pytest.raises(trc.TrcError, match="rc=-1"):
         trc.planes_advise(h, 7, esize, m + 1)
+
+
+@pytest.mark.parametrize("codec", LOW4, ids=lambda c: trc.CODEC_NAMES[c])
+def test_aplanes_refuses_a_low_nibble_coder_before_any_device(codec):
+    """the coder is refused before the input is uploaded for its histograms: 0, the reason, nothing written, with or without a GPU"""
+    d = AL.gen("monotone", 4, MS[0], 3, 1)
+    out = np.full(d.size + 4096, 0xA5, dtype=np.uint8)
+    a = trc.PlanesAdvice()
+    a.filter = 77
+    cn = trc.ss_prm((4, 7)) if codec in trc.SSBIT else 0
+    for chunk in (0, SEG):
+        assert trc.lib().trc_encode_aplanes_host(codec, d.ctypes.data, d.size, 4, chunk, out.ctypes.data, out.size, cn, a) == 0
+        assert LOW4_TEXT in trc.lib().trc_last_error().decode()
+    assert (out == 0xA5).all() and a.filter == 77
+    with pytest.raises(trc.TrcError, match=LOW4_TEXT):
+        trc.encode_aplanes_host(codec, d, 4, 0, prm=(4, 7))
 
 
 def test_hist_bytes():

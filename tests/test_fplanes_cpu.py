@@ -13,6 +13,7 @@ import pytest
 
 import fplanes_lib as FL
 import trc
+from planes_matrix_lib import LOW4, LOW4_TEXT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ANY = 2**64 - 1
@@ -145,24 +146,25 @@ def test_restarts_really_restart(esize, filt):
 
 
 # ---- trc_fplanes_check on hand-made containers ------------------------------------------------------------------------------
-def section(codec, m, chunk, clens):
+def section(codec, m, chunk, clens, cdfnum=0):
     lens = [min(chunk, m - i * chunk) for i in range(len(clens))]
     pay = sum(min(l, ln) for l, ln in zip(clens, lens))
-    hdr = struct.pack("<IBBHIIQQ", 0x31435254, codec, 1, 0, chunk, len(clens), m, pay)
+    hdr = struct.pack("<IBBHIIQQ", 0x31435254, codec, 1, cdfnum, chunk, len(clens), m, pay)
     return hdr + struct.pack("<%dI" % len(clens), *clens) + bytes(range(256)) * (pay // 256) + bytes(range(pay % 256))
 
 
-def make(esize=2, t=0, codec=trc.RCA, m=600, chunk=256, clens=(256, 40, 9), magic=trc.PLANES_MAGIC, version=1):
-    """a TRCP container of a non-static coder: header, offsets, esize sections (each 8-aligned), t tail bytes"""
+def make(esize=2, t=0, codec=trc.RCA, m=600, chunk=256, clens=(256, 40, 9), magic=trc.PLANES_MAGIC, version=1, cdfnum=0):
+    """a TRCP container of a non-static coder: header, offsets, esize sections (each 8-aligned), t tail bytes; cdfnum: the two
+    parameters of an ss coder"""
     n = m * esize + t
-    secs = [section(codec, m, chunk, clens)] * esize
+    secs = [section(codec, m, chunk, clens, cdfnum)] * esize
     pos, off, body = 32 + 8 * esize, [], b""
     for s in secs:
         off.append(pos)
         s = s + b"\0" * (-len(s) % 8)
         body += s
         pos += len(s)
-    hdr = struct.pack("<IBBBBIIQQ", magic, codec, version, esize, t, chunk, 0, n, pos + t)
+    hdr = struct.pack("<IBBBBIIQQ", magic, codec, version, esize, t, chunk, cdfnum, n, pos + t)
     return hdr + struct.pack("<%dQ" % esize, *off) + body + bytes([0xEE] * t), n
 
 
@@ -212,6 +214,45 @@ def test_check_rejects_each_defect():
     assert check(good, outlen=n - 1) != 0 and "caller expects" in err()                  # another length than the caller expects
     with pytest.raises(trc.TrcError, match="filter 3"):
         trc.fplanes_check(wrap(inner, filt=3))
+
+
+def prm_of(codec):
+    return trc.ss_prm((4, 7)) if codec in trc.SSBIT else 0
+
+
+@pytest.mark.parametrize("codec", LOW4, ids=lambda c: trc.CODEC_NAMES[c])
+def test_check_rejects_a_low_nibble_coder(codec):
+    """the TRCP container of a coder of in[i] & 15 behind a sound 16-byte prefix: refused by the check and by every decoder that
+    reads a TRCF container, before a device is looked for"""
+    L = trc.lib()
+    for esize, t in ((2, 1), (4, 0), (8, 7)):
+        inner, n = make(esize, t, codec=codec, cdfnum=prm_of(codec))
+        for filt in FL.FILTERS:
+            buf = wrap(inner, filt=filt)
+            assert check(buf) != 0 and LOW4_TEXT in err() and "codec %d" % codec in err()
+            with pytest.raises(trc.TrcError, match=LOW4_TEXT):
+                trc.fplanes_check(buf, n)
+            out = np.full(n + 64, 0xA5, dtype=np.uint8)
+            for name in ("trc_decode_fplanes_host", "trc_decode_xplanes_host"):
+                assert getattr(L, name)(buf.ctypes.data, buf.size, out.ctypes.data, n) == 0 and LOW4_TEXT in err(), name
+            assert L.trc_decode_fplanes_range_host(buf.ctypes.data, buf.size, 0, 8, out.ctypes.data) == 0 and LOW4_TEXT in err()
+            assert (out == 0xA5).all()
+    for codec_ok in (trc.RCU3, trc.RCU3SS):                        # the varint neighbours of the same table macros code whole bytes
+        inner, n = make(4, 3, codec=codec_ok, cdfnum=prm_of(codec_ok))
+        assert check(wrap(inner)) == 0, err()
+
+
+@pytest.mark.parametrize("codec", LOW4, ids=lambda c: trc.CODEC_NAMES[c])
+def test_host_encode_refuses_a_low_nibble_coder_before_any_device(codec):
+    L = trc.lib()
+    d = FL.gen("monotone", 4, 5000, 3, 1)
+    out = np.full(d.size + 4096, 0xA5, dtype=np.uint8)
+    for filt in FL.FILTERS:
+        assert L.trc_encode_fplanes_host(codec, filt, d.ctypes.data, d.size, 4, 256, out.ctypes.data, out.size, prm_of(codec)) == 0
+        assert LOW4_TEXT in err() and "codec %d" % codec in err()
+        with pytest.raises(trc.TrcError, match=LOW4_TEXT):
+            trc.host_encode_fplanes(codec, filt, d, 4, 0, prm=(4, 7))
+    assert (out == 0xA5).all()
 
 
 def test_bound():

@@ -12,6 +12,7 @@ import pytest
 import fplanes_lib as FL
 import planes_lib as PL
 import trc
+from planes_matrix_lib import assert_same_container
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -164,23 +165,6 @@ def coded(torch, codec, esize, filt, chunk=CHUNK, m=M6):
             out.append(pc)
         _cache[key] = (d, out[0], out[1])
     return _cache[key]
-
-
-def assert_same_container(fc, pc, esize, codec, tag):
-    assert np.array_equal(fc.tail[:esize - 1].cpu().numpy(), pc.tail[:esize - 1].cpu().numpy()), tag + ": tail"
-    coded_chunks = 0
-    for k in range(esize):
-        clen, payload, total = fc.result(k)
-        exp_clen, exp_payload, exp_total = pc.result(k)
-        assert total == exp_total, tag + ": total of plane %d" % k
-        assert np.array_equal(clen, exp_clen), tag + ": directory of plane %d" % k
-        assert np.array_equal(payload, exp_payload), tag + ": payload of plane %d" % k
-        assert (fc.payload[k * fc.pitch + total:k * fc.pitch + total + 64].cpu().numpy() == 0x5A).all(), tag + ": bytes behind the payload"
-        if codec in trc.STATIC:
-            (cdf, status), (exp_cdf, exp_status) = fc.cdf_of(k), pc.cdf_of(k)
-            assert status == exp_status == fc.m and np.array_equal(cdf, exp_cdf), tag + ": CDF of plane %d" % k
-        coded_chunks += int((clen < np.minimum(fc.chunk, fc.m - np.arange(0, fc.m, fc.chunk))).sum())
-    assert coded_chunks, tag + ": the input is meant to compress somewhere"
 
 
 def assert_decodes(torch, fc, d, tag):

@@ -13,6 +13,7 @@ import trc_testlib as T
 import nibbit_lib as NL
 import sweep_lib as S
 from gpu_contracts import to_dev, torch_cuda  # noqa: F401 (torch_cuda: the fixture)
+from planes_matrix_lib import chunk_of, mixed_input  # noqa: F401 (the generator, shared with test_gpu_planes_matrix.py)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,27 +27,9 @@ CODECS = [trc.ANS4S, trc.RCS1, trc.RCS2, trc.RCSM, trc.RCB, trc.RCA, trc.RCAI, t
 NIBBLE = (trc.RCA4, trc.RC4)                                   # values 0..15 in, never stored raw: 4 bits per byte at the worst
 
 
-def chunk_of(codec):
-    return 1024 if codec == trc.ANSO1 else 256
-
-
 def make_input(codec):
     """chunks alternate between uniform and skewed data of the coder's kind -> (n, chunk, bytes)"""
-    chunk = chunk_of(codec)
-    n = (NCHUNKS - 1) * chunk + TAIL
-    if codec in S.FAMILY:
-        skew, uni = S.gen(codec, S.HEAD[S.FAMILY[codec]], n, 5), S.uniform(n, 6)
-    elif codec in NL.CODECS:
-        nib = codec in NL.NIBBLE
-        skew, uni = NL.gen("nib_skew" if nib else "bytes_small", n, 5), NL.gen("nib_uniform" if nib else "bytes_uniform", n, 6)
-    elif codec in T.NIBBLE_CODECS:
-        skew, uni = T.nibble_bytes(n, 5, "geo"), T.nibble_bytes(n, 6, "uniform")
-    elif codec in T.VLC_CODECS:
-        skew, uni = T.int_bytes(n, T.VLC_ELEM[codec], "small", 5), T.int_bytes(n, T.VLC_ELEM[codec], "wide", 6)
-    else:
-        skew, uni = T.nibble_bytes(n, 5, "geo"), T.uniform_bytes(n, 6)
-    d = np.where((np.arange(n) // chunk) % 2 == 0, uni[:n], skew[:n]).astype(np.uint8)
-    return n, chunk, d
+    return mixed_input(codec, NCHUNKS, TAIL)
 
 
 def encoded(torch, codec, n, chunk, d):

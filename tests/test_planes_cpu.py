@@ -10,6 +10,7 @@ import pytest
 
 import planes_lib as PL
 import trc
+from planes_matrix_lib import ASSIGNED, LOW4, LOW4_TEXT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ANY = 2**64 - 1
@@ -83,18 +84,19 @@ def test_bound():
 
 
 # ---- trc_planes_check on hand-made containers -------------------------------------------------------------------------------
-def section(codec, m, chunk, clens):
+def section(codec, m, chunk, clens, cdfnum=0):
     lens = [min(chunk, m - i * chunk) for i in range(len(clens))]
     pay = sum(min(l, ln) for l, ln in zip(clens, lens))
-    hdr = struct.pack("<IBBHIIQQ", 0x31435254, codec, 1, 0, chunk, len(clens), m, pay)
+    hdr = struct.pack("<IBBHIIQQ", 0x31435254, codec, 1, cdfnum, chunk, len(clens), m, pay)
     return hdr + struct.pack("<%dI" % len(clens), *clens) + bytes(range(256)) * (pay // 256) + bytes(range(pay % 256))
 
 
 def make(esize=2, t=0, codec=trc.RCA, m=600, chunk=256, clens=(256, 40, 9), magic=trc.PLANES_MAGIC, version=1, hdr_esize=None,
-         hdr_tail=None, size_delta=0, off_delta=None, sections=None):
-    """a TRCP container of a non-static coder: header, offsets, esize sections (each 8-aligned), t tail bytes"""
+         hdr_tail=None, size_delta=0, off_delta=None, sections=None, cdfnum=0):
+    """a TRCP container of a non-static coder: header, offsets, esize sections (each 8-aligned), t tail bytes; cdfnum: the two
+    parameters of an ss coder, in the header and in every section"""
     n = m * esize + t
-    secs = sections or [section(codec, m, chunk, clens)] * esize
+    secs = sections or [section(codec, m, chunk, clens, cdfnum)] * esize
     pos, off, body = 32 + 8 * esize, [], b""
     for s in secs:
         off.append(pos)
@@ -105,7 +107,7 @@ def make(esize=2, t=0, codec=trc.RCA, m=600, chunk=256, clens=(256, 40, 9), magi
         off[off_delta[0]] += off_delta[1]
     size = pos + t + size_delta
     hdr = struct.pack("<IBBBBIIQQ", magic, codec, version, esize if hdr_esize is None else hdr_esize, t if hdr_tail is None else hdr_tail,
-                      chunk, 0, n, size)
+                      chunk, cdfnum, n, size)
     return np.frombuffer(hdr + struct.pack("<%dQ" % esize, *off) + body + bytes([0xEE] * t), dtype=np.uint8).copy(), n
 
 
@@ -184,6 +186,74 @@ def test_check_static_and_ss_fields():
     assert check(ss(trc.ss_prm((4, 7)))) == 0
     assert check(ss(trc.ss_prm((0, 7)))) != 0
     assert check(ss(trc.ss_prm((4, 16)))) != 0
+
+
+# ---- the low-nibble coders ------------------------------------------------------------------------------------------------------
+def prm_of(codec):
+    return trc.ss_prm((4, 7)) if codec in trc.SSBIT else 0
+
+
+def test_work_bytes_of_every_coder():
+    """the seven coders of in[i] & 15 have no planes workspace; every other assigned id has one"""
+    L = trc.lib()
+    assert len(LOW4) == 7 and set(LOW4) < set(ASSIGNED)
+    for esize in PL.ESIZES:
+        n = 4096 * esize + esize - 1
+        for codec in ASSIGNED:
+            w = L.trc_planes_work_bytes(codec, n, esize, 256)
+            r = [L.trc_planes_range_work_bytes(codec, n, esize, 256, count) for count in (1, 16)]
+            if codec in LOW4:
+                assert w == 0 and r == [0, 0], (trc.CODEC_NAMES[codec], esize)
+            else:
+                assert w and all(r), (trc.CODEC_NAMES[codec], esize)
+    for esize in PL.ESIZES:
+        n = (1 << 20) * esize
+        assert L.trc_planes_work_bytes(trc.ANSB, n, esize, 8192) and L.trc_planes_range_work_bytes(trc.ANSB, n, esize, 8192, 1)
+        assert L.trc_planes_work_bytes(trc.ANSB, n, esize, 16384) == 0 and L.trc_planes_range_work_bytes(trc.ANSB, n, esize, 16384, 1) == 0
+
+
+@pytest.mark.parametrize("codec", LOW4, ids=lambda c: trc.CODEC_NAMES[c])
+def test_check_rejects_a_low_nibble_coder(codec):
+    """a container that is well formed in every other respect: its planes would come back as in[i] & 15"""
+    L = trc.lib()
+    for esize, t in ((2, 1), (4, 0), (8, 7)):
+        buf, n = make(esize, t, codec=codec, cdfnum=prm_of(codec))
+        assert check(buf) != 0 and LOW4_TEXT in err(), trc.CODEC_NAMES[codec]
+        assert "codec %d" % codec in err()
+        with pytest.raises(trc.TrcError, match=LOW4_TEXT):
+            trc.planes_check(buf, n)
+        # the sections alone are sound TRC1 containers of that coder: nothing but the coder's kind is wrong
+        for _, cont in trc.parse_planes(buf)[1]:
+            assert L.trc_container_check(cont.ctypes.data, cont.size, codec, n // esize) == 0
+        # every host decoder checks first, before a device is looked for
+        out = np.full(n + 64, 0xA5, dtype=np.uint8)
+        for name in ("trc_decode_planes_host", "trc_decode_xplanes_host"):
+            assert getattr(L, name)(buf.ctypes.data, buf.size, out.ctypes.data, n) == 0 and LOW4_TEXT in err(), name
+        assert L.trc_decode_planes_range_host(buf.ctypes.data, buf.size, 0, 8, out.ctypes.data) == 0 and LOW4_TEXT in err()
+        assert (out == 0xA5).all()
+
+
+@pytest.mark.parametrize("codec", (trc.RCU3, trc.RCU3SS), ids=lambda c: trc.CODEC_NAMES[c])
+def test_check_accepts_the_varint_neighbours(codec):
+    """rows of the same table macros as rc4s / rc4ss that code whole bytes"""
+    for esize, t in ((2, 1), (4, 0), (8, 7)):
+        buf, n = make(esize, t, codec=codec, cdfnum=prm_of(codec))
+        assert check(buf) == 0 and check(buf, outlen=n) == 0, err()
+        trc.planes_check(buf, n)
+
+
+@pytest.mark.parametrize("codec", LOW4, ids=lambda c: trc.CODEC_NAMES[c])
+def test_host_encode_refuses_a_low_nibble_coder_before_any_device(codec):
+    """with or without a GPU: 0, the reason, and an untouched output"""
+    L = trc.lib()
+    d = PL.weights(3000, 2)
+    out = np.full(d.size + 4096, 0xA5, dtype=np.uint8)
+    for chunk in (0, 256):
+        assert L.trc_encode_planes_host(codec, d.ctypes.data, d.size, 2, chunk, out.ctypes.data, out.size, prm_of(codec)) == 0
+        assert LOW4_TEXT in err() and "codec %d" % codec in err()
+    assert (out == 0xA5).all()
+    with pytest.raises(trc.TrcError, match=LOW4_TEXT):
+        trc.host_encode_planes(codec, d, 2, 256, prm=(4, 7))
 
 
 # ---- the definition against the reference ---------------------------------------------------------------------------------

@@ -97,7 +97,7 @@ static size_t word_area(const TrcCodec &c, size_t nchunks) { return trc_word_slo
     { .id = i, LAUNCH(f), .streams = st, .gather = g, .cdf = true, .wave_ns = ns, .round_lanes = lanes, .auto_max = 4096u, \
       .chunk_max = TRC_CHUNK_MAX, .pad = 128, .s2_mul = s2mul, .s2_add = s2add, KERNELS(ke, kd) }
 #define ADAPTIVE(i, f, st, nib, g, stream, ns, lanes, s2mul, s2add, ke, kd) \
-    { .id = i, LAUNCH(f), .streams = st, .nibble = nib, .gather = g, .gate = stream, .prog = stream, .wave_ns = ns, .round_lanes = lanes, \
+    { .id = i, LAUNCH(f), .streams = st, .nibble = nib, .low4 = nib != 0, .gather = g, .gate = stream, .prog = stream, .wave_ns = ns, .round_lanes = lanes, \
       .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, .pad = 128, .s2_mul = s2mul, .s2_add = s2add, KERNELS(ke, kd) }
 #define VLC(i, ns) \
     { .id = i, LAUNCH(vlc), .variant = (i - TRC_VLCU16) >> 1, .elem = ((i - TRC_VLCU16) & 1) ? 4 : 2, .gather = TRC_GATHER_AUX, .aux = true, \
@@ -128,13 +128,13 @@ static size_t word_area(const TrcCodec &c, size_t nchunks) { return trc_word_slo
 // wave_ns from the chunk-16384 runs of the 100 MB sweep in profiles/nibbit/nibbit_notes.md (chip a tenth full); round_lanes from
 // the sweep's best chunk: rc4s 512 (256 is no faster), rc4cs 1024, rcu3s 1536 (four waves per CU, as its LDS allows)
 #define NIBBIT(i, ns, lanes) \
-    { .id = i, LAUNCH(nibbit), .k = i - TRC_RC4, .gather = TRC_GATHER_START, .wave_ns = ns, .round_lanes = lanes, \
+    { .id = i, LAUNCH(nibbit), .k = i - TRC_RC4, .low4 = i - TRC_RC4 < 2, .gather = TRC_GATHER_START, .wave_ns = ns, .round_lanes = lanes, \
       .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, .pad = 128, KERNELS("trc_rc_nib_enc_kernel", "trc_rc_nib_dec_kernel") }
 // the same shape on the dual-rate "ss" predictor (trc_rc_ss.hip: rc4ss 4 KiB of LDS per wave, rcss 64 KiB, rcu3ss 74.75 KiB, rc4css
 // none); the call's two shift parameters travel in `cdfnum` (TRC_SS_PRM).  wave_ns and round_lanes are those of the "s" counterparts (rcs, rc4s, rc4cs, rcu3s) until the sweep of
 // profiles/ssbit/ssbit_notes.md has been run: not measured
 #define SSBIT(i, kk, ns, lanes) \
-    { .id = i, LAUNCH(ssbit), .k = kk, .gather = TRC_GATHER_START, .ss = true, .wave_ns = ns, .round_lanes = lanes, \
+    { .id = i, LAUNCH(ssbit), .k = kk, .low4 = kk < 2, .gather = TRC_GATHER_START, .ss = true, .wave_ns = ns, .round_lanes = lanes, \
       .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, .pad = 128, KERNELS("trc_rc_ss_enc_kernel", "trc_rc_ss_dec_kernel") }
 // what an id without a coder answers to trc_auto_chunk_codec / trc_round_chunk
 #define NONE(i) { .id = i, .wave_ns = 400, .round_lanes = 327680u, .auto_max = TRC_AUTO_CHUNK_MAX, .chunk_max = TRC_CHUNK_MAX, KERNELS("", "") }

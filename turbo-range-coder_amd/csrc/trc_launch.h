@@ -114,6 +114,7 @@ struct TrcCodec {
     int8_t k;                  // index within the family (integer, Turbo-VLC bitwise, word, nibble / varint coders); the order-1 bitwise context (0 rccs, 1 rcxs)
     int8_t streams;            // static / adaptive / vnibble range coders: 1 or 2 streams; -1: rccdfsm
     int8_t nibble;             // adaptive coders on values 0..15
+    bool low4;                 // codes in[i] & 15 and decodes to it, never stores raw (the seven `turborc -n` coders): the byte-plane calls refuse it
     int8_t variant;            // Turbo-VLC: 0 u, 1 v, 2 vz (over rANS: 0 u, 1 v)
     int8_t zz;                 // Turbo-VLC over rANS: zigzag-delta form
     int8_t elem;               // Turbo-VLC: element bytes (2 or 4)

@@ -4,7 +4,10 @@
 //
 // Nothing here knows a coder: plane k's (clen, payload, total) is what trc_encode_dev returns for the m bytes of plane k, so every
 // contract of the per-plane calls (chunk parity, raw fallback, random access) holds for each plane as it stands.
+// One property of a coder is asked for: the seven low-nibble coders (TrcCodec::low4) code in[i] & 15 and never store raw, so planes
+// coded with them would come back without their high nibbles.  Every entry point here refuses them, with PLANES_LOW4 as the reason.
 #include <math.h>
+#define PLANES_LOW4 "codec %d keeps only the low four bits of a byte: the byte-plane calls do not take it"
 
 // ---- workspace -------------------------------------------------------------------------------------------------------------------
 // esize slices, `slice` bytes apart (a multiple of 256, so the slices are the planes of the split / join kernels with pitch = slice):
@@ -14,7 +17,7 @@ static bool planes_esize_ok(unsigned esize) { return esize == 2 || esize == 4 ||
 static bool planes_map(int codec, size_t n, unsigned esize, uint32_t chunk, PlanesMap &P)
 {
     const TrcCodec &r = codec_row(codec);
-    if (!r.enc || !planes_esize_ok(esize) || n < esize || !chunk_ok(chunk) || chunk > r.chunk_max) return false;
+    if (!r.enc || r.low4 || !planes_esize_ok(esize) || n < esize || !chunk_ok(chunk) || chunk > r.chunk_max) return false;
     P.m = n / esize;
     P.nc = (P.m + chunk - 1) / chunk;
     if (P.nc > 0x7fffffffu) return false;
@@ -31,7 +34,7 @@ extern "C" size_t trc_planes_work_bytes(int codec, size_t n, unsigned esize, uin
 // the range form: the plane buffer holds `count` chunks, the per-plane workspace is the one of trc_decode_range_dev
 static bool planes_range_map(int codec, size_t n, unsigned esize, uint32_t chunk, size_t count, PlanesMap &P)
 {
-    if (!planes_esize_ok(esize) || n < esize) return false;
+    if (codec_row(codec).low4 || !planes_esize_ok(esize) || n < esize) return false;
     P.m = n / esize;
     P.work = up256(trc_range_work_bytes(codec, P.m, chunk, count));
     if (!P.work) return false;
@@ -50,6 +53,7 @@ extern "C" size_t trc_planes_range_work_bytes(int codec, size_t n, unsigned esiz
 static int planes_common(const char *who, int codec, size_t n, unsigned esize, const void *d_work)
 {
     if (codec & (TRC_TABLES_READY | TRC_DIR_READY)) return fail(TRC_E_ARG, "%s: TRC_TABLES_READY / TRC_DIR_READY do not apply to planes", who);
+    if (codec_row(codec).low4) return fail(TRC_E_ARG, "%s: " PLANES_LOW4, who, codec);
     if (!planes_esize_ok(esize)) return fail(TRC_E_ARG, "%s: esize %u (2, 4 or 8)", who, esize);
     if (n < esize) return fail(TRC_E_ARG, "%s: %zu bytes hold no element of %u bytes", who, n, esize);
     if (!d_work || ((uintptr_t)d_work & 255)) return fail(TRC_E_ARG, "%s: workspace must be 256-byte aligned", who);
@@ -194,6 +198,7 @@ static int planes_verdict(const void *buf, size_t buflen, size_t outlen, trc_pla
     if (h.magic != TRC_PLANES_MAGIC || h.version != 1) BAD("bad magic/version");
     if (!planes_esize_ok(h.esize)) BAD("esize %u (2, 4 or 8)", h.esize);
     if (!codec_ok(h.codec)) BAD("codec %u", h.codec);
+    if (codec_row(h.codec).low4) BAD(PLANES_LOW4, (int)h.codec);      // (a section names the header's coder or is refused below)
     const TrcCodec &r = codec_row(h.codec);
     if (h.n < h.esize || h.tail != h.n % h.esize) BAD("tail %u of n = %llu, esize %u", h.tail, (unsigned long long)h.n, h.esize);
     if (outlen != (size_t)-1 && h.n != outlen) BAD("holds %llu bytes, caller expects %zu", (unsigned long long)h.n, outlen);
@@ -298,6 +303,7 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
                                  void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice = nullptr)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
+    if (codec_row(codec).low4) { fail(TRC_E_ARG, "encode_planes_host: " PLANES_LOW4, codec); return 0; }      // before anything is uploaded
     if (!in || !out || !planes_esize_ok(esize) || n < esize) { fail(TRC_E_ARG, "encode_planes_host: bad arguments (esize %u, %zu bytes)", esize, n); return 0; }
     const TrcCodec &r = codec_row(codec);
     const size_t m = n / esize;
