@@ -1,7 +1,8 @@
 """The workspace contracts of a device-resident coder, checked against a hash fixture entry (tests/golden/sweep.json,
 bytesweep.json): the device_roundtrip sequence of test_gpu_parity.py for the coders the oracle restatement does not cover.  Every
 decode is compared byte for byte with guard bytes behind n; every encode with the fixture's hashes and 64 guard bytes behind the
-payload.  prm: the parameter pair of an "ss" coder, handed to DeviceCoder.encode / decode only where given.
+payload.  prm: the parameter pair of an "ss" coder, handed to DeviceCoder.encode / decode only where given.  cdf: (uint16 array,
+cdfnum) of a static coder, set on the coder under test (DeviceCoder.set_cdf) before anything runs and on the decode-only receiver.
 
 Below them, what the test_gpu_<family>.py files share: the torch_cuda fixture (imported by name), the vectors loader,
 decode_fixture, large_roundtrip, refused_like_rcb and reference_harness."""
@@ -46,9 +47,15 @@ def _prm(prm):
     return {} if prm is None else {"prm": tuple(prm)}
 
 
-def encode_checked(torch, dc, d_in, n, ent, tag, diagnose=None, prm=None):
+def _set_cdf(dc, cdf):
+    if cdf is not None:
+        dc.set_cdf(cdf[0], cdf[1])
+
+
+def encode_checked(torch, dc, d_in, n, ent, tag, diagnose=None, prm=None, cdf=None):
     """encode into a payload filled with 0x5A: lengths, payload and total hash to the fixture's, the 64 bytes behind the
     total still hold 0x5A.  diagnose(clen, payload) -> str adds detail to a mismatch (it never decides)."""
+    _set_cdf(dc, cdf)
     dc.payload.fill_(0x5A)
     dc.total.fill_(-1)
     dc.encode(d_in, n, **_prm(prm))
@@ -63,8 +70,9 @@ def encode_checked(torch, dc, d_in, n, ent, tag, diagnose=None, prm=None):
     return clen, payload
 
 
-def decode_checked(torch, dc, d, n, fill, tag, prm=None, **kw):
+def decode_checked(torch, dc, d, n, fill, tag, prm=None, cdf=None, **kw):
     """d: what the decoder must return (the input; for a nibble coder its low nibbles where the chunk is coded)"""
+    _set_cdf(dc, cdf)
     kw.update(_prm(prm))
     d_out = torch.full((n + 512,), fill, dtype=torch.uint8, device="cuda:0")
     dc.decode(d_out, n, **kw)
@@ -74,18 +82,20 @@ def decode_checked(torch, dc, d, n, fill, tag, prm=None, **kw):
     assert (out[n:] == fill).all(), "%s: the decoder wrote past n" % (tag,)
 
 
-def roundtrip(torch, dc, d, d_in, ent, tag, diagnose=None, prm=None):
+def roundtrip(torch, dc, d, d_in, ent, tag, diagnose=None, prm=None, cdf=None):
     """encode parity and one round trip"""
     n = d.size
+    _set_cdf(dc, cdf)
     encode_checked(torch, dc, d_in, n, ent, tag + " encode", diagnose, prm)
     decode_checked(torch, dc, d, n, 0xA5, tag + " decode", prm)
 
 
-def contracts(torch, dc, d, d_in, ent, tag, diagnose=None, prm=None):
+def contracts(torch, dc, d, d_in, ent, tag, diagnose=None, prm=None, cdf=None):
     """encode; decode; decode under TRC_DIR_READY; encode again into the used workspace; decode under TRC_DIR_READY after that
     encode; a second coder whose workspace is 0xEE and has never encoded decodes the first one's directory and payload with
     TRC_DIR_READY off, on, on"""
     n = d.size
+    _set_cdf(dc, cdf)
     encode_checked(torch, dc, d_in, n, ent, tag + " encode", diagnose, prm)
     decode_checked(torch, dc, d, n, 0xA5, tag + " decode", prm)
     decode_checked(torch, dc, d, n, 0x5A, tag + " decode with TRC_DIR_READY (after a decode)", prm, dir_ready=True)
@@ -93,6 +103,7 @@ def contracts(torch, dc, d, d_in, ent, tag, diagnose=None, prm=None):
     decode_checked(torch, dc, d, n, 0x5A, tag + " decode with TRC_DIR_READY (after an encode)", prm, dir_ready=True)
     rx = trc.DeviceCoder(dc.codec, n, dc.chunk, "cuda:0")
     rx.work.fill_(0xEE)
+    _set_cdf(rx, cdf)
     for flag in (False, True, True):
         decode_checked(torch, rx, d, n, 0x3C, tag + " decode-only workspace, dir_ready=%s" % flag, prm, clen=dc.clen, payload=dc.payload,
                        dir_ready=flag)

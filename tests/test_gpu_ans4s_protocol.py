@@ -16,7 +16,8 @@
 for chunk 256 and 512, 1 / 17 / 64 / 65 / 200 chunks (a partial wave, exactly one, one and a lane, several), whole last chunks and a
 ragged one (its length no multiple of 4 or of 64), in each workgroup shape of the encoder (TRC_ENC_WPB = 1 / 4 / 12, read once per
 process: a fresh child for each).  Expected lengths and payloads are the oracle's encode of every chunk, computed once here and
-handed to the children in a file; the children compare the device's directory and payload with it byte for byte and decode."""
+handed to the children in a file; the children compare the device's directory and payload with it byte for byte and decode.
+The other three static coders and the other CDF shapes (frequent symbol at the top, small alphabets): tests/test_gpu_static_cdf.py."""
 import os
 import subprocess
 import sys

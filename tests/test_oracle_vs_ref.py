@@ -4,6 +4,7 @@ the prebuilt library did not travel); the golden vectors cover that case."""
 import numpy as np
 import pytest
 
+import static_cdf_lib as SC
 import trc_testlib as T
 from golden.make_golden import gen
 
@@ -11,10 +12,32 @@ pytestmark = pytest.mark.skipif(not T.have_ref(), reason="oracle/_ref/libtrc_ref
 CODECS = [T.ANS4S, T.RCS1, T.RCS2, T.RCA, T.ANSA, T.RCB, T.RCAI, T.RCSM, T.ANSO1, T.ANSB]
 
 
-@pytest.mark.parametrize("kind", ["zipf", "text", "runs", "uniform", "nibble", "binary"])
+def _fuzz_under_made_cdfs(sizes):
+    """the static coders under the hand-made CDFs of static_cdf_lib (the frequent symbol at the bottom, the middle, the top; runs of
+    f = 1; 16, 3, 2 and 1 symbols), on every pattern of that library in turn: here the data does not follow the CDF"""
+    for i, n in enumerate(sizes):
+        for j, name in enumerate(SC.CDFS):
+            cdf, cdfnum = SC.cdf(name)
+            pat = (i + j) % len(SC.PATTERNS)
+            d = SC.pattern_rows(name, [pat], n, 7000 + n)[0]
+            for codec in T.STATIC_CODECS:
+                if codec == T.RCS2 and n < 2:
+                    continue
+                tag = (name, SC.PATTERNS[pat], n, T.CODEC_NAMES[codec])
+                a = T.orc_enc(codec, d, cdf, cdfnum)
+                assert np.array_equal(a, T.ref_enc(codec, d, cdf, cdfnum)), tag
+                assert np.array_equal(T.orc_dec(codec, a, n, cdf, cdfnum), d), tag
+                rd = T.ref_dec(codec, a, n, cdf, cdfnum)
+                assert rd is None or np.array_equal(rd, d), tag
+
+
+@pytest.mark.parametrize("kind", ["zipf", "text", "runs", "uniform", "nibble", "binary", "made_cdf"])
 def test_fuzz_against_reference(kind):
+    """made_cdf: the CDF comes from static_cdf_lib instead of orc_cdfini(d), for the static coders among CODECS"""
     rng = np.random.default_rng(12345)
     sizes = [1, 2, 3, 9, 10, 11, 70, 71, 4095, 4096, 4097] + [int(x) for x in rng.integers(12, 70000, 12)]
+    if kind == "made_cdf":
+        return _fuzz_under_made_cdfs(sizes)
     for n in sizes:
         d = gen(kind, n, 7000 + n)
         r, cdf, cdfnum = T.orc_cdfini(d)
