@@ -520,6 +520,74 @@ size_t trc_encode_aplanes_host(int codec, const void *in, size_t n, unsigned esi
                                void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice);
 size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *out, size_t outlen);
 
+/* ---- batched byte planes: many separate allocations in one coded call, any one of them decodable ------------------------
+ * A checkpoint is hundreds of tensors of one dtype, a KV-cache a pool of pages, a table a set of columns: many allocations, each
+ * too small to fill the device and too many to launch the planes calls once apiece.  A batch codes them as ONE planes call over
+ * a VIRTUAL buffer that exists nowhere:
+ *        esize in {2, 4, 8}; chunk by the chunk rule; `count` items, item i = n[i] bytes at d_ptr[i], n[i] >= esize, n[i] % esize == 0
+ *        m[i] = n[i] / esize;   nc[i] = ceil(m[i] / chunk);   first[i] = nc[0] + .. + nc[i - 1];   NC = first[count]
+ *        V(items, esize, chunk) = the items in order, every item BUT THE LAST followed by zero elements up to nc[i] * chunk elements
+ *        M = (NC - nc[count - 1]) * chunk + m[count - 1] elements,  M * esize bytes  (a batch has whole elements only: no tail)
+ * The whole contract:  encode_batch(codec, items, ...)  ==  trc_encode_planes_dev(codec, V, M * esize, esize, chunk, ...)  byte for
+ * byte -- directory, payload, totals, per-plane CDFs and statuses -- in buffers of that call's shapes: d_clen[esize * NC], planes
+ * trc_planes_pitch(M * esize, esize) apart, d_total[esize], d_cdf at TRC_PLANES_CDF_STRIDE.  Item i owns chunks [first[i], first[i]
+ * + nc[i]) of every plane, so "decode item i alone" is a chunk range; a batch of one item is the plain call on that item.
+ *
+ * `items` is a HOST array the caller may free or reuse as soon as a call returns: the call copies what its kernels need (32 bytes
+ * per item) to the table on the device before it returns, and that copy waits for the work enqueued on `stream` before it;
+ * everything else only enqueues work.  Items lie anywhere on the device, 16-byte aligned, and -- unlike every other entry point --
+ * need NO TRC_PAD of readable slack: the kernels read bytes [0, n[i]) of item i and nothing else, a tensor may end where its
+ * allocation ends.  Writes: split [0, M) of every plane, the pad zeros included; join [0, n[i]) of every requested item; the
+ * coded calls their coded buffers, as the planes calls do.
+ *
+ * TRC_E_ARG, before anything is enqueued: count == 0 or > TRC_PLANES_BATCH_MAX, n[i] < esize or n[i] % esize != 0 (any item), a
+ * bad esize or chunk, NC > 0x7fffffff, a d_ptr that is NULL or not 16-byte aligned on an item the call touches, first_item +
+ * item_count > count, TRC_TABLES_READY / TRC_DIR_READY, the seven low-nibble coders.  A workspace or table that is too small is
+ * TRC_E_WORK.  The work-bytes functions return 0 for what the calls reject (and for item_count == 0, which needs none).
+ *
+ * trc_planes_batch_plan_host (host only, no GPU needed) validates sizes, esize and chunk -- it looks at no pointer, so that a
+ * caller who will decode a few items may plan with the others NULL -- and returns the figures of the equivalent planes call;
+ * first_chunk (may be NULL) receives first[0 .. count].
+ * The two kernels on their own: trc_planes_split_batch_dev writes the planes of V (d_planes 256-byte aligned, pitch a multiple
+ * of 256 and at least M); trc_planes_join_batch_dev scatters items [first_item, first_item + item_count) back from planes whose
+ * element 0 is the first requested item's first element (64-byte aligned, so d_planes + first[first_item] * chunk of a whole
+ * batch's planes serves; pitch at least the elements of the range), looking at no other item's pointer.  d_table: 256-byte
+ * aligned, trc_planes_batch_table_bytes(items the call touches, their chunks) bytes.  TRC_PLANES_GRID caps their grids as it
+ * does the unbatched kernels'.
+ * The coded calls: the batched split into the workspace, then trc_cdfini_dev (static coders) + trc_encode_dev per plane exactly
+ * as trc_encode_planes_dev; decode runs trc_decode_range_dev per plane over chunks [first[first_item], first[first_item +
+ * item_count)) and the batched join over them into the items' own d_ptr.  Items outside the range are not looked at beyond their
+ * n, and their d_ptr may be NULL; item_count == 0 is TRC_OK with nothing enqueued.  Workspace: 256-byte aligned,
+ * trc_planes_batch_work_bytes (encode) / trc_planes_batch_range_work_bytes (decode: grows with the requested chunks, not with M). */
+#define TRC_PLANES_BATCH_MAX 1048576u          /* items per call */
+typedef struct trc_planes_item { void *d_ptr; uint64_t n; } trc_planes_item;     /* host array; const for encode */
+typedef struct trc_planes_batch_plan {
+    uint64_t m_total;       /* M */
+    uint64_t n_virtual;     /* M * esize: the n of the equivalent planes call */
+    uint64_t chunks;        /* NC */
+    uint64_t pitch;         /* trc_planes_pitch(n_virtual, esize) */
+    uint64_t pad_elems;     /* zero elements added */
+} trc_planes_batch_plan;
+int    trc_planes_batch_plan_host(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                  trc_planes_batch_plan *plan, uint64_t *first_chunk);
+size_t trc_planes_batch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk);
+size_t trc_planes_batch_range_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                         size_t first_item, size_t item_count);
+int trc_planes_split_batch_dev(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                               void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream);
+int trc_planes_join_batch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, size_t count,
+                              size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                              void *d_table, size_t table_bytes, void *stream);
+size_t trc_planes_batch_table_bytes(size_t count, uint64_t chunks);
+int trc_encode_planes_batch_dev(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                void *d_work, size_t work_bytes, void *stream);
+int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                const trc_planes_item *items, size_t count, size_t first_item, size_t item_count,
+                                unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                void *d_work, size_t work_bytes, void *stream);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

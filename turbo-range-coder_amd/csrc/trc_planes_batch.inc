@@ -1,0 +1,106 @@
+// trc_planes_batch.inc -- the coded planes calls over a BATCH of separate allocations (included by trc_api.hip behind
+// trc_planes.inc): the batched split / join kernels (trc_planes_batch.hip) around the per-plane loop of trc_planes.inc.
+//
+// The planes of the virtual buffer V(items, esize, chunk) (include/trc_hip.h) are ordinary planes of M elements, so everything here
+// is the unbatched call on (M * esize, esize, chunk) with another split in front or another join behind; item i is the chunk range
+// [first[i], first[i] + nc[i]) of every plane.  Nothing here knows a coder.
+//   workspace: the planes workspace of (M * esize, esize, chunk) -- planes_map / planes_range_map -- followed by the table
+int trc_planes_batch_plan_quiet(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, trc_planes_batch_plan *plan, uint64_t *first_chunk);
+int trc_planes_batch_ptrs_ok(const trc_planes_item *items, size_t first_item, size_t item_count);
+
+extern "C" size_t trc_planes_batch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+{
+    trc_planes_batch_plan B;
+    PlanesMap P;
+    if (trc_planes_batch_plan_quiet(items, count, esize, chunk, &B, nullptr) || !trc_planes_batch_ptrs_ok(items, 0, count)) return 0;
+    if (!planes_map(codec, (size_t)B.n_virtual, esize, chunk, P)) return 0;
+    return esize * P.slice + trc_planes_batch_table_bytes(count, B.chunks);
+}
+
+// the chunk range of items [first_item, first_item + item_count) of a planned batch
+static void batch_chunk_range(const trc_planes_item *items, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, size_t &c0, size_t &cnt)
+{
+    c0 = cnt = 0;
+    for (size_t i = 0; i < first_item + item_count; i++) {
+        const size_t nc = (size_t)((items[i].n / esize + chunk - 1) / chunk);
+        if (i < first_item) c0 += nc; else cnt += nc;
+    }
+}
+extern "C" size_t trc_planes_batch_range_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                                    size_t first_item, size_t item_count)
+{
+    trc_planes_batch_plan B;
+    PlanesMap P;
+    if (trc_planes_batch_plan_quiet(items, count, esize, chunk, &B, nullptr)) return 0;
+    if (first_item > count || item_count > count - first_item || !item_count || !trc_planes_batch_ptrs_ok(items, first_item, item_count)) return 0;
+    size_t c0, cnt;
+    batch_chunk_range(items, first_item, item_count, esize, chunk, c0, cnt);
+    if (!planes_range_map(codec, (size_t)B.n_virtual, esize, chunk, cnt, P)) return 0;
+    return esize * P.slice + trc_planes_batch_table_bytes(item_count, cnt);
+}
+
+extern "C" int trc_encode_planes_batch_dev(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                           uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                           uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                           void *d_work, size_t work_bytes, void *stream)
+{
+    trc_planes_batch_plan B;
+    int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
+    if (rc) return rc;
+    const size_t n = (size_t)B.n_virtual;
+    if ((rc = planes_common("encode_planes_batch", codec, n, esize, d_work))) return rc;
+    if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
+    const TrcCodec &r = codec_row(codec);
+    if (r.cdf && !d_status) return fail(TRC_E_ARG, "encode_planes_batch: a static coder needs d_status (one int32 per plane)");
+    if (!r.cdf && d_status) return fail(TRC_E_ARG, "encode_planes_batch: codec %d builds no CDF: d_status must be NULL", codec);
+    PlanesMap P;
+    if (!planes_map(codec, n, esize, chunk, P)) return fail(TRC_E_ARG, "encode_planes_batch: bad (codec, items, esize, chunk)");
+    if (!trc_planes_batch_ptrs_ok(items, 0, count)) return fail(TRC_E_ARG, "encode_planes_batch: every item's pointer must be non-null and 16-byte aligned");
+    const size_t table = trc_planes_batch_table_bytes(count, B.chunks), need = esize * P.slice + table;
+    if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
+    if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
+        return fail(TRC_E_ARG, "encode_planes_batch: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned");
+    uint8_t *w = (uint8_t *)d_work;
+    if ((rc = trc_planes_split_batch_dev(items, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream))) return rc;
+    for (unsigned k = 0; k < esize; k++) {         // as trc_encode_fplanes_dev
+        uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
+        uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
+        if (r.cdf && (rc = trc_cdfini_dev(plane, P.m, cdf, cdfnum, d_status + k, pw, stream))) return rc;
+        if ((rc = trc_encode_dev(codec, plane, P.m, chunk, cdf, cdfnum, d_clen + k * P.nc, (uint8_t *)d_payload + k * P.buf, d_total + k,
+                                 pw, P.work, stream))) return rc;
+    }
+    return TRC_OK;
+}
+
+extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                           const trc_planes_item *items, size_t count, size_t first_item, size_t item_count,
+                                           unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                           void *d_work, size_t work_bytes, void *stream)
+{
+    trc_planes_batch_plan B;
+    int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
+    if (rc) return rc;
+    const size_t n = (size_t)B.n_virtual, m = (size_t)B.m_total, nc = (size_t)B.chunks;
+    if ((rc = planes_common("decode_planes_batch", codec, n, esize, d_work))) return rc;
+    if ((rc = check_common(codec, m, chunk, d_cdf, cdfnum))) return rc;
+    if (first_item > count || item_count > count - first_item)
+        return fail(TRC_E_ARG, "decode_planes_batch: items [%zu, %zu + %zu) of %zu", first_item, first_item, item_count, count);
+    if (item_count == 0) return TRC_OK;
+    if (!trc_planes_batch_ptrs_ok(items, first_item, item_count)) return fail(TRC_E_ARG, "decode_planes_batch: every requested item's pointer must be non-null and 16-byte aligned");
+    size_t c0, cnt;
+    batch_chunk_range(items, first_item, item_count, esize, chunk, c0, cnt);
+    PlanesMap P;
+    if (!planes_range_map(codec, n, esize, chunk, cnt, P)) return fail(TRC_E_ARG, "decode_planes_batch: bad (codec, items, esize, chunk)");
+    const size_t table = trc_planes_batch_table_bytes(item_count, cnt), need = esize * P.slice + table;
+    if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
+    if (!d_clen || !d_payload || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3))
+        return fail(TRC_E_ARG, "decode_planes_batch: d_clen must be 4-byte, d_payload 2-byte aligned");
+    const TrcCodec &r = codec_row(codec);
+    uint8_t *w = (uint8_t *)d_work;
+    for (unsigned k = 0; k < esize; k++) {         // as trc_decode_fplanes_range_dev; the pad behind an item is decoded with it
+        uint8_t *plane = w + k * P.slice;
+        if ((rc = trc_decode_range_dev(codec, d_clen + k * nc, (const uint8_t *)d_payload + k * (size_t)B.pitch, m, chunk, c0, cnt,
+                                       r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
+    }
+    return trc_planes_join_batch_dev(w, P.slice, items, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
+}

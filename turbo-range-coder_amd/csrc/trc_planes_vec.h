@@ -1,6 +1,7 @@
 // trc_planes_vec.h -- what the plane kernels share (trc_planes.hip: split / join; trc_fplanes.hip: the same with a zigzag-delta
-// or xor filter; trc_planes_hist.hip: the histograms of the filtered planes): the byte separation of one thread's vector of 8
-// elements in registers, the filters' forward step, the launch shape and the argument rules.
+// or xor filter; trc_planes_hist.hip: the histograms of the filtered planes; trc_planes_batch.hip: split / join over a table of
+// separate allocations): the byte separation of one thread's vector of 8 elements in registers, the filters' forward step, the
+// launch shape and the argument rules.
 #ifndef TRC_PLANES_VEC_H
 #define TRC_PLANES_VEC_H
 #include <hip/hip_runtime.h>

@@ -69,6 +69,16 @@ class Range(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("first_chunk", "nchunks", "payload_off", "payload_len", "out_skip", "out_bytes")]
 
 
+class PlanesItem(C.Structure):
+    """struct trc_planes_item (include/trc_hip.h)"""
+    _fields_ = [("d_ptr", C.c_void_p), ("n", C.c_uint64)]
+
+
+class PlanesBatchPlan(C.Structure):
+    """struct trc_planes_batch_plan (include/trc_hip.h)"""
+    _fields_ = [(f, C.c_uint64) for f in ("m_total", "n_virtual", "chunks", "pitch", "pad_elems")]
+
+
 class PlanesAdvice(C.Structure):
     """struct trc_planes_advice (include/trc_hip.h)"""
     _fields_ = [("filter", C.c_int), ("esize", C.c_uint), ("filters", C.c_uint), ("m", C.c_uint64),
@@ -160,6 +170,21 @@ def lib():
         l.trc_encode_aplanes_host.restype = _sz
         l.trc_encode_aplanes_host.argtypes = [C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint, C.POINTER(PlanesAdvice)]
         l.trc_decode_xplanes_host.restype = _sz; l.trc_decode_xplanes_host.argtypes = [_vp, _sz, _vp, _sz]
+        _it = C.POINTER(PlanesItem)
+        l.trc_planes_batch_plan_host.restype = C.c_int
+        l.trc_planes_batch_plan_host.argtypes = [_it, _sz, C.c_uint, C.c_uint32, C.POINTER(PlanesBatchPlan), C.POINTER(C.c_uint64)]
+        l.trc_planes_batch_work_bytes.restype = _sz; l.trc_planes_batch_work_bytes.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32]
+        l.trc_planes_batch_range_work_bytes.restype = _sz
+        l.trc_planes_batch_range_work_bytes.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, _sz, _sz]
+        l.trc_planes_batch_table_bytes.restype = _sz; l.trc_planes_batch_table_bytes.argtypes = [_sz, C.c_uint64]
+        l.trc_planes_split_batch_dev.restype = C.c_int
+        l.trc_planes_split_batch_dev.argtypes = [_it, _sz, C.c_uint, C.c_uint32, _vp, _sz, _vp, _sz, _vp]
+        l.trc_planes_join_batch_dev.restype = C.c_int
+        l.trc_planes_join_batch_dev.argtypes = [_vp, _sz, _it, _sz, _sz, _sz, C.c_uint, C.c_uint32, _vp, _sz, _vp]
+        l.trc_encode_planes_batch_dev.restype = C.c_int
+        l.trc_encode_planes_batch_dev.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        l.trc_decode_planes_batch_dev.restype = C.c_int
+        l.trc_decode_planes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _sz, _sz, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _sz, _vp]
         l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
         l.trc_decode_host.restype = _sz; l.trc_decode_host.argtypes = [C.c_int, _vp, _sz, _vp, _sz, _vp, C.c_uint]
         l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
@@ -449,6 +474,112 @@ class PlanesCoder:
         clen = self.clen[4 * k * self.nch:4 * (k + 1) * self.nch].cpu().numpy().view(np.uint32).copy()
         payload = self.payload[k * self.pitch:k * self.pitch + tot].cpu().numpy().copy()
         return clen, payload, tot
+
+
+# ------------------------------------------------------- batched byte planes (include/trc_hip.h) ---
+PLANES_BATCH_MAX = 1 << 20
+
+
+def planes_items(pairs):
+    """a trc_planes_item array (host) of (device address or None, bytes) pairs"""
+    arr = (PlanesItem * max(len(pairs), 1))()
+    for i, (ptr, n) in enumerate(pairs):
+        arr[i].d_ptr, arr[i].n = ptr, n
+    return arr
+
+
+def planes_batch_plan(items, count, esize, chunk):
+    """trc_planes_batch_plan_host (needs no device) -> (dict of the plan's fields, first_chunk: list of count + 1)"""
+    p = PlanesBatchPlan()
+    first = (C.c_uint64 * (count + 1))()
+    _chk(lib().trc_planes_batch_plan_host(items, count, esize, chunk, C.byref(p), first))
+    return {f: int(getattr(p, f)) for f, _ in PlanesBatchPlan._fields_}, list(first)
+
+
+def planes_split_batch(items, count, esize, chunk, d_planes, pitch, d_table, table_bytes):
+    """enqueue trc_planes_split_batch_dev: the planes of the items' virtual buffer, plane k at d_planes[k * pitch:]"""
+    _chk(lib().trc_planes_split_batch_dev(items, count, esize, chunk, d_planes.data_ptr(), pitch, d_table.data_ptr(), table_bytes,
+                                          _cur_stream(d_planes)))
+
+
+def planes_join_batch(d_planes, offset, pitch, items, count, first_item, item_count, esize, chunk, d_table, table_bytes):
+    """enqueue trc_planes_join_batch_dev from d_planes[offset:] (offset = first_chunk[first_item] * chunk into a whole batch's planes)"""
+    _chk(lib().trc_planes_join_batch_dev(d_planes.data_ptr() + offset, pitch, items, count, first_item, item_count, esize, chunk,
+                                         d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
+class PlanesBatchCoder:
+    """The coded buffers of one batch of device tensors of one element size (bf16 / fp16: 2, fp32: 4, fp64 / int64: 8), coded by
+    trc_encode_planes_batch_dev as the planes of their virtual buffer: self.clen / payload / total / cdf / status are laid out as
+    PlanesCoder's for n = plan["n_virtual"].  decode(first_item, item_count) writes those items back into the tensors given (the
+    encoded ones by default).  Plumbing only."""
+
+    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None):
+        """esize: the element size where the tensors do not say it themselves (uint8 tensors of whole elements)"""
+        import torch
+        self.torch = torch
+        tensors = list(tensors)
+        if not tensors or any(not t.is_cuda or not t.is_contiguous() or t.element_size() != tensors[0].element_size() for t in tensors):
+            raise TrcError("a batch is a non-empty list of contiguous device tensors of one element size")
+        self.codec, self.chunk, self.esize, self.count = codec, chunk, esize or tensors[0].element_size(), len(tensors)
+        self.dev = tensors[0].device
+        self.sizes = [t.numel() * t.element_size() for t in tensors]
+        self.items = self._items(tensors)
+        self.plan, self.first = planes_batch_plan(self.items, self.count, self.esize, chunk)
+        self.nch, self.pitch = self.plan["chunks"], self.plan["pitch"]
+        self.cdfnum = _cdfnum(codec, cdfnum, prm)
+        self.work_bytes = lib().trc_planes_batch_work_bytes(codec, self.items, self.count, self.esize, chunk)
+        if self.work_bytes == 0:
+            raise TrcError("bad (codec, tensors, chunk)")
+        self.guard, self._guards = guard, []
+        self.work = self._buf(self.work_bytes)
+        self.clen = self._buf(4 * self.esize * self.nch)
+        self.payload = self._buf(self.esize * self.pitch)
+        self.total = self._buf(8 * self.esize)
+        self.cdf = self._buf(2 * self.esize * PLANES_CDF_STRIDE)
+        self.status = self._buf(4 * self.esize)
+        self.range_work, self.range_work_bytes = None, 0
+        self._tensors = tensors
+
+    _buf = PlanesCoder._buf
+    guards_ok = PlanesCoder.guards_ok
+    _stream = PlanesCoder._stream
+    cdf_of = PlanesCoder.cdf_of
+    result = PlanesCoder.result
+
+    def _items(self, tensors):
+        """tensors of the batch's sizes; None where decode is not to look"""
+        if len(tensors) != self.count or any(t is not None and t.numel() * t.element_size() != n for t, n in zip(tensors, self.sizes)):
+            raise TrcError("the tensors do not have the batch's sizes")
+        return planes_items([(t.data_ptr() if t is not None else None, n) for t, n in zip(tensors, self.sizes)])
+
+    def encode(self, flags=0):
+        st = self.codec in STATIC
+        _chk(lib().trc_encode_planes_batch_dev(self.codec | flags, self.items, self.count, self.esize, self.chunk,
+                                               self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                                               self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(),
+                                               self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode(self, first_item=0, item_count=None, out=None, flags=0):
+        """items [first_item, first_item + item_count) into out[i] (a list of count tensors, None outside the range; default: the
+        encoded tensors), in a workspace of its own that grows with the requested chunks"""
+        item_count = self.count - first_item if item_count is None else item_count
+        items = self.items if out is None else self._items(list(out))
+        need = lib().trc_planes_batch_range_work_bytes(self.codec, items, self.count, self.esize, self.chunk, first_item, item_count)
+        if need > self.range_work_bytes:
+            self.range_work, self.range_work_bytes = self._buf(need), need
+        if self.range_work is None:                            # nothing to size a workspace by: the call rejects or ignores these arguments itself
+            self.range_work = self._buf(0)
+        _chk(lib().trc_decode_planes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.count,
+                                               first_item, item_count, self.esize, self.chunk,
+                                               self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                               self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+
+    def stored_bytes(self):
+        """Synchronise: payload + directory (+ CDFs of a static coder) of all planes"""
+        self.torch.cuda.synchronize(self.dev)
+        tot = self.total[:8 * self.esize].cpu().numpy().view("<u8")
+        return int(tot.sum()) + self.esize * (4 * self.nch + (2 * (self.cdfnum + 1) if self.codec in STATIC else 0))
 
 
 # ------------------------------------------------------ reference-signature layer (host pointers) ---
