@@ -588,6 +588,46 @@ int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, const void *d
                                 unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                 void *d_work, size_t work_bytes, void *stream);
 
+/* ---- batched byte planes with a predictor filter PER ITEM ------------------------------------------------------------------
+ * The columns of a table and the pages of a cache are where the structure lies between neighbouring elements, and a table mixes
+ * natures at one element width: ids and timestamps want the zigzag delta, float columns want nothing.  So the filter of a batch is
+ * chosen per item.  `filters` is a HOST array of `count` bytes, filters[i] one of TRC_FILTER_NONE / ZDELTA / XOR, with the lifetime
+ * rule of `items`: free again when the call returns.
+ *        G(i)  = item i                                        where filters[i] == TRC_FILTER_NONE
+ *              = F(filters[i], seg = chunk, esize, item i)     otherwise          (the F of the filtered planes; items have no tail)
+ *        VF(items, filters, esize, chunk) = V([G(0), .., G(count - 1)], esize, chunk)
+ * Every item is filtered as if it stood alone, then the virtual buffer is built as before: the predictor restarts at every chunk and
+ * items start on chunk boundaries, so an item never sees its neighbour, the pad behind an item stays ZERO bytes in every plane (VF is
+ * V of the filtered items, not F of V), and plan, M, NC, first[] and pitch are those of the unfiltered batch.
+ * The whole contract:  encode_fbatch(codec, items, filters, ...)  ==  trc_encode_planes_dev(codec, VF, M * esize, esize, chunk, ...)
+ * byte for byte -- directory, payload, totals, per-plane CDFs and statuses -- in buffers of that call's shapes.  So:
+ *   - filters == NULL or all TRC_FILTER_NONE IS the unfiltered batched call of the same name, launching its kernels;
+ *   - a batch of one item with filter f is trc_encode_fplanes_dev(codec, f, item, ...) on that item;
+ *   - item i is still chunks [first[i], first[i] + nc[i]) of every plane and its inverse scan is local to them: any item range
+ *     decodes alone, as before.
+ *
+ * Every argument, alignment, workspace and table rule is the one of the unfiltered batched call with the same name, the no-slack
+ * read rule included (the kernels read bytes [0, n[i]) of item i and nothing else); trc_planes_batch_work_bytes,
+ * trc_planes_batch_range_work_bytes and trc_planes_batch_table_bytes serve unchanged: the filter needs no workspace and travels in
+ * the item's 32-byte record.  The join and the decoder take the filters of the WHOLE batch (count entries) and validate all of them.
+ * Errors: those of the unfiltered calls, and TRC_E_ARG with the item's index in trc_last_error() for a filter id outside {0, 1, 2}.
+ * The order of the checks is the plan (sizes, esize, chunk: host only), then the filters, then pointers and buffers -- so a bad
+ * filter is reported without a device.  The seven low-nibble coders, TRC_TABLES_READY and TRC_DIR_READY are refused as before.
+ * Any batch with a filter other than NONE runs one filtered split (join) kernel in place of the unfiltered one. */
+int trc_planes_split_fbatch_dev(const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+                                void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream);
+int trc_planes_join_fbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, size_t count,
+                               size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                               void *d_table, size_t table_bytes, void *stream);
+int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+                                 uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                 uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                 void *d_work, size_t work_bytes, void *stream);
+int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                 const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
+                                 unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_work, size_t work_bytes, void *stream);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

@@ -288,3 +288,6 @@ extern "C" int trc_planes_join_batch_dev(const void *d_planes, size_t pitch, con
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_join_batch: %s", hipGetErrorString(e));
 }
+
+// ---- the same with a predictor filter per item ----------------------------------------------------------------------------------
+#include "trc_fplanes_batch.inc"

@@ -7,6 +7,7 @@
 //   workspace: the planes workspace of (M * esize, esize, chunk) -- planes_map / planes_range_map -- followed by the table
 int trc_planes_batch_plan_quiet(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, trc_planes_batch_plan *plan, uint64_t *first_chunk);
 int trc_planes_batch_ptrs_ok(const trc_planes_item *items, size_t first_item, size_t item_count);
+int trc_planes_batch_filters(const char *who, const uint8_t *filters, size_t count, bool *any);      // trc_fplanes_batch.inc
 
 extern "C" size_t trc_planes_batch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
 {
@@ -39,29 +40,30 @@ extern "C" size_t trc_planes_batch_range_work_bytes(int codec, const trc_planes_
     return esize * P.slice + trc_planes_batch_table_bytes(item_count, cnt);
 }
 
-extern "C" int trc_encode_planes_batch_dev(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
-                                           uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
-                                           uint32_t *d_clen, void *d_payload, uint64_t *d_total,
-                                           void *d_work, size_t work_bytes, void *stream)
+// both encoders: filters == NULL is the unfiltered batch (the filtered split hands an all-NONE batch to the unfiltered kernels)
+static int encode_batch(const char *who, int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+                        uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status, uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                        void *d_work, size_t work_bytes, void *stream)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
+    if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
     const size_t n = (size_t)B.n_virtual;
-    if ((rc = planes_common("encode_planes_batch", codec, n, esize, d_work))) return rc;
+    if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
     const TrcCodec &r = codec_row(codec);
-    if (r.cdf && !d_status) return fail(TRC_E_ARG, "encode_planes_batch: a static coder needs d_status (one int32 per plane)");
-    if (!r.cdf && d_status) return fail(TRC_E_ARG, "encode_planes_batch: codec %d builds no CDF: d_status must be NULL", codec);
+    if (r.cdf && !d_status) return fail(TRC_E_ARG, "%s: a static coder needs d_status (one int32 per plane)", who);
+    if (!r.cdf && d_status) return fail(TRC_E_ARG, "%s: codec %d builds no CDF: d_status must be NULL", who, codec);
     PlanesMap P;
-    if (!planes_map(codec, n, esize, chunk, P)) return fail(TRC_E_ARG, "encode_planes_batch: bad (codec, items, esize, chunk)");
-    if (!trc_planes_batch_ptrs_ok(items, 0, count)) return fail(TRC_E_ARG, "encode_planes_batch: every item's pointer must be non-null and 16-byte aligned");
+    if (!planes_map(codec, n, esize, chunk, P)) return fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk)", who);
+    if (!trc_planes_batch_ptrs_ok(items, 0, count)) return fail(TRC_E_ARG, "%s: every item's pointer must be non-null and 16-byte aligned", who);
     const size_t table = trc_planes_batch_table_bytes(count, B.chunks), need = esize * P.slice + table;
     if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
     if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
-        return fail(TRC_E_ARG, "encode_planes_batch: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned");
+        return fail(TRC_E_ARG, "%s: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned", who);
     uint8_t *w = (uint8_t *)d_work;
-    if ((rc = trc_planes_split_batch_dev(items, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream))) return rc;
+    if ((rc = trc_planes_split_fbatch_dev(items, filters, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream))) return rc;
     for (unsigned k = 0; k < esize; k++) {         // as trc_encode_fplanes_dev
         uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
         uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
@@ -72,29 +74,47 @@ extern "C" int trc_encode_planes_batch_dev(int codec, const trc_planes_item *ite
     return TRC_OK;
 }
 
-extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
-                                           const trc_planes_item *items, size_t count, size_t first_item, size_t item_count,
-                                           unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+extern "C" int trc_encode_planes_batch_dev(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                           uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                           uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                                            void *d_work, size_t work_bytes, void *stream)
+{
+    return encode_batch("encode_planes_batch", codec, items, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+                        d_work, work_bytes, stream);
+}
+extern "C" int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+                                            uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                            uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                            void *d_work, size_t work_bytes, void *stream)
+{
+    return encode_batch("encode_fplanes_batch", codec, items, filters, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+                        d_work, work_bytes, stream);
+}
+
+static int decode_batch(const char *who, int codec, const uint32_t *d_clen, const void *d_payload,
+                        const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
+                        unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                        void *d_work, size_t work_bytes, void *stream)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
+    if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
     const size_t n = (size_t)B.n_virtual, m = (size_t)B.m_total, nc = (size_t)B.chunks;
-    if ((rc = planes_common("decode_planes_batch", codec, n, esize, d_work))) return rc;
+    if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, m, chunk, d_cdf, cdfnum))) return rc;
     if (first_item > count || item_count > count - first_item)
-        return fail(TRC_E_ARG, "decode_planes_batch: items [%zu, %zu + %zu) of %zu", first_item, first_item, item_count, count);
+        return fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
     if (item_count == 0) return TRC_OK;
-    if (!trc_planes_batch_ptrs_ok(items, first_item, item_count)) return fail(TRC_E_ARG, "decode_planes_batch: every requested item's pointer must be non-null and 16-byte aligned");
+    if (!trc_planes_batch_ptrs_ok(items, first_item, item_count)) return fail(TRC_E_ARG, "%s: every requested item's pointer must be non-null and 16-byte aligned", who);
     size_t c0, cnt;
     batch_chunk_range(items, first_item, item_count, esize, chunk, c0, cnt);
     PlanesMap P;
-    if (!planes_range_map(codec, n, esize, chunk, cnt, P)) return fail(TRC_E_ARG, "decode_planes_batch: bad (codec, items, esize, chunk)");
+    if (!planes_range_map(codec, n, esize, chunk, cnt, P)) return fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk)", who);
     const size_t table = trc_planes_batch_table_bytes(item_count, cnt), need = esize * P.slice + table;
     if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
     if (!d_clen || !d_payload || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3))
-        return fail(TRC_E_ARG, "decode_planes_batch: d_clen must be 4-byte, d_payload 2-byte aligned");
+        return fail(TRC_E_ARG, "%s: d_clen must be 4-byte, d_payload 2-byte aligned", who);
     const TrcCodec &r = codec_row(codec);
     uint8_t *w = (uint8_t *)d_work;
     for (unsigned k = 0; k < esize; k++) {         // as trc_decode_fplanes_range_dev; the pad behind an item is decoded with it
@@ -102,5 +122,22 @@ extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, co
         if ((rc = trc_decode_range_dev(codec, d_clen + k * nc, (const uint8_t *)d_payload + k * (size_t)B.pitch, m, chunk, c0, cnt,
                                        r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return trc_planes_join_batch_dev(w, P.slice, items, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
+    return trc_planes_join_fbatch_dev(w, P.slice, items, filters, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
+}
+
+extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                           const trc_planes_item *items, size_t count, size_t first_item, size_t item_count,
+                                           unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                           void *d_work, size_t work_bytes, void *stream)
+{
+    return decode_batch("decode_planes_batch", codec, d_clen, d_payload, items, nullptr, count, first_item, item_count, esize, chunk, d_cdf, cdfnum,
+                        d_work, work_bytes, stream);
+}
+extern "C" int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                            const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
+                                            unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                            void *d_work, size_t work_bytes, void *stream)
+{
+    return decode_batch("decode_fplanes_batch", codec, d_clen, d_payload, items, filters, count, first_item, item_count, esize, chunk, d_cdf, cdfnum,
+                        d_work, work_bytes, stream);
 }

@@ -185,6 +185,15 @@ def lib():
         l.trc_encode_planes_batch_dev.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
         l.trc_decode_planes_batch_dev.restype = C.c_int
         l.trc_decode_planes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _sz, _sz, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _sz, _vp]
+        _fl = C.POINTER(C.c_uint8)                  # the per-item filters of the filtered batch calls: a host array, or None
+        l.trc_planes_split_fbatch_dev.restype = C.c_int
+        l.trc_planes_split_fbatch_dev.argtypes = [_it, _fl] + l.trc_planes_split_batch_dev.argtypes[1:]
+        l.trc_planes_join_fbatch_dev.restype = C.c_int
+        l.trc_planes_join_fbatch_dev.argtypes = [_vp, _sz, _it, _fl] + l.trc_planes_join_batch_dev.argtypes[3:]
+        l.trc_encode_fplanes_batch_dev.restype = C.c_int
+        l.trc_encode_fplanes_batch_dev.argtypes = [C.c_int, _it, _fl] + l.trc_encode_planes_batch_dev.argtypes[2:]
+        l.trc_decode_fplanes_batch_dev.restype = C.c_int
+        l.trc_decode_fplanes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _fl] + l.trc_decode_planes_batch_dev.argtypes[4:]
         l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
         l.trc_decode_host.restype = _sz; l.trc_decode_host.argtypes = [C.c_int, _vp, _sz, _vp, _sz, _vp, C.c_uint]
         l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
@@ -508,13 +517,37 @@ def planes_join_batch(d_planes, offset, pitch, items, count, first_item, item_co
                                          d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
 
 
+def planes_filters(filters, count):
+    """the per-item filters of a batch as the host array the filtered batch calls take: None (no filter), one int for every item,
+    or a sequence of `count` ints.  Values are not judged here: the library does that."""
+    if filters is None:
+        return None
+    f = [filters] * count if isinstance(filters, int) else [int(x) for x in filters]
+    if len(f) != count or any(not 0 <= x <= 255 for x in f):
+        raise TrcError("filters: one byte per item of the batch")
+    return (C.c_uint8 * max(count, 1))(*f)
+
+
+def planes_split_fbatch(items, filters, count, esize, chunk, d_planes, pitch, d_table, table_bytes):
+    """enqueue trc_planes_split_fbatch_dev: planes_split_batch of the items filtered one by one (filters: see planes_filters)"""
+    _chk(lib().trc_planes_split_fbatch_dev(items, planes_filters(filters, count), count, esize, chunk, d_planes.data_ptr(), pitch,
+                                           d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
+def planes_join_fbatch(d_planes, offset, pitch, items, filters, count, first_item, item_count, esize, chunk, d_table, table_bytes):
+    """enqueue trc_planes_join_fbatch_dev from d_planes[offset:], the inverse of planes_split_fbatch (filters: those of the whole batch)"""
+    _chk(lib().trc_planes_join_fbatch_dev(d_planes.data_ptr() + offset, pitch, items, planes_filters(filters, count), count, first_item,
+                                          item_count, esize, chunk, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
 class PlanesBatchCoder:
     """The coded buffers of one batch of device tensors of one element size (bf16 / fp16: 2, fp32: 4, fp64 / int64: 8), coded by
     trc_encode_planes_batch_dev as the planes of their virtual buffer: self.clen / payload / total / cdf / status are laid out as
     PlanesCoder's for n = plan["n_virtual"].  decode(first_item, item_count) writes those items back into the tensors given (the
-    encoded ones by default).  Plumbing only."""
+    encoded ones by default).  filters (None, one FILTER_* for all items, or one per item) puts a predictor filter in front of
+    each item's planes: the trc_*_fplanes_batch_dev calls, and decode() passes the same filters on.  Plumbing only."""
 
-    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None):
+    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None):
         """esize: the element size where the tensors do not say it themselves (uint8 tensors of whole elements)"""
         import torch
         self.torch = torch
@@ -525,6 +558,7 @@ class PlanesBatchCoder:
         self.dev = tensors[0].device
         self.sizes = [t.numel() * t.element_size() for t in tensors]
         self.items = self._items(tensors)
+        self.filters = planes_filters(filters, self.count)
         self.plan, self.first = planes_batch_plan(self.items, self.count, self.esize, chunk)
         self.nch, self.pitch = self.plan["chunks"], self.plan["pitch"]
         self.cdfnum = _cdfnum(codec, cdfnum, prm)
@@ -555,10 +589,12 @@ class PlanesBatchCoder:
 
     def encode(self, flags=0):
         st = self.codec in STATIC
-        _chk(lib().trc_encode_planes_batch_dev(self.codec | flags, self.items, self.count, self.esize, self.chunk,
-                                               self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
-                                               self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(),
-                                               self.work.data_ptr(), self.work_bytes, self._stream()))
+        tail = (self.count, self.esize, self.chunk, self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream())
+        if self.filters is None:
+            _chk(lib().trc_encode_planes_batch_dev(self.codec | flags, self.items, *tail))
+        else:
+            _chk(lib().trc_encode_fplanes_batch_dev(self.codec | flags, self.items, self.filters, *tail))
 
     def decode(self, first_item=0, item_count=None, out=None, flags=0):
         """items [first_item, first_item + item_count) into out[i] (a list of count tensors, None outside the range; default: the
@@ -570,10 +606,12 @@ class PlanesBatchCoder:
             self.range_work, self.range_work_bytes = self._buf(need), need
         if self.range_work is None:                            # nothing to size a workspace by: the call rejects or ignores these arguments itself
             self.range_work = self._buf(0)
-        _chk(lib().trc_decode_planes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.count,
-                                               first_item, item_count, self.esize, self.chunk,
-                                               self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
-                                               self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+        tail = (self.count, first_item, item_count, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                self.range_work.data_ptr(), self.range_work_bytes, self._stream())
+        if self.filters is None:
+            _chk(lib().trc_decode_planes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, *tail))
+        else:
+            _chk(lib().trc_decode_fplanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.filters, *tail))
 
     def stored_bytes(self):
         """Synchronise: payload + directory (+ CDFs of a static coder) of all planes"""
