@@ -32,6 +32,27 @@ __device__ __forceinline__ uint4 trc_ld16_a2(const u8 *p)
 }
 __device__ __forceinline__ u32 trc_ld32_a2(const u8 *p) { return *(const u32_a2 *)p; }
 
+// the same load through a pointer that is known to point to global memory although the compiler cannot see it (it came out of a
+// table in LDS): global_load_dwordx4 instead of flat_load_dwordx4
+__device__ __forceinline__ uint4 trc_ld16_a2_global(const u8 *p)
+{
+    typedef u32 v4u_a2 __attribute__((ext_vector_type(4), aligned(2)));
+    const v4u_a2 v = *(const __attribute__((address_space(1))) v4u_a2 *)(uintptr_t)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// bytes [sh, sh + 16) of the 32-byte string t | u, sh = 0 .. 15: t's bytes from sh on, then u's first sh bytes
+__device__ __forceinline__ uint4 trc_splice16(uint4 t, uint4 u, u32 sh)
+{
+    const u32 x[8] = { t.x, t.y, t.z, t.w, u.x, u.y, u.z, u.w };
+    const u32 ws = sh >> 2, bs = sh & 3u;
+    u32 y[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) y[i] = ws == 0u ? x[i] : ws == 1u ? x[i + 1] : ws == 2u ? x[i + 2] : x[i + 3];
+    return make_uint4(__builtin_amdgcn_alignbyte(y[1], y[0], bs), __builtin_amdgcn_alignbyte(y[2], y[1], bs),
+                      __builtin_amdgcn_alignbyte(y[3], y[2], bs), __builtin_amdgcn_alignbyte(y[4], y[3], bs));
+}
+
 // streaming 16-byte accesses (chunk bytes: read once by an encoder, written once by a decoder): the nontemporal hint
 // keeps them from displacing the lines that are revisited (staged segments, payload lines).  Headline step 227 ->
 // 217 us.  NOT for the gather's reads of the staged payloads: with the hint the step is back to 228 us.

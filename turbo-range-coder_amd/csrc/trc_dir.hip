@@ -131,7 +131,7 @@ void trc_launch_range_dir(const uint32_t *d_clen, uint32_t nchunks, size_t n, ui
 // [rest at the start of region B]).  A vector belongs to the piece that holds its FIRST byte and a fixed set of
 // threads walks the vectors of one piece, so nothing is searched: every load address follows from the prefix table
 // in LDS and a thread's loads are independent.  A vector that runs past its piece takes the rest from the next piece
-// (second load, merged by byte mask); if even the next piece ends inside it (tiny pieces) it is assembled byte by
+// (second load, the two spliced); if either piece is shorter than 16 bytes (tiny pieces) it is assembled byte by
 // byte.  (History, 100 MB / chunk 512: chunk-after-chunk copy 55 us, per-vector binary search 54 us, this walk 49 us;
 // the two-part layout went from a per-chunk wave copy, 152 us, to the same walk.)
 #ifndef TRC_GATHER_VPT
@@ -209,7 +209,25 @@ __global__ __launch_bounds__(256) TRC_GATHER_ATTR void trc_gather_kernel(const u
         const u8 *sa = src_of(k);
         const u8 *sb = k + 1 < NP ? src_of(k + 1) : sa;
         const u32 e2 = ex_s[k + 2 > NP ? NP : k + 2];
-        const u32 vl = v_hi - 1u;                               // only the piece's last vector can straddle its end
+        // No load leaves the piece it takes bytes from (DESIGN.md "The gather's loads stay inside their pieces"): a vector that
+        // runs past the end of piece k loads the piece's LAST 16 bytes instead (offset pl - 16: its own bytes are the top sp of
+        // them), the next piece gives its FIRST 16 bytes, and trc_splice16 cuts the vector out of the two.  Pieces shorter than
+        // 16 bytes on either side go byte by byte.  Slots past the piece's last vector load nothing.
+        const u32 pl = e1 - e0;
+        const bool a16 = pl >= 16u;                             // piece k can give a 16-byte load
+        const bool b16 = k + 1 < NP && e2 - e1 >= 16u;          // the next piece can
+        auto bytewise = [&](u32 dv) {                           // three or more pieces inside 16 bytes, or a piece below 16 bytes
+            u32 kk = k;
+            const u8 *p = sa;
+            for (u32 q = 0; q < 16; q++) {
+                while (dv + q >= ex_s[kk + 1]) { kk++; p = src_of(kk); }
+                dst0[dv + q] = p[dv + q - ex_s[kk]];
+            }
+        };
+        if (!a16) {                                             // at most one vector starts inside a piece this short
+            if (sub == 0 && v_lo < v_hi) bytewise(head + (v_lo << 4));
+            return;
+        }
         for (u32 v0 = v_lo + sub; v0 < v_hi; v0 += VPT * TPP) {  // VPT vectors per thread per trip
             uint4 a[VPT], b[VPT];
             u32 d[VPT];
@@ -219,14 +237,13 @@ __global__ __launch_bounds__(256) TRC_GATHER_ATTR void trc_gather_kernel(const u
                 const u32 v = v0 + TPP * (u32)j;
                 ok[j] = v < v_hi;
                 d[j] = head + ((ok[j] ? v : v0) << 4);
-                a[j] = trc_ld16_a2(sa + (d[j] - e0));
+                a[j] = make_uint4(0u, 0u, 0u, 0u);
+                if (ok[j]) a[j] = trc_ld16_a2_global(sa + trc_min(d[j] - e0, pl - 16u));
                 b[j] = a[j];
             }
 #pragma unroll
-            for (int j = 0; j < (int)VPT; j++) {
-                const u32 v = v0 + TPP * (u32)j;
-                if (ok[j] && v == vl && d[j] + 16u > e1 && d[j] + 16u <= e2) b[j] = trc_ld16_a2(sb - (e1 - d[j]));
-            }
+            for (int j = 0; j < (int)VPT; j++)
+                if (ok[j] && d[j] + 16u > e1 && b16) b[j] = trc_ld16_a2_global(sb);
 #pragma unroll
             for (int j = 0; j < (int)VPT; j++) {
                 if (!ok[j]) continue;
@@ -235,24 +252,8 @@ __global__ __launch_bounds__(256) TRC_GATHER_ATTR void trc_gather_kernel(const u
                 // 29.9 -> 41.0; the nontemporal hint 29.8 -> 39.4 and the decoder behind it 60.4 -> 69.5, profiles/r05_notes.md; its
                 // stores stay plain)
                 if (sp >= 16u) { *(uint4 *)(dst0 + d[j]) = a[j]; continue; }
-                if (d[j] + 16u <= e2) {
-                    const u32 aw[4] = { a[j].x, a[j].y, a[j].z, a[j].w }, bw[4] = { b[j].x, b[j].y, b[j].z, b[j].w };
-                    u32 r[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int nb = (int)sp - 4 * q;
-                        const u32 m = nb >= 4 ? 0xffffffffu : nb <= 0 ? 0u : ((1u << (8 * nb)) - 1u);
-                        r[q] = (aw[q] & m) | (bw[q] & ~m);
-                    }
-                    *(uint4 *)(dst0 + d[j]) = make_uint4(r[0], r[1], r[2], r[3]);
-                } else {                                       // three or more pieces inside 16 bytes: byte by byte
-                    u32 kk = k;
-                    const u8 *p = sa;
-                    for (u32 q = 0; q < 16; q++) {
-                        while (d[j] + q >= ex_s[kk + 1]) { kk++; p = src_of(kk); }
-                        dst0[d[j] + q] = p[d[j] + q - ex_s[kk]];
-                    }
-                }
+                if (b16) *(uint4 *)(dst0 + d[j]) = trc_splice16(a[j], b[j], 16u - sp);
+                else bytewise(d[j]);
             }
         }
     }
