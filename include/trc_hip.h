@@ -628,6 +628,52 @@ int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, const void *
                                  unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                  void *d_work, size_t work_bytes, void *stream);
 
+/* ---- the batch advisor: which filter for which item? -------------------------------------------------------------------------
+ * The planes advisor above reads one contiguous buffer with TRC_PAD behind it; the items of a batch are neither.  These calls are
+ * that advisor over the batch's pointer table: ONE launch reads every item of an item range once and leaves the plane histograms
+ * of every requested filter per item, and a host function turns them into one filter id per item by the same 1/64 rule.
+ *
+ * trc_planes_hist_batch_dev(filters, items, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes, stream).
+ * The whole contract: for j in [0, item_count) the 3 * esize * 256 counters at d_hist + j * 3 * esize * 256 equal, exactly, what
+ *        trc_planes_hist_dev(filters, items[first_item + j].d_ptr, items[first_item + j].n, esize, seg = chunk, ...)
+ * writes: the predictor restarts every `chunk` elements of the item (where the filtered batch calls restart it), the batch's pad
+ * elements are counted nowhere, rows of filters not requested stay zero -- so every slice serves trc_planes_advise as it stands.
+ * The call zeroes trc_planes_hist_batch_bytes(item_count, esize) = item_count * trc_planes_hist_bytes(esize) bytes on the stream
+ * first and writes nothing behind them.  It keeps the batch's no-slack rule: it reads bytes [0, n[i]) of a requested item and
+ * nothing else.  Items outside the range are looked at for their n only, and their d_ptr may be NULL; item_count == 0 is TRC_OK with
+ * nothing enqueued.  Checks, in this order: the plan (sizes, esize, chunk: host only), filters in 1 .. 7, the range, the pointers
+ * (the requested items' as in the other batched calls, d_hist 8-byte aligned), the table: 256-byte aligned,
+ * trc_planes_batch_table_bytes(item_count, the chunks of the range) bytes, TRC_E_WORK where it is smaller.  `items` is free again
+ * when the call returns, as in the other batched calls; apart from that upload the call only enqueues work.  TRC_PLANES_GRID and
+ * TRC_PLANES_HIST_ROUND_VECS act as on trc_planes_hist_dev.
+ *
+ * trc_planes_advise_batch (host only, no GPU needed): entry i of filters_out (and of advice, count entries, may be NULL) is exactly
+ * what trc_planes_advise(hist + i * 3 * esize * 256, filters, esize, n[i] / esize, &a) gives -- same estimates, same ties, same 1/64
+ * rule.  It looks at no d_ptr.  Where an item fails (a row that does not sum to its elements, n[i] no whole number of elements) the
+ * call returns TRC_E_ARG with that item's index in trc_last_error() and writes nothing to filters_out (entries of advice in front
+ * of the failing item may have been written); count == 0, a bad esize or filters outside 1 .. 7 are TRC_E_ARG as well.
+ *
+ * trc_planes_advise_batch_dev does both and SYNCHRONISES: it is the one device call of this header that waits for `stream`, because
+ * the choice is made on the host (the choice must be trc_planes_advise's bit for bit, and a device log2 would not promise that at
+ * the 1/64 edge).  It walks the batch in slabs of consecutive items whose histograms fit TRC_PLANES_ADVISE_SLAB_BYTES: per slab
+ * trc_planes_hist_batch_dev, a copy of the histograms to the host, trc_planes_advise_batch.  The result is what the three pieces
+ * give when called by hand on the whole batch.  d_work: 256-byte aligned, trc_planes_advise_batch_work_bytes bytes = the slab's
+ * histograms and the table of the largest slab; it does not grow with count beyond that (0 for what the call rejects).
+ * TRC_PLANES_ADVISE_SLAB_ITEMS in the environment lowers the items per slab (test aid).  Every item's d_ptr is read.  On an error
+ * nothing is written to filters_out. */
+#define TRC_PLANES_ADVISE_SLAB_BYTES (8u << 20)
+size_t trc_planes_hist_batch_bytes(size_t item_count, unsigned esize);   /* 0 for a bad esize / 0 items */
+int    trc_planes_hist_batch_dev(unsigned filters, const trc_planes_item *items, size_t count,
+                                 size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                                 uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);
+int    trc_planes_advise_batch(const uint64_t *hist, unsigned filters, unsigned esize,
+                               const trc_planes_item *items, size_t count,
+                               uint8_t *filters_out, trc_planes_advice *advice /* count entries, may be NULL */);
+size_t trc_planes_advise_batch_work_bytes(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk);
+int    trc_planes_advise_batch_dev(unsigned filters, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                   uint8_t *filters_out, trc_planes_advice *advice,
+                                   void *d_work, size_t work_bytes, void *stream);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

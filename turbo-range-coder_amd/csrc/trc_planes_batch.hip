@@ -1,5 +1,6 @@
 // trc_planes_batch.hip -- byte planes of MANY separate allocations (tensors of a checkpoint, pages of a cache, columns of a table):
-// a split that gathers from a pointer table into one long plane per byte position, the join that scatters back, and the plan.
+// a split that gathers from a pointer table into one long plane per byte position, the join that scatters back, and the plan; behind
+// them the same with a filter per item (trc_fplanes_batch.inc) and the advisor's histograms per item (trc_planes_hist_batch.inc).
 //
 // Layout (include/trc_hip.h): item i has m[i] elements and nc[i] = ceil(m[i] / chunk) chunks; every item starts on
 // a chunk boundary of the VIRTUAL buffer V, every item but the last is followed by zero elements up to nc[i] * chunk, so V has
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "trc_planes_vec.h"
+#include "trc_planes_count.h"                     // the advisor's LDS counters (trc_planes_hist_batch.inc)
 
 // one item as the kernels see it; `first` and `v0` count from the first chunk of the call's chunk range
 struct BatchRec { uint64_t ptr, m, v0, first; };        // base address, elements, first vector (first * chunk / 8), first chunk
@@ -291,3 +293,6 @@ extern "C" int trc_planes_join_batch_dev(const void *d_planes, size_t pitch, con
 
 // ---- the same with a predictor filter per item ----------------------------------------------------------------------------------
 #include "trc_fplanes_batch.inc"
+
+// ---- the advisor's histograms, per item ---------------------------------------------------------------------------------------
+#include "trc_planes_hist_batch.inc"

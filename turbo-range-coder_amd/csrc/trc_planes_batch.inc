@@ -141,3 +141,105 @@ extern "C" int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, c
     return decode_batch("decode_fplanes_batch", codec, d_clen, d_payload, items, filters, count, first_item, item_count, esize, chunk, d_cdf, cdfnum,
                         d_work, work_bytes, stream);
 }
+
+// ---- the batch advisor: a filter per item from the histograms of trc_planes_hist_batch_dev ---------------------------------------
+int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                              uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);      // trc_planes_hist_batch.inc
+
+// trc_planes_advise on items [base, base + count) of a batch, hist = the first one's slice: choice[i] and advice[i] (may be NULL)
+// count from `base` as well; the index in an error's text is the item's index in the batch
+static int advise_items(const uint64_t *hist, unsigned filters, unsigned esize, const trc_planes_item *items, size_t base, size_t count,
+                        uint8_t *choice, trc_planes_advice *advice)
+{
+    const size_t slice = (size_t)3 * esize * 256;
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t n = items[base + i].n;
+        if (n < esize || n % esize)
+            return fail(TRC_E_ARG, "planes_advise_batch: item %zu has %llu bytes: not a whole number (at least one) of %u-byte elements", base + i, (unsigned long long)n, esize);
+        trc_planes_advice a;
+        if (trc_planes_advise(hist + i * slice, filters, esize, (size_t)(n / esize), &a)) {
+            char why[400];
+            snprintf(why, sizeof why, "%s", g_err);
+            return fail(TRC_E_ARG, "planes_advise_batch: item %zu: %s", base + i, why);
+        }
+        choice[base + i] = (uint8_t)a.filter;
+        if (advice) advice[base + i] = a;
+    }
+    return TRC_OK;
+}
+
+// host only.  The choices reach filters_out only when every item has passed.
+extern "C" int trc_planes_advise_batch(const uint64_t *hist, unsigned filters, unsigned esize, const trc_planes_item *items, size_t count,
+                                       uint8_t *filters_out, trc_planes_advice *advice)
+{
+    if (!hist || !items || !filters_out) return fail(TRC_E_ARG, "planes_advise_batch: null histograms, items or filters_out");
+    if (count == 0 || count > TRC_PLANES_BATCH_MAX) return fail(TRC_E_ARG, "planes_advise_batch: %zu items (1 .. %u)", count, TRC_PLANES_BATCH_MAX);
+    if (filters < 1 || filters > 7) return fail(TRC_E_ARG, "planes_advise_batch: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", filters);
+    if (!planes_esize_ok(esize)) return fail(TRC_E_ARG, "planes_advise_batch: esize %u (2, 4 or 8)", esize);
+    std::vector<uint8_t> choice(count);
+    const int rc = advise_items(hist, filters, esize, items, 0, count, choice.data(), advice);
+    if (rc) return rc;
+    memcpy(filters_out, choice.data(), count);
+    return TRC_OK;
+}
+
+// items per slab of trc_planes_advise_batch_dev: what TRC_PLANES_ADVISE_SLAB_BYTES of histograms hold; TRC_PLANES_ADVISE_SLAB_ITEMS
+// in the environment lowers it (test aid: a small batch in several slabs)
+static size_t advise_slab_items(unsigned esize)
+{
+    size_t s = TRC_PLANES_ADVISE_SLAB_BYTES / trc_planes_hist_bytes(esize);
+    const char *e = getenv("TRC_PLANES_ADVISE_SLAB_ITEMS");
+    if (e) { const long x = strtol(e, 0, 10); if (x >= 1 && (size_t)x < s) s = (size_t)x; }
+    return s;
+}
+// the table of the largest slab of a planned batch
+static size_t advise_table_bytes(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+{
+    const size_t slab = advise_slab_items(esize);
+    size_t table = 0;
+    for (size_t i0 = 0; i0 < count; i0 += slab) {
+        const size_t cnt = count - i0 < slab ? count - i0 : slab;
+        uint64_t chunks = 0;
+        for (size_t i = i0; i < i0 + cnt; i++) chunks += (items[i].n / esize + chunk - 1) / chunk;
+        const size_t t = trc_planes_batch_table_bytes(cnt, chunks);
+        if (t > table) table = t;
+    }
+    return table;
+}
+// the slab's histograms | the table of the largest slab
+extern "C" size_t trc_planes_advise_batch_work_bytes(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+{
+    if (trc_planes_batch_plan_quiet(items, count, esize, chunk, nullptr, nullptr) || !trc_planes_batch_ptrs_ok(items, 0, count)) return 0;
+    return TRC_PLANES_ADVISE_SLAB_BYTES + advise_table_bytes(items, count, esize, chunk);
+}
+
+extern "C" int trc_planes_advise_batch_dev(unsigned filters, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                           uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
+{
+    trc_planes_batch_plan B;
+    int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
+    if (rc) return rc;
+    if (filters < 1 || filters > 7) return fail(TRC_E_ARG, "planes_advise_batch: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", filters);
+    if (!filters_out) return fail(TRC_E_ARG, "planes_advise_batch: null filters_out");
+    if (!trc_planes_batch_ptrs_ok(items, 0, count)) return fail(TRC_E_ARG, "planes_advise_batch: every item's pointer must be non-null and 16-byte aligned");
+    if (!d_work || ((uintptr_t)d_work & 255)) return fail(TRC_E_ARG, "planes_advise_batch: the workspace must be 256-byte aligned");
+    const size_t table = advise_table_bytes(items, count, esize, chunk), need = TRC_PLANES_ADVISE_SLAB_BYTES + table;
+    if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
+    const size_t slab = advise_slab_items(esize), slice = (size_t)3 * esize * 256;
+    hipStream_t s = (hipStream_t)stream;
+    uint64_t *d_hist = (uint64_t *)d_work;
+    std::vector<uint64_t> hist((count < slab ? count : slab) * slice);
+    std::vector<uint8_t> choice(count);
+    for (size_t i0 = 0; i0 < count; i0 += slab) {
+        const size_t cnt = count - i0 < slab ? count - i0 : slab;
+        if ((rc = trc_planes_hist_batch_run(filters, items, i0, cnt, esize, chunk, d_hist, (uint8_t *)d_work + TRC_PLANES_ADVISE_SLAB_BYTES, table, s))) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        HIPCHK(hipMemcpyAsync(hist.data(), d_hist, cnt * slice * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if ((rc = advise_items(hist.data(), filters, esize, items, i0, cnt, choice.data(), advice))) return rc;
+    }
+    memcpy(filters_out, choice.data(), count);
+    return TRC_OK;
+}

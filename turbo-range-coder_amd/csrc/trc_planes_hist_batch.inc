@@ -1,0 +1,174 @@
+// trc_planes_hist_batch.inc -- the planes advisor over a BATCH (included by trc_planes_batch.hip behind its kernels): the histograms
+// of trc_planes_hist.hip, every plane under every requested filter, for every item of an item range from ONE launch, through the
+// batch's pointer table.  Slice j of d_hist is what trc_planes_hist_dev writes for item first_item + j with seg = chunk.
+//
+// The counting is that of trc_planes_hist_kernel (trc_planes_count.h: the same LDS rows of replicated bins, the same adds); what
+// differs is who counts what.  A workgroup's LDS counters can belong to one item at a time, and a grid-stride loop over the vectors
+// of the virtual buffer would mix items within a turn.  So workgroup b owns the contiguous chunk run [b * cpw, (b + 1) * cpw) of the
+// range and walks it item by item: chunk_item[c] names the item of the run's next chunk, all 256 threads count the item's vectors
+// that lie in the run, the counters are flushed to that item's global rows (one 64-bit atomicAdd per non-zero bin, bins rotated by
+// the workgroup's number), and the walk goes on behind the item's last chunk.  A long item is shared by several workgroups, whose
+// atomics merge; a run of short items costs one flush -- a scan of all the LDS rows -- per item.  Where the run holds ALL of an item's
+// chunks and the flush is the item's only one, nobody else adds to those rows (the host has zeroed them): the sums are STORED, a
+// whole row at a time.  That is every item of a batch of short items, whose 3 * ESIZE * 256 counters per item -- 24 KiB for the 4 KiB of a
+// 1024-element fp32 item -- would otherwise arrive at the rate of the device's atomics (profiles/planes/abatch_notes.md).
+//
+// READS: bytes [0, m * ESIZE) of an item and nothing else.  Only whole vectors (8 * lv + 8 <= m) are loaded as 16-byte words; the
+// element in front of a vector is asked for only where the vector does not open a chunk, so it is not the item's first; the item's
+// last m % 8 elements go one per lane, each with the element in front of it.  The pad behind an item has no vector here: the loop
+// ends at the item's last whole vector, so pad elements are counted nowhere.
+
+// nc chunks in the range, cpw of them per workgroup (gridDim.x * cpw >= nc).  hist: 3 * ESIZE * 256 counters per record of rec[],
+// zero on entry.  Dynamic LDS: (requested filters * ESIZE * 256 * 4) << cshift bytes.  round_vecs >= 1.
+template <int ESIZE> __global__ __launch_bounds__(TRC_PLANES_BLOCK)
+void trc_planes_hist_batch_kernel(const BatchRec *__restrict__ rec, const u32 *__restrict__ chunk_item, u32 nc, u32 cpw, u32 chunk,
+                                  u32 filters, u32 cshift, u32 round_vecs, u64a *__restrict__ hist)
+{
+    typedef typename Elem<ESIZE>::T T;
+    typedef typename Elem<ESIZE>::M M;
+    constexpr int NW = 2 * ESIZE, NQ = NW / 4;
+    extern __shared__ __attribute__((aligned(16))) u32 sm[];
+    const u32 tid = threadIdx.x, copy = tid & ((1u << cshift) - 1u);
+    const u32 nf = __builtin_popcount(filters), words = (nf * ESIZE * 256u) << cshift, fwords = (ESIZE * 256u) << cshift;
+    const u32 row_n = copy, row_z = row_n + (filters & 1u ? fwords : 0u), row_x = row_z + (filters & 2u ? fwords : 0u);
+    const bool with_n = filters & 1u, with_z = filters & 2u, with_x = filters & 4u;
+    for (u32 i = tid; i < words; i += TRC_PLANES_BLOCK) sm[i] = 0;
+    __syncthreads();
+
+    // the workgroup's counters to the rows of one item, and zero again; the whole workgroup calls it
+    // (store: nobody else adds to these rows and nothing has been added to them yet)
+    auto flush = [&](u64a *h, bool store) __attribute__((always_inline)) {
+        __syncthreads();
+        for (u32 i = tid; i < nf * ESIZE * 256u; i += TRC_PLANES_BLOCK) {
+            const u32 row = i >> 8, bin = ((i & 255u) + 37u * blockIdx.x) & 255u;
+            u32 *c = sm + ((row * 256u + bin) << cshift);
+            u32 sum = 0;
+            for (u32 q = 0; q < (1u << cshift); q++) { sum += c[q]; c[q] = 0; }
+            u32 f = row / ESIZE;                                         // the row's filter id: the f-th requested one
+            f = f == 0 ? (with_n ? 0u : with_z ? 1u : 2u) : f == 1 ? (with_n && with_z ? 1u : 2u) : 2u;
+            u64a *dst = &h[((size_t)f * ESIZE + row % ESIZE) * 256u + bin];
+            if (store) *dst = (u64a)sum;
+            else if (sum) atomicAdd(dst, (u64a)sum);
+        }
+        __syncthreads();
+    };
+
+    const u32 vpc = chunk / TRC_PLANES_VEC, rstep = TRC_PLANES_BLOCK % vpc;
+    const u32 c_lo = blockIdx.x * cpw, c_hi = nc - c_lo < cpw ? nc : c_lo + cpw;      // (the host: c_lo < nc)
+    for (u32 c = c_lo; c < c_hi; ) {
+        // everything that shapes the walk is the same in all lanes: the item, its record, the turns of the loop (flush holds barriers)
+        const u32 item = __builtin_amdgcn_readfirstlane(chunk_item[c]);
+        const BatchRec r = rec[item];
+        const u32 first = (u32)r.first, nci = (u32)((r.m + chunk - 1) / chunk);
+        const u32 c_end = first + nci < c_hi ? first + nci : c_hi;       // the run's part of the item: chunks [c, c_end)
+        const size_t nvi = r.m / TRC_PLANES_VEC;                         // the item's whole vectors
+        const size_t lv0 = (size_t)(c - first) * vpc, lv_run = (size_t)(c_end - first) * vpc, lv1 = lv_run < nvi ? lv_run : nvi;
+        const size_t turns = lv1 > lv0 ? (lv1 - lv0 + TRC_PLANES_BLOCK - 1) / TRC_PLANES_BLOCK : 0;
+        const uint8_t *in = (const uint8_t *)r.ptr;
+        const M *el = (const M *)in;
+        u64a *h = hist + (size_t)item * (TRC_PHIST_FILTERS * ESIZE * 256u);
+        bool alone = c == first && c_end == first + nci;                 // the item is this run's alone, and not flushed yet
+        u32 rr = tid % vpc, since = 0;                                   // the vector's place in its chunk (lv0 opens one): 0 opens one
+        size_t lv = lv0 + tid;
+        for (size_t it = 0; it < turns; it++, lv += TRC_PLANES_BLOCK) {
+            if (lv < lv1) {
+                const uint4 *src = (const uint4 *)(in + lv * (TRC_PLANES_VEC * ESIZE));
+                u32 w[NW];
+#pragma unroll
+                for (int q = 0; q < NQ; q++) { const uint4 x = src[q]; w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w; }
+                T prev = 0;
+                if (rr && (filters & 6u)) prev = el[lv * TRC_PLANES_VEC - 1];
+                if (with_n) count_vec<ESIZE>(sm, row_n, cshift, w);
+                if (filters & 6u) {
+                    T e[TRC_PLANES_VEC], y[TRC_PLANES_VEC];
+                    unpack<ESIZE>(w, e);
+                    if (with_z) {
+#pragma unroll
+                        for (int j = 0; j < TRC_PLANES_VEC; j++) y[j] = fwd<ESIZE, TRC_FILTER_ZDELTA>(e[j], j ? e[j - 1] : prev);
+                        pack<ESIZE>(y, w);
+                        count_vec<ESIZE>(sm, row_z, cshift, w);
+                    }
+                    if (with_x) {
+#pragma unroll
+                        for (int j = 0; j < TRC_PLANES_VEC; j++) y[j] = fwd<ESIZE, TRC_FILTER_XOR>(e[j], j ? e[j - 1] : prev);
+                        pack<ESIZE>(y, w);
+                        count_vec<ESIZE>(sm, row_x, cshift, w);
+                    }
+                }
+            }
+            rr += rstep;
+            if (rr >= vpc) rr -= vpc;
+            if (++since == round_vecs && it + 1 < turns) { flush(h, alone); alone = false; since = 0; }
+        }
+        // the elements behind the item's last whole vector (at most 7), one per lane, where the run holds the item's last chunk
+        if (c_end == first + nci) {
+            const u32 rest = (u32)(r.m - nvi * TRC_PLANES_VEC);
+            if (tid < rest) {
+                const size_t i = nvi * TRC_PLANES_VEC + tid;
+                const T x = (T)el[i], p = i % chunk ? (T)el[i - 1] : (T)0;
+                if (with_n) count_elem<ESIZE>(sm, row_n, cshift, x);
+                if (with_z) count_elem<ESIZE>(sm, row_z, cshift, fwd<ESIZE, TRC_FILTER_ZDELTA>(x, p));
+                if (with_x) count_elem<ESIZE>(sm, row_x, cshift, fwd<ESIZE, TRC_FILTER_XOR>(x, p));
+            }
+        }
+        flush(h, alone);
+        c = c_end;
+    }
+}
+
+extern "C" size_t trc_planes_hist_batch_bytes(size_t item_count, unsigned esize)
+{
+    if (item_count > TRC_PLANES_BATCH_MAX) return 0;
+    return item_count * trc_planes_hist_bytes(esize);
+}
+
+// the call behind its plan and range checks: items [first_item, first_item + item_count) of a batch that batch_plan has accepted,
+// item_count >= 1.  Also what trc_planes_advise_batch_dev (trc_planes_batch.inc) runs once per slab.
+int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                              uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream)
+{
+    std::vector<BatchRec> recs;
+    uint64_t chunks, elems;
+    int rc = batch_range("planes_hist_batch", items, first_item, item_count, esize, chunk, chunks, elems, &recs);
+    if (rc) return rc;
+    if (!d_hist || ((uintptr_t)d_hist & 7)) return trc_fail(TRC_E_ARG, "planes_hist_batch: the histograms must be 8-byte aligned");
+    if ((rc = batch_table_args("planes_hist_batch", item_count, chunks, d_table, table_bytes))) return rc;
+    const unsigned nf = (unsigned)__builtin_popcount(filters), rows = nf * esize;
+    uint32_t cshift = 0;                           // copies per bin, as trc_planes_hist_dev chooses them
+    while ((2u << cshift) <= TRC_PHIST_COPIES_MAX && ((size_t)rows * 1024u << (cshift + 1)) <= TRC_PHIST_LDS) cshift++;
+    const size_t lds = (size_t)rows * 1024u << cshift;
+    uint32_t rv = TRC_PHIST_ROUND_VECS;            // TRC_PLANES_HIST_ROUND_VECS (test aid), as there
+    const char *e = getenv("TRC_PLANES_HIST_ROUND_VECS");
+    if (e) { const long x = strtol(e, 0, 10); if (x >= 1 && x < (long)TRC_PHIST_ROUND_VECS) rv = (uint32_t)x; }
+    // a workgroup per 256 vectors of the range under the caps of trc_planes_hist_dev, then whole chunks per workgroup
+    unsigned grid = batch_grid((size_t)chunks * (chunk / TRC_PLANES_VEC));
+    if (grid > TRC_PHIST_GRID_MAX) grid = TRC_PHIST_GRID_MAX;
+    if (grid > chunks) grid = (unsigned)chunks;
+    const u32 nc = (u32)chunks, cpw = (nc + grid - 1) / grid;
+    grid = (nc + cpw - 1) / cpw;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t he = hipMemsetAsync(d_hist, 0, trc_planes_hist_batch_bytes(item_count, esize), s);
+    if (he != hipSuccess) return trc_fail(TRC_E_HIP, "planes_hist_batch: %s", hipGetErrorString(he));
+    const BatchRec *d_rec;
+    const u32 *d_map;
+    if ((rc = batch_table("planes_hist_batch", recs, chunks, d_table, s, d_rec, d_map))) return rc;
+    const dim3 g(grid), b(TRC_PLANES_BLOCK);
+    if (esize == 2) hipLaunchKernelGGL((trc_planes_hist_batch_kernel<2>), g, b, lds, s, d_rec, d_map, nc, cpw, chunk, filters, cshift, rv, (u64a *)d_hist);
+    else if (esize == 4) hipLaunchKernelGGL((trc_planes_hist_batch_kernel<4>), g, b, lds, s, d_rec, d_map, nc, cpw, chunk, filters, cshift, rv, (u64a *)d_hist);
+    else hipLaunchKernelGGL((trc_planes_hist_batch_kernel<8>), g, b, lds, s, d_rec, d_map, nc, cpw, chunk, filters, cshift, rv, (u64a *)d_hist);
+    he = hipGetLastError();
+    return he == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_hist_batch: %s", hipGetErrorString(he));
+}
+
+extern "C" int trc_planes_hist_batch_dev(unsigned filters, const trc_planes_item *items, size_t count,
+                                         size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                                         uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream)
+{
+    int rc = batch_plan("planes_hist_batch", items, count, esize, chunk, nullptr, nullptr);
+    if (rc) return rc;
+    if (filters < 1 || filters > 7) return trc_fail(TRC_E_ARG, "planes_hist_batch: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", filters);
+    if (first_item > count || item_count > count - first_item)
+        return trc_fail(TRC_E_ARG, "planes_hist_batch: items [%zu, %zu + %zu) of %zu", first_item, first_item, item_count, count);
+    if (item_count == 0) return TRC_OK;
+    return trc_planes_hist_batch_run(filters, items, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes, stream);
+}

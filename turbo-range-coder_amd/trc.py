@@ -194,6 +194,15 @@ def lib():
         l.trc_encode_fplanes_batch_dev.argtypes = [C.c_int, _it, _fl] + l.trc_encode_planes_batch_dev.argtypes[2:]
         l.trc_decode_fplanes_batch_dev.restype = C.c_int
         l.trc_decode_fplanes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _fl] + l.trc_decode_planes_batch_dev.argtypes[4:]
+        _ad = C.POINTER(PlanesAdvice)               # the batch advisor: advice per item, or None
+        l.trc_planes_hist_batch_bytes.restype = _sz; l.trc_planes_hist_batch_bytes.argtypes = [_sz, C.c_uint]
+        l.trc_planes_hist_batch_dev.restype = C.c_int
+        l.trc_planes_hist_batch_dev.argtypes = [C.c_uint, _it, _sz, _sz, _sz, C.c_uint, C.c_uint32, _vp, _vp, _sz, _vp]
+        l.trc_planes_advise_batch.restype = C.c_int
+        l.trc_planes_advise_batch.argtypes = [_vp, C.c_uint, C.c_uint, _it, _sz, _fl, _ad]
+        l.trc_planes_advise_batch_work_bytes.restype = _sz; l.trc_planes_advise_batch_work_bytes.argtypes = [_it, _sz, C.c_uint, C.c_uint32]
+        l.trc_planes_advise_batch_dev.restype = C.c_int
+        l.trc_planes_advise_batch_dev.argtypes = [C.c_uint, _it, _sz, C.c_uint, C.c_uint32, _fl, _ad, _vp, _sz, _vp]
         l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
         l.trc_decode_host.restype = _sz; l.trc_decode_host.argtypes = [C.c_int, _vp, _sz, _vp, _sz, _vp, C.c_uint]
         l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
@@ -545,7 +554,9 @@ class PlanesBatchCoder:
     trc_encode_planes_batch_dev as the planes of their virtual buffer: self.clen / payload / total / cdf / status are laid out as
     PlanesCoder's for n = plan["n_virtual"].  decode(first_item, item_count) writes those items back into the tensors given (the
     encoded ones by default).  filters (None, one FILTER_* for all items, or one per item) puts a predictor filter in front of
-    each item's planes: the trc_*_fplanes_batch_dev calls, and decode() passes the same filters on.  Plumbing only."""
+    each item's planes: the trc_*_fplanes_batch_dev calls, and decode() passes the same filters on.  filters="auto": encode() first
+    asks the batch advisor (planes_advise_batch_dev, which waits for the stream) about the tensors' current contents, leaves its
+    choice in self.filters and what decided in self.advice, and codes exactly as if that list had been given.  Plumbing only."""
 
     def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None):
         """esize: the element size where the tensors do not say it themselves (uint8 tensors of whole elements)"""
@@ -558,7 +569,8 @@ class PlanesBatchCoder:
         self.dev = tensors[0].device
         self.sizes = [t.numel() * t.element_size() for t in tensors]
         self.items = self._items(tensors)
-        self.filters = planes_filters(filters, self.count)
+        self.auto, self.advice = isinstance(filters, str) and filters == "auto", None
+        self.filters = None if self.auto else planes_filters(filters, self.count)
         self.plan, self.first = planes_batch_plan(self.items, self.count, self.esize, chunk)
         self.nch, self.pitch = self.plan["chunks"], self.plan["pitch"]
         self.cdfnum = _cdfnum(codec, cdfnum, prm)
@@ -588,6 +600,9 @@ class PlanesBatchCoder:
         return planes_items([(t.data_ptr() if t is not None else None, n) for t, n in zip(tensors, self.sizes)])
 
     def encode(self, flags=0):
+        if self.auto:                                          # the advisor on what the tensors hold now; then as if that list had been given
+            chosen, self.advice = planes_advise_batch_dev(self.items, self.esize, self.chunk, 7, self.count, self.dev)
+            self.filters = planes_filters(chosen, self.count)
         st = self.codec in STATIC
         tail = (self.count, self.esize, self.chunk, self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
                 self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream())
@@ -892,6 +907,52 @@ def planes_advise(hist, filters, esize, m):
     a = PlanesAdvice()
     _chk(lib().trc_planes_advise(hist.ctypes.data, filters, esize, m, C.byref(a)))
     return _advice_dict(a)
+
+
+def planes_hist_batch_bytes(item_count, esize):
+    return lib().trc_planes_hist_batch_bytes(item_count, esize)
+
+
+def planes_hist_batch(filters, items, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes):
+    """enqueue trc_planes_hist_batch_dev: slice j of d_hist (3 * esize * 256 uint64 each; zeroed by the call) = the histograms
+    planes_hist would leave for item first_item + j of the batch alone, with seg = chunk"""
+    _chk(lib().trc_planes_hist_batch_dev(filters, items, count, first_item, item_count, esize, chunk, d_hist.data_ptr(),
+                                         d_table.data_ptr(), table_bytes, _cur_stream(d_hist)))
+
+
+def planes_advise_batch(hist, filters, esize, items, count, advice=True):
+    """trc_planes_advise_batch on histograms in host memory (uint64, 3 * esize * 256 per item; needs no device)
+    -> (the filter per item: list of ints, the advice per item: list of dicts, or None where advice is False)"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    if esize in (2, 4, 8) and hist.size < count * 3 * esize * 256:
+        raise TrcError("planes_advise_batch: %d histogram words for %d items" % (hist.size, count))
+    out = (C.c_uint8 * max(count, 1))()
+    adv = (PlanesAdvice * max(count, 1))() if advice else None
+    _chk(lib().trc_planes_advise_batch(hist.ctypes.data, filters, esize, items, count, out, adv))
+    return [int(x) for x in out[:count]], [_advice_dict(a) for a in adv[:count]] if advice else None
+
+
+def planes_advise_batch_dev(batch, esize=None, chunk=4096, filters=7, count=None, device="cuda", advice=True):
+    """trc_planes_advise_batch_dev on a list of device tensors of one element size, or on a trc_planes_item array (planes_items;
+    esize is then required, count defaults to the array's length, the workspace lies on `device`), in a workspace of its own.
+    Waits for the current stream.  -> as planes_advise_batch"""
+    import torch
+    if isinstance(batch, C.Array):
+        items, count = batch, len(batch) if count is None else count
+        dev = torch.device(device)
+    else:
+        tensors = list(batch)
+        if not tensors or any(not t.is_cuda or not t.is_contiguous() for t in tensors):
+            raise TrcError("a batch is a non-empty list of contiguous device tensors of one element size")
+        items, count = planes_items([(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]), len(tensors)
+        esize, dev = esize or tensors[0].element_size(), tensors[0].device
+    need = lib().trc_planes_advise_batch_work_bytes(items, count, esize, chunk)      # (0: the call names the reason itself)
+    work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    out = (C.c_uint8 * max(count, 1))()
+    adv = (PlanesAdvice * max(count, 1))() if advice else None
+    _chk(lib().trc_planes_advise_batch_dev(filters, items, count, esize, chunk, out, adv, work.data_ptr(), need,
+                                           torch.cuda.current_stream(dev).cuda_stream))
+    return [int(x) for x in out[:count]], [_advice_dict(a) for a in adv[:count]] if advice else None
 
 
 def encode_aplanes_host(codec, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
