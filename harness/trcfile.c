@@ -16,6 +16,13 @@
  *   trcfile a <id> <esize> <in> <out>   as p or f, whichever the library's planes advisor chooses from the order-0 histograms of the
  *                                 planes under no filter, z and x (trc_encode_aplanes_host): the file is what p or f would have
  *                                 written; prints the three estimates and the choice (n, z or x)
+ *   trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>...   compress a BATCH: every input file is one item (a tensor, a page, a
+ *                                 column) of esize-byte elements, all of them in one coded call; one filter letter for all items (n =
+ *                                 none), or a = the library's batch advisor chooses per item and every choice is printed.  The file is
+ *                                 the library's TRCB container (trc_hip.h), which records every item's length and filter
+ *   trcfile B <in> <first> <count> <out>   items [first, first + count) of a file of b, their bytes concatenated: only the chunks
+ *                                 that cover them are sent to the GPU
+ *   trcfile l <in>                list a file of b: count, esize, chunk, coder and every item's bytes and filter (needs no GPU)
  *   trcfile d <in> <out>          decompress (files of c, p, f and a)
  *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p or f: only the
  *                                 chunks that cover them are sent to the GPU and decoded (trc_decode_range_host)
@@ -245,6 +252,73 @@ int main(int argc, char **argv)
                adv.total_bits[0] / 8, adv.total_bits[1] / 8, adv.total_bits[2] / 8, "nzx"[adv.filter]);
         return 0;
     }
+    if (argc >= 8 && !strcmp(argv[1], "b")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        const uint32_t chunk = (uint32_t)strtoul(argv[4], 0, 10);
+        const char *fl = argv[5];
+        const size_t count = (size_t)(argc - 7);
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (strlen(fl) != 1 || !strchr("nzxa", fl[0])) { fprintf(stderr, "filter %s: n (none), z (zigzag delta), x (xor) or a (the advisor, per item)\n", fl); return 2; }
+        trc_planes_item *items = calloc(count, sizeof *items);
+        uint8_t *filters = calloc(count, 1);
+        if (!items || !filters) { perror("malloc"); return 2; }
+        size_t total = 0;
+        for (size_t i = 0; i < count; i++) {
+            size_t n;
+            if (!(items[i].d_ptr = slurp(argv[7 + i], &n))) return 2;
+            items[i].n = n; total += n;
+            filters[i] = fl[0] == 'z' ? TRC_FILTER_ZDELTA : fl[0] == 'x' ? TRC_FILTER_XOR : TRC_FILTER_NONE;
+        }
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u, chunk %u: esize is 2, 4 or 8, the chunk 0 or a multiple of 64, and every file holds whole elements, at least one\n", esize, chunk); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        const size_t l = fl[0] == 'a' ? trc_encode_aplanes_batch_host(codec, items, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap, filters)
+                                      : trc_encode_planes_batch_host(codec, items, filters, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[6], out, l)) return 2;
+        if (fl[0] == 'a') for (size_t i = 0; i < count; i++) printf("item %zu: %llu bytes, choice %c  %s\n", i, (unsigned long long)items[i].n, "nzx"[filters[i]], argv[7 + i]);
+        printf("%zu items, %zu -> %zu bytes (%.2f%%)  %u planes\n", count, total, l, 100.0 * l / total, esize);
+        return 0;
+    }
+    if ((argc == 6 && !strcmp(argv[1], "B")) || (argc == 3 && !strcmp(argv[1], "l"))) {
+        const int list = argv[1][0] == 'l';
+        size_t fl;
+        unsigned char *fb = slurp(argv[2], &fl);
+        if (!fb) return 2;
+        trc_planes_batch_hdr h;
+        if (trc_planes_batch_info(fb, fl, &h, 0, 0, 0)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        const size_t count = (size_t)h.count;
+        uint64_t *n = calloc(count, sizeof *n);
+        uint8_t *filters = calloc(count, 1);
+        if (!n || !filters) { perror("malloc"); return 2; }
+        if (trc_planes_batch_info(fb, fl, &h, n, filters, count)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        if (list) {
+            trc_planes_hdr ph;
+            memcpy(&ph, fb + h.inner, sizeof ph);
+            printf("%llu items, esize %u, chunk %u, codec %u, %llu -> %llu bytes\n", (unsigned long long)h.count, h.esize, h.chunk, ph.codec,
+                   (unsigned long long)h.bytes, (unsigned long long)h.size);
+            for (size_t i = 0; i < count; i++) printf("item %zu: %llu bytes, filter %c\n", i, (unsigned long long)n[i], "nzx"[filters[i]]);
+            return 0;
+        }
+        const size_t first = (size_t)strtoull(argv[3], 0, 10), cnt = (size_t)strtoull(argv[4], 0, 10);
+        if (!cnt || first > count || cnt > count - first) { fprintf(stderr, "items [%zu, %zu + %zu) of %zu\n", first, first, cnt, count); return 2; }
+        trc_planes_item *items = calloc(count, sizeof *items);
+        if (!items) { perror("malloc"); return 2; }
+        size_t bytes = 0;
+        for (size_t i = first; i < first + cnt; i++) bytes += (size_t)n[i];
+        unsigned char *out = malloc(bytes + 1024);
+        if (!out) { perror("malloc"); return 2; }
+        size_t pos = 0;
+        for (size_t i = 0; i < count; i++) {
+            items[i].n = n[i];
+            if (i >= first && i < first + cnt) { items[i].d_ptr = out + pos; pos += (size_t)n[i]; }
+        }
+        if (trc_decode_planes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST) != bytes) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+        return write_file(argv[5], out, bytes);
+    }
     if (argc == 4 && !strcmp(argv[1], "d")) {
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
@@ -451,6 +525,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4)\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in>\n");
     return 2;
 }

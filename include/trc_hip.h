@@ -674,6 +674,103 @@ int    trc_planes_advise_batch_dev(unsigned filters, const trc_planes_item *item
                                    uint8_t *filters_out, trc_planes_advice *advice,
                                    void *d_work, size_t work_bytes, void *stream);
 
+/* ---- batched byte planes: the TRCB container, packed on the device -------------------------------------------------------------
+ * A coded batch is loose device buffers (d_clen, payload planes `pitch` apart -- as large as the input --, d_total, CDFs) and a
+ * caller who remembers codec, esize, chunk, cdfnum, every item's length and every item's filter.  The TRCB container is the same
+ * batch in ONE compact, self-describing piece, little endian:
+ *   trc_planes_batch_hdr (48 B) | uint64 n[count] | uint8 filter[count], zero-padded to a multiple of 8 | inner
+ *   inner = the TRCP container of VF(items, filters, esize, chunk):  n = M * esize, tail = 0
+ * The whole contract: bytes [inner, size) are byte for byte what trc_encode_planes_host(codec, VF, M * esize, esize, chunk, ...)
+ * writes at the same chunk, with VF, M and first[] those of the batched calls above; unfiltered items are filter 0, and a batch
+ * without filters stores `count` zero bytes (one layout).  So trc_planes_check, trc_container_check and trc_container_range work
+ * on the inner part and its sections as they stand, and item i is chunks [first[i], first[i] + nc[i]) of every section.
+ *
+ * Host only, no GPU needed:
+ *   trc_planes_batch_auto_chunk   what chunk 0 means: the chunk trc_encode_planes_host resolves for n = sum n[i] (trc_auto_chunk_codec
+ *                                 on the element count, then the coder's floor and largest chunk); 0 for a bad batch or coder.
+ *   trc_planes_batch_bound        48 + table + trc_planes_bound(M * esize, esize, chunk, cdfnum) + TRC_PAD: what d_out / out must
+ *                                 hold (the container is always shorter); chunk 0 as above; 0 for what the calls reject.  It looks
+ *                                 at no pointer.
+ *   trc_planes_batch_layout_host  from the planes' payload sizes total[esize]: `inner`, off[k] = where the inner container's section
+ *                                 k starts (from the TRCB start; a multiple of 8; a static coder's CDF, up8(2 (cdfnum + 1)) bytes,
+ *                                 then the 32-byte TRC1 header, the directory, the payload) and `size`.  TRC_E_ARG where total[k] > M.
+ *   trc_planes_batch_check        (count_expected (size_t)-1 = any) magic, version, both zero fields, esize, the chunk rule, count,
+ *                                 inner == 48 + 8 count + up8(count), inner < size <= buflen, every n[i] a whole number (at least one)
+ *                                 of elements, filters in {0, 1, 2}, zero filter padding, bytes == sum n[i], NC <= 0x7fffffff,
+ *                                 trc_planes_check(buf + inner, size - inner, M * esize), and the inner header's esize and chunk
+ *                                 equal to the outer ones, its tail 0, its size == size - inner.  A failure leaves the reason in
+ *                                 trc_last_error(), prefixed "batch container:", naming the item where one is at fault.
+ *   trc_planes_batch_info         the check, then the header and the first min(cap, count) table entries (n, filters: may be NULL):
+ *                                 what a reader allocates by.
+ *
+ * trc_planes_batch_pack_dev writes the container in device memory from the outputs of trc_encode_(f)planes_batch_dev for these items
+ * and filters (filters NULL = none), WITHOUT a host round trip: one kernel whose workgroups each re-derive the section offsets from
+ * d_total and copy their share of directories, payloads and CDFs, write the headers and the zero bytes up to every multiple of 8.
+ * When `stream` reaches the end of the call d_out[0, size) is the container and *d_size = size.  d_out 16-byte, d_size 8-byte aligned;
+ * out_bytes >= trc_planes_batch_bound, else TRC_E_WORK; nothing at or behind d_out + size is written.  Checks: those of the batched
+ * decode -- the plan, then the filters, then the buffers; no d_ptr is looked at.  The call only enqueues work, but for the upload of
+ * the host-known front (header with `size` still open, n[], filters), which follows the lifetime rule of the batched calls' table:
+ * items and filters are free again on return.  Where a static coder's d_status[k] < 0 or d_total[k] > M the kernel stores *d_size = 0
+ * and d_out is undefined.  TRC_PLANES_GRID caps the grid as it does the other plane kernels'.
+ *
+ * trc_decode_planes_batch_packed_dev decodes items [first_item, first_item + item_count) straight from a container in device memory
+ * (8-byte aligned, cont_bytes >= size, TRC_PAD readable bytes behind `size`: a buffer of trc_planes_batch_bound bytes has them):
+ * plane k's directory, payload and CDF are read where they lie.  `total` is a HOST array of the planes' payload sizes (the payload
+ * field of the sections' headers) from which trc_planes_batch_layout_host gives the offsets; layout.size > cont_bytes is TRC_E_ARG.
+ * Otherwise the call is trc_decode_fplanes_batch_dev: same checks, workspace (trc_planes_batch_range_work_bytes), launches; it only
+ * enqueues work and trusts d_cont as every _dev call trusts its buffers.
+ *
+ * Through host pointers (the caller's current device, no striping): `out` is host memory; items_on says where the ITEMS lie --
+ * TRC_ITEMS_DEV: d_ptr are device addresses as in the batched calls; TRC_ITEMS_HOST: host addresses of any alignment, gathered
+ * through a page-locked staging buffer so that thousands of small items do not pay a copy apiece.  Encode: the batched encode, the
+ * pack kernel, one synchronise to read *d_size, one copy of `size` bytes; returns the size, 0 on error.  chunk 0 =
+ * trc_planes_batch_auto_chunk; cdfnum as for trc_encode_planes_host.  trc_encode_aplanes_batch_host asks the batch advisor first
+ * (trc_planes_advise_batch_dev, all three filters) and writes exactly what the explicit call writes for that list, which filters_out
+ * (count bytes, may be NULL) receives.  The low-nibble coders and a bad filter id are refused before any device is needed.
+ * trc_decode_planes_batch_host checks the container (trc_planes_batch_check with `count`), wants items[i].n == n[i] for ALL count
+ * entries (d_ptr may be NULL outside the range), sends only the covering chunks of every section and joins into the items; returns
+ * the bytes delivered, 0 on error.  trc_decode_xplanes_host does not take this container. */
+#define TRC_PLANES_BATCH_MAGIC 0x42435254u   /* "TRCB" */
+typedef struct trc_planes_batch_hdr {
+    uint32_t magic;      /* TRC_PLANES_BATCH_MAGIC */
+    uint8_t  version;    /* 1 */
+    uint8_t  esize;      /* 2, 4 or 8 */
+    uint16_t zero;
+    uint32_t chunk;
+    uint32_t zero2;
+    uint64_t count;      /* items, 1 .. TRC_PLANES_BATCH_MAX */
+    uint64_t inner;      /* offset of the TRCP container = 48 + 8 count + up8(count) */
+    uint64_t size;       /* the whole container */
+    uint64_t bytes;      /* sum of n[i] */
+} trc_planes_batch_hdr;  /* 48 bytes, little endian */
+typedef struct trc_planes_batch_layout {
+    uint64_t inner;      /* offset of the inner TRCP container */
+    uint64_t off[8];     /* section k of the inner container, from the TRCB start */
+    uint64_t size;       /* the whole container */
+} trc_planes_batch_layout;
+enum { TRC_ITEMS_HOST = 0, TRC_ITEMS_DEV = 1 };
+uint32_t trc_planes_batch_auto_chunk(int codec, const trc_planes_item *items, size_t count, unsigned esize);
+size_t trc_planes_batch_bound(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum);
+int    trc_planes_batch_layout_host(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                    unsigned cdfnum, const uint64_t *total, trc_planes_batch_layout *L);
+int    trc_planes_batch_check(const void *buf, size_t buflen, size_t count_expected);
+int    trc_planes_batch_info(const void *buf, size_t buflen, trc_planes_batch_hdr *h, uint64_t *n, uint8_t *filters, size_t cap);
+int trc_planes_batch_pack_dev(int codec, const trc_planes_item *items, const uint8_t *filters, size_t count,
+                              unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                              const int32_t *d_status, const uint32_t *d_clen, const void *d_payload,
+                              const uint64_t *d_total, void *d_out, size_t out_bytes, uint64_t *d_size, void *stream);
+int trc_decode_planes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
+                                       const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
+                                       unsigned esize, uint32_t chunk, unsigned cdfnum, const uint64_t *total /* host, esize entries */,
+                                       void *d_work, size_t work_bytes, void *stream);
+size_t trc_encode_planes_batch_host(int codec, const trc_planes_item *items, const uint8_t *filters /* NULL: none */,
+                                    size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on,
+                                    void *out, size_t outcap);
+size_t trc_encode_aplanes_batch_host(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                     unsigned cdfnum, int items_on, void *out, size_t outcap, uint8_t *filters_out /* may be NULL */);
+size_t trc_decode_planes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
+                                    size_t first_item, size_t item_count, int items_on);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

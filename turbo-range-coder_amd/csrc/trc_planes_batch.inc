@@ -91,18 +91,39 @@ extern "C" int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *it
                         d_work, work_bytes, stream);
 }
 
-static int decode_batch(const char *who, int codec, const uint32_t *d_clen, const void *d_payload,
+// the coded buffers of a batch, plane by plane: wherever the directories, payloads and CDFs (static coders; else NULL) of the planes lie
+struct BatchCoded { const uint32_t *clen[8]; const uint8_t *payload[8]; const uint16_t *cdf[8]; };
+// ... of the batched calls' flat buffers: directories NC entries, payloads `pitch` bytes, CDFs TRC_PLANES_CDF_STRIDE entries apart
+// (a batch the plan rejects: plane 0 alone, which is all decode_batch looks at before it says why)
+static BatchCoded coded_flat(const uint32_t *d_clen, const void *d_payload, const uint16_t *d_cdf,
+                             const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+{
+    BatchCoded S;
+    memset(&S, 0, sizeof S);
+    trc_planes_batch_plan B;
+    const bool ok = !trc_planes_batch_plan_quiet(items, count, esize, chunk, &B, nullptr);
+    for (unsigned k = 0; k < (ok ? esize : 1u); k++) {
+        S.clen[k] = d_clen ? d_clen + k * (size_t)(ok ? B.chunks : 0) : nullptr;
+        S.payload[k] = d_payload ? (const uint8_t *)d_payload + k * (size_t)(ok ? B.pitch : 0) : nullptr;
+        S.cdf[k] = d_cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
+    }
+    return S;
+}
+
+// sub_m != 0: the coded buffers hold the covering chunks of the requested items alone, as a coded buffer of sub_m elements (the
+// host-pointer decoder, trc_planes_container.inc); else they hold the whole batch
+static int decode_batch(const char *who, int codec, const BatchCoded &S,
                         const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
-                        unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
-                        void *d_work, size_t work_bytes, void *stream)
+                        unsigned esize, uint32_t chunk, unsigned cdfnum,
+                        void *d_work, size_t work_bytes, void *stream, size_t sub_m = 0)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
     if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
-    const size_t n = (size_t)B.n_virtual, m = (size_t)B.m_total, nc = (size_t)B.chunks;
+    const size_t m = sub_m ? sub_m : (size_t)B.m_total, n = m * esize;
     if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
-    if ((rc = check_common(codec, m, chunk, d_cdf, cdfnum))) return rc;
+    if ((rc = check_common(codec, m, chunk, S.cdf[0], cdfnum))) return rc;
     if (first_item > count || item_count > count - first_item)
         return fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
     if (item_count == 0) return TRC_OK;
@@ -113,14 +134,14 @@ static int decode_batch(const char *who, int codec, const uint32_t *d_clen, cons
     if (!planes_range_map(codec, n, esize, chunk, cnt, P)) return fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk)", who);
     const size_t table = trc_planes_batch_table_bytes(item_count, cnt), need = esize * P.slice + table;
     if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
-    if (!d_clen || !d_payload || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3))
+    if (!S.clen[0] || !S.payload[0] || ((uintptr_t)S.payload[0] & 1) || ((uintptr_t)S.clen[0] & 3))
         return fail(TRC_E_ARG, "%s: d_clen must be 4-byte, d_payload 2-byte aligned", who);
     const TrcCodec &r = codec_row(codec);
     uint8_t *w = (uint8_t *)d_work;
     for (unsigned k = 0; k < esize; k++) {         // as trc_decode_fplanes_range_dev; the pad behind an item is decoded with it
         uint8_t *plane = w + k * P.slice;
-        if ((rc = trc_decode_range_dev(codec, d_clen + k * nc, (const uint8_t *)d_payload + k * (size_t)B.pitch, m, chunk, c0, cnt,
-                                       r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
+        if ((rc = trc_decode_range_dev(codec, S.clen[k], S.payload[k], m, chunk, sub_m ? 0 : c0, cnt,
+                                       r.cdf ? S.cdf[k] : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
     return trc_planes_join_fbatch_dev(w, P.slice, items, filters, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
 }
@@ -130,16 +151,16 @@ extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, co
                                            unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                            void *d_work, size_t work_bytes, void *stream)
 {
-    return decode_batch("decode_planes_batch", codec, d_clen, d_payload, items, nullptr, count, first_item, item_count, esize, chunk, d_cdf, cdfnum,
-                        d_work, work_bytes, stream);
+    return decode_batch("decode_planes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), items, nullptr, count,
+                        first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
                                             const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
                                             unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    return decode_batch("decode_fplanes_batch", codec, d_clen, d_payload, items, filters, count, first_item, item_count, esize, chunk, d_cdf, cdfnum,
-                        d_work, work_bytes, stream);
+    return decode_batch("decode_fplanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), items, filters, count,
+                        first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 
 // ---- the batch advisor: a filter per item from the histograms of trc_planes_hist_batch_dev ---------------------------------------

@@ -79,6 +79,17 @@ class PlanesBatchPlan(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("m_total", "n_virtual", "chunks", "pitch", "pad_elems")]
 
 
+class PlanesBatchHdr(C.Structure):
+    """struct trc_planes_batch_hdr (include/trc_hip.h)"""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint8), ("esize", C.c_uint8), ("zero", C.c_uint16), ("chunk", C.c_uint32),
+                ("zero2", C.c_uint32), ("count", C.c_uint64), ("inner", C.c_uint64), ("size", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class PlanesBatchLayout(C.Structure):
+    """struct trc_planes_batch_layout (include/trc_hip.h)"""
+    _fields_ = [("inner", C.c_uint64), ("off", C.c_uint64 * 8), ("size", C.c_uint64)]
+
+
 class PlanesAdvice(C.Structure):
     """struct trc_planes_advice (include/trc_hip.h)"""
     _fields_ = [("filter", C.c_int), ("esize", C.c_uint), ("filters", C.c_uint), ("m", C.c_uint64),
@@ -203,6 +214,24 @@ def lib():
         l.trc_planes_advise_batch_work_bytes.restype = _sz; l.trc_planes_advise_batch_work_bytes.argtypes = [_it, _sz, C.c_uint, C.c_uint32]
         l.trc_planes_advise_batch_dev.restype = C.c_int
         l.trc_planes_advise_batch_dev.argtypes = [C.c_uint, _it, _sz, C.c_uint, C.c_uint32, _fl, _ad, _vp, _sz, _vp]
+        l.trc_planes_batch_auto_chunk.restype = C.c_uint32; l.trc_planes_batch_auto_chunk.argtypes = [C.c_int, _it, _sz, C.c_uint]
+        l.trc_planes_batch_bound.restype = _sz; l.trc_planes_batch_bound.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_planes_batch_layout_host.restype = C.c_int
+        l.trc_planes_batch_layout_host.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint, C.POINTER(C.c_uint64), C.POINTER(PlanesBatchLayout)]
+        l.trc_planes_batch_check.restype = C.c_int; l.trc_planes_batch_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_batch_info.restype = C.c_int
+        l.trc_planes_batch_info.argtypes = [_vp, _sz, C.POINTER(PlanesBatchHdr), C.POINTER(C.c_uint64), _fl, _sz]
+        l.trc_planes_batch_pack_dev.restype = C.c_int
+        l.trc_planes_batch_pack_dev.argtypes = [C.c_int, _it, _fl, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]
+        l.trc_decode_planes_batch_packed_dev.restype = C.c_int
+        l.trc_decode_planes_batch_packed_dev.argtypes = [C.c_int, _vp, _sz, _it, _fl, _sz, _sz, _sz, C.c_uint, C.c_uint32, C.c_uint,
+                                                         C.POINTER(C.c_uint64), _vp, _sz, _vp]
+        l.trc_encode_planes_batch_host.restype = _sz
+        l.trc_encode_planes_batch_host.argtypes = [C.c_int, _it, _fl, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz]
+        l.trc_encode_aplanes_batch_host.restype = _sz
+        l.trc_encode_aplanes_batch_host.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz, _fl]
+        l.trc_decode_planes_batch_host.restype = _sz
+        l.trc_decode_planes_batch_host.argtypes = [_vp, _sz, _it, _sz, _sz, _sz, C.c_int]
         l.trc_encode_host.restype = _sz; l.trc_encode_host.argtypes = [C.c_int, _vp, _sz, C.c_uint32, _vp, _sz, _vp, C.c_uint]
         l.trc_decode_host.restype = _sz; l.trc_decode_host.argtypes = [C.c_int, _vp, _sz, _vp, _sz, _vp, C.c_uint]
         l.trc_container_bound.restype = _sz; l.trc_container_bound.argtypes = [_sz, C.c_uint32]
@@ -628,6 +657,42 @@ class PlanesBatchCoder:
         else:
             _chk(lib().trc_decode_fplanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.filters, *tail))
 
+    def pack(self, guard=0):
+        """enqueue trc_planes_batch_pack_dev on what encode() left, then synchronise to read the size -> (the TRCB container: a uint8
+        device tensor trimmed to its size, with what remains of the planes_batch_bound bytes readable behind it; the size).  guard:
+        0xA5 from the container's start through to the bound and that many bytes past it; self.pack_guard = the tensor's bytes behind
+        the container, which must still be 0xA5.  The full buffer stays in self.packed."""
+        st = self.codec in STATIC
+        bound = lib().trc_planes_batch_bound(self.codec, self.items, self.count, self.esize, self.chunk, self.cdfnum)
+        if bound == 0:
+            raise TrcError("bad (codec, tensors, chunk, cdfnum)")
+        buf = self.torch.full((bound + guard,), 0xA5 if guard else 0, dtype=self.torch.uint8, device=self.dev)
+        d_size = self.torch.zeros(1, dtype=self.torch.int64, device=self.dev)
+        _chk(lib().trc_planes_batch_pack_dev(self.codec, self.items, self.filters, self.count, self.esize, self.chunk,
+                                             self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                                             self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(),
+                                             buf.data_ptr(), bound, d_size.data_ptr(), self._stream()))
+        size = int(d_size.item())
+        self.packed, self.pack_guard = buf, buf[size:]
+        return buf[:size], size
+
+    def decode_packed(self, d_cont, total, first_item=0, item_count=None, out=None, cont_bytes=None, work_bytes=None):
+        """the inverse of pack(): items [first_item, first_item + item_count) straight from the container d_cont (a uint8 device tensor;
+        `total`: the planes' payload sizes, as parse_planes_batch gives them) into out[i] (default: the encoded tensors).  cont_bytes /
+        work_bytes: what the call is told instead of the truth (the tests' argument errors)"""
+        item_count = self.count - first_item if item_count is None else item_count
+        items = self.items if out is None else self._items(list(out))
+        need = lib().trc_planes_batch_range_work_bytes(self.codec, items, self.count, self.esize, self.chunk, first_item, item_count)
+        if need > self.range_work_bytes:
+            self.range_work, self.range_work_bytes = self._buf(need), need
+        if self.range_work is None:
+            self.range_work = self._buf(0)
+        tot = (C.c_uint64 * 8)(*[int(x) for x in total])
+        _chk(lib().trc_decode_planes_batch_packed_dev(self.codec, d_cont.data_ptr(), d_cont.numel() if cont_bytes is None else cont_bytes,
+                                                      items, self.filters, self.count, first_item, item_count, self.esize, self.chunk,
+                                                      self.cdfnum, tot, self.range_work.data_ptr(),
+                                                      need if work_bytes is None else work_bytes, self._stream()))
+
     def stored_bytes(self):
         """Synchronise: payload + directory (+ CDFs of a static coder) of all planes"""
         self.torch.cuda.synchronize(self.dev)
@@ -982,3 +1047,114 @@ def encode_host_container(codec, data, chunk, cdf=None, cdfnum=256, prm=(5, 6)):
     if l == 0:
         raise TrcError(lib().trc_last_error().decode())
     return out[:l].copy()
+
+
+# ------------------------------------------------------- the TRCB container of a batch (include/trc_hip.h) ---
+PLANES_BATCH_MAGIC = 0x42435254                                # "TRCB"
+PLANES_BATCH_HDR = 48
+ITEMS_HOST, ITEMS_DEV = 0, 1
+
+
+def planes_batch_bound(codec, sizes, esize, chunk=0, cdfnum=0):
+    """trc_planes_batch_bound for items of `sizes` bytes (needs no device, looks at no pointer); 0: what the calls reject"""
+    return lib().trc_planes_batch_bound(codec, planes_items([(None, n) for n in sizes]), len(sizes), esize, chunk, cdfnum)
+
+
+def planes_batch_auto_chunk(codec, sizes, esize):
+    return lib().trc_planes_batch_auto_chunk(codec, planes_items([(None, n) for n in sizes]), len(sizes), esize)
+
+
+def planes_batch_layout(codec, sizes, esize, chunk, cdfnum, total):
+    """trc_planes_batch_layout_host -> dict(inner, off: list of esize, size)"""
+    L = PlanesBatchLayout()
+    tot = (C.c_uint64 * 8)(*[int(x) for x in total])
+    _chk(lib().trc_planes_batch_layout_host(codec, planes_items([(None, n) for n in sizes]), len(sizes), esize, chunk, cdfnum, tot, C.byref(L)))
+    return {"inner": int(L.inner), "off": [int(x) for x in L.off[:esize]], "size": int(L.size)}
+
+
+def planes_batch_check(buf, count=None):
+    """trc_planes_batch_check (needs no device); raises TrcError with the reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_planes_batch_check(buf.ctypes.data, buf.size, _sz(-1).value if count is None else count))
+
+
+def planes_batch_info(buf, cap=None):
+    """trc_planes_batch_info -> (dict of the header's fields, n: list, filters: list) of the first min(cap, count) items"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    h = PlanesBatchHdr()
+    if cap is None:
+        _chk(lib().trc_planes_batch_info(buf.ctypes.data, buf.size, C.byref(h), None, None, 0))
+        cap = int(h.count)
+    n, f = (C.c_uint64 * max(cap, 1))(), (C.c_uint8 * max(cap, 1))()
+    _chk(lib().trc_planes_batch_info(buf.ctypes.data, buf.size, C.byref(h), n, f, cap))
+    got = min(cap, int(h.count))
+    return {k: int(getattr(h, k)) for k, _ in PlanesBatchHdr._fields_}, [int(x) for x in n[:got]], [int(x) for x in f[:got]]
+
+
+def parse_planes_batch(buf):
+    """a checked TRCB container -> dict(the header's fields, n: list, filters: list, codec, cdfnum, total: the planes' payload sizes,
+    off: the sections' offsets from the TRCB start); the inner TRCP container is buf[inner:size]"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    h, n, f = planes_batch_info(buf)
+    inner = buf[h["inner"]:h["size"]]
+    codec, esize = int(inner[4]), int(inner[6])
+    cdfnum = int(inner[12:16].view("<u4")[0])
+    off = [int(x) for x in inner[PLANES_HDR:PLANES_HDR + 8 * esize].view("<u8")]
+    cdfb = (2 * (cdfnum + 1) + 7) & ~7 if codec in STATIC else 0
+    total = [int(inner[o + cdfb + 24:o + cdfb + 32].view("<u8")[0]) for o in off]
+    return dict(h, n=n, filters=f, codec=codec, cdfnum=cdfnum, total=total, off=[h["inner"] + o for o in off])
+
+
+def _batch_host_items(arrays):
+    """-> (trc_planes_item array, items_on, what keeps the memory alive) of numpy arrays (host) or device tensors"""
+    arrays = list(arrays)
+    if arrays and not isinstance(arrays[0], np.ndarray):
+        keep = [t.contiguous() for t in arrays]
+        return planes_items([(t.data_ptr(), t.numel() * t.element_size()) for t in keep]), ITEMS_DEV, keep
+    keep = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+    return planes_items([(a.ctypes.data, a.size) for a in keep]), ITEMS_HOST, keep
+
+
+def host_encode_planes_batch(codec, arrays, esize, chunk=0, filters=None, cdfnum=256, prm=(5, 6)):
+    """trc_encode_planes_batch_host on numpy arrays (host items) or device tensors (device items): filters None, one id for all, a
+    list, or "auto" (trc_encode_aplanes_batch_host) -> the TRCB container (np.uint8); with "auto": (container, the filters chosen)"""
+    items, on, keep = _batch_host_items(arrays)
+    count = len(keep)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(lib().trc_planes_batch_bound(codec, items, count, esize, chunk, cn), 64), dtype=np.uint8)
+    if isinstance(filters, str) and filters == "auto":
+        chosen = (C.c_uint8 * max(count, 1))()
+        l = lib().trc_encode_aplanes_batch_host(codec, items, count, esize, chunk, cn, on, out.ctypes.data, out.size, chosen)
+    else:
+        chosen = None
+        l = lib().trc_encode_planes_batch_host(codec, items, planes_filters(filters, count), count, esize, chunk, cn, on, out.ctypes.data, out.size)
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy() if chosen is None else (out[:l].copy(), [int(x) for x in chosen[:count]])
+
+
+def host_decode_planes_batch(comp, first_item=0, item_count=None, out=None, sizes=None):
+    """trc_decode_planes_batch_host: items [first_item, first_item + item_count) of a TRCB container -> a list of np.uint8 arrays, or,
+    out given (a list of count device tensors, None outside the range), into those -> the bytes delivered.  sizes: what the call is
+    told the items hold instead of the container's own table (the tests' argument errors)"""
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    h, n, _ = planes_batch_info(comp)
+    count = h["count"]
+    item_count = count - first_item if item_count is None else item_count
+    sizes = n if sizes is None else sizes
+    wanted = range(first_item, first_item + item_count)
+    if out is None:
+        res = [np.full(n[i] + 64, 0xA5, dtype=np.uint8) if i in wanted else None for i in range(count)]
+        items = planes_items([(res[i].ctypes.data if i in wanted else None, sizes[i]) for i in range(count)])
+        on = ITEMS_HOST
+    else:
+        items = planes_items([(out[i].data_ptr() if out[i] is not None else None, sizes[i]) for i in range(count)])
+        on = ITEMS_DEV
+    l = lib().trc_decode_planes_batch_host(comp.ctypes.data, comp.size, items, count, first_item, item_count, on)
+    if l != sum(n[i] for i in wanted):
+        raise TrcError(lib().trc_last_error().decode())
+    if out is not None:
+        return l
+    if any((res[i][n[i]:] != 0xA5).any() for i in wanted):
+        raise TrcError("trc_decode_planes_batch_host wrote past an item")
+    return [res[i][:n[i]].copy() for i in wanted]
