@@ -36,7 +36,8 @@
 //     the asm form is always one ds_read_b128, and the reads of the NEXT four symbols are in flight while the current
 //     four are coded.
 //   * renorm words go to the ring speculatively every symbol (the slot of the next unit is always free); the cursor
-//     is kept as a halfword counter that a compare's carry decrements (v_subb), ring address = and + shift-add.
+//     is a halfword counter that a compare's carry decrements (v_subb), ring address = and + shift-add (the interleaved
+//     ring keeps the counter spread over the address bits: ans_cur below).
 // one rANS step (ece, anscdf_.h:90-94): renorm-emit, then st = (st/f)<<15 + st%f + c0.
 //   e = { m, (2^15-f) | sh<<24, f<<16, c0' }:  q = umulhi(st, m) >> sh == st / f  for st < 2^31
 //   (f == 1 uses m = 2^32-1, sh = 0, c0' = c0 + 2^15-1: umulhi gives st-1, see trc_dir.hip)
@@ -46,15 +47,32 @@
 // it as a mask on gfx950); speculative 16-bit store; st = VCC ? st >> 16 : st as ONE v_cndmask with an SDWA source
 // select (WORD_1 of st); cursor -= VCC (v_subbrev).  The division half (mul_hi, SDWA shift, mul24, add3) follows in the same
 // block (left to the compiler it came with an s_nop per symbol behind the asm block: 1-1.5 % of the kernel).
-__device__ __forceinline__ void ans_put(u32 &st, const trc_v4u e, u32 rbase, u32 &wn)
+// The ring is the INTERLEAVED one (StreamOut<.., IL = true>, trc_io.h: dword d of every lane in row d, bank = lane), and the address of
+// ring halfword h, (h >> 1) * 256 + (h & 1) * 2 + the lane's column, is not linear in h.  The cursor of the symbol step is therefore
+// kept SPREAD: V = (h >> 1) << 7 | (h & 1), bits 1..6 zero, so that 2 V is the address offset.  V - 1 borrows through the zero bits
+// into the row and leaves them set; the `and` that masked the halfword counter to the ring in the lane-major form clears them again
+// (0xf81: five row bits and the parity, which also wraps the ring).  The same three instructions per symbol (and, shift-add,
+// subtract-with-borrow); how many units a piece took is read off the halfword index before and after it (at most 16 per piece, one
+// per step of the ragged tail: the ring has 64).
+__device__ __forceinline__ u32 ans_cur(u32 wpos)
+{
+    const u32 h = ~(wpos >> 1);                                 // the next unit goes to ring halfword h & 63 (the stream grows DOWN)
+    return ((h & 62u) << 6) | (h & 1u);
+}
+__device__ __forceinline__ u32 ans_cur_wpos(u32 wpos, u32 cur)   // wpos after the steps that took `cur` from ans_cur(wpos) to where it is
+{
+    const u32 h0 = ~(wpos >> 1), h1 = ((cur >> 6) & 62u) | (cur & 1u);
+    return wpos + (((h0 - h1) & 63u) << 1);
+}
+__device__ __forceinline__ void ans_put(u32 &st, const trc_v4u e, u32 rbase, u32 &cur)
 {
     u32 t;
     // the whole step in one block, division included (mul_hi, SDWA shift by the entry's shift byte, mul24, add3): the compiler puts
     // a wait state behind an asm block whose result the next instruction reads (it cannot see which instruction wrote it),
     // which was an s_nop per symbol between the renorm block and the division -- 1-1.5 % of the kernel at every chunk size
     asm volatile("v_cmp_ge_u32_e32 vcc, %0, %3\n\t"
-                 "v_and_b32_e32 %2, 63, %1\n\t"
-                 "v_lshl_add_u32 %2, %2, 1, %4\n\t"
+                 "v_and_b32_e32 %1, %8, %1\n\t"
+                 "v_lshl_add_u32 %2, %1, 1, %4\n\t"
                  "ds_write_b16 %2, %0\n\t"
                  "v_cndmask_b32_sdwa %0, %0, %0, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t"
                  "v_subbrev_co_u32_e32 %1, vcc, 0, %1, vcc\n\t"
@@ -62,7 +80,7 @@ __device__ __forceinline__ void ans_put(u32 &st, const trc_v4u e, u32 rbase, u32
                  "v_lshrrev_b32_sdwa %2, %6, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD\n\t"
                  "v_mul_u32_u24_e32 %2, %2, %6\n\t"
                  "v_add3_u32 %0, %0, %7, %2"
-                 : "+v"(st), "+v"(wn), "=&v"(t) : "v"(e.z), "v"(rbase), "v"(e.x), "v"(e.y), "v"(e.w) : "vcc", "memory");
+                 : "+v"(st), "+v"(cur), "=&v"(t) : "v"(e.z), "v"(rbase), "v"(e.x), "v"(e.y), "v"(e.w), "s"(0xf81u) : "vcc", "memory");
 }
 // table address of byte k of w: (byte << 4) in one SDWA shift
 template <int K>
@@ -121,10 +139,10 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
     QuadIn tin; tin.base = in + (u64)wc.c0 * chunk;
     // write-through drains, full rounds only (trc_io.h).  G = 32: between two drain calls a lane codes one 16-byte piece, at most one
     // 2-byte unit per symbol; the ragged tail (up to 63 symbols = 126 bytes) goes into a ring that is still empty
-    StreamOut<true, false, false, true, 32u> so;
+    StreamOut<true, false, false, true, 32u, true> so;         // (the interleaved ring: its stores never conflict, trc_io.h)
     so.rings = wbase;
     so.scratch = scratch; so.stride = stride; so.c0 = wc.c0; so.wpos = 0; so.nfl = 0;
-    const u32 rbase = (u32)(uintptr_t)(so.rings - smem) + trc_raddr(lane, 0);    // this lane's ring, as an LDS byte address
+    const u32 rbase = (u32)(uintptr_t)(so.rings - smem) + so.ra(lane, 0);        // this lane's ring, as an LDS byte address
     const uint4 *etab1 = (const uint4 *)smem;                                    // generic view for the ragged tail
 
     const u32 S = chunk / TRC_SEG;
@@ -160,9 +178,9 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
                 pos--;
                 const uint4 e = etab1[(u32)mine[pos]];
                 const trc_v4u ev = { e.x, e.y, e.z, e.w };
-                u32 wn = ~(so.wpos >> 1);
+                u32 wn = ans_cur(so.wpos);
                 if (pos >= body || !(pos & 1u)) ans_put(st0, ev, rbase, wn); else ans_put(st1, ev, rbase, wn);
-                so.wpos = (~wn) << 1;                           // (the top segment is a lane's first: <= 126 bytes into an empty ring)
+                so.wpos = ans_cur_wpos(so.wpos, wn);            // (the top segment is a lane's first: <= 126 bytes into an empty ring)
             }
             act = false;
         }
@@ -170,7 +188,7 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
         for (int k = 3; k >= 0; k--) {
             if (act) {
                 const uint4 v = tin.read((u32)k);
-                u32 wn = ~(so.wpos >> 1);                       // halfword cursor: next unit -> ring halfword wn & 63
+                u32 wn = ans_cur(so.wpos);                      // ring cursor of the next unit
                 EncQuad a, b;
                 // four dwords, top first; the reads of dword d-1 fly while dword d is coded.  LDS operations issued
                 // after a's reads when a is waited for: 4 (b's reads) [+ 4 ring writes of the dword before]
@@ -186,7 +204,7 @@ __global__ __launch_bounds__(BLOCK) void trc_ans4s_enc_kernel(
                 ans_put(st1, a.e3, rbase, wn); ans_put(st0, a.e2, rbase, wn); ans_put(st1, a.e1, rbase, wn); ans_put(st0, a.e0, rbase, wn);
                 ANS_WAIT4(b, 4);
                 ans_put(st1, b.e3, rbase, wn); ans_put(st0, b.e2, rbase, wn); ans_put(st1, b.e1, rbase, wn); ans_put(st0, b.e0, rbase, wn);
-                so.wpos = (~wn) << 1;
+                so.wpos = ans_cur_wpos(so.wpos, wn);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the ring writes above are not in the compiler's books
             if (k == 0 && s > 0) take(s - 1u);                  // (this segment's last piece has been read)

@@ -16,7 +16,8 @@
 //
 // LDS rows are padded so that the per-lane accesses are bank-conflict free:
 //   tiles: row stride 80 B  (20 dwords: 16 consecutive rows x 4 banks cover all 64 banks for b128)
-//   rings: row stride 132 B (33 dwords: lanes at equal ring offsets hit 32 distinct banks)
+//   rings: row stride 132 B (33 dwords: lanes at equal ring offsets hit 32 distinct banks); the two rings of the static rANS coders
+//          are interleaved instead (dword d of every lane in row d: bank = lane at any offset; StreamOut's and StreamInT's IL)
 #pragma once
 #include "trc_dev.h"
 
@@ -30,9 +31,11 @@
 // Byte address, inside one wave's ring array, of ring offset `off` (0..127) of lane `lane`.
 //   default: lane-major rows of 132 bytes (33 dwords: conflict-free while lanes sit at equal offsets,
 //     ~3-way conflicts once the data-dependent offsets drift apart).
-//   (dword d of every lane's ring in row d never conflicts, but costs one more VALU op per access: measured decode 124 vs 113 us,
-//     encode 101 vs 99 us in favour of the linear form -- the ring is not where the LDS conflict cycles come from.  StreamInT<true>,
-//     the static rANS decoder's ring, is interleaved for another reason: trc_ans_static.hip.)
+//   (dword d of every lane's ring in row d never conflicts.  Round 1 measured it at one more VALU op per access, on kernels that were
+//     bound by their vector instructions then: decode 124 vs 113 us, encode 101 vs 99 us in favour of the linear form.  SUPERSEDED for
+//     the static rANS coders: both now use the interleaved form at no extra instruction per symbol -- StreamInT<true> since round 3,
+//     StreamOut<.., IL = true> since profiles/ans4s_lds/ans4s_lds_notes.md, where the drifted ring stores turned out to be a third of
+//     the encoder's LDS bank-conflict cycles.)
 __device__ __forceinline__ u32 trc_raddr(u32 lane, u32 off) { return lane * TRC_SRING_STRIDE + off; }
 
 __device__ __forceinline__ u32 trc_mbcnt(u64 mask)   // number of set bits of mask below this lane
@@ -325,9 +328,30 @@ struct QuadOut {
 // every round serves the 16 lowest ready lanes, so the loop reaches all of them), and the caller adds at most G before it calls
 // again.  G is the CALLER's bound and is stated where StreamOut is instantiated; the bytes and their places in the region do not
 // depend on when a segment leaves, so the payload is the same under either rule.  (QUAD streams keep the plain rule.)
-template <bool DOWN, bool PAIR = false, bool QUAD = false, bool WT = false, u32 G = 0u>
+// IL (the static rANS encoder), the ring LAYOUT, in the spirit of StreamInT<IL>: where ring offset `off` of a lane waits inside the
+// wave's ring array.  The bytes, their order and their places in the region do not depend on it.
+//   IL = false  lane-major rows of 132 bytes (trc_raddr).  Conflict-free while the lanes sit at equal offsets; once the data-dependent
+//               cursors have drifted apart the bank of a unit is (lane + off / 4) mod 32, which is random: ~3.4 LDS cycles per 32-lane
+//               group for a store whose own cost is 2.
+//   IL = true   dword d of every lane's ring in row d (a row = 64 lanes x 4 B = 256 B): the bank of a unit is the lane, whatever the
+//               cursor is, so a wave's speculative stores never conflict.  The drain reads a segment as four dwords per helper lane at
+//               row offsets +0 / +256 / +512 / +768 (two ds_read2st64_b32); the four lanes of a helper quad read one source lane's
+//               column, one bank, so THESE reads conflict 4-way -- 0.64 rounds per 16-symbol piece against 16 stores.  32 rows x 256 B
+//               = 8192 of the 8448 bytes per wave (TRC_SRING_BYTES: LDS per workgroup is the same under both forms).  16-bit units
+//               only, one lane per ring, drained by the wave.
+// Measured on the static rANS encoder (100 MB of text, chunk 512; profiles/ans4s_lds/ans4s_lds_notes.md): SQ_LDS_BANK_CONFLICT 8.5 ->
+// 5.6 and SQ_LDS_IDX_ACTIVE 15.4 -> 12.6 cycles per wave-symbol, 51.3 -> 49.8 us.  A second form with the two halfwords of a dword 128
+// bytes apart (address linear in the halfword index, eight 16-bit reads per helper lane in the drain) stored as conflict-free and was
+// 0.5 us SLOWER than the lane-major ring; it is not in the tree.
+template <bool DOWN, bool PAIR = false, bool QUAD = false, bool WT = false, u32 G = 0u, bool IL = false>
 struct StreamOut {
     static_assert(G == 0u || (!QUAD && G + TRC_SEG <= TRC_SRING - 2u), "full-round drains: one lane per ring, and a ready lane must not be urgent by itself");
+    static_assert(!IL || (!PAIR && !QUAD), "the interleaved ring: one lane per ring");
+    // byte address, inside the wave's ring array, of (even) ring offset `off` of row `row`
+    static __device__ __forceinline__ u32 ra(u32 row, u32 off)
+    {
+        return IL ? ((off >> 2) << 8) + (row << 2) + (off & 2u) : trc_raddr(row, off);
+    }
     u8 *rings;           // this wave's ring array (LDS)
     u8 *scratch;         // global scratch, region of chunk c is [c*stride, (c+1)*stride)
     u32 stride;
@@ -339,7 +363,7 @@ struct StreamOut {
     // (QUAD) a 16-bit unit at stream position p of the shared stream, where `take`; nothing moves
     __device__ __forceinline__ void put16_at(bool take, u32 p, u32 v)
     {
-        if (take) *(u16 *)(rings + trc_raddr(ring_row(), roff16(p))) = (u16)v;
+        if (take) *(u16 *)(rings + ra(ring_row(), roff16(p))) = (u16)v;
     }
     __device__ __forceinline__ u32 my_stride() const { return (PAIR && (trc_lane() & 1u)) ? stride_b : stride; }
     __device__ __forceinline__ u8 *my_region() const
@@ -356,22 +380,24 @@ struct StreamOut {
     // only advance when `take` (no exec-mask branch in the symbol loop)
     __device__ __forceinline__ void put16_if(bool take, u32 v)
     {
-        *(u16 *)(rings + trc_raddr(trc_lane(), roff16(wpos))) = (u16)v;
+        *(u16 *)(rings + ra(trc_lane(), roff16(wpos))) = (u16)v;
         wpos += take ? 2u : 0u;
     }
     __device__ __forceinline__ void put32_if(bool take, u32 v)          // same, 32-bit unit (a full ring is drained before 4 bytes are missing)
     {
+        static_assert(!IL, "the interleaved ring takes 16-bit units only");
         *(u32 *)(rings + trc_raddr(trc_lane(), roff32(wpos))) = v;
         wpos += take ? 4u : 0u;
     }
-    __device__ __forceinline__ void put16(u32 v) { *(u16 *)(rings + trc_raddr(trc_lane(), roff16(wpos))) = (u16)v; wpos += 2; }
-    __device__ __forceinline__ void put32(u32 v) { *(u32 *)(rings + trc_raddr(trc_lane(), roff32(wpos))) = v; wpos += 4; }
+    __device__ __forceinline__ void put16(u32 v) { *(u16 *)(rings + ra(trc_lane(), roff16(wpos))) = (u16)v; wpos += 2; }
+    __device__ __forceinline__ void put32(u32 v) { static_assert(!IL, "the interleaved ring takes 16-bit units only"); *(u32 *)(rings + trc_raddr(trc_lane(), roff32(wpos))) = v; wpos += 4; }
 
     __device__ __forceinline__ u32 pending() const { return wpos - TRC_SEG * nfl; }
     // one lane moving its own oldest segment to the region (bursts only: runs of 0xFFFFFFFF words
     // released by a range-coder carry can exceed what a period may append)
     __device__ __forceinline__ void self_drain()
     {
+        static_assert(!IL, "the interleaved ring is drained by the wave");
         const u32 ro = DOWN ? ((0u - TRC_SEG * (nfl + 1u)) & (TRC_SRING - 1)) : ((TRC_SEG * nfl) & (TRC_SRING - 1));
         u8 *reg = my_region();
         u8 *d = DOWN ? reg + my_stride() - (size_t)TRC_SEG * (nfl + 1u) : reg + (size_t)TRC_SEG * nfl;
@@ -417,7 +443,7 @@ struct StreamOut {
             const u64 pmask = mask & trc_ballot(rank < 16u);
             const bool pick = able && full() && rank < 16u;     // (the lanes of pmask)
             const u32 ro = DOWN ? ((0u - TRC_SEG * (nfl + 1u)) & (TRC_SRING - 1)) : ((TRC_SEG * nfl) & (TRC_SRING - 1));
-            const u32 from = rw + trc_raddr(ring_row(), ro);
+            const u32 from = rw + ra(ring_row(), ro);
             // place in the scratch array relative to the wave's first region (63 regions of at most 64 KiB + slack: 32 bits; offsets
             // are multiples of 64, so bit 0 can name the array: PAIR, odd lane = second stream)
             const u32 to = (my_row() * my_stride() + (DOWN ? my_stride() - TRC_SEG * (nfl + 1u) : TRC_SEG * nfl)) | (PAIR ? lane & 1u : 0u);
@@ -428,9 +454,10 @@ struct StreamOut {
             const u32 q = lane >> 2, part = (lane & 3u) << 4;
             if (q < cnt && q < 16u) {
                 typedef __attribute__((address_space(3))) u32 lds_u32;
-                const u32 a = from_q + part;
-                const u32 s0 = *(const lds_u32 *)(uintptr_t)a, s1 = *(const lds_u32 *)(uintptr_t)(a + 4u);
-                const u32 s2 = *(const lds_u32 *)(uintptr_t)(a + 8u), s3 = *(const lds_u32 *)(uintptr_t)(a + 12u);
+                // piece `part` of the segment: 16 bytes further on (lane-major), four rows of 256 bytes further on (interleaved)
+                const u32 a = from_q + (IL ? part << 6 : part), st = IL ? 256u : 4u;
+                const u32 s0 = *(const lds_u32 *)(uintptr_t)a, s1 = *(const lds_u32 *)(uintptr_t)(a + st);
+                const u32 s2 = *(const lds_u32 *)(uintptr_t)(a + 2u * st), s3 = *(const lds_u32 *)(uintptr_t)(a + 3u * st);
                 u8 *base = (PAIR && (to_q & 1u)) ? scratch_b + (size_t)c0 * stride_b : scratch + (size_t)c0 * stride;
 if constexpr (WT) {                                // (an asm store is not in the compiler's vmcnt books: nothing in these kernels reads it back)
                     const trc_v4u vv = { s0, s1, s2, s3 };
