@@ -13,6 +13,10 @@
  *                                 previous element, restarted at every chunk -- for integer columns and smooth series (sorted ids,
  *                                 timestamps, sampled signals).  The file is the library's filtered planes container: 16 bytes
  *                                 "TRCF" | u8 filter | u8 1 | u16 0 | u64 size, then the TRCP container of the filtered data
+ *   trcfile s <id> <esize> <z|x> <stride> <in> <out>   as f for INTERLEAVED data (rows of K fields, stereo / 5.1 PCM, xyz points, complex
+ *                                 pairs): the filter predicts from the element <stride> back, 2 .. 8.  The file is the library's
+ *                                 strided planes container: 16 bytes "TRCS" | u8 filter | u8 1 | u16 stride | u64 size, then the TRCP
+ *                                 container of the filtered data
  *   trcfile a <id> <esize> <in> <out>   as p or f, whichever the library's planes advisor chooses from the order-0 histograms of the
  *                                 planes under no filter, z and x (trc_encode_aplanes_host): the file is what p or f would have
  *                                 written; prints the three estimates and the choice (n, z or x)
@@ -23,8 +27,8 @@
  *   trcfile B <in> <first> <count> <out>   items [first, first + count) of a file of b, their bytes concatenated: only the chunks
  *                                 that cover them are sent to the GPU
  *   trcfile l <in>                list a file of b: count, esize, chunk, coder and every item's bytes and filter (needs no GPU)
- *   trcfile d <in> <out>          decompress (files of c, p, f and a)
- *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p or f: only the
+ *   trcfile d <in> <out>          decompress (files of c, p, f, s and a)
+ *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p, f or s: only the
  *                                 chunks that cover them are sent to the GPU and decoded (trc_decode_range_host)
  *
  * File = "TRCF" | u8 id | u8 cdfnum-1 | u16 0 | u64 raw length | u64 stored length | [cdf: (cdfnum+1) x u16, static coders]
@@ -113,6 +117,8 @@ static int is_planes(const unsigned char *fb, size_t fl) { return fl >= 4 && !me
 /* a file of `trcfile f`.  `trcfile c` opens its files with the same four letters; there byte 5 is 0 for the coders without a CDF
  * and bytes 16 .. 19 belong to a length, here byte 5 is the version 1 and a TRCP container starts at byte 16 */
 static int is_fplanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCF", 4) && fb[5] == 1 && !memcmp(fb + 16, "TRCP", 4); }
+/* a file of `trcfile s` */
+static int is_splanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCS", 4) && !memcmp(fb + 16, "TRCP", 4); }
 static int write_file(const char *path, const unsigned char *p, size_t n)
 {
     FILE *f = fopen(path, "wb");
@@ -232,6 +238,27 @@ int main(int argc, char **argv)
         printf("%zu -> %zu bytes (%.2f%%)  %u planes, filter %s\n", n, l, 100.0 * l / n, esize, argv[4]);
         return 0;
     }
+    if (argc == 8 && !strcmp(argv[1], "s")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id), stride = atoi(argv[5]);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        const int filter = !strcmp(argv[4], "z") ? TRC_FILTER_ZDELTA : !strcmp(argv[4], "x") ? TRC_FILTER_XOR : TRC_FILTER_NONE;
+        size_t n;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (filter == TRC_FILTER_NONE) { fprintf(stderr, "filter %s: z (zigzag delta) or x (xor)\n", argv[4]); return 2; }
+        if (stride < 2 || stride > TRC_STRIDE_MAX) { fprintf(stderr, "stride %s: 2 .. %d (stride 1 is trcfile f)\n", argv[5], TRC_STRIDE_MAX); return 2; }
+        unsigned char *in = slurp(argv[6], &n);
+        if (!in) return 2;
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_splanes_bound(n, esize, 0, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u with %zu bytes: esize is 2, 4 or 8 and the file holds at least one element\n", esize, n); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        const size_t l = trc_encode_splanes_host(codec, filter, stride, in, n, esize, 0, out, cap, cdfnum);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[7], out, l)) return 2;
+        printf("%zu -> %zu bytes (%.2f%%)  %u planes, filter %s, stride %d\n", n, l, 100.0 * l / n, esize, argv[4], stride);
+        return 0;
+    }
     if (argc == 6 && !strcmp(argv[1], "a")) {
         const int id = atoi(argv[2]), codec = lib_codec(id);
         const unsigned esize = (unsigned)atoi(argv[3]);
@@ -323,12 +350,12 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
-        /* a file of `trcfile p`, f or a: untrusted, so checked against what was read; the library looks at the magic itself
-         * (trc_decode_xplanes_host = trc_decode_planes_host or trc_decode_fplanes_host) */
-        if (is_fplanes(fb, fl) || is_planes(fb, fl)) {
-            const size_t lead = is_planes(fb, fl) ? 0 : sizeof(trc_fplanes_hdr);
+        /* a file of `trcfile p`, f, s or a: untrusted, so checked against what was read; the library looks at the magic itself
+         * (trc_decode_xplanes_host = trc_decode_planes_host, trc_decode_fplanes_host or trc_decode_splanes_host) */
+        if (is_fplanes(fb, fl) || is_splanes(fb, fl) || is_planes(fb, fl)) {
+            const size_t lead = is_planes(fb, fl) ? 0 : sizeof(trc_fplanes_hdr);     /* (the TRCS prefix has the TRCF prefix's size) */
             trc_planes_hdr ph;
-            if (lead ? trc_fplanes_check(fb, fl, (size_t)-1) : trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            if (is_splanes(fb, fl) ? trc_splanes_check(fb, fl, (size_t)-1) : lead ? trc_fplanes_check(fb, fl, (size_t)-1) : trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
             memcpy(&ph, fb + lead, sizeof ph);
             unsigned char *out = malloc((size_t)ph.n + 1024);
             if (!out) { perror("malloc"); return 2; }
@@ -366,6 +393,17 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        if (is_splanes(fb, fl)) {
+            const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
+            trc_planes_hdr ph;
+            if (trc_splanes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            memcpy(&ph, fb + sizeof(trc_splanes_hdr), sizeof ph);
+            if (!len || off > ph.n || len > ph.n - off) { fprintf(stderr, "range outside the file's %llu bytes\n", (unsigned long long)ph.n); return 2; }
+            unsigned char *out = malloc((size_t)len + 1024);
+            if (!out) { perror("malloc"); return 2; }
+            if (trc_decode_splanes_range_host(fb, fl, (size_t)off, (size_t)len, out) != len) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            return write_file(argv[5], out, (size_t)len);
+        }
         if (is_fplanes(fb, fl)) {
             const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
             trc_planes_hdr ph;
@@ -525,6 +563,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in>\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in>\n");
     return 2;
 }

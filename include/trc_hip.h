@@ -504,7 +504,8 @@ int    trc_fplanes_check(const void *buf, size_t buflen, size_t outlen);
  * trc_encode_planes_host (a TRCP container) where the choice is TRC_FILTER_NONE, trc_encode_fplanes_host(..., choice, ...) (a TRCF
  * container) otherwise; out must hold trc_fplanes_bound bytes; *advice (may be NULL) receives what decided.
  * trc_decode_xplanes_host reads either container: it looks at the magic and calls trc_decode_planes_host or
- * trc_decode_fplanes_host; any other magic returns 0 with the reason in trc_last_error(). */
+ * trc_decode_fplanes_host (or, for the TRCS container of the strided filters below, trc_decode_splanes_host); any other magic
+ * returns 0 with the reason in trc_last_error(). */
 typedef struct trc_planes_advice {
     int      filter;             /* the choice: TRC_FILTER_NONE, TRC_FILTER_ZDELTA or TRC_FILTER_XOR */
     unsigned esize, filters;     /* as given */
@@ -519,6 +520,67 @@ int    trc_planes_advise(const uint64_t *hist, unsigned filters, unsigned esize,
 size_t trc_encode_aplanes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
                                void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice);
 size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *out, size_t outlen);
+
+/* ---- byte planes behind a STRIDED predictor filter: interleaved data -------------------------------------------------
+ * Rows of K same-width fields, stereo / 5.1 / 7.1 PCM, xyz(w) points, complex pairs, RGB(A)16: the element in front belongs to
+ * another series, and a filter that predicts from it is worse than none.  With a stride S in 1 .. TRC_STRIDE_MAX the predictor of
+ * the filtered planes above reaches S elements back; everything not named here is as it is there:
+ *        p[i] = 0 where i % seg < S, else x[i - S]
+ *        y[i] = zigzag(x[i] - p[i] mod 2^w)  (TRC_FILTER_ZDELTA)      x[i] ^ p[i]  (TRC_FILTER_XOR)
+ *        F_S(filter, seg, esize, in) = the y's followed by the t untouched tail bytes;   F_1 = F
+ * The predictor still restarts every seg elements, whether or not S divides seg: a chunk range still decodes from its own bytes
+ * alone and every per-chunk contract carries over.  The filter enum is untouched; the stride is an argument of calls of its own.
+ *
+ * The whole contract:  splanes(filter, S, ..., in)  ==  planes(..., F_S(filter, chunk, esize, in))  byte for byte -- directory,
+ * payload, tail, totals, statuses and per-plane CDFs.  Arguments, alignment, flags and workspace (trc_planes_work_bytes /
+ * trc_planes_range_work_bytes: the filter needs none) are those of the fplanes calls, with `int stride` behind `int filter`.
+ * A stride outside 1 .. TRC_STRIDE_MAX is TRC_E_ARG, reported ahead of everything else, pointers included, so without a device.
+ * With stride == 1 or filter == TRC_FILTER_NONE a device call IS the fplanes call and launches its kernels.
+ *
+ * trc_planes_hist_stride_dev has the layout and the rules of trc_planes_hist_dev, with the rows of filters 1 and 2 counted under
+ * F_stride (the row of TRC_FILTER_NONE does not depend on it), so trc_planes_advise serves on its output as it stands; a caller
+ * picks among strides by comparing total_bits of several calls.  The advisor does not search strides by itself.
+ *
+ * Host pointers: the TRCS container = trc_splanes_hdr (16 bytes: the TRCF prefix with the stride where that one has its reserved
+ * field) in front of the TRCP container of F_S(filter, chunk, esize, in); bytes [16, size) are byte-identical to
+ * trc_encode_planes_host(codec, F_S(in), ...) at the same resolved chunk.  trc_encode_splanes_host takes filter 1 or 2 and stride
+ * 2 .. TRC_STRIDE_MAX: stride 1 returns 0 and names trc_encode_fplanes_host, TRC_FILTER_NONE names trc_encode_planes_host (one
+ * layout per content); out must hold trc_splanes_bound = trc_planes_bound + 16 bytes.  The decoders read everything from the two
+ * headers.  trc_splanes_check (host only, no GPU needed) validates magic, version 1, filter 1 or 2, stride 2 .. TRC_STRIDE_MAX,
+ * 16 < size <= buflen, then trc_planes_check(buf + 16, size - 16, outlen); the decoders call it first.  trc_decode_xplanes_host
+ * reads a TRCS container too. */
+#define TRC_STRIDE_MAX 8
+int trc_planes_split_sfilter_dev(int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg,
+                                 void *d_planes, size_t pitch, void *d_tail, void *stream);
+int trc_planes_join_sfilter_dev(int filter, int stride, const void *d_planes, size_t pitch, const void *d_tail,
+                                size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream);
+int trc_encode_splanes_dev(int codec, int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                           uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                           uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                           void *d_work, size_t work_bytes, void *stream);
+int trc_decode_splanes_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                           size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                           void *d_out, void *d_work, size_t work_bytes, void *stream);
+int trc_decode_splanes_range_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload,
+                                 size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                 const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_out, void *d_work, size_t work_bytes, void *stream);
+int trc_planes_hist_stride_dev(unsigned filters, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg,
+                               uint64_t *d_hist, void *stream);
+#define TRC_SPLANES_MAGIC 0x53435254u   /* "TRCS" */
+typedef struct trc_splanes_hdr {
+    uint32_t magic;      /* TRC_SPLANES_MAGIC */
+    uint8_t  filter;     /* TRC_FILTER_ZDELTA or TRC_FILTER_XOR */
+    uint8_t  version;    /* 1 */
+    uint16_t stride;     /* 2 .. TRC_STRIDE_MAX */
+    uint64_t size;       /* 16 + the inner TRCP container's size */
+} trc_splanes_hdr;       /* 16 bytes, little endian */
+size_t trc_splanes_bound(size_t n, unsigned esize, uint32_t chunk, unsigned cdfnum);
+size_t trc_encode_splanes_host(int codec, int filter, int stride, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                               void *out, size_t outcap, unsigned cdfnum);
+size_t trc_decode_splanes_host(const void *in, size_t inlen, void *out, size_t outlen);
+size_t trc_decode_splanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
+int    trc_splanes_check(const void *buf, size_t buflen, size_t outlen);
 
 /* ---- batched byte planes: many separate allocations in one coded call, any one of them decodable ------------------------
  * A checkpoint is hundreds of tensors of one dtype, a KV-cache a pool of pages, a table a set of columns: many allocations, each

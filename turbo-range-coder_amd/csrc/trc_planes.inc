@@ -69,10 +69,23 @@ static int filter_common(const char *who, int filter)
     return TRC_OK;
 }
 
-extern "C" int trc_encode_fplanes_dev(int codec, int filter, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
-                                      uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
-                                      uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
-                                      void *d_work, size_t work_bytes, void *stream)
+// The strided forms (trc_splanes.hip, trc_splanes.inc) are the same three calls with another split / join: stride 1 is the fplanes
+// call, whose kernels it launches.  The stride itself is vetted by trc_splanes.inc before it gets here.
+static int split_any(int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg, void *d_planes, size_t pitch, void *d_tail, void *stream)
+{
+    return stride == 1 ? trc_planes_split_filter_dev(filter, d_in, n, esize, seg, d_planes, pitch, d_tail, stream)
+                       : trc_planes_split_sfilter_dev(filter, stride, d_in, n, esize, seg, d_planes, pitch, d_tail, stream);
+}
+static int join_any(int filter, int stride, const void *d_planes, size_t pitch, const void *d_tail, size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream)
+{
+    return stride == 1 ? trc_planes_join_filter_dev(filter, d_planes, pitch, d_tail, n, esize, seg, d_out, stream)
+                       : trc_planes_join_sfilter_dev(filter, stride, d_planes, pitch, d_tail, n, esize, seg, d_out, stream);
+}
+
+static int planes_encode_dev(int codec, int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                             uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                             uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                             void *d_work, size_t work_bytes, void *stream)
 {
     int rc = filter_common("encode_planes", filter);
     if (rc) return rc;
@@ -87,7 +100,7 @@ extern "C" int trc_encode_fplanes_dev(int codec, int filter, const void *d_in, s
     if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
         return fail(TRC_E_ARG, "encode_planes: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned");
     uint8_t *w = (uint8_t *)d_work;
-    if ((rc = trc_planes_split_filter_dev(filter, d_in, n, esize, chunk, w, P.slice, d_tail, stream))) return rc;
+    if ((rc = split_any(filter, stride, d_in, n, esize, chunk, w, P.slice, d_tail, stream))) return rc;
     for (unsigned k = 0; k < esize; k++) {
         uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
         uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
@@ -96,6 +109,13 @@ extern "C" int trc_encode_fplanes_dev(int codec, int filter, const void *d_in, s
                                  pw, P.work, stream))) return rc;
     }
     return TRC_OK;
+}
+extern "C" int trc_encode_fplanes_dev(int codec, int filter, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                                      uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                      uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                                      void *d_work, size_t work_bytes, void *stream)
+{
+    return planes_encode_dev(codec, filter, 1, d_in, n, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total, d_tail, d_work, work_bytes, stream);
 }
 
 extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
@@ -107,9 +127,9 @@ extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsi
                                   d_work, work_bytes, stream);
 }
 
-extern "C" int trc_decode_fplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
-                                      size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
-                                      void *d_out, void *d_work, size_t work_bytes, void *stream)
+static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                             size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                             void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
     int rc = filter_common("decode_planes", filter);
     if (rc) return rc;
@@ -127,7 +147,13 @@ extern "C" int trc_decode_fplanes_dev(int codec, int filter, const uint32_t *d_c
         if ((rc = trc_decode_dev(codec, d_clen + k * P.nc, (const uint8_t *)d_payload + k * P.buf, P.m, chunk,
                                  r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return trc_planes_join_filter_dev(filter, w, P.slice, d_tail, n, esize, chunk, d_out, stream);
+    return join_any(filter, stride, w, P.slice, d_tail, n, esize, chunk, d_out, stream);
+}
+extern "C" int trc_decode_fplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                                      size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                      void *d_out, void *d_work, size_t work_bytes, void *stream)
+{
+    return planes_decode_dev(codec, filter, 1, d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
                                      size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
@@ -136,10 +162,10 @@ extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const vo
     return trc_decode_fplanes_dev(codec, TRC_FILTER_NONE, d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 
-extern "C" int trc_decode_fplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload,
-                                            size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
-                                            const uint16_t *d_cdf, unsigned cdfnum,
-                                            void *d_out, void *d_work, size_t work_bytes, void *stream)
+static int planes_decode_range_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload,
+                                   size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                   const uint16_t *d_cdf, unsigned cdfnum,
+                                   void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
     int rc = filter_common("decode_planes_range", filter);
     if (rc) return rc;
@@ -164,7 +190,14 @@ extern "C" int trc_decode_fplanes_range_dev(int codec, int filter, const uint32_
         if ((rc = trc_decode_range_dev(codec, d_clen + k * nc, (const uint8_t *)d_payload + k * pitch, m, chunk, first_chunk, count,
                                        r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return trc_planes_join_filter_dev(filter, w, P.slice, nullptr, elems * esize, esize, chunk, d_out, stream);       // (the range opens a segment)
+    return join_any(filter, stride, w, P.slice, nullptr, elems * esize, esize, chunk, d_out, stream);       // (the range opens a segment)
+}
+extern "C" int trc_decode_fplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload,
+                                            size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                            const uint16_t *d_cdf, unsigned cdfnum,
+                                            void *d_out, void *d_work, size_t work_bytes, void *stream)
+{
+    return planes_decode_range_dev(codec, filter, 1, d_clen, d_payload, n, esize, chunk, first_chunk, count, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_planes_range_dev(int codec, const uint32_t *d_clen, const void *d_payload,
                                            size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
@@ -300,7 +333,7 @@ extern "C" int trc_planes_advise(const uint64_t *hist, unsigned filters, unsigne
 // that choice: the TRCP container, behind the 16-byte TRCF prefix where the choice is a filter.
 #define PLANES_FILTER_AUTO (-1)
 static size_t planes_host_encode(int codec, int filter, const void *in, size_t n, unsigned esize, uint32_t chunk,
-                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice = nullptr)
+                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice = nullptr, int stride = 1)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
     if (codec_row(codec).low4) { fail(TRC_E_ARG, "encode_planes_host: " PLANES_LOW4, codec); return 0; }      // before anything is uploaded
@@ -345,7 +378,7 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
             out = (uint8_t *)out + lead; outcap -= lead;
         }
     }
-    if (trc_encode_fplanes_dev(codec, filter, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+    if (planes_encode_dev(codec, filter, stride, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                               d_clen, d_payload, d_total, d_tail, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
     uint64_t total[8];
     int32_t status[8];
@@ -420,7 +453,8 @@ static void planes_sections(const uint8_t *b, const trc_planes_hdr &h, PlanesSec
 }
 
 // elements [first_chunk * chunk, ...) of `count` chunks -- or, whole = true, everything with the tail -- decoded to c.d_in
-static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const trc_planes_hdr &h, bool whole, size_t first_chunk, size_t count, size_t elems)
+static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const trc_planes_hdr &h, bool whole, size_t first_chunk, size_t count, size_t elems,
+                                 int stride = 1)
 {
     const TrcCodec &r = codec_row(h.codec);
     const unsigned esize = h.esize;
@@ -448,13 +482,13 @@ static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const
         if (R.payload_len) PCHK(hipMemcpyAsync(d_payload + k * P.buf, pay + R.payload_off, (size_t)R.payload_len, hipMemcpyHostToDevice, s));
     }
     if (whole && h.tail) PCHK(hipMemcpyAsync(d_tail, b + h.size - h.tail, h.tail, hipMemcpyHostToDevice, s));
-    if (trc_decode_fplanes_dev(h.codec, filter, d_clen, d_payload, d_tail, nsub, esize, h.chunk, r.cdf ? d_cdf : nullptr, h.cdfnum,
+    if (planes_decode_dev(h.codec, filter, stride, d_clen, d_payload, d_tail, nsub, esize, h.chunk, r.cdf ? d_cdf : nullptr, h.cdfnum,
                               c.d_in, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
     return nsub;
 }
 
 // the two decoders of a TRCP container whose content is F(filter, chunk, esize, original)
-static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, void *out, size_t outlen)
+static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, void *out, size_t outlen, int stride = 1)
 {
     if (trc_planes_check(in, inlen, outlen)) return 0;
     trc_planes_hdr h;
@@ -463,7 +497,7 @@ static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, v
     std::unique_lock<std::mutex> lk;
     if (planes_ctx(cp, lk)) return 0;
     const size_t m = (size_t)(h.n / h.esize);
-    if (!planes_host_decode(*cp, filter, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m)) return 0;
+    if (!planes_host_decode(*cp, filter, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m, stride)) return 0;
     hipStream_t s = cp->s_k[0];
     PCHK(hipMemcpyAsync(out, cp->d_in, (size_t)h.n, hipMemcpyDeviceToHost, s));
     PCHK(hipStreamSynchronize(s));
@@ -476,7 +510,7 @@ extern "C" size_t trc_decode_planes_host(const void *in, size_t inlen, void *out
     return planes_host_decode_all(TRC_FILTER_NONE, in, inlen, out, outlen);
 }
 
-static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen, size_t offset, size_t len, void *out)
+static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen, size_t offset, size_t len, void *out, int stride = 1)
 {
     if (trc_planes_check(in, inlen, (size_t)-1)) return 0;
     trc_planes_hdr h;
@@ -492,7 +526,7 @@ static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen,
         HostCtx *cp = nullptr;
         std::unique_lock<std::mutex> lk;
         if (planes_ctx(cp, lk)) return 0;
-        if (!planes_host_decode(*cp, filter, b, h, false, c0, c1 - c0 + 1, elems)) return 0;
+        if (!planes_host_decode(*cp, filter, b, h, false, c0, c1 - c0 + 1, elems, stride)) return 0;
         hipStream_t s = cp->s_k[0];
         PCHK(hipMemcpyAsync(out, cp->d_in + (offset - c0 * (size_t)h.chunk * h.esize), lb, hipMemcpyDeviceToHost, s));
         PCHK(hipStreamSynchronize(s));
@@ -581,6 +615,7 @@ extern "C" size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *ou
     if (inlen >= sizeof magic) memcpy(&magic, in, sizeof magic);
     if (magic == TRC_PLANES_MAGIC) return trc_decode_planes_host(in, inlen, out, outlen);
     if (magic == TRC_FPLANES_MAGIC) return trc_decode_fplanes_host(in, inlen, out, outlen);
-    fail(TRC_E_ARG, "decode_xplanes_host: neither a planes (TRCP) nor a filtered planes (TRCF) container");
+    if (magic == TRC_SPLANES_MAGIC) return trc_decode_splanes_host(in, inlen, out, outlen);
+    fail(TRC_E_ARG, "decode_xplanes_host: neither a planes (TRCP) nor a filtered planes (TRCF, TRCS) container");
     return 0;
 }

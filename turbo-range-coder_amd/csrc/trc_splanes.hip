@@ -1,0 +1,336 @@
+// trc_splanes.hip -- the filtered split and join of trc_fplanes.hip with a STRIDED predictor: element i is predicted from element
+// i - S of its restart segment, S = 2 .. 8 (TRC_STRIDE_MAX), for data that interleaves S series of one element width (rows of S
+// fields, stereo / 5.1 / 7.1 PCM, xyz(w) points, complex pairs, RGB(A)16).  Stride 1 is trc_fplanes.hip and never comes here.
+//
+// Definition (include/trc_hip.h): p[i] = 0 where i % seg < S, else x[i - S];  y[i] = zigzag(x[i] - p[i] mod 2^w)  or  x[i] ^ p[i];
+// plane k = byte k of every y[i].  The tail bytes are not filtered.
+//
+// Split is the stride-1 kernel with a longer reach backwards: a thread owns a vector of 8 elements, seg is a multiple of 64, so a
+// vector never straddles a restart, and with S <= 8 the only elements it lacks are the last S of the vector in front of it.  It
+// loads the 16-byte words of that vector that hold them (their line is fetched by the neighbour anyway); a vector that opens a
+// segment loads nothing and predicts zero for its first S elements.  S is a template argument, so every index is static.
+//
+// Join undoes S interleaved prefix sums (or prefix xors) that restart every seg elements, in the shape of trc_fplanes_join_kernel:
+// a wave per span, tiles of 512 elements, 8 per lane, the next tile's plane loads issued before this tile is scanned, spans of 8
+// short segments with a segmented wave scan, the input's last partial vector moved element by element.  What changes is the scan.
+// An element's CLASS is its position in the segment mod S; the S classes are S independent scans.
+//   - in the lane: e[j] = op(e[j], e[j - S]) for j >= S, so the lane's last S elements are its per-class totals;
+//   - which class the lane's element j has depends on where the lane stands in its segment: (nin + j) % S.  The totals are brought
+//     into class order by a rotate -- none where S divides 8 (nin is a multiple of 8), a chain of selects on nin % S otherwise; no
+//     register array is indexed dynamically;
+//   - S segmented wave scans (six __shfl_up steps each), plus the carry of S values out of the previous tile for the lanes whose
+//     segment began in an earlier tile; the carry is kept in class order, so it needs no rotate.  16-bit elements go two classes
+//     to a word through the scans (v_pk_add_u16 / xor): the shuffles are what the scan costs, and this halves them;
+//   - the sums of the lanes in front are rotated back to the lane's element order and added per element.
+// No LDS beyond what the shuffles use, no scratch, no workspace, no dependency between workgroups.
+// operand, op, tile_load and wrap_seg are trc_fplanes.hip's, repeated here so that the stride-1 kernels compile from the file they
+// were in, untouched.
+#include "trc_planes_vec.h"
+
+#define TRC_FPLANES_TILE (64 * TRC_PLANES_VEC)      // elements a wave handles per step of the join
+
+// the scan's operand of y and the scan's operation, as in trc_fplanes.hip
+template <int ESIZE, int FILTER> __device__ __forceinline__ typename Elem<ESIZE>::T operand(typename Elem<ESIZE>::T y)
+{
+    typedef typename Elem<ESIZE>::T T;
+    if constexpr (FILTER == TRC_FILTER_XOR) return y;
+    return (y >> 1) ^ ((T)0 - (y & 1));
+}
+template <int FILTER, typename T> __device__ __forceinline__ T op(T a, T b) { return FILTER == TRC_FILTER_XOR ? a ^ b : a + b; }
+
+// the last S elements of the vector in front of vector v, at pe[8 - S .. 7]; only the 16-byte words that hold them are loaded
+template <int ESIZE, int S> __device__ __forceinline__ void load_front(const uint8_t *__restrict__ in, size_t v, typename Elem<ESIZE>::T *pe)
+{
+    constexpr int NW = 2 * ESIZE, NQ = NW / 4, Q0 = NQ - (S * ESIZE + 15) / 16;
+    const uint4 *src = (const uint4 *)(in + (v - 1) * (TRC_PLANES_VEC * ESIZE));
+    u32 w[NW];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        uint4 x = make_uint4(0u, 0u, 0u, 0u);
+        if (q >= Q0) x = src[q];
+        w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w;
+    }
+    unpack<ESIZE>(w, pe);
+}
+
+// in: 16-byte aligned, m * ESIZE + t bytes.  planes: 256-byte aligned, pitch a multiple of 256.  seg: a multiple of 64.  r0 =
+// (m / 8 * 8) % seg, where the elements behind the last whole vector lie in their segment.  Writes [0, m) of every plane and
+// [0, t) of tail, nothing else; reads nothing in front of `in`.
+template <int ESIZE, int FILTER, int S> __global__ __launch_bounds__(TRC_PLANES_BLOCK)
+void trc_splanes_split_kernel(const uint8_t *__restrict__ in, size_t m, u32 t, u32 seg, u32 r0, uint8_t *__restrict__ planes, size_t pitch, uint8_t *__restrict__ tail)
+{
+    typedef typename Elem<ESIZE>::T T;
+    typedef typename Elem<ESIZE>::M M;
+    constexpr int NW = 2 * ESIZE, NQ = NW / 4;
+    const size_t nv = m / TRC_PLANES_VEC, step = (size_t)gridDim.x * TRC_PLANES_BLOCK;
+    const M *el = (const M *)in;
+    const u32 vseg = seg / TRC_PLANES_VEC, v0 = blockIdx.x * TRC_PLANES_BLOCK + threadIdx.x, rstep = (u32)step % vseg;
+    u32 r = v0 % vseg;                             // the vector's place in its segment: 0 opens one
+    for (size_t v = v0; v < nv; v += step) {
+        const uint4 *src = (const uint4 *)(in + v * (TRC_PLANES_VEC * ESIZE));
+        u32 w[NW];
+#pragma unroll
+        for (int q = 0; q < NQ; q++) { const uint4 x = src[q]; w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w; }
+        T pe[TRC_PLANES_VEC];
+#pragma unroll
+        for (int j = 0; j < TRC_PLANES_VEC; j++) pe[j] = 0;
+        if (r) load_front<ESIZE, S>(in, v, pe);
+        T e[TRC_PLANES_VEC], y[TRC_PLANES_VEC];
+        unpack<ESIZE>(w, e);
+#pragma unroll
+        for (int j = 0; j < TRC_PLANES_VEC; j++) y[j] = fwd<ESIZE, FILTER>(e[j], j >= S ? e[j - S] : pe[TRC_PLANES_VEC - S + j]);
+        pack<ESIZE>(y, w);
+        uint2 p[ESIZE];
+        vec_split<ESIZE>(w, p);
+#pragma unroll
+        for (int k = 0; k < ESIZE; k++) *(uint2 *)(planes + k * pitch + v * TRC_PLANES_VEC) = p[k];
+        r += rstep;
+        if (r >= vseg) r -= vseg;
+    }
+    // the elements behind the last whole vector (at most 7), one per lane, and the tail bytes (at most ESIZE - 1)
+    if (blockIdx.x == 0) {
+        const u32 rest = (u32)(m - nv * TRC_PLANES_VEC), g = threadIdx.x;
+        if (g < rest) {
+            const size_t i = nv * TRC_PLANES_VEC + g;
+            const T y = fwd<ESIZE, FILTER>((T)el[i], r0 + g >= (u32)S ? (T)el[i - S] : (T)0);      // (r0 + g >= S: i >= S)
+#pragma unroll
+            for (int k = 0; k < ESIZE; k++) planes[k * pitch + i] = (uint8_t)(y >> (8 * k));
+        } else if (g < rest + t) tail[g - rest] = in[m * ESIZE + (g - rest)];
+    }
+}
+
+// the bytes of `cnt` elements from `base` on, of every plane: 8 = a whole vector, 0 = none (zeros: the scan's identity)
+template <int ESIZE> __device__ __forceinline__ void tile_load(const uint8_t *__restrict__ planes, size_t pitch, size_t base, u32 cnt, uint2 *p)
+{
+#pragma unroll
+    for (int k = 0; k < ESIZE; k++) p[k] = make_uint2(0u, 0u);
+    if (cnt == TRC_PLANES_VEC) {
+#pragma unroll
+        for (int k = 0; k < ESIZE; k++) p[k] = *(const uint2 *)(planes + k * pitch + base);
+    } else if (cnt) {                              // the input's last vector
+#pragma unroll
+        for (int k = 0; k < ESIZE; k++) {
+            uint64_t a = 0;
+#pragma unroll
+            for (int j = 0; j < TRC_PLANES_VEC - 1; j++) if ((u32)j < cnt) a |= (uint64_t)planes[k * pitch + base + j] << (8 * j);
+            p[k] = make_uint2((u32)a, (u32)(a >> 32));
+        }
+    }
+}
+
+// x < 3 * seg -> x % seg
+__device__ __forceinline__ u32 wrap_seg(u32 x, u32 seg)
+{
+    if (x >= seg) x -= seg;
+    if (x >= seg) x -= seg;
+    return x;
+}
+
+// out[i] = a[(i + r) % S], r in [0, S): a rotate by 1, by 2 and by 4, each taken where r has that bit -- selects over static
+// indices, three per value
+template <int S, typename T> __device__ __forceinline__ void rotate(const T *a, u32 r, T *out)
+{
+    T x[S];
+#pragma unroll
+    for (int i = 0; i < S; i++) x[i] = a[i];
+#pragma unroll
+    for (int b = 1; b < S; b <<= 1) {
+        const bool take = r & (u32)b;
+        T y[S];
+#pragma unroll
+        for (int i = 0; i < S; i++) y[i] = take ? x[(i + b) % S] : x[i];
+#pragma unroll
+        for (int i = 0; i < S; i++) x[i] = y[i];
+    }
+#pragma unroll
+    for (int i = 0; i < S; i++) out[i] = x[i];
+}
+
+// 16-bit sums two to a word (v_pk_add_u16), so that a wave scan of 16-bit elements moves two classes per shuffle
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+template <int FILTER> __device__ __forceinline__ u32 pkop(u32 a, u32 b)
+{
+    if constexpr (FILTER == TRC_FILTER_XOR) return a ^ b;
+    return __builtin_bit_cast(u32, (us2)(__builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b)));
+}
+
+// N segmented inclusive wave scans (six __shfl_up steps each): inc[c] = the lane's total of value c on entry.  A lane adds what lies
+// at most `reach` lanes in front of it.  before[c] = the sum of the lanes in front of this one in its segment, those of earlier
+// tiles included where take_carry says the segment began there; carry[c] = the running value where this tile ends.
+template <int FILTER, int N, typename V, bool PK> __device__ __forceinline__ void wave_scan(V *inc, V *carry, V *before, u32 reach, bool take_carry)
+{
+    auto f = [](V a, V b) __attribute__((always_inline)) { if constexpr (PK) return (V)pkop<FILTER>((u32)a, (u32)b); else return op<FILTER>(a, b); };
+#pragma unroll
+    for (u32 d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (int c = 0; c < N; c++) {
+            const V o = __shfl_up(inc[c], d);
+            if (reach >= d) inc[c] = f(inc[c], o);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < N; c++) {
+        const V in_carry = take_carry ? carry[c] : (V)0, b = __shfl_up(inc[c], 1u);
+        before[c] = f(in_carry, reach ? b : (V)0);
+        carry[c] = __shfl(f(inc[c], in_carry), 63);
+    }
+}
+
+// the mirror image: writes [0, m * ESIZE + t) of out, nothing else.  Spans, tiles and the segmented scan's reach are those of
+// trc_fplanes_join_kernel; carry[c] = the running value of class c at the end of the previous tile.
+template <int ESIZE, int FILTER, int S> __global__ __launch_bounds__(TRC_PLANES_BLOCK)
+void trc_splanes_join_kernel(const uint8_t *__restrict__ planes, size_t pitch, const uint8_t *__restrict__ tail, size_t m, u32 t, u32 seg, u32 span,
+                             size_t nspan, uint8_t *__restrict__ out)
+{
+    typedef typename Elem<ESIZE>::T T;
+    typedef typename Elem<ESIZE>::M M;
+    constexpr int NW = 2 * ESIZE, NQ = NW / 4, V = TRC_PLANES_VEC;
+    constexpr bool ROT = (V % S) != 0;                                   // S divides 8: a lane's element j has class j % S
+    constexpr int NP = ESIZE == 2 ? (S + 1) / 2 : S;                     // values the wave scans
+    const u32 lane = threadIdx.x & 63u;
+    const size_t waves = (size_t)gridDim.x * (TRC_PLANES_BLOCK / 64);
+    size_t s = (size_t)blockIdx.x * (TRC_PLANES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // the span, the tile in it,
+    u32 tile = 0;                                                                                                   // the span's length: one per wave
+    if (s < nspan) {
+        u32 len = (u32)(m - s * span < span ? m - s * span : span);
+        u32 at = lane * V;                                               // the lane's first element in the span ...
+        u32 nin = wrap_seg(at, seg);                                     // ... and in its segment (span <= 8 * seg, a tile < 3 * seg)
+        u32 ncnt = at < len ? (len - at < V ? len - at : V) : 0;
+        size_t nbase = s * span + at;
+        uint2 pn[ESIZE];
+        tile_load<ESIZE>(planes, pitch, nbase, ncnt, pn);
+        T carry[NP];                                                     // (16-bit elements: two classes to a word, T is u32)
+#pragma unroll
+        for (int c = 0; c < NP; c++) carry[c] = 0;
+        for (;;) {
+            uint2 p[ESIZE];
+#pragma unroll
+            for (int k = 0; k < ESIZE; k++) p[k] = pn[k];
+            const size_t base = nbase;
+            const u32 cnt = ncnt, ahead = nin / V;                       // lanes' worth of elements in front of this one in its segment
+            const u32 r8 = ROT ? nin % (u32)S : 0u;                      // the class of the lane's first element
+            // the wave's next tile: its loads are under way while this one is scanned
+            tile++;
+            bool more = true;
+            if (tile * TRC_FPLANES_TILE >= len) {
+                s += waves; tile = 0;
+                more = s < nspan;
+                if (more) len = (u32)(m - s * span < span ? m - s * span : span);
+                nin = wrap_seg(lane * V, seg);
+            } else nin = wrap_seg(nin + TRC_FPLANES_TILE, seg);
+            if (more) {
+                at = tile * TRC_FPLANES_TILE + lane * V;
+                ncnt = at < len ? (len - at < V ? len - at : V) : 0;
+                nbase = s * span + at;
+                tile_load<ESIZE>(planes, pitch, nbase, ncnt, pn);
+            }
+            u32 w[NW];
+            vec_join<ESIZE>(p, w);
+            T e[V];
+            unpack<ESIZE>(w, e);
+#pragma unroll
+            for (int j = 0; j < V; j++) e[j] = operand<ESIZE, FILTER>(e[j]);
+#pragma unroll
+            for (int j = S; j < V; j++) e[j] = op<FILTER>(e[j], e[j - S]);
+            // the lane's totals by class: element 8 - S + i has class (r8 + 8 + i) % S
+            T inc[S];
+            if constexpr (ROT) {
+                const u32 rot = (r8 + V) % (u32)S;
+                rotate<S>(e + V - S, rot ? (u32)S - rot : 0u, inc);
+            } else {
+#pragma unroll
+                for (int c = 0; c < S; c++) inc[c] = e[V - S + c];
+            }
+            const u32 reach = ahead < lane ? ahead : lane;               // lanes in front of this one in its segment and in this tile
+            T before[S];                                                 // per class: the lanes in front of it, and the earlier tiles
+            if constexpr (ESIZE == 2) {                                  // two classes to a word: half the shuffles
+                u32 pk[NP], pb[NP];
+#pragma unroll
+                for (int i = 0; i < NP; i++) {
+                    constexpr int LAST = S - 1;
+                    const int hi = 2 * i + 1 < S ? 2 * i + 1 : LAST;     // (an odd S: the last word holds one class)
+                    pk[i] = (inc[2 * i] & 0xffffu) | (2 * i + 1 < S ? inc[hi] << 16 : 0u);
+                }
+                wave_scan<FILTER, NP, u32, true>(pk, carry, pb, reach, ahead > lane);
+#pragma unroll
+                for (int c = 0; c < S; c++) before[c] = c & 1 ? pb[c / 2] >> 16 : pb[c / 2];       // (junk above bit 15, as everywhere)
+            } else wave_scan<FILTER, S, T, false>(inc, carry, before, reach, ahead > lane);
+            if constexpr (ROT) {
+                T loc[S];
+                rotate<S>(before, r8, loc);                              // loc[i] = before[(r8 + i) % S]: element j takes loc[j % S]
+#pragma unroll
+                for (int j = 0; j < V; j++) e[j] = op<FILTER>(e[j], loc[j % S]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; j++) e[j] = op<FILTER>(e[j], before[j % S]);
+            }
+            if (cnt == V) {
+                pack<ESIZE>(e, w);
+                uint4 *dst = (uint4 *)(out + base * ESIZE);
+#pragma unroll
+                for (int q = 0; q < NQ; q++) dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+            } else if (cnt) {
+#pragma unroll
+                for (int j = 0; j < V - 1; j++) if ((u32)j < cnt) ((M *)out)[base + j] = (M)e[j];
+            }
+            if (!more) break;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < t) out[m * ESIZE + threadIdx.x] = tail[threadIdx.x];
+}
+
+// ---- the C-ABI ---------------------------------------------------------------------------------------------------------------
+// what the strided calls check ahead of everything else, pointers included: the stride, then filter and restart length
+static int sfilter_args(const char *who, int filter, int stride, uint32_t seg)
+{
+    if (stride < 1 || stride > TRC_STRIDE_MAX) return trc_fail(TRC_E_ARG, "%s: stride %d (1 .. %d)", who, stride, TRC_STRIDE_MAX);
+    if (filter != TRC_FILTER_NONE && filter != TRC_FILTER_ZDELTA && filter != TRC_FILTER_XOR)
+        return trc_fail(TRC_E_ARG, "%s: filter %d (0 none, 1 zigzag delta, 2 xor)", who, filter);
+    if (seg < TRC_CHUNK_MIN || seg > TRC_CHUNK_MAX || seg % 64u)
+        return trc_fail(TRC_E_ARG, "%s: restart length %u: must be a multiple of 64 in [%u,%u]", who, seg, TRC_CHUNK_MIN, TRC_CHUNK_MAX);
+    return TRC_OK;
+}
+
+typedef void (*split_fn)(const uint8_t *, size_t, u32, u32, u32, uint8_t *, size_t, uint8_t *);
+typedef void (*join_fn)(const uint8_t *, size_t, const uint8_t *, size_t, u32, u32, u32, size_t, uint8_t *);
+#define SPLANES_STRIDES(K, E, F) { K<E, F, 2>, K<E, F, 3>, K<E, F, 4>, K<E, F, 5>, K<E, F, 6>, K<E, F, 7>, K<E, F, 8> }
+#define SPLANES_TABLE(K) { { SPLANES_STRIDES(K, 2, TRC_FILTER_ZDELTA), SPLANES_STRIDES(K, 2, TRC_FILTER_XOR) }, \
+                           { SPLANES_STRIDES(K, 4, TRC_FILTER_ZDELTA), SPLANES_STRIDES(K, 4, TRC_FILTER_XOR) }, \
+                           { SPLANES_STRIDES(K, 8, TRC_FILTER_ZDELTA), SPLANES_STRIDES(K, 8, TRC_FILTER_XOR) } }
+// [esize 2 / 4 / 8][filter - 1][stride - 2]
+static const split_fn split_kernels[3][2][TRC_STRIDE_MAX - 1] = SPLANES_TABLE(trc_splanes_split_kernel);
+static const join_fn join_kernels[3][2][TRC_STRIDE_MAX - 1] = SPLANES_TABLE(trc_splanes_join_kernel);
+static int esize_row(unsigned esize) { return esize == 2 ? 0 : esize == 4 ? 1 : 2; }
+
+extern "C" int trc_planes_split_sfilter_dev(int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg,
+                                            void *d_planes, size_t pitch, void *d_tail, void *stream)
+{
+    int rc = sfilter_args("planes_split_sfilter", filter, stride, seg);
+    if (rc) return rc;
+    if (stride == 1 || filter == TRC_FILTER_NONE) return trc_planes_split_filter_dev(filter, d_in, n, esize, seg, d_planes, pitch, d_tail, stream);
+    if ((rc = planes_args("planes_split_sfilter", d_in, n, esize, d_planes, pitch, d_tail))) return rc;
+    const size_t m = n / esize;
+    const uint32_t t = (uint32_t)(n % esize), r0 = (uint32_t)((m / TRC_PLANES_VEC * TRC_PLANES_VEC) % seg);
+    hipLaunchKernelGGL(split_kernels[esize_row(esize)][filter - 1][stride - 2], dim3(planes_grid(m)), dim3(TRC_PLANES_BLOCK), 0, (hipStream_t)stream,
+                       (const uint8_t *)d_in, m, t, seg, r0, (uint8_t *)d_planes, pitch, (uint8_t *)d_tail);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_split_sfilter: %s", hipGetErrorString(e));
+}
+
+extern "C" int trc_planes_join_sfilter_dev(int filter, int stride, const void *d_planes, size_t pitch, const void *d_tail,
+                                           size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream)
+{
+    int rc = sfilter_args("planes_join_sfilter", filter, stride, seg);
+    if (rc) return rc;
+    if (stride == 1 || filter == TRC_FILTER_NONE) return trc_planes_join_filter_dev(filter, d_planes, pitch, d_tail, n, esize, seg, d_out, stream);
+    if ((rc = planes_args("planes_join_sfilter", d_out, n, esize, d_planes, pitch, d_tail))) return rc;
+    const uint32_t t = (uint32_t)(n % esize), span = seg < TRC_FPLANES_TILE ? 8 * seg : seg;
+    const size_t m = n / esize, nspan = (m + span - 1) / span;
+    // a wave per span, TRC_PLANES_GRID as for the other plane kernels
+    const size_t want = (nspan + TRC_PLANES_BLOCK / 64 - 1) / (TRC_PLANES_BLOCK / 64);
+    const unsigned cap = planes_grid_cap(), grid = want > cap ? cap : (unsigned)want;
+    hipLaunchKernelGGL(join_kernels[esize_row(esize)][filter - 1][stride - 2], dim3(grid), dim3(TRC_PLANES_BLOCK), 0, (hipStream_t)stream,
+                       (const uint8_t *)d_planes, pitch, (const uint8_t *)d_tail, m, t, seg, span, nspan, (uint8_t *)d_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_join_sfilter: %s", hipGetErrorString(e));
+}

@@ -181,6 +181,22 @@ def lib():
         l.trc_encode_aplanes_host.restype = _sz
         l.trc_encode_aplanes_host.argtypes = [C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint, C.POINTER(PlanesAdvice)]
         l.trc_decode_xplanes_host.restype = _sz; l.trc_decode_xplanes_host.argtypes = [_vp, _sz, _vp, _sz]
+        l.trc_planes_split_sfilter_dev.restype = C.c_int
+        l.trc_planes_split_sfilter_dev.argtypes = [C.c_int, C.c_int] + l.trc_planes_split_filter_dev.argtypes[1:]
+        l.trc_planes_join_sfilter_dev.restype = C.c_int
+        l.trc_planes_join_sfilter_dev.argtypes = [C.c_int, C.c_int] + l.trc_planes_join_filter_dev.argtypes[1:]
+        l.trc_encode_splanes_dev.restype = C.c_int; l.trc_encode_splanes_dev.argtypes = [C.c_int, C.c_int, C.c_int] + l.trc_encode_planes_dev.argtypes[1:]
+        l.trc_decode_splanes_dev.restype = C.c_int; l.trc_decode_splanes_dev.argtypes = [C.c_int, C.c_int, C.c_int] + l.trc_decode_planes_dev.argtypes[1:]
+        l.trc_decode_splanes_range_dev.restype = C.c_int
+        l.trc_decode_splanes_range_dev.argtypes = [C.c_int, C.c_int, C.c_int] + l.trc_decode_planes_range_dev.argtypes[1:]
+        l.trc_planes_hist_stride_dev.restype = C.c_int
+        l.trc_planes_hist_stride_dev.argtypes = [C.c_uint, C.c_int] + l.trc_planes_hist_dev.argtypes[1:]
+        l.trc_splanes_bound.restype = _sz; l.trc_splanes_bound.argtypes = [_sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_encode_splanes_host.restype = _sz
+        l.trc_encode_splanes_host.argtypes = [C.c_int, C.c_int, C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint]
+        l.trc_decode_splanes_host.restype = _sz; l.trc_decode_splanes_host.argtypes = [_vp, _sz, _vp, _sz]
+        l.trc_decode_splanes_range_host.restype = _sz; l.trc_decode_splanes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
+        l.trc_splanes_check.restype = C.c_int; l.trc_splanes_check.argtypes = [_vp, _sz, _sz]
         _it = C.POINTER(PlanesItem)
         l.trc_planes_batch_plan_host.restype = C.c_int
         l.trc_planes_batch_plan_host.argtypes = [_it, _sz, C.c_uint, C.c_uint32, C.POINTER(PlanesBatchPlan), C.POINTER(C.c_uint64)]
@@ -1034,6 +1050,71 @@ def encode_aplanes_host(codec, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
 
 def host_decode_xplanes(comp, n):
     return _host_decode_guarded("trc_decode_xplanes_host", comp, n)
+
+
+# -------------------------------------------- byte planes behind a strided filter: interleaved data (include/trc_hip.h) ---
+SPLANES_MAGIC = 0x53435254                                     # "TRCS"
+SPLANES_HDR = 16
+STRIDE_MAX = 8
+
+
+def planes_split_sfilter(filt, stride, d_in, n, esize, seg, d_planes, pitch, d_tail=None):
+    """enqueue trc_planes_split_sfilter_dev: planes_split_filter with the predictor `stride` elements back (1 .. STRIDE_MAX)"""
+    _chk(lib().trc_planes_split_sfilter_dev(filt, stride, d_in.data_ptr(), n, esize, seg, d_planes.data_ptr(), pitch,
+                                            d_tail.data_ptr() if d_tail is not None else None, _cur_stream(d_in)))
+
+
+def planes_join_sfilter(filt, stride, d_planes, pitch, d_tail, n, esize, seg, d_out):
+    """enqueue trc_planes_join_sfilter_dev, the inverse of planes_split_sfilter"""
+    _chk(lib().trc_planes_join_sfilter_dev(filt, stride, d_planes.data_ptr(), pitch, d_tail.data_ptr() if d_tail is not None else None, n,
+                                           esize, seg, d_out.data_ptr(), _cur_stream(d_out)))
+
+
+class StridedPlanesCoder(PlanesCoder):
+    """PlanesCoder through the trc_*_splanes_dev calls: the same buffers and results, of the elements filtered against the element
+    `stride` back (restart = chunk).  stride=1 is FilteredPlanesCoder, filter=FILTER_NONE the unfiltered coder."""
+    _ENC, _DEC, _DEC_RANGE = "trc_encode_splanes_dev", "trc_decode_splanes_dev", "trc_decode_splanes_range_dev"
+
+    def __init__(self, codec, n, esize, chunk=4096, device="cuda", cdfnum=256, prm=(5, 6), guard=0, filter=FILTER_NONE, stride=1):
+        super().__init__(codec, n, esize, chunk, device, cdfnum=cdfnum, prm=prm, guard=guard)
+        self.filter, self.stride = filter, stride
+
+    def _lead(self):
+        return (self.filter, self.stride)
+
+
+def planes_hist_stride(filters, stride, d_in, n, esize, seg, d_hist):
+    """enqueue trc_planes_hist_stride_dev: planes_hist with the rows of the zigzag-delta and xor filters counted under `stride`"""
+    _chk(lib().trc_planes_hist_stride_dev(filters, stride, d_in.data_ptr(), n, esize, seg, d_hist.data_ptr(), _cur_stream(d_in)))
+
+
+def splanes_bound(n, esize, chunk=0, cdfnum=0):
+    return lib().trc_splanes_bound(n, esize, chunk, cdfnum)
+
+
+def host_encode_splanes(codec, filt, stride, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
+    """trc_encode_splanes_host -> the TRCS container (np.uint8): 16 bytes, then the TRCP container of the strided-filtered data"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(splanes_bound(data.size, esize, chunk, cn), 64), dtype=np.uint8)
+    l = lib().trc_encode_splanes_host(codec, filt, stride, data.ctypes.data, data.size, esize, chunk, out.ctypes.data, out.size, cn)
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy()
+
+
+def host_decode_splanes(comp, n):
+    return _host_decode_guarded("trc_decode_splanes_host", comp, n)
+
+
+def host_decode_splanes_range(comp, offset, length):
+    return _host_decode_guarded("trc_decode_splanes_range_host", comp, length, offset)
+
+
+def splanes_check(buf, outlen=None):
+    """trc_splanes_check on a TRCS container in host memory (needs no device); raises TrcError with the library's reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_splanes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
 
 
 def encode_host_container(codec, data, chunk, cdf=None, cdfnum=256, prm=(5, 6)):
