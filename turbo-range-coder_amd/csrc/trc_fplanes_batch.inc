@@ -9,42 +9,13 @@
 // at most 2^13 vectors).  `first` has room as well, but the map kernel compares it as 64 bits and serves here as it stands.
 //
 // Split = trc_planes_split_batch_kernel + the forward step of trc_fplanes_split_kernel: the one element a thread lacks is the one in
-// front of its vector, in the same item unless the vector opens a chunk.  Join = the scanning join of trc_fplanes_join_kernel (one
-// wave per span of V, tiles of 512 elements, the next tile's loads in flight while this one is scanned, a segmented wave scan, the
-// carry of lane 63) with the map of the batch kernels behind the scan: a lane finds its item only to know which operation it scans
-// with, how much of its vector it stores and where.  A span of 8 short chunks may cross items of different filters; the segmented
-// scan never combines across a chunk and a chunk has one filter, so the operation is the lane's own (selects: a scan
-// per filter, taken where a tile's lanes agree, measured no faster -- profiles/planes/fbatch_notes.md).
-
-// ---- the pieces of the scanning join, as in trc_fplanes.hip (a translation unit of its own, left as it is; keep the two alike)
-#define TRC_FPLANES_TILE (64 * TRC_PLANES_VEC)      // elements a wave handles per step of the join
-
-// the bytes of `cnt` elements from `base` on, of every plane: 8 = a whole vector, 0 = none (zeros: the scan's identity)
-template <int ESIZE> __device__ __forceinline__ void tile_load(const uint8_t *__restrict__ planes, size_t pitch, size_t base, u32 cnt, uint2 *p)
-{
-#pragma unroll
-    for (int k = 0; k < ESIZE; k++) p[k] = make_uint2(0u, 0u);
-    if (cnt == TRC_PLANES_VEC) {
-#pragma unroll
-        for (int k = 0; k < ESIZE; k++) p[k] = *(const uint2 *)(planes + k * pitch + base);
-    } else if (cnt) {                              // the range's last vector
-#pragma unroll
-        for (int k = 0; k < ESIZE; k++) {
-            uint64_t a = 0;
-#pragma unroll
-            for (int j = 0; j < TRC_PLANES_VEC - 1; j++) if ((u32)j < cnt) a |= (uint64_t)planes[k * pitch + base + j] << (8 * j);
-            p[k] = make_uint2((u32)a, (u32)(a >> 32));
-        }
-    }
-}
-
-// x < 3 * seg -> x % seg
-__device__ __forceinline__ u32 wrap_seg(u32 x, u32 seg)
-{
-    if (x >= seg) x -= seg;
-    if (x >= seg) x -= seg;
-    return x;
-}
+// front of its vector, in the same item unless the vector opens a chunk.  Join = the scanning join of trc_fplanes_join_kernel at
+// stride 1 (trc_planes_scan.h: one wave per span of V, tiles of 512 elements, the next tile's loads in flight while this one is
+// scanned, a segmented wave scan, the carry of lane 63; the walk stands here as in that kernel -- keep the two alike) with the map of
+// the batch kernels behind the scan: a lane finds its item only to know which operation it scans with, how much of its vector it
+// stores and where.  A span of 8 short chunks may cross items of different filters; the segmented scan never combines across a chunk
+// and a chunk has one filter, so the operation is the lane's own (selects: a scan per filter, taken where a tile's lanes agree,
+// measured no faster -- profiles/planes/fbatch_notes.md).
 
 #define FBATCH_SHIFT 62
 #define FBATCH_V0(r) ((r).v0 & (((uint64_t)1 << FBATCH_SHIFT) - 1))
@@ -242,71 +213,4 @@ int trc_planes_batch_filters(const char *who, const uint8_t *filters, size_t cou
 static void fbatch_pack(std::vector<BatchRec> &recs, const uint8_t *filters)
 {
     for (size_t i = 0; i < recs.size(); i++) recs[i].v0 |= (uint64_t)filters[i] << FBATCH_SHIFT;
-}
-
-extern "C" int trc_planes_split_fbatch_dev(const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
-                                           void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
-{
-    trc_planes_batch_plan P;
-    int rc = batch_plan("planes_split_fbatch", items, count, esize, chunk, &P, nullptr);
-    if (rc) return rc;
-    bool any;
-    if ((rc = trc_planes_batch_filters("planes_split_fbatch", filters, count, &any))) return rc;
-    if (!any) return trc_planes_split_batch_dev(items, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
-    if (!d_planes || ((uintptr_t)d_planes & 255)) return trc_fail(TRC_E_ARG, "planes_split_fbatch: the planes must be 256-byte aligned");
-    if ((pitch & 255) || pitch < P.m_total) return trc_fail(TRC_E_ARG, "planes_split_fbatch: pitch %zu must be a multiple of 256 and at least %llu", pitch, (unsigned long long)P.m_total);
-    if ((rc = batch_table_args("planes_split_fbatch", count, P.chunks, d_table, table_bytes))) return rc;
-    std::vector<BatchRec> recs;
-    uint64_t chunks, elems;
-    if ((rc = batch_range("planes_split_fbatch", items, 0, count, esize, chunk, chunks, elems, &recs))) return rc;
-    fbatch_pack(recs, filters);
-    hipStream_t s = (hipStream_t)stream;
-    const BatchRec *d_rec;
-    const u32 *d_map;
-    if ((rc = batch_table("planes_split_fbatch", recs, chunks, d_table, s, d_rec, d_map))) return rc;
-    const size_t M = (size_t)elems, nv = (M + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
-    const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    const dim3 grid(batch_grid(nv)), block(TRC_PLANES_BLOCK);
-    if (esize == 2) hipLaunchKernelGGL(trc_fplanes_split_batch_kernel<2>, grid, block, 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
-    else if (esize == 4) hipLaunchKernelGGL(trc_fplanes_split_batch_kernel<4>, grid, block, 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
-    else hipLaunchKernelGGL(trc_fplanes_split_batch_kernel<8>, grid, block, 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_split_fbatch: %s", hipGetErrorString(e));
-}
-
-extern "C" int trc_planes_join_fbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, size_t count,
-                                          size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
-                                          void *d_table, size_t table_bytes, void *stream)
-{
-    int rc = batch_plan("planes_join_fbatch", items, count, esize, chunk, nullptr, nullptr);
-    if (rc) return rc;
-    bool any;
-    if ((rc = trc_planes_batch_filters("planes_join_fbatch", filters, count, &any))) return rc;
-    if (!any) return trc_planes_join_batch_dev(d_planes, pitch, items, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
-    if (first_item > count || item_count > count - first_item)
-        return trc_fail(TRC_E_ARG, "planes_join_fbatch: items [%zu, %zu + %zu) of %zu", first_item, first_item, item_count, count);
-    if (item_count == 0) return TRC_OK;
-    std::vector<BatchRec> recs;
-    uint64_t chunks, elems;
-    if ((rc = batch_range("planes_join_fbatch", items, first_item, item_count, esize, chunk, chunks, elems, &recs))) return rc;
-    fbatch_pack(recs, filters + first_item);
-    if (!d_planes || ((uintptr_t)d_planes & 63)) return trc_fail(TRC_E_ARG, "planes_join_fbatch: the planes must be 64-byte aligned");
-    if ((pitch & 255) || pitch < elems) return trc_fail(TRC_E_ARG, "planes_join_fbatch: pitch %zu must be a multiple of 256 and at least %llu", pitch, (unsigned long long)elems);
-    if ((rc = batch_table_args("planes_join_fbatch", item_count, chunks, d_table, table_bytes))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const BatchRec *d_rec;
-    const u32 *d_map;
-    if ((rc = batch_table("planes_join_fbatch", recs, chunks, d_table, s, d_rec, d_map))) return rc;
-    const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    const u32 span = chunk < TRC_FPLANES_TILE ? 8 * chunk : chunk;
-    const size_t nspan = ((size_t)elems + span - 1) / span;
-    // a wave per span, TRC_PLANES_GRID as for the other plane kernels
-    const size_t want = (nspan + TRC_PLANES_BLOCK / 64 - 1) / (TRC_PLANES_BLOCK / 64);
-    const unsigned cap = planes_grid_cap();
-    const dim3 grid(want > cap ? cap : (unsigned)want), block(TRC_PLANES_BLOCK);
-    if (esize == 2) hipLaunchKernelGGL(trc_fplanes_join_batch_kernel<2>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, (size_t)elems, chunk, span, nspan);
-    else if (esize == 4) hipLaunchKernelGGL(trc_fplanes_join_batch_kernel<4>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, (size_t)elems, chunk, span, nspan);
-    else hipLaunchKernelGGL(trc_fplanes_join_batch_kernel<8>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, (size_t)elems, chunk, span, nspan);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_join_fbatch: %s", hipGetErrorString(e));
 }

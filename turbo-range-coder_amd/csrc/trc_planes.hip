@@ -78,11 +78,9 @@ extern "C" int trc_planes_split_dev(const void *d_in, size_t n, unsigned esize, 
     if (rc) return rc;
     const size_t m = n / esize;
     const uint32_t t = (uint32_t)(n % esize);
-    const dim3 grid(planes_grid(m)), block(TRC_PLANES_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    if (esize == 2) hipLaunchKernelGGL(trc_planes_split_kernel<2>, grid, block, 0, s, (const uint8_t *)d_in, m, t, (uint8_t *)d_planes, pitch, (uint8_t *)d_tail);
-    else if (esize == 4) hipLaunchKernelGGL(trc_planes_split_kernel<4>, grid, block, 0, s, (const uint8_t *)d_in, m, t, (uint8_t *)d_planes, pitch, (uint8_t *)d_tail);
-    else hipLaunchKernelGGL(trc_planes_split_kernel<8>, grid, block, 0, s, (const uint8_t *)d_in, m, t, (uint8_t *)d_planes, pitch, (uint8_t *)d_tail);
+    static void (*const kernels[3])(const uint8_t *, size_t, u32, uint8_t *, size_t, uint8_t *) = TRC_BY_ESIZE(trc_planes_split_kernel);
+    hipLaunchKernelGGL(kernels[esize_row(esize)], dim3(planes_grid(m)), dim3(TRC_PLANES_BLOCK), 0, (hipStream_t)stream,
+                       (const uint8_t *)d_in, m, t, (uint8_t *)d_planes, pitch, (uint8_t *)d_tail);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_split: %s", hipGetErrorString(e));
 }
@@ -93,11 +91,9 @@ extern "C" int trc_planes_join_dev(const void *d_planes, size_t pitch, const voi
     if (rc) return rc;
     const size_t m = n / esize;
     const uint32_t t = (uint32_t)(n % esize);
-    const dim3 grid(planes_grid(m)), block(TRC_PLANES_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    if (esize == 2) hipLaunchKernelGGL(trc_planes_join_kernel<2>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, (const uint8_t *)d_tail, m, t, (uint8_t *)d_out);
-    else if (esize == 4) hipLaunchKernelGGL(trc_planes_join_kernel<4>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, (const uint8_t *)d_tail, m, t, (uint8_t *)d_out);
-    else hipLaunchKernelGGL(trc_planes_join_kernel<8>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, (const uint8_t *)d_tail, m, t, (uint8_t *)d_out);
+    static void (*const kernels[3])(const uint8_t *, size_t, const uint8_t *, size_t, u32, uint8_t *) = TRC_BY_ESIZE(trc_planes_join_kernel);
+    hipLaunchKernelGGL(kernels[esize_row(esize)], dim3(planes_grid(m)), dim3(TRC_PLANES_BLOCK), 0, (hipStream_t)stream,
+                       (const uint8_t *)d_planes, pitch, (const uint8_t *)d_tail, m, t, (uint8_t *)d_out);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_join: %s", hipGetErrorString(e));
 }

@@ -62,14 +62,9 @@ static int planes_common(const char *who, int codec, size_t n, unsigned esize, c
 
 // The three calls with a filter (trc_fplanes.hip) between the elements and the planes; with TRC_FILTER_NONE the filter forms of split
 // and join are the plain ones.  The restart length is the chunk, which check_common has vetted by the time split or join see it.
-static int filter_common(const char *who, int filter)
-{
-    if (filter != TRC_FILTER_NONE && filter != TRC_FILTER_ZDELTA && filter != TRC_FILTER_XOR)
-        return fail(TRC_E_ARG, "%s: filter %d (0 none, 1 zigzag delta, 2 xor)", who, filter);
-    return TRC_OK;
-}
+int trc_planes_filter_arg(const char *who, int filter);     // trc_fplanes.hip: the filter id, with the text of the split / join calls
 
-// The strided forms (trc_splanes.hip, trc_splanes.inc) are the same three calls with another split / join: stride 1 is the fplanes
+// The strided forms (trc_fplanes.hip, trc_splanes.inc) are the same three calls with another split / join: stride 1 is the fplanes
 // call, whose kernels it launches.  The stride itself is vetted by trc_splanes.inc before it gets here.
 static int split_any(int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg, void *d_planes, size_t pitch, void *d_tail, void *stream)
 {
@@ -87,7 +82,7 @@ static int planes_encode_dev(int codec, int filter, int stride, const void *d_in
                              uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
                              void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = filter_common("encode_planes", filter);
+    int rc = trc_planes_filter_arg("encode_planes", filter);
     if (rc) return rc;
     if ((rc = planes_common("encode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
@@ -131,7 +126,7 @@ static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *
                              size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                              void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = filter_common("decode_planes", filter);
+    int rc = trc_planes_filter_arg("decode_planes", filter);
     if (rc) return rc;
     if ((rc = planes_common("decode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
@@ -167,7 +162,7 @@ static int planes_decode_range_dev(int codec, int filter, int stride, const uint
                                    const uint16_t *d_cdf, unsigned cdfnum,
                                    void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = filter_common("decode_planes_range", filter);
+    int rc = trc_planes_filter_arg("decode_planes_range", filter);
     if (rc) return rc;
     if ((rc = planes_common("decode_planes_range", codec, n, esize, d_work))) return rc;
     const size_t m = n / esize;

@@ -23,7 +23,7 @@
 // readable slack behind them.
 #include <vector>
 
-#include "trc_planes_vec.h"
+#include "trc_planes_scan.h"                      // the scanning join (trc_fplanes_batch.inc)
 #include "trc_planes_count.h"                     // the advisor's LDS counters (trc_planes_hist_batch.inc)
 
 // one item as the kernels see it; `first` and `v0` count from the first chunk of the call's chunk range
@@ -236,63 +236,102 @@ static int batch_table_args(const char *who, size_t count, uint64_t chunks, cons
     return TRC_OK;
 }
 
-extern "C" int trc_planes_split_batch_dev(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
-                                          void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+// ---- the kernels with a predictor filter per item --------------------------------------------------------------------------------
+#include "trc_fplanes_batch.inc"
+
+// ---- split and join, with filters and without --------------------------------------------------------------------------------------
+typedef void (*split_batch_fn)(const BatchRec *, const u32 *, u32, u32, size_t, size_t, uint8_t *, size_t);
+static const split_batch_fn split_batch_kernels[2][3] = { TRC_BY_ESIZE(trc_planes_split_batch_kernel), TRC_BY_ESIZE(trc_fplanes_split_batch_kernel) };     // [any filter][esize_row]
+static void (*const join_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t) = TRC_BY_ESIZE(trc_planes_join_batch_kernel);
+static void (*const fjoin_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t, u32, u32, size_t) = TRC_BY_ESIZE(trc_fplanes_join_batch_kernel);
+
+// filters == NULL: the batch call; a batch whose filters are all TRC_FILTER_NONE is that call too, and says so in its messages
+static int split_batch(const char *who, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+                       void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
     trc_planes_batch_plan P;
-    int rc = batch_plan("planes_split_batch", items, count, esize, chunk, &P, nullptr);
+    int rc = batch_plan(who, items, count, esize, chunk, &P, nullptr);
     if (rc) return rc;
-    if (!d_planes || ((uintptr_t)d_planes & 255)) return trc_fail(TRC_E_ARG, "planes_split_batch: the planes must be 256-byte aligned");
-    if ((pitch & 255) || pitch < P.m_total) return trc_fail(TRC_E_ARG, "planes_split_batch: pitch %zu must be a multiple of 256 and at least %llu", pitch, (unsigned long long)P.m_total);
-    if ((rc = batch_table_args("planes_split_batch", count, P.chunks, d_table, table_bytes))) return rc;
+    bool any;
+    if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
+    if (!any) who = "planes_split_batch";
+    if (!d_planes || ((uintptr_t)d_planes & 255)) return trc_fail(TRC_E_ARG, "%s: the planes must be 256-byte aligned", who);
+    if ((pitch & 255) || pitch < P.m_total) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)P.m_total);
+    if ((rc = batch_table_args(who, count, P.chunks, d_table, table_bytes))) return rc;
     std::vector<BatchRec> recs;
     uint64_t chunks, elems;
-    if ((rc = batch_range("planes_split_batch", items, 0, count, esize, chunk, chunks, elems, &recs))) return rc;
+    if ((rc = batch_range(who, items, 0, count, esize, chunk, chunks, elems, &recs))) return rc;
+    if (any) fbatch_pack(recs, filters);
     hipStream_t s = (hipStream_t)stream;
     const BatchRec *d_rec;
     const u32 *d_map;
-    if ((rc = batch_table("planes_split_batch", recs, chunks, d_table, s, d_rec, d_map))) return rc;
+    if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
     const size_t M = (size_t)elems, nv = (M + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
     const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    const dim3 grid(batch_grid(nv)), block(TRC_PLANES_BLOCK);
-    if (esize == 2) hipLaunchKernelGGL(trc_planes_split_batch_kernel<2>, grid, block, 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
-    else if (esize == 4) hipLaunchKernelGGL(trc_planes_split_batch_kernel<4>, grid, block, 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
-    else hipLaunchKernelGGL(trc_planes_split_batch_kernel<8>, grid, block, 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
+    hipLaunchKernelGGL(split_batch_kernels[any][esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_split_batch: %s", hipGetErrorString(e));
+    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(e));
 }
 
+static int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, size_t count,
+                      size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, void *d_table, size_t table_bytes, void *stream)
+{
+    int rc = batch_plan(who, items, count, esize, chunk, nullptr, nullptr);
+    if (rc) return rc;
+    bool any;
+    if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
+    if (!any) who = "planes_join_batch";
+    if (first_item > count || item_count > count - first_item)
+        return trc_fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
+    if (item_count == 0) return TRC_OK;
+    std::vector<BatchRec> recs;
+    uint64_t chunks, elems;
+    if ((rc = batch_range(who, items, first_item, item_count, esize, chunk, chunks, elems, &recs))) return rc;
+    if (any) fbatch_pack(recs, filters + first_item);
+    if (!d_planes || ((uintptr_t)d_planes & 63)) return trc_fail(TRC_E_ARG, "%s: the planes must be 64-byte aligned", who);
+    if ((pitch & 255) || pitch < elems) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)elems);
+    if ((rc = batch_table_args(who, item_count, chunks, d_table, table_bytes))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const BatchRec *d_rec;
+    const u32 *d_map;
+    if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
+    const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
+    if (any) {                                     // the scanning join: a wave per span
+        u32 span;
+        size_t nspan;
+        const unsigned grid = join_grid((size_t)elems, chunk, span, nspan);
+        hipLaunchKernelGGL(fjoin_batch_kernels[esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp,
+                           (size_t)elems, chunk, span, nspan);
+    } else {
+        const size_t nv = ((size_t)elems + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
+        hipLaunchKernelGGL(join_batch_kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, nv);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+extern "C" int trc_planes_split_batch_dev(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                          void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+{
+    return split_batch("planes_split_batch", items, nullptr, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+}
+extern "C" int trc_planes_split_fbatch_dev(const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+                                           void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+{
+    return split_batch("planes_split_fbatch", items, filters, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+}
 extern "C" int trc_planes_join_batch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, size_t count,
                                          size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
                                          void *d_table, size_t table_bytes, void *stream)
 {
-    int rc = batch_plan("planes_join_batch", items, count, esize, chunk, nullptr, nullptr);
-    if (rc) return rc;
-    if (first_item > count || item_count > count - first_item)
-        return trc_fail(TRC_E_ARG, "planes_join_batch: items [%zu, %zu + %zu) of %zu", first_item, first_item, item_count, count);
-    if (item_count == 0) return TRC_OK;
-    std::vector<BatchRec> recs;
-    uint64_t chunks, elems;
-    if ((rc = batch_range("planes_join_batch", items, first_item, item_count, esize, chunk, chunks, elems, &recs))) return rc;
-    if (!d_planes || ((uintptr_t)d_planes & 63)) return trc_fail(TRC_E_ARG, "planes_join_batch: the planes must be 64-byte aligned");
-    if ((pitch & 255) || pitch < elems) return trc_fail(TRC_E_ARG, "planes_join_batch: pitch %zu must be a multiple of 256 and at least %llu", pitch, (unsigned long long)elems);
-    if ((rc = batch_table_args("planes_join_batch", item_count, chunks, d_table, table_bytes))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const BatchRec *d_rec;
-    const u32 *d_map;
-    if ((rc = batch_table("planes_join_batch", recs, chunks, d_table, s, d_rec, d_map))) return rc;
-    const size_t nv = ((size_t)elems + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
-    const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    const dim3 grid(batch_grid(nv)), block(TRC_PLANES_BLOCK);
-    if (esize == 2) hipLaunchKernelGGL(trc_planes_join_batch_kernel<2>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, nv);
-    else if (esize == 4) hipLaunchKernelGGL(trc_planes_join_batch_kernel<4>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, nv);
-    else hipLaunchKernelGGL(trc_planes_join_batch_kernel<8>, grid, block, 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, nv);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_join_batch: %s", hipGetErrorString(e));
+    return join_batch("planes_join_batch", d_planes, pitch, items, nullptr, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
 }
-
-// ---- the same with a predictor filter per item ----------------------------------------------------------------------------------
-#include "trc_fplanes_batch.inc"
+extern "C" int trc_planes_join_fbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, size_t count,
+                                          size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                                          void *d_table, size_t table_bytes, void *stream)
+{
+    return join_batch("planes_join_fbatch", d_planes, pitch, items, filters, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
+}
 
 // ---- the advisor's histograms, per item ---------------------------------------------------------------------------------------
 #include "trc_planes_hist_batch.inc"

@@ -2,8 +2,8 @@
 // of trc_planes_hist.hip, every plane under every requested filter, for every item of an item range from ONE launch, through the
 // batch's pointer table.  Slice j of d_hist is what trc_planes_hist_dev writes for item first_item + j with seg = chunk.
 //
-// The counting is that of trc_planes_hist_kernel (trc_planes_count.h: the same LDS rows of replicated bins, the same adds); what
-// differs is who counts what.  A workgroup's LDS counters can belong to one item at a time, and a grid-stride loop over the vectors
+// The counting is that of trc_planes_hist_kernel (trc_planes_count.h: the same LDS rows of replicated bins, the same adds, the same
+// flush); what differs is who counts what.  A workgroup's LDS counters can belong to one item at a time, and a grid-stride loop over the vectors
 // of the virtual buffer would mix items within a turn.  So workgroup b owns the contiguous chunk run [b * cpw, (b + 1) * cpw) of the
 // range and walks it item by item: chunk_item[c] names the item of the run's next chunk, all 256 threads count the item's vectors
 // that lie in the run, the counters are flushed to that item's global rows (one 64-bit atomicAdd per non-zero bin, bins rotated by
@@ -28,35 +28,13 @@ void trc_planes_hist_batch_kernel(const BatchRec *__restrict__ rec, const u32 *_
     typedef typename Elem<ESIZE>::M M;
     constexpr int NW = 2 * ESIZE, NQ = NW / 4;
     extern __shared__ __attribute__((aligned(16))) u32 sm[];
-    const u32 tid = threadIdx.x, copy = tid & ((1u << cshift) - 1u);
-    const u32 nf = __builtin_popcount(filters), words = (nf * ESIZE * 256u) << cshift, fwords = (ESIZE * 256u) << cshift;
-    const u32 row_n = copy, row_z = row_n + (filters & 1u ? fwords : 0u), row_x = row_z + (filters & 2u ? fwords : 0u);
-    const bool with_n = filters & 1u, with_z = filters & 2u, with_x = filters & 4u;
-    for (u32 i = tid; i < words; i += TRC_PLANES_BLOCK) sm[i] = 0;
-    __syncthreads();
-
-    // the workgroup's counters to the rows of one item, and zero again; the whole workgroup calls it
-    // (store: nobody else adds to these rows and nothing has been added to them yet)
-    auto flush = [&](u64a *h, bool store) __attribute__((always_inline)) {
-        __syncthreads();
-        for (u32 i = tid; i < nf * ESIZE * 256u; i += TRC_PLANES_BLOCK) {
-            const u32 row = i >> 8, bin = ((i & 255u) + 37u * blockIdx.x) & 255u;
-            u32 *c = sm + ((row * 256u + bin) << cshift);
-            u32 sum = 0;
-            for (u32 q = 0; q < (1u << cshift); q++) { sum += c[q]; c[q] = 0; }
-            u32 f = row / ESIZE;                                         // the row's filter id: the f-th requested one
-            f = f == 0 ? (with_n ? 0u : with_z ? 1u : 2u) : f == 1 ? (with_n && with_z ? 1u : 2u) : 2u;
-            u64a *dst = &h[((size_t)f * ESIZE + row % ESIZE) * 256u + bin];
-            if (store) *dst = (u64a)sum;
-            else if (sum) atomicAdd(dst, (u64a)sum);
-        }
-        __syncthreads();
-    };
+    const u32 tid = threadIdx.x;
+    const HistRows R = hist_rows<ESIZE>(sm, filters, cshift);
 
     const u32 vpc = chunk / TRC_PLANES_VEC, rstep = TRC_PLANES_BLOCK % vpc;
     const u32 c_lo = blockIdx.x * cpw, c_hi = nc - c_lo < cpw ? nc : c_lo + cpw;      // (the host: c_lo < nc)
     for (u32 c = c_lo; c < c_hi; ) {
-        // everything that shapes the walk is the same in all lanes: the item, its record, the turns of the loop (flush holds barriers)
+        // everything that shapes the walk is the same in all lanes: the item, its record, the turns of the loop (the flush holds barriers)
         const u32 item = __builtin_amdgcn_readfirstlane(chunk_item[c]);
         const BatchRec r = rec[item];
         const u32 first = (u32)r.first, nci = (u32)((r.m + chunk - 1) / chunk);
@@ -76,42 +54,25 @@ void trc_planes_hist_batch_kernel(const BatchRec *__restrict__ rec, const u32 *_
                 u32 w[NW];
 #pragma unroll
                 for (int q = 0; q < NQ; q++) { const uint4 x = src[q]; w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w; }
-                T prev = 0;
-                if (rr && (filters & 6u)) prev = el[lv * TRC_PLANES_VEC - 1];
-                if (with_n) count_vec<ESIZE>(sm, row_n, cshift, w);
-                if (filters & 6u) {
-                    T e[TRC_PLANES_VEC], y[TRC_PLANES_VEC];
-                    unpack<ESIZE>(w, e);
-                    if (with_z) {
+                T pe[TRC_PLANES_VEC];
 #pragma unroll
-                        for (int j = 0; j < TRC_PLANES_VEC; j++) y[j] = fwd<ESIZE, TRC_FILTER_ZDELTA>(e[j], j ? e[j - 1] : prev);
-                        pack<ESIZE>(y, w);
-                        count_vec<ESIZE>(sm, row_z, cshift, w);
-                    }
-                    if (with_x) {
-#pragma unroll
-                        for (int j = 0; j < TRC_PLANES_VEC; j++) y[j] = fwd<ESIZE, TRC_FILTER_XOR>(e[j], j ? e[j - 1] : prev);
-                        pack<ESIZE>(y, w);
-                        count_vec<ESIZE>(sm, row_x, cshift, w);
-                    }
-                }
+                for (int j = 0; j < TRC_PLANES_VEC; j++) pe[j] = 0;
+                if (rr && (filters & 6u)) pe[TRC_PLANES_VEC - 1] = el[lv * TRC_PLANES_VEC - 1];
+                count_filtered<ESIZE, 1>(sm, R, cshift, w, pe);
             }
             rr += rstep;
             if (rr >= vpc) rr -= vpc;
-            if (++since == round_vecs && it + 1 < turns) { flush(h, alone); alone = false; since = 0; }
+            if (++since == round_vecs && it + 1 < turns) { hist_flush<ESIZE>(sm, R, cshift, h, alone); alone = false; since = 0; }
         }
         // the elements behind the item's last whole vector (at most 7), one per lane, where the run holds the item's last chunk
         if (c_end == first + nci) {
             const u32 rest = (u32)(r.m - nvi * TRC_PLANES_VEC);
             if (tid < rest) {
                 const size_t i = nvi * TRC_PLANES_VEC + tid;
-                const T x = (T)el[i], p = i % chunk ? (T)el[i - 1] : (T)0;
-                if (with_n) count_elem<ESIZE>(sm, row_n, cshift, x);
-                if (with_z) count_elem<ESIZE>(sm, row_z, cshift, fwd<ESIZE, TRC_FILTER_ZDELTA>(x, p));
-                if (with_x) count_elem<ESIZE>(sm, row_x, cshift, fwd<ESIZE, TRC_FILTER_XOR>(x, p));
+                count_filtered_elem<ESIZE>(sm, R, cshift, (T)el[i], i % chunk ? (T)el[i - 1] : (T)0);
             }
         }
-        flush(h, alone);
+        hist_flush<ESIZE>(sm, R, cshift, h, alone);
         c = c_end;
     }
 }
@@ -133,13 +94,7 @@ int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, si
     if (rc) return rc;
     if (!d_hist || ((uintptr_t)d_hist & 7)) return trc_fail(TRC_E_ARG, "planes_hist_batch: the histograms must be 8-byte aligned");
     if ((rc = batch_table_args("planes_hist_batch", item_count, chunks, d_table, table_bytes))) return rc;
-    const unsigned nf = (unsigned)__builtin_popcount(filters), rows = nf * esize;
-    uint32_t cshift = 0;                           // copies per bin, as trc_planes_hist_dev chooses them
-    while ((2u << cshift) <= TRC_PHIST_COPIES_MAX && ((size_t)rows * 1024u << (cshift + 1)) <= TRC_PHIST_LDS) cshift++;
-    const size_t lds = (size_t)rows * 1024u << cshift;
-    uint32_t rv = TRC_PHIST_ROUND_VECS;            // TRC_PLANES_HIST_ROUND_VECS (test aid), as there
-    const char *e = getenv("TRC_PLANES_HIST_ROUND_VECS");
-    if (e) { const long x = strtol(e, 0, 10); if (x >= 1 && x < (long)TRC_PHIST_ROUND_VECS) rv = (uint32_t)x; }
+    const HistShape hs = hist_shape(filters, esize);
     // a workgroup per 256 vectors of the range under the caps of trc_planes_hist_dev, then whole chunks per workgroup
     unsigned grid = batch_grid((size_t)chunks * (chunk / TRC_PLANES_VEC));
     if (grid > TRC_PHIST_GRID_MAX) grid = TRC_PHIST_GRID_MAX;
@@ -152,10 +107,8 @@ int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, si
     const BatchRec *d_rec;
     const u32 *d_map;
     if ((rc = batch_table("planes_hist_batch", recs, chunks, d_table, s, d_rec, d_map))) return rc;
-    const dim3 g(grid), b(TRC_PLANES_BLOCK);
-    if (esize == 2) hipLaunchKernelGGL((trc_planes_hist_batch_kernel<2>), g, b, lds, s, d_rec, d_map, nc, cpw, chunk, filters, cshift, rv, (u64a *)d_hist);
-    else if (esize == 4) hipLaunchKernelGGL((trc_planes_hist_batch_kernel<4>), g, b, lds, s, d_rec, d_map, nc, cpw, chunk, filters, cshift, rv, (u64a *)d_hist);
-    else hipLaunchKernelGGL((trc_planes_hist_batch_kernel<8>), g, b, lds, s, d_rec, d_map, nc, cpw, chunk, filters, cshift, rv, (u64a *)d_hist);
+    static void (*const kernels[3])(const BatchRec *, const u32 *, u32, u32, u32, u32, u32, u32, u64a *) = TRC_BY_ESIZE(trc_planes_hist_batch_kernel);
+    hipLaunchKernelGGL(kernels[esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), hs.lds, s, d_rec, d_map, nc, cpw, chunk, filters, hs.cshift, hs.round_vecs, (u64a *)d_hist);
     he = hipGetLastError();
     return he == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_hist_batch: %s", hipGetErrorString(he));
 }

@@ -1,7 +1,12 @@
-// trc_planes_vec.h -- what the plane kernels share (trc_planes.hip: split / join; trc_fplanes.hip: the same with a zigzag-delta
-// or xor filter; trc_planes_hist.hip: the histograms of the filtered planes; trc_planes_batch.hip: split / join over a table of
-// separate allocations): the byte separation of one thread's vector of 8 elements in registers, the filters' forward step, the
-// launch shape and the argument rules.
+// trc_planes_vec.h -- what the plane kernels share: the byte separation of one thread's vector of 8 elements in registers, the
+// filters' forward step over a vector, the launch shape, the kernel tables' row and the argument rules.
+//   trc_planes.hip              split / join
+//   trc_fplanes.hip             the same behind a zigzag-delta or xor filter, of every stride (join: trc_planes_scan.h)
+//   trc_planes_hist.hip         the advisor's histograms of the filtered planes, of every stride (trc_planes_count.h)
+//   trc_planes_batch.hip        split / join over a table of separate allocations; includes
+//     trc_fplanes_batch.inc       the same with a filter per item (join: trc_planes_scan.h)
+//     trc_planes_hist_batch.inc   the advisor's histograms per item (trc_planes_count.h)
+//   trc_planes_pack.hip         the batch container's packing (trc_planes_pack.h)
 #ifndef TRC_PLANES_VEC_H
 #define TRC_PLANES_VEC_H
 #include <hip/hip_runtime.h>
@@ -62,7 +67,7 @@ template <int ESIZE> __device__ __forceinline__ void vec_join(const uint2 *p, u3
     }
 }
 
-// ---- what the filter kernels share (trc_fplanes.hip: split / join; trc_planes_hist.hip: the advisor's histograms)
+// ---- what the filter kernels share (split / join, the advisor's histograms)
 template <int ESIZE> struct Elem { typedef u32 T; typedef u32 M; };          // T: the register type of an element, M: its type in memory
 template <> struct Elem<2> { typedef u32 T; typedef uint16_t M; };           // (16-bit elements are computed in 32 bits and truncated when packed)
 template <> struct Elem<8> { typedef uint64_t T; typedef uint64_t M; };
@@ -98,6 +103,21 @@ template <int ESIZE, int FILTER> __device__ __forceinline__ typename Elem<ESIZE>
     return ((d << 1) ^ ((T)0 - (d >> (W - 1)))) & MASK;
 }
 
+// the last S elements of the vector in front of vector v, at pe[8 - S .. 7]; only the 16-byte words that hold them are loaded
+template <int ESIZE, int S> __device__ __forceinline__ void load_front(const uint8_t *__restrict__ in, size_t v, typename Elem<ESIZE>::T *pe)
+{
+    constexpr int NW = 2 * ESIZE, NQ = NW / 4, Q0 = NQ - (S * ESIZE + 15) / 16;
+    const uint4 *src = (const uint4 *)(in + (v - 1) * (TRC_PLANES_VEC * ESIZE));
+    u32 w[NW];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        uint4 x = make_uint4(0u, 0u, 0u, 0u);
+        if (q >= Q0) x = src[q];
+        w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w;
+    }
+    unpack<ESIZE>(w, pe);
+}
+
 // workgroups of a launch over m elements; TRC_PLANES_GRID in the environment lowers the cap (tuning aid, and how the tests make
 // a small input take the grid-stride loop more than once)
 static unsigned planes_grid_cap()
@@ -115,6 +135,10 @@ static unsigned planes_grid(size_t m)
 }
 
 static bool esize_ok(unsigned esize) { return esize == 2 || esize == 4 || esize == 8; }
+
+// kernels are picked from tables: [esize_row(esize)], then [filter - 1] and [stride - 1] where a kernel has them
+static int esize_row(unsigned esize) { return esize == 2 ? 0 : esize == 4 ? 1 : 2; }
+#define TRC_BY_ESIZE(K) { K<2>, K<4>, K<8> }
 
 static int planes_args(const char *who, const void *d_flat, size_t n, unsigned esize, const void *d_planes, size_t pitch, const void *d_tail)
 {

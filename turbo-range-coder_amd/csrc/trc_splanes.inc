@@ -1,5 +1,5 @@
 // trc_splanes.inc -- the coded planes calls behind a STRIDED predictor filter (included by trc_api.hip behind trc_planes.inc): the
-// device-resident calls, which are those of trc_planes.inc with the split / join of trc_splanes.hip, and the TRCS container, which
+// device-resident calls, which are those of trc_planes.inc with the strided split / join of trc_fplanes.hip, and the TRCS container, which
 // is the TRCF container with the stride where that one has its reserved field.  Nothing here knows a coder or a kernel.
 
 // the stride is looked at ahead of everything else, pointers included
