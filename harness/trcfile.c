@@ -26,7 +26,9 @@
  *                                 the library's TRCB container (trc_hip.h), which records every item's length and filter
  *   trcfile B <in> <first> <count> <out>   items [first, first + count) of a file of b, their bytes concatenated: only the chunks
  *                                 that cover them are sent to the GPU
- *   trcfile l <in>                list a file of b: count, esize, chunk, coder and every item's bytes and filter (needs no GPU)
+ *   trcfile l <in>                list a file of b: count, esize, chunk, coder and every item's bytes and filter (needs no GPU).  B and l
+ *                                 also read the library's TRCT container (a TRCB container behind a stride per item, which this
+ *                                 tool does not write); l then adds a stride column
  *   trcfile d <in> <out>          decompress (files of c, p, f, s and a)
  *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p, f or s: only the
  *                                 chunks that cover them are sent to the GPU and decoded (trc_decode_range_host)
@@ -315,19 +317,24 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        /* a TRCT file: the strides of the items, then the TRCB container (this tool reads it; it does not write one) */
+        const int strided = fl >= 4 && !memcmp(fb, "TRCT", 4);
         trc_planes_batch_hdr h;
-        if (trc_planes_batch_info(fb, fl, &h, 0, 0, 0)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
-        const size_t count = (size_t)h.count;
+        if (strided ? trc_planes_sbatch_info(fb, fl, &h, 0, 0, 0, 0) : trc_planes_batch_info(fb, fl, &h, 0, 0, 0)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        const size_t count = (size_t)h.count, lead = strided ? sizeof(trc_planes_sbatch_hdr) + ((count + 15) & ~(size_t)15) : 0;
         uint64_t *n = calloc(count, sizeof *n);
-        uint8_t *filters = calloc(count, 1);
-        if (!n || !filters) { perror("malloc"); return 2; }
-        if (trc_planes_batch_info(fb, fl, &h, n, filters, count)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        uint8_t *filters = calloc(count, 1), *strides = calloc(count, 1);
+        if (!n || !filters || !strides) { perror("malloc"); return 2; }
+        if (strided ? trc_planes_sbatch_info(fb, fl, &h, n, filters, strides, count) : trc_planes_batch_info(fb, fl, &h, n, filters, count)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
         if (list) {
             trc_planes_hdr ph;
-            memcpy(&ph, fb + h.inner, sizeof ph);
+            memcpy(&ph, fb + lead + h.inner, sizeof ph);
             printf("%llu items, esize %u, chunk %u, codec %u, %llu -> %llu bytes\n", (unsigned long long)h.count, h.esize, h.chunk, ph.codec,
-                   (unsigned long long)h.bytes, (unsigned long long)h.size);
-            for (size_t i = 0; i < count; i++) printf("item %zu: %llu bytes, filter %c\n", i, (unsigned long long)n[i], "nzx"[filters[i]]);
+                   (unsigned long long)h.bytes, (unsigned long long)(lead + h.size));
+            for (size_t i = 0; i < count; i++) {
+                if (strided) printf("item %zu: %llu bytes, filter %c, stride %u\n", i, (unsigned long long)n[i], "nzx"[filters[i]], strides[i]);
+                else printf("item %zu: %llu bytes, filter %c\n", i, (unsigned long long)n[i], "nzx"[filters[i]]);
+            }
             return 0;
         }
         const size_t first = (size_t)strtoull(argv[3], 0, 10), cnt = (size_t)strtoull(argv[4], 0, 10);
@@ -343,7 +350,8 @@ int main(int argc, char **argv)
             items[i].n = n[i];
             if (i >= first && i < first + cnt) { items[i].d_ptr = out + pos; pos += (size_t)n[i]; }
         }
-        if (trc_decode_planes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST) != bytes) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+        if ((strided ? trc_decode_splanes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST)
+                     : trc_decode_planes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST)) != bytes) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
         return write_file(argv[5], out, bytes);
     }
     if (argc == 4 && !strcmp(argv[1], "d")) {

@@ -833,6 +833,101 @@ size_t trc_encode_aplanes_batch_host(int codec, const trc_planes_item *items, si
 size_t trc_decode_planes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
                                     size_t first_item, size_t item_count, int items_on);
 
+/* ---- batched byte planes with a filter AND A STRIDE per item: interleaved items in a batch ------------------------------------
+ * A table handed over as a batch often has items that are row-major blocks of K same-width fields -- (id, t0, t1, counter) rows,
+ * xyz(w) points, stereo or 5.1 PCM pages, complex pairs -- next to plain columns and float tensors.  For such an item the predictor
+ * of the filtered batch, the element directly in front, is worse than none; the strided filter above predicts from the element K
+ * back.  Here the stride is chosen per item, as the filter is.  `strides` is a HOST array of `count` bytes with the lifetime rule
+ * of `items` and `filters`; every entry must be in 1 .. TRC_STRIDE_MAX.
+ *        GS(i) = item i                                                  where filters[i] == TRC_FILTER_NONE   (strides[i] has no effect)
+ *              = F_{strides[i]}(filters[i], seg = chunk, esize, item i)  otherwise     (the F_S of the strided planes; items have no tail)
+ *        VS(items, filters, strides, esize, chunk) = V([GS(0) .. GS(count - 1)], esize, chunk)
+ * Unchanged from the filtered batch: plan, M, NC, first[], pitch, table bytes and workspace; the pad behind an item, zero bytes in
+ * every plane; the predictor restarting at every chunk of the item, whether or not S divides the chunk; item i being chunks
+ * [first[i], first[i] + nc[i]) of every plane, any item range decoding alone; and items needing no readable slack: the kernels read
+ * bytes [0, n[i]) of an item and nothing else.
+ * The whole contract:  encode_sbatch(codec, items, filters, strides, ...)  ==  trc_encode_planes_dev(codec, VS, M * esize, esize,
+ * chunk, ...) byte for byte -- directory, payload, totals, per-plane CDFs and statuses.  So:
+ *   - strides == NULL, or 1 for every item whose filter is not NONE, IS the fplanes_batch call of the same kind and launches exactly
+ *     its kernels (and says so in its messages);
+ *   - a batch of one item with filter f and stride s is trc_encode_splanes_dev(codec, f, s, item, ...) on that item.
+ * The arguments are those of the fbatch calls with `strides` behind `filters`; join and decode take the strides of the WHOLE batch.
+ * Errors: those of the fbatch calls, and TRC_E_ARG with the item's index in trc_last_error() for a stride outside
+ * 1 .. TRC_STRIDE_MAX.  The order of the checks is the plan, then the filters, then the strides, then pointers and buffers -- so a
+ * bad stride is reported without a device.  The stride travels in the item's 32-byte record next to the filter.
+ *
+ * trc_planes_hist_sbatch_dev is trc_planes_hist_batch_dev under the items' strides: slice j is exactly what
+ * trc_planes_hist_stride_dev(filters, strides[first_item + j], item, n, esize, seg = chunk, ...) writes for that item alone, so
+ * trc_planes_advise_batch serves on it unchanged.  (`filters` is that call's bit set; the checks are the plan, the bit set, the
+ * strides, the range, pointers, table.)  trc_planes_advise_sbatch_dev is trc_planes_advise_batch_dev over these histograms -- same
+ * workspace function, same slabs, same synchronise: it picks the filter per item under the caller's strides and searches no strides.
+ *
+ * The TRCT container.  trc_planes_batch_check rejects other versions and non-zero reserved fields of TRCB, so the strides do not go
+ * into it: as TRCS does for TRCF, a prefix carries them, little endian:
+ *   trc_planes_sbatch_hdr (16 B) | uint8 stride[count], zero-padded to a multiple of 16 | the TRCB container of the batch
+ * The TRCB front is as for (items, filters), the inner TRCP container is that of VS, and the TRCB header's `size` is the TRCB part's
+ * own: the whole size is prefix + that, prefix = 16 + up16(count).  The stored stride of an item without a filter is 1.  One layout
+ * per content: a batch in which no item with a filter has a stride above 1 is a TRCB container, and trc_encode_splanes_batch_host and
+ * trc_planes_sbatch_pack_dev refuse it (TRC_E_ARG, naming trc_encode_planes_batch_host / trc_planes_batch_pack_dev).
+ * Host only, no GPU needed:
+ *   trc_planes_sbatch_bound   trc_planes_batch_bound + prefix; 0 for what the calls reject.
+ *   trc_planes_sbatch_check   magic, version, the zero fields, count in 1 .. TRC_PLANES_BATCH_MAX (and == count_expected unless that is
+ *                             (size_t)-1), the prefix within buflen, strides in 1 .. TRC_STRIDE_MAX, zero padding, then
+ *                             trc_planes_batch_check on the rest, its count equal to the prefix's, and stride 1 wherever the filter is
+ *                             NONE.  A failure leaves the reason in trc_last_error(), prefixed "strided batch container:".
+ *   trc_planes_sbatch_info    trc_planes_batch_info (the TRCB header, n, filters) plus the strides: the first min(cap, count) entries
+ *                             of each (n, filters, strides: may be NULL), nothing behind them.
+ * trc_planes_sbatch_pack_dev uploads the host-known prefix and runs trc_planes_batch_pack_dev on d_out + prefix (a multiple of 16, so
+ * that call's alignment holds); *d_size comes out as the WHOLE size (0 as there), on the stream, without a host round trip.
+ * out_bytes >= trc_planes_sbatch_bound.  The checks are the plan, the filters, the strides, then those of that call.
+ * trc_decode_splanes_batch_packed_dev is trc_decode_planes_batch_packed_dev on a TRCT container: d_cont is its start (16-byte
+ * aligned), cont_bytes and TRC_PAD count from there; `strides` are the caller's, as `filters` are.
+ * trc_encode_splanes_batch_host / trc_decode_splanes_batch_host mirror the TRCB pair, TRC_ITEMS_HOST / TRC_ITEMS_DEV included; the
+ * decoder takes filters and strides from the container.  trc_decode_xplanes_host does not take this container either. */
+#define TRC_PLANES_SBATCH_MAGIC 0x54435254u   /* "TRCT" */
+typedef struct trc_planes_sbatch_hdr {
+    uint32_t magic;      /* TRC_PLANES_SBATCH_MAGIC */
+    uint8_t  version;    /* 1 */
+    uint8_t  zero;
+    uint16_t zero2;
+    uint64_t count;      /* items: that of the TRCB container behind the strides */
+} trc_planes_sbatch_hdr; /* 16 bytes, little endian */
+size_t trc_planes_sbatch_bound(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum);
+int    trc_planes_sbatch_check(const void *buf, size_t buflen, size_t count_expected);
+int    trc_planes_sbatch_info(const void *buf, size_t buflen, trc_planes_batch_hdr *h, uint64_t *n, uint8_t *filters, uint8_t *strides, size_t cap);
+int trc_planes_sbatch_pack_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                               unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                               const int32_t *d_status, const uint32_t *d_clen, const void *d_payload,
+                               const uint64_t *d_total, void *d_out, size_t out_bytes, uint64_t *d_size, void *stream);
+int trc_decode_splanes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
+                                        const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                                        size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, unsigned cdfnum,
+                                        const uint64_t *total /* host, esize entries */, void *d_work, size_t work_bytes, void *stream);
+size_t trc_encode_splanes_batch_host(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                                     size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on,
+                                     void *out, size_t outcap);
+size_t trc_decode_splanes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
+                                     size_t first_item, size_t item_count, int items_on);
+int trc_planes_split_sbatch_dev(const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize,
+                                uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream);
+int trc_planes_join_sbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                               size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                               void *d_table, size_t table_bytes, void *stream);
+int trc_encode_splanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                                 unsigned esize, uint32_t chunk, uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                 uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                 void *d_work, size_t work_bytes, void *stream);
+int trc_decode_splanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                 const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                                 size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_work, size_t work_bytes, void *stream);
+int trc_planes_hist_sbatch_dev(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count,
+                               size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                               uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);
+int trc_planes_advise_sbatch_dev(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize,
+                                 uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice,
+                                 void *d_work, size_t work_bytes, void *stream);
+
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass
  * rANS encoders and the order-1 model fill included (the directory/gather kernels are not coder kernels).

@@ -75,56 +75,6 @@ void trc_fplanes_split_kernel(const uint8_t *__restrict__ in, size_t m, u32 t, u
     }
 }
 
-// out[i] = a[(i + r) % S], r in [0, S): a rotate by 1, by 2 and by 4, each taken where r has that bit -- selects over static
-// indices, three per value
-template <int S, typename T> __device__ __forceinline__ void rotate(const T *a, u32 r, T *out)
-{
-    T x[S];
-#pragma unroll
-    for (int i = 0; i < S; i++) x[i] = a[i];
-#pragma unroll
-    for (int b = 1; b < S; b <<= 1) {
-        const bool take = r & (u32)b;
-        T y[S];
-#pragma unroll
-        for (int i = 0; i < S; i++) y[i] = take ? x[(i + b) % S] : x[i];
-#pragma unroll
-        for (int i = 0; i < S; i++) x[i] = y[i];
-    }
-#pragma unroll
-    for (int i = 0; i < S; i++) out[i] = x[i];
-}
-
-// 16-bit sums two to a word (v_pk_add_u16), so that a wave scan of 16-bit elements moves two classes per shuffle
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-template <int FILTER> __device__ __forceinline__ u32 pkop(u32 a, u32 b)
-{
-    if constexpr (FILTER == TRC_FILTER_XOR) return a ^ b;
-    return __builtin_bit_cast(u32, (us2)(__builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b)));
-}
-
-// N segmented inclusive wave scans (six __shfl_up steps each): inc[c] = the lane's total of value c on entry.  A lane adds what lies
-// at most `reach` lanes in front of it.  before[c] = the sum of the lanes in front of this one in its segment, those of earlier
-// tiles included where take_carry says the segment began there; carry[c] = the running value where this tile ends.
-template <int FILTER, int N, typename V, bool PK> __device__ __forceinline__ void wave_scan(V *inc, V *carry, V *before, u32 reach, bool take_carry)
-{
-    auto f = [](V a, V b) __attribute__((always_inline)) { if constexpr (PK) return (V)pkop<FILTER>((u32)a, (u32)b); else return op<FILTER>(a, b); };
-#pragma unroll
-    for (u32 d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int c = 0; c < N; c++) {
-            const V o = __shfl_up(inc[c], d);
-            if (reach >= d) inc[c] = f(inc[c], o);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < N; c++) {
-        const V in_carry = take_carry ? carry[c] : (V)0, b = __shfl_up(inc[c], 1u);
-        before[c] = f(in_carry, reach ? b : (V)0);
-        carry[c] = __shfl(f(inc[c], in_carry), 63);
-    }
-}
-
 // the mirror image of the split: writes [0, m * ESIZE + t) of out, nothing else.  span, nspan: join_grid (trc_planes_scan.h, which
 // also says how the walk goes and why).  carry[c] = the running value of class c at the end of the previous tile.  The walk is the
 // one trc_fplanes_join_batch_kernel has; it stands in both kernels as text, not as a shared function: profiles/planes/refactor_notes.md.

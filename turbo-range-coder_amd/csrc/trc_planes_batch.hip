@@ -1,6 +1,7 @@
 // trc_planes_batch.hip -- byte planes of MANY separate allocations (tensors of a checkpoint, pages of a cache, columns of a table):
 // a split that gathers from a pointer table into one long plane per byte position, the join that scatters back, and the plan; behind
-// them the same with a filter per item (trc_fplanes_batch.inc) and the advisor's histograms per item (trc_planes_hist_batch.inc).
+// them the same with a filter per item (trc_fplanes_batch.inc), with a filter and a stride per item (trc_splanes_batch.inc) and the
+// advisor's histograms per item (trc_planes_hist_batch.inc).
 //
 // Layout (include/trc_hip.h): item i has m[i] elements and nc[i] = ceil(m[i] / chunk) chunks; every item starts on
 // a chunk boundary of the VIRTUAL buffer V, every item but the last is followed by zero elements up to nc[i] * chunk, so V has
@@ -239,21 +240,29 @@ static int batch_table_args(const char *who, size_t count, uint64_t chunks, cons
 // ---- the kernels with a predictor filter per item --------------------------------------------------------------------------------
 #include "trc_fplanes_batch.inc"
 
-// ---- split and join, with filters and without --------------------------------------------------------------------------------------
-typedef void (*split_batch_fn)(const BatchRec *, const u32 *, u32, u32, size_t, size_t, uint8_t *, size_t);
-static const split_batch_fn split_batch_kernels[2][3] = { TRC_BY_ESIZE(trc_planes_split_batch_kernel), TRC_BY_ESIZE(trc_fplanes_split_batch_kernel) };     // [any filter][esize_row]
-static void (*const join_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t) = TRC_BY_ESIZE(trc_planes_join_batch_kernel);
-static void (*const fjoin_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t, u32, u32, size_t) = TRC_BY_ESIZE(trc_fplanes_join_batch_kernel);
+// ---- the kernels with a filter and a stride per item -----------------------------------------------------------------------------
+#include "trc_splanes_batch.inc"
 
-// filters == NULL: the batch call; a batch whose filters are all TRC_FILTER_NONE is that call too, and says so in its messages
-static int split_batch(const char *who, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+// ---- split and join: plain, with filters, with filters and strides -----------------------------------------------------------------
+typedef void (*split_batch_fn)(const BatchRec *, const u32 *, u32, u32, size_t, size_t, uint8_t *, size_t);
+static const split_batch_fn split_batch_kernels[3][3] = { TRC_BY_ESIZE(trc_planes_split_batch_kernel), TRC_BY_ESIZE(trc_fplanes_split_batch_kernel),
+                                                          TRC_BY_ESIZE(trc_splanes_split_batch_kernel) };     // [none, any filter, a stride above 1][esize_row]
+static void (*const join_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t) = TRC_BY_ESIZE(trc_planes_join_batch_kernel);
+typedef void (*fjoin_batch_fn)(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t, u32, u32, size_t);
+static const fjoin_batch_fn fjoin_batch_kernels[2][3] = { TRC_BY_ESIZE(trc_fplanes_join_batch_kernel), TRC_BY_ESIZE(trc_splanes_join_batch_kernel) };     // [a stride above 1][esize_row]
+
+// filters == NULL: the batch call; a batch whose filters are all TRC_FILTER_NONE is that call too, and says so in its messages.
+// strides == NULL: the filtered batch call; a batch in which no item with a filter has a stride above 1 is that call too, likewise
+static int split_batch(const char *who, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize, uint32_t chunk,
                        void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
     trc_planes_batch_plan P;
     int rc = batch_plan(who, items, count, esize, chunk, &P, nullptr);
     if (rc) return rc;
-    bool any;
+    bool any, strided;
     if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
+    if ((rc = trc_planes_batch_strides(who, filters, strides, count, &strided))) return rc;
+    if (!strided && strides) who = "planes_split_fbatch";
     if (!any) who = "planes_split_batch";
     if (!d_planes || ((uintptr_t)d_planes & 255)) return trc_fail(TRC_E_ARG, "%s: the planes must be 256-byte aligned", who);
     if ((pitch & 255) || pitch < P.m_total) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)P.m_total);
@@ -262,24 +271,27 @@ static int split_batch(const char *who, const trc_planes_item *items, const uint
     uint64_t chunks, elems;
     if ((rc = batch_range(who, items, 0, count, esize, chunk, chunks, elems, &recs))) return rc;
     if (any) fbatch_pack(recs, filters);
+    if (strided) sbatch_pack(recs, filters, strides);
     hipStream_t s = (hipStream_t)stream;
     const BatchRec *d_rec;
     const u32 *d_map;
     if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
     const size_t M = (size_t)elems, nv = (M + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
     const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    hipLaunchKernelGGL(split_batch_kernels[any][esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
+    hipLaunchKernelGGL(split_batch_kernels[strided ? 2 : any][esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(e));
 }
 
-static int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, size_t count,
-                      size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, void *d_table, size_t table_bytes, void *stream)
+static int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                      size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, void *d_table, size_t table_bytes, void *stream)
 {
     int rc = batch_plan(who, items, count, esize, chunk, nullptr, nullptr);
     if (rc) return rc;
-    bool any;
+    bool any, strided;
     if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
+    if ((rc = trc_planes_batch_strides(who, filters, strides, count, &strided))) return rc;
+    if (!strided && strides) who = "planes_join_fbatch";
     if (!any) who = "planes_join_batch";
     if (first_item > count || item_count > count - first_item)
         return trc_fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
@@ -288,6 +300,7 @@ static int join_batch(const char *who, const void *d_planes, size_t pitch, const
     uint64_t chunks, elems;
     if ((rc = batch_range(who, items, first_item, item_count, esize, chunk, chunks, elems, &recs))) return rc;
     if (any) fbatch_pack(recs, filters + first_item);
+    if (strided) sbatch_pack(recs, filters + first_item, strides + first_item);
     if (!d_planes || ((uintptr_t)d_planes & 63)) return trc_fail(TRC_E_ARG, "%s: the planes must be 64-byte aligned", who);
     if ((pitch & 255) || pitch < elems) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)elems);
     if ((rc = batch_table_args(who, item_count, chunks, d_table, table_bytes))) return rc;
@@ -300,7 +313,7 @@ static int join_batch(const char *who, const void *d_planes, size_t pitch, const
         u32 span;
         size_t nspan;
         const unsigned grid = join_grid((size_t)elems, chunk, span, nspan);
-        hipLaunchKernelGGL(fjoin_batch_kernels[esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp,
+        hipLaunchKernelGGL(fjoin_batch_kernels[strided][esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp,
                            (size_t)elems, chunk, span, nspan);
     } else {
         const size_t nv = ((size_t)elems + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
@@ -313,24 +326,35 @@ static int join_batch(const char *who, const void *d_planes, size_t pitch, const
 extern "C" int trc_planes_split_batch_dev(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
                                           void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
-    return split_batch("planes_split_batch", items, nullptr, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+    return split_batch("planes_split_batch", items, nullptr, nullptr, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_split_fbatch_dev(const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
                                            void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
-    return split_batch("planes_split_fbatch", items, filters, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+    return split_batch("planes_split_fbatch", items, filters, nullptr, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_join_batch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, size_t count,
                                          size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
                                          void *d_table, size_t table_bytes, void *stream)
 {
-    return join_batch("planes_join_batch", d_planes, pitch, items, nullptr, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
+    return join_batch("planes_join_batch", d_planes, pitch, items, nullptr, nullptr, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_join_fbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, size_t count,
                                           size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
                                           void *d_table, size_t table_bytes, void *stream)
 {
-    return join_batch("planes_join_fbatch", d_planes, pitch, items, filters, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
+    return join_batch("planes_join_fbatch", d_planes, pitch, items, filters, nullptr, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
+}
+extern "C" int trc_planes_split_sbatch_dev(const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize,
+                                           uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+{
+    return split_batch("planes_split_sbatch", items, filters, strides, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+}
+extern "C" int trc_planes_join_sbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                                          size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                                          void *d_table, size_t table_bytes, void *stream)
+{
+    return join_batch("planes_join_sbatch", d_planes, pitch, items, filters, strides, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
 }
 
 // ---- the advisor's histograms, per item ---------------------------------------------------------------------------------------

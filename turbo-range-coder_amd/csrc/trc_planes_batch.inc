@@ -8,6 +8,7 @@
 int trc_planes_batch_plan_quiet(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, trc_planes_batch_plan *plan, uint64_t *first_chunk);
 int trc_planes_batch_ptrs_ok(const trc_planes_item *items, size_t first_item, size_t item_count);
 int trc_planes_batch_filters(const char *who, const uint8_t *filters, size_t count, bool *any);      // trc_fplanes_batch.inc
+int trc_planes_batch_strides(const char *who, const uint8_t *filters, const uint8_t *strides, size_t count, bool *strided);      // trc_splanes_batch.inc
 
 extern "C" size_t trc_planes_batch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
 {
@@ -40,8 +41,9 @@ extern "C" size_t trc_planes_batch_range_work_bytes(int codec, const trc_planes_
     return esize * P.slice + trc_planes_batch_table_bytes(item_count, cnt);
 }
 
-// both encoders: filters == NULL is the unfiltered batch (the filtered split hands an all-NONE batch to the unfiltered kernels)
-static int encode_batch(const char *who, int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
+// the encoders: filters == NULL is the unfiltered batch, strides == NULL the filtered one (the split hands an all-NONE batch to the
+// unfiltered kernels and a batch without a stride above 1 to the filtered ones)
+static int encode_batch(const char *who, int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize, uint32_t chunk,
                         uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status, uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                         void *d_work, size_t work_bytes, void *stream)
 {
@@ -49,6 +51,7 @@ static int encode_batch(const char *who, int codec, const trc_planes_item *items
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
     if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
+    if ((rc = trc_planes_batch_strides(who, filters, strides, count, nullptr))) return rc;      // then a bad stride
     const size_t n = (size_t)B.n_virtual;
     if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
@@ -63,7 +66,7 @@ static int encode_batch(const char *who, int codec, const trc_planes_item *items
     if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
         return fail(TRC_E_ARG, "%s: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned", who);
     uint8_t *w = (uint8_t *)d_work;
-    if ((rc = trc_planes_split_fbatch_dev(items, filters, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream))) return rc;
+    if ((rc = trc_planes_split_sbatch_dev(items, filters, strides, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream))) return rc;
     for (unsigned k = 0; k < esize; k++) {         // as trc_encode_fplanes_dev
         uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
         uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
@@ -79,7 +82,7 @@ extern "C" int trc_encode_planes_batch_dev(int codec, const trc_planes_item *ite
                                            uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                                            void *d_work, size_t work_bytes, void *stream)
 {
-    return encode_batch("encode_planes_batch", codec, items, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+    return encode_batch("encode_planes_batch", codec, items, nullptr, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
                         d_work, work_bytes, stream);
 }
 extern "C" int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
@@ -87,7 +90,15 @@ extern "C" int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *it
                                             uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    return encode_batch("encode_fplanes_batch", codec, items, filters, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+    return encode_batch("encode_fplanes_batch", codec, items, filters, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+                        d_work, work_bytes, stream);
+}
+extern "C" int trc_encode_splanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                                            unsigned esize, uint32_t chunk, uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                            uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                            void *d_work, size_t work_bytes, void *stream)
+{
+    return encode_batch("encode_splanes_batch", codec, items, filters, strides, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
                         d_work, work_bytes, stream);
 }
 
@@ -115,12 +126,13 @@ static BatchCoded coded_flat(const uint32_t *d_clen, const void *d_payload, cons
 static int decode_batch(const char *who, int codec, const BatchCoded &S,
                         const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
                         unsigned esize, uint32_t chunk, unsigned cdfnum,
-                        void *d_work, size_t work_bytes, void *stream, size_t sub_m = 0)
+                        void *d_work, size_t work_bytes, void *stream, size_t sub_m = 0, const uint8_t *strides = nullptr)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
     if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
+    if ((rc = trc_planes_batch_strides(who, filters, strides, count, nullptr))) return rc;      // then a bad stride
     const size_t m = sub_m ? sub_m : (size_t)B.m_total, n = m * esize;
     if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, m, chunk, S.cdf[0], cdfnum))) return rc;
@@ -143,7 +155,7 @@ static int decode_batch(const char *who, int codec, const BatchCoded &S,
         if ((rc = trc_decode_range_dev(codec, S.clen[k], S.payload[k], m, chunk, sub_m ? 0 : c0, cnt,
                                        r.cdf ? S.cdf[k] : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return trc_planes_join_fbatch_dev(w, P.slice, items, filters, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
+    return trc_planes_join_sbatch_dev(w, P.slice, items, filters, strides, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
 }
 
 extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
@@ -162,10 +174,18 @@ extern "C" int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, c
     return decode_batch("decode_fplanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), items, filters, count,
                         first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
+extern "C" int trc_decode_splanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                            const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                                            size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                            void *d_work, size_t work_bytes, void *stream)
+{
+    return decode_batch("decode_splanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), items, filters, count,
+                        first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream, 0, strides);
+}
 
 // ---- the batch advisor: a filter per item from the histograms of trc_planes_hist_batch_dev ---------------------------------------
-int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
-                              uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);      // trc_planes_hist_batch.inc
+int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t first_item, size_t item_count,
+                              unsigned esize, uint32_t chunk, uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);      // trc_planes_hist_batch.inc
 
 // trc_planes_advise on items [base, base + count) of a batch, hist = the first one's slice: choice[i] and advice[i] (may be NULL)
 // count from `base` as well; the index in an error's text is the item's index in the batch
@@ -234,13 +254,15 @@ extern "C" size_t trc_planes_advise_batch_work_bytes(const trc_planes_item *item
     return TRC_PLANES_ADVISE_SLAB_BYTES + advise_table_bytes(items, count, esize, chunk);
 }
 
-extern "C" int trc_planes_advise_batch_dev(unsigned filters, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
-                                           uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
+// both advisors: strides == NULL is trc_planes_advise_batch_dev
+static int advise_batch_dev(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize, uint32_t chunk,
+                            uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
     if (filters < 1 || filters > 7) return fail(TRC_E_ARG, "planes_advise_batch: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", filters);
+    if ((rc = trc_planes_batch_strides("planes_advise_sbatch", nullptr, strides, count, nullptr))) return rc;
     if (!filters_out) return fail(TRC_E_ARG, "planes_advise_batch: null filters_out");
     if (!trc_planes_batch_ptrs_ok(items, 0, count)) return fail(TRC_E_ARG, "planes_advise_batch: every item's pointer must be non-null and 16-byte aligned");
     if (!d_work || ((uintptr_t)d_work & 255)) return fail(TRC_E_ARG, "planes_advise_batch: the workspace must be 256-byte aligned");
@@ -253,7 +275,7 @@ extern "C" int trc_planes_advise_batch_dev(unsigned filters, const trc_planes_it
     std::vector<uint8_t> choice(count);
     for (size_t i0 = 0; i0 < count; i0 += slab) {
         const size_t cnt = count - i0 < slab ? count - i0 : slab;
-        if ((rc = trc_planes_hist_batch_run(filters, items, i0, cnt, esize, chunk, d_hist, (uint8_t *)d_work + TRC_PLANES_ADVISE_SLAB_BYTES, table, s))) {
+        if ((rc = trc_planes_hist_batch_run(filters, items, strides, i0, cnt, esize, chunk, d_hist, (uint8_t *)d_work + TRC_PLANES_ADVISE_SLAB_BYTES, table, s))) {
             (void)hipStreamSynchronize(s);
             return rc;
         }
@@ -263,4 +285,16 @@ extern "C" int trc_planes_advise_batch_dev(unsigned filters, const trc_planes_it
     }
     memcpy(filters_out, choice.data(), count);
     return TRC_OK;
+}
+
+extern "C" int trc_planes_advise_batch_dev(unsigned filters, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                           uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
+{
+    return advise_batch_dev(filters, items, nullptr, count, esize, chunk, filters_out, advice, d_work, work_bytes, stream);
+}
+// the filter per item under the caller's strides: the slab walk above over trc_planes_hist_sbatch_dev's histograms
+extern "C" int trc_planes_advise_sbatch_dev(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize,
+                                            uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
+{
+    return advise_batch_dev(filters, items, strides, count, esize, chunk, filters_out, advice, d_work, work_bytes, stream);
 }

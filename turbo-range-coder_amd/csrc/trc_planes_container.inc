@@ -210,22 +210,23 @@ extern "C" int trc_planes_batch_pack_dev(int codec, const trc_planes_item *items
 }
 
 // ---- decoding a packed container where it lies ------------------------------------------------------------------------------------
-extern "C" int trc_decode_planes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
-                                                  const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
-                                                  unsigned esize, uint32_t chunk, unsigned cdfnum, const uint64_t *total,
-                                                  void *d_work, size_t work_bytes, void *stream)
+// both packed decoders: d_cont = the TRCB container, `lead` bytes into the buffer of cont_bytes the caller named (the TRCT prefix, or 0)
+static int packed_decode(const char *who, int codec, const void *d_cont, size_t lead, size_t cont_bytes,
+                         const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, size_t first_item, size_t item_count,
+                         unsigned esize, uint32_t chunk, unsigned cdfnum, const uint64_t *total,
+                         void *d_work, size_t work_bytes, void *stream)
 {
-    const char *who = "decode_planes_batch_packed";
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
     if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;
+    if ((rc = trc_planes_batch_strides(who, filters, strides, count, nullptr))) return rc;
     if ((rc = container_common(who, codec & ~(TRC_TABLES_READY | TRC_DIR_READY), esize))) return rc;
     if (!d_cont || ((uintptr_t)d_cont & 7) || !total) return fail(TRC_E_ARG, "%s: d_cont must be 8-byte aligned, total a host array of %u entries", who, esize);
     const TrcCodec &r = codec_row(codec);
     trc_planes_batch_layout L;
     if ((rc = trc_planes_batch_layout_host(codec, items, count, esize, chunk, cdfnum, total, &L))) return rc;
-    if (L.size > cont_bytes) return fail(TRC_E_ARG, "%s: the container has %llu bytes, d_cont holds %zu", who, (unsigned long long)L.size, cont_bytes);
+    if (lead + L.size > cont_bytes) return fail(TRC_E_ARG, "%s: the container has %llu bytes, d_cont holds %zu", who, (unsigned long long)(lead + L.size), cont_bytes);
     const size_t cdfb = planes_cdf_bytes(r, r.cdf || r.ss ? cdfnum : 0);
     BatchCoded S;
     memset(&S, 0, sizeof S);
@@ -235,7 +236,15 @@ extern "C" int trc_decode_planes_batch_packed_dev(int codec, const void *d_cont,
         S.clen[k] = (const uint32_t *)(sec + cdfb + sizeof(trc_container_hdr));
         S.payload[k] = sec + cdfb + sizeof(trc_container_hdr) + 4 * (size_t)B.chunks;
     }
-    return decode_batch(who, codec, S, items, filters, count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
+    return decode_batch(who, codec, S, items, filters, count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream, 0, strides);
+}
+extern "C" int trc_decode_planes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
+                                                  const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
+                                                  unsigned esize, uint32_t chunk, unsigned cdfnum, const uint64_t *total,
+                                                  void *d_work, size_t work_bytes, void *stream)
+{
+    return packed_decode("decode_planes_batch_packed", codec, d_cont, 0, cont_bytes, items, filters, nullptr, count, first_item, item_count,
+                         esize, chunk, cdfnum, total, d_work, work_bytes, stream);
 }
 
 // ---- host pointers: the plain single-device context of planes_host_encode, no striping ----------------------------------------------
@@ -281,7 +290,8 @@ static int batch_items_up(HostCtx &c, hipStream_t s, const trc_planes_item *item
     return flush();
 }
 
-static size_t batch_host_encode(const char *who, int codec, const trc_planes_item *items, const uint8_t *filters, bool choose, uint8_t *filters_out,
+// strides given: the TRCT container (trc_encode_splanes_batch_host); it refuses a batch that is a TRCB container's
+static size_t batch_host_encode(const char *who, int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, bool choose, uint8_t *filters_out,
                                 size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
@@ -292,8 +302,11 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     trc_planes_batch_plan B;
     if (trc_planes_batch_plan_host(items, count, esize, chunk ? chunk : TRC_CHUNK_AUTO_MIN, &B, nullptr)) return 0;     // (chunk 0 here: a bad batch, and the plan says why)
     if (trc_planes_batch_filters(who, filters, count, nullptr)) return 0;
+    bool strided = false;
+    if (trc_planes_batch_strides(who, filters, strides, count, &strided)) return 0;
+    if (strides && !strided) { fail(TRC_E_ARG, "%s: no item with a filter has a stride above 1: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
     if (!r.cdf && !r.ss) cdfnum = 0;
-    const size_t bound = trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
+    const size_t bound = strides ? trc_planes_sbatch_bound(codec, items, count, esize, chunk, cdfnum) : trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
     PlanesMap P;
     if (!bound || !planes_map(codec, (size_t)B.n_virtual, esize, chunk, P)) { fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk %u, cdfnum 0x%x)", who, chunk, cdfnum); return 0; }
     for (size_t i = 0; i < count; i++)
@@ -330,10 +343,12 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
         if (trc_planes_advise_batch_dev(7, dev.data(), count, esize, chunk, chosen.data(), nullptr, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
         filters = chosen.data();
     }
-    if (trc_encode_fplanes_batch_dev(codec, dev.data(), filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+    if (trc_encode_splanes_batch_dev(codec, dev.data(), filters, strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                                      d_clen, d_payload, d_total, c.d_work[0], c.cap_work[0], s) ||
-        trc_planes_batch_pack_dev(codec, dev.data(), filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
-                                  d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s)) { (void)hipStreamSynchronize(s); return 0; }
+        (strides ? trc_planes_sbatch_pack_dev(codec, dev.data(), filters, strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+                                              d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s)
+                 : trc_planes_batch_pack_dev(codec, dev.data(), filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+                                             d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s))) { (void)hipStreamSynchronize(s); return 0; }
     uint64_t size = 0;
     BCHK(hipMemcpyAsync(&size, d_size, sizeof size, hipMemcpyDeviceToHost, s));
     BCHK(hipStreamSynchronize(s));
@@ -348,20 +363,18 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
 extern "C" size_t trc_encode_planes_batch_host(int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize,
                                                uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap)
 {
-    return batch_host_encode("encode_planes_batch_host", codec, items, filters, false, nullptr, count, esize, chunk, cdfnum, items_on, out, outcap);
+    return batch_host_encode("encode_planes_batch_host", codec, items, filters, nullptr, false, nullptr, count, esize, chunk, cdfnum, items_on, out, outcap);
 }
 extern "C" size_t trc_encode_aplanes_batch_host(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
                                                 unsigned cdfnum, int items_on, void *out, size_t outcap, uint8_t *filters_out)
 {
-    return batch_host_encode("encode_aplanes_batch_host", codec, items, nullptr, true, filters_out, count, esize, chunk, cdfnum, items_on, out, outcap);
+    return batch_host_encode("encode_aplanes_batch_host", codec, items, nullptr, nullptr, true, filters_out, count, esize, chunk, cdfnum, items_on, out, outcap);
 }
 
-extern "C" size_t trc_decode_planes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
-                                               size_t first_item, size_t item_count, int items_on)
+// both host decoders behind their checks: in = a checked TRCB container; strides = the TRCT prefix's (NULL: a TRCB container alone)
+static size_t batch_host_decode(const char *who, const void *in, const uint8_t *strides, const trc_planes_item *items, size_t count,
+                                size_t first_item, size_t item_count, int items_on)
 {
-    const char *who = "decode_planes_batch_host";
-    if (!in || !items || (items_on != TRC_ITEMS_HOST && items_on != TRC_ITEMS_DEV)) { fail(TRC_E_ARG, "%s: bad arguments", who); return 0; }
-    if (trc_planes_batch_check(in, inlen, count)) return 0;
     const uint8_t *b = (const uint8_t *)in;
     trc_planes_batch_hdr h;
     memcpy(&h, b, sizeof h);
@@ -426,7 +439,7 @@ extern "C" size_t trc_decode_planes_batch_host(const void *in, size_t inlen, con
         D.clen[k] = d_clen + k * cnt;
         D.payload[k] = d_payload + k * P.buf;
     }
-    if (decode_batch(who, p.codec, D, dev.data(), filters, count, first_item, item_count, esize, chunk, p.cdfnum, c.d_work[0], c.cap_work[0], s, elems)) {
+    if (decode_batch(who, p.codec, D, dev.data(), filters, count, first_item, item_count, esize, chunk, p.cdfnum, c.d_work[0], c.cap_work[0], s, elems, strides)) {
         (void)hipStreamSynchronize(s);
         return 0;
     }
@@ -439,3 +452,132 @@ extern "C" size_t trc_decode_planes_batch_host(const void *in, size_t inlen, con
     return delivered;
 }
 #undef BCHK
+
+extern "C" size_t trc_decode_planes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
+                                               size_t first_item, size_t item_count, int items_on)
+{
+    const char *who = "decode_planes_batch_host";
+    if (!in || !items || (items_on != TRC_ITEMS_HOST && items_on != TRC_ITEMS_DEV)) { fail(TRC_E_ARG, "%s: bad arguments", who); return 0; }
+    if (trc_planes_batch_check(in, inlen, count)) return 0;
+    return batch_host_decode(who, in, nullptr, items, count, first_item, item_count, items_on);
+}
+
+// ---- the TRCT container: the strides of a batch in front of its TRCB container ---------------------------------------------------
+//   trc_planes_sbatch_hdr (16 B) | uint8 stride[count], zero-padded to a multiple of 16 | the TRCB container of (items, filters), inner = VS
+static inline size_t sbatch_prefix_bytes(size_t count) { return sizeof(trc_planes_sbatch_hdr) + ((count + 15) & ~(size_t)15); }
+
+extern "C" size_t trc_planes_sbatch_bound(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum)
+{
+    const size_t b = trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
+    return b ? sbatch_prefix_bytes(count) + b : 0;
+}
+
+// the verdict and, where it is good, the TRCB header and the prefix's length
+static int sbatch_verdict(const void *buf, size_t buflen, size_t count_expected, trc_planes_batch_hdr &h, size_t &prefix, char *why, size_t whysz)
+{
+#define BAD(...) do { snprintf(why, whysz, "strided batch container: " __VA_ARGS__); return TRC_E_ARG; } while (0)
+    trc_planes_sbatch_hdr t;
+    if (!buf || buflen < sizeof t) BAD("%zu bytes is shorter than the header", buflen);
+    memcpy(&t, buf, sizeof t);
+    if (t.magic != TRC_PLANES_SBATCH_MAGIC) BAD("bad magic 0x%08x", t.magic);
+    if (t.version != 1) BAD("version %u (1)", t.version);
+    if (t.zero || t.zero2) BAD("reserved fields are 0x%x / 0x%x, must be 0", t.zero, t.zero2);
+    if (t.count < 1 || t.count > TRC_PLANES_BATCH_MAX) BAD("%llu items (1 .. %u)", (unsigned long long)t.count, TRC_PLANES_BATCH_MAX);
+    if (count_expected != (size_t)-1 && t.count != count_expected) BAD("holds %llu items, caller expects %zu", (unsigned long long)t.count, count_expected);
+    const size_t count = (size_t)t.count;
+    prefix = sbatch_prefix_bytes(count);
+    if (buflen < prefix) BAD("%zu bytes is shorter than the strides of %zu items", buflen, count);
+    const uint8_t *b = (const uint8_t *)buf, *st = b + sizeof t;
+    for (size_t i = 0; i < count; i++) if (st[i] < 1 || st[i] > TRC_STRIDE_MAX) BAD("item %zu: stride %u (1 .. %d)", i, (unsigned)st[i], TRC_STRIDE_MAX);
+    for (size_t i = count; i < prefix - sizeof t; i++) if (st[i]) BAD("the stride padding must be zero bytes");
+    char sub[400];
+    if (batch_verdict(b + prefix, buflen - prefix, (size_t)-1, h, sub, sizeof sub)) BAD("%s", sub);
+    if (h.count != t.count) BAD("%llu strides in front of a batch container of %llu items", (unsigned long long)t.count, (unsigned long long)h.count);
+    const uint8_t *fl = b + prefix + sizeof h + 8 * count;
+    for (size_t i = 0; i < count; i++)
+        if (fl[i] == TRC_FILTER_NONE && st[i] != 1) BAD("item %zu: stride %u on an item without a filter (1)", i, (unsigned)st[i]);
+    return TRC_OK;
+#undef BAD
+}
+extern "C" int trc_planes_sbatch_check(const void *buf, size_t buflen, size_t count_expected)
+{
+    trc_planes_batch_hdr h;
+    size_t prefix;
+    char why[500];
+    return sbatch_verdict(buf, buflen, count_expected, h, prefix, why, sizeof why) ? fail(TRC_E_ARG, "%s", why) : TRC_OK;
+}
+extern "C" int trc_planes_sbatch_info(const void *buf, size_t buflen, trc_planes_batch_hdr *h, uint64_t *n, uint8_t *filters, uint8_t *strides, size_t cap)
+{
+    trc_planes_batch_hdr hh;
+    size_t prefix;
+    char why[500];
+    if (!h) return fail(TRC_E_ARG, "planes_sbatch_info: null header");
+    if (sbatch_verdict(buf, buflen, (size_t)-1, hh, prefix, why, sizeof why)) return fail(TRC_E_ARG, "%s", why);
+    *h = hh;
+    const size_t cnt = cap < hh.count ? cap : (size_t)hh.count;
+    const uint8_t *b = (const uint8_t *)buf;
+    if (n) memcpy(n, b + prefix + sizeof hh, 8 * cnt);
+    if (filters) memcpy(filters, b + prefix + sizeof hh + 8 * (size_t)hh.count, cnt);
+    if (strides) memcpy(strides, b + sizeof(trc_planes_sbatch_hdr), cnt);
+    return TRC_OK;
+}
+
+extern "C" int trc_planes_sbatch_pack_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                                          unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                          const int32_t *d_status, const uint32_t *d_clen, const void *d_payload,
+                                          const uint64_t *d_total, void *d_out, size_t out_bytes, uint64_t *d_size, void *stream)
+{
+    const char *who = "planes_sbatch_pack";
+    trc_planes_batch_plan B;
+    int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
+    if (rc) return rc;
+    if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;
+    bool strided;
+    if ((rc = trc_planes_batch_strides(who, filters, strides, count, &strided))) return rc;
+    if (!strided) return fail(TRC_E_ARG, "%s: no item with a filter has a stride above 1: that batch is a TRCB container (trc_planes_batch_pack_dev)", who);
+    const size_t prefix = sbatch_prefix_bytes(count);
+    if (d_out && out_bytes < prefix) return fail(TRC_E_WORK, "%s: d_out holds %zu B < required %zu B (trc_planes_sbatch_bound)", who, out_bytes,
+                                                 trc_planes_sbatch_bound(codec, items, count, esize, chunk, cdfnum));
+    // the TRCB part: every other check, its front and the pack kernel; it enqueues nothing unless all of them pass
+    if ((rc = trc_planes_batch_pack_dev(codec, items, filters, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+                                        d_out ? (uint8_t *)d_out + prefix : nullptr, d_out ? out_bytes - prefix : 0, d_size, stream))) return rc;
+    std::vector<uint8_t> f(prefix, 0);
+    trc_planes_sbatch_hdr t;
+    memset(&t, 0, sizeof t);
+    t.magic = TRC_PLANES_SBATCH_MAGIC; t.version = 1; t.count = count;
+    memcpy(f.data(), &t, sizeof t);
+    for (size_t i = 0; i < count; i++) f[sizeof t + i] = filters[i] == TRC_FILTER_NONE ? 1 : strides[i];
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemcpyWithStream(d_out, f.data(), prefix, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return fail(TRC_E_HIP, "%s: prefix upload: %s", who, hipGetErrorString(e));
+    return trc_planes_pack_lead_launch(d_size, prefix, s);
+}
+
+extern "C" int trc_decode_splanes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
+                                                   const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
+                                                   size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, unsigned cdfnum,
+                                                   const uint64_t *total, void *d_work, size_t work_bytes, void *stream)
+{
+    const size_t prefix = sbatch_prefix_bytes(count <= TRC_PLANES_BATCH_MAX ? count : 0);     // (a bad count: the plan says so before d_cont is looked at)
+    return packed_decode("decode_splanes_batch_packed", codec, d_cont ? (const uint8_t *)d_cont + prefix : nullptr, prefix, cont_bytes, items, filters,
+                         strides, count, first_item, item_count, esize, chunk, cdfnum, total, d_work, work_bytes, stream);
+}
+
+extern "C" size_t trc_encode_splanes_batch_host(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                                                size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on,
+                                                void *out, size_t outcap)
+{
+    const char *who = "encode_splanes_batch_host";
+    if (!strides) { fail(TRC_E_ARG, "%s: no strides: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
+    return batch_host_encode(who, codec, items, filters, strides, false, nullptr, count, esize, chunk, cdfnum, items_on, out, outcap);
+}
+
+extern "C" size_t trc_decode_splanes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
+                                                size_t first_item, size_t item_count, int items_on)
+{
+    const char *who = "decode_splanes_batch_host";
+    if (!in || !items || (items_on != TRC_ITEMS_HOST && items_on != TRC_ITEMS_DEV)) { fail(TRC_E_ARG, "%s: bad arguments", who); return 0; }
+    if (trc_planes_sbatch_check(in, inlen, count)) return 0;
+    const size_t prefix = sbatch_prefix_bytes(count);
+    return batch_host_decode(who, (const uint8_t *)in + prefix, (const uint8_t *)in + sizeof(trc_planes_sbatch_hdr), items, count, first_item, item_count, items_on);
+}

@@ -84,16 +84,23 @@ extern "C" size_t trc_planes_hist_batch_bytes(size_t item_count, unsigned esize)
 }
 
 // the call behind its plan and range checks: items [first_item, first_item + item_count) of a batch that batch_plan has accepted,
-// item_count >= 1.  Also what trc_planes_advise_batch_dev (trc_planes_batch.inc) runs once per slab.
-int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
-                              uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream)
+// item_count >= 1.  Also what trc_planes_advise_batch_dev (trc_planes_batch.inc) runs once per slab.  strides: those of the whole
+// batch, vetted (NULL: 1); where a predicted row is counted and a requested item's stride is above 1, every item is counted against
+// the element strides[i] back by trc_planes_hist_sbatch_kernel (trc_splanes_batch.inc), else by the kernel above.
+int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t first_item, size_t item_count,
+                              unsigned esize, uint32_t chunk, uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream)
 {
+    bool strided = false;
+    for (size_t i = 0; strides && (filters & 6u) && i < item_count; i++) strided |= strides[first_item + i] > 1;
+    const char *who = strided ? "planes_hist_sbatch" : "planes_hist_batch";
     std::vector<BatchRec> recs;
     uint64_t chunks, elems;
-    int rc = batch_range("planes_hist_batch", items, first_item, item_count, esize, chunk, chunks, elems, &recs);
+    int rc = batch_range(who, items, first_item, item_count, esize, chunk, chunks, elems, &recs);
     if (rc) return rc;
-    if (!d_hist || ((uintptr_t)d_hist & 7)) return trc_fail(TRC_E_ARG, "planes_hist_batch: the histograms must be 8-byte aligned");
-    if ((rc = batch_table_args("planes_hist_batch", item_count, chunks, d_table, table_bytes))) return rc;
+    if (strided)
+        for (size_t i = 0; i < item_count; i++) recs[i].v0 |= (uint64_t)(strides[first_item + i] - 1) << SBATCH_SHIFT;
+    if (!d_hist || ((uintptr_t)d_hist & 7)) return trc_fail(TRC_E_ARG, "%s: the histograms must be 8-byte aligned", who);
+    if ((rc = batch_table_args(who, item_count, chunks, d_table, table_bytes))) return rc;
     const HistShape hs = hist_shape(filters, esize);
     // a workgroup per 256 vectors of the range under the caps of trc_planes_hist_dev, then whole chunks per workgroup
     unsigned grid = batch_grid((size_t)chunks * (chunk / TRC_PLANES_VEC));
@@ -103,25 +110,41 @@ int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, si
     grid = (nc + cpw - 1) / cpw;
     hipStream_t s = (hipStream_t)stream;
     hipError_t he = hipMemsetAsync(d_hist, 0, trc_planes_hist_batch_bytes(item_count, esize), s);
-    if (he != hipSuccess) return trc_fail(TRC_E_HIP, "planes_hist_batch: %s", hipGetErrorString(he));
+    if (he != hipSuccess) return trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(he));
     const BatchRec *d_rec;
     const u32 *d_map;
-    if ((rc = batch_table("planes_hist_batch", recs, chunks, d_table, s, d_rec, d_map))) return rc;
-    static void (*const kernels[3])(const BatchRec *, const u32 *, u32, u32, u32, u32, u32, u32, u64a *) = TRC_BY_ESIZE(trc_planes_hist_batch_kernel);
-    hipLaunchKernelGGL(kernels[esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), hs.lds, s, d_rec, d_map, nc, cpw, chunk, filters, hs.cshift, hs.round_vecs, (u64a *)d_hist);
+    if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
+    static void (*const kernels[2][3])(const BatchRec *, const u32 *, u32, u32, u32, u32, u32, u32, u64a *) =
+        { TRC_BY_ESIZE(trc_planes_hist_batch_kernel), TRC_BY_ESIZE(trc_planes_hist_sbatch_kernel) };       // [a stride above 1][esize_row]
+    hipLaunchKernelGGL(kernels[strided][esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), hs.lds, s, d_rec, d_map, nc, cpw, chunk, filters, hs.cshift, hs.round_vecs, (u64a *)d_hist);
     he = hipGetLastError();
-    return he == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "planes_hist_batch: %s", hipGetErrorString(he));
+    return he == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(he));
+}
+
+// both calls: strides == NULL is trc_planes_hist_batch_dev
+static int hist_batch(const char *who, unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count,
+                      size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                      uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream)
+{
+    int rc = batch_plan(who, items, count, esize, chunk, nullptr, nullptr);
+    if (rc) return rc;
+    if (filters < 1 || filters > 7) return trc_fail(TRC_E_ARG, "%s: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", who, filters);
+    if ((rc = trc_planes_batch_strides(who, nullptr, strides, count, nullptr))) return rc;
+    if (first_item > count || item_count > count - first_item)
+        return trc_fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
+    if (item_count == 0) return TRC_OK;
+    return trc_planes_hist_batch_run(filters, items, strides, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes, stream);
 }
 
 extern "C" int trc_planes_hist_batch_dev(unsigned filters, const trc_planes_item *items, size_t count,
                                          size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
                                          uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream)
 {
-    int rc = batch_plan("planes_hist_batch", items, count, esize, chunk, nullptr, nullptr);
-    if (rc) return rc;
-    if (filters < 1 || filters > 7) return trc_fail(TRC_E_ARG, "planes_hist_batch: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", filters);
-    if (first_item > count || item_count > count - first_item)
-        return trc_fail(TRC_E_ARG, "planes_hist_batch: items [%zu, %zu + %zu) of %zu", first_item, first_item, item_count, count);
-    if (item_count == 0) return TRC_OK;
-    return trc_planes_hist_batch_run(filters, items, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes, stream);
+    return hist_batch("planes_hist_batch", filters, items, nullptr, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes, stream);
+}
+extern "C" int trc_planes_hist_sbatch_dev(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count,
+                                          size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                                          uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream)
+{
+    return hist_batch("planes_hist_sbatch", filters, items, strides, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes, stream);
 }

@@ -22,5 +22,6 @@ struct PackArgs {
 };
 
 int trc_planes_pack_launch(const PackArgs &a, hipStream_t s);
+int trc_planes_pack_lead_launch(uint64_t *d_size, uint64_t lead, hipStream_t s);       // *d_size += lead where it is not 0
 
 #endif

@@ -1,6 +1,6 @@
 // trc_planes_scan.h -- the scanning join of the filtered byte planes: what it is, and the pieces that trc_fplanes_join_kernel
-// (trc_fplanes.hip: one buffer, every stride) and trc_fplanes_join_batch_kernel (trc_fplanes_batch.inc: the items of a batch, a filter
-// per item) share.
+// (trc_fplanes.hip: one buffer, every stride), trc_fplanes_join_batch_kernel (trc_fplanes_batch.inc: the items of a batch, a filter
+// per item) and trc_splanes_join_batch_kernel (trc_splanes_batch.inc: a filter and a stride per item) share.
 //
 // A join with a predictor filter undoes a prefix sum (or prefix xor) that restarts every seg elements.  One WAVE walks one segment in
 // tiles of 512 elements, 8 per lane: join the planes' bytes to elements, undo the zigzag, scan the lane's 8 serially, scan the 64
@@ -13,7 +13,9 @@
 // the spans w, w + waves, ...  The last vector of the input may hold fewer than 8 elements; that one lane moves its elements singly.
 // No LDS beyond what the shuffles use, no workspace, no dependency between workgroups.
 //
-// Here: the tile, the launch shape, a tile's loads, the segment arithmetic, the scan's operand and operation.  The walk itself -- the
+// Here: the tile, the launch shape, a tile's loads, the segment arithmetic, the scan's operand and operation, and what the strided
+// scans are made of (the class rotate, the packed 16-bit operation, the S-class wave scan: trc_fplanes_join_kernel and
+// trc_splanes_join_batch_kernel of trc_splanes_batch.inc, where the stride is the item's).  The walk itself -- the
 // span / tile advance, the prefetch, the whole / partial vector store -- is written out in both kernels: as one __forceinline__
 // function taking the kernels' parts as functors it compiled to slower code (5 - 18 % on the 32- and 64-bit joins, measured:
 // profiles/planes/refactor_notes.md), so a change to it is made in both places.
@@ -67,6 +69,56 @@ __device__ __forceinline__ u32 wrap_seg(u32 x, u32 seg)
     if (x >= seg) x -= seg;
     if (x >= seg) x -= seg;
     return x;
+}
+
+// out[i] = a[(i + r) % S], r in [0, S): a rotate by 1, by 2 and by 4, each taken where r has that bit -- selects over static
+// indices, three per value
+template <int S, typename T> __device__ __forceinline__ void rotate(const T *a, u32 r, T *out)
+{
+    T x[S];
+#pragma unroll
+    for (int i = 0; i < S; i++) x[i] = a[i];
+#pragma unroll
+    for (int b = 1; b < S; b <<= 1) {
+        const bool take = r & (u32)b;
+        T y[S];
+#pragma unroll
+        for (int i = 0; i < S; i++) y[i] = take ? x[(i + b) % S] : x[i];
+#pragma unroll
+        for (int i = 0; i < S; i++) x[i] = y[i];
+    }
+#pragma unroll
+    for (int i = 0; i < S; i++) out[i] = x[i];
+}
+
+// 16-bit sums two to a word (v_pk_add_u16), so that a wave scan of 16-bit elements moves two classes per shuffle
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+template <int FILTER> __device__ __forceinline__ u32 pkop(u32 a, u32 b)
+{
+    if constexpr (FILTER == TRC_FILTER_XOR) return a ^ b;
+    return __builtin_bit_cast(u32, (us2)(__builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b)));
+}
+
+// N segmented inclusive wave scans (six __shfl_up steps each): inc[c] = the lane's total of value c on entry.  A lane adds what lies
+// at most `reach` lanes in front of it.  before[c] = the sum of the lanes in front of this one in its segment, those of earlier
+// tiles included where take_carry says the segment began there; carry[c] = the running value where this tile ends.
+template <int FILTER, int N, typename V, bool PK> __device__ __forceinline__ void wave_scan(V *inc, V *carry, V *before, u32 reach, bool take_carry)
+{
+    auto f = [](V a, V b) __attribute__((always_inline)) { if constexpr (PK) return (V)pkop<FILTER>((u32)a, (u32)b); else return op<FILTER>(a, b); };
+#pragma unroll
+    for (u32 d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (int c = 0; c < N; c++) {
+            const V o = __shfl_up(inc[c], d);
+            if (reach >= d) inc[c] = f(inc[c], o);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < N; c++) {
+        const V in_carry = take_carry ? carry[c] : (V)0, b = __shfl_up(inc[c], 1u);
+        before[c] = f(in_carry, reach ? b : (V)0);
+        carry[c] = __shfl(f(inc[c], in_carry), 63);
+    }
 }
 
 #endif

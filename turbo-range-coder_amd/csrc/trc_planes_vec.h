@@ -5,6 +5,7 @@
 //   trc_planes_hist.hip         the advisor's histograms of the filtered planes, of every stride (trc_planes_count.h)
 //   trc_planes_batch.hip        split / join over a table of separate allocations; includes
 //     trc_fplanes_batch.inc       the same with a filter per item (join: trc_planes_scan.h)
+//     trc_splanes_batch.inc       the same with a filter and a stride per item: split, join, histograms
 //     trc_planes_hist_batch.inc   the advisor's histograms per item (trc_planes_count.h)
 //   trc_planes_pack.hip         the batch container's packing (trc_planes_pack.h)
 #ifndef TRC_PLANES_VEC_H

@@ -230,6 +230,31 @@ def lib():
         l.trc_planes_advise_batch_work_bytes.restype = _sz; l.trc_planes_advise_batch_work_bytes.argtypes = [_it, _sz, C.c_uint, C.c_uint32]
         l.trc_planes_advise_batch_dev.restype = C.c_int
         l.trc_planes_advise_batch_dev.argtypes = [C.c_uint, _it, _sz, C.c_uint, C.c_uint32, _fl, _ad, _vp, _sz, _vp]
+        l.trc_planes_split_sbatch_dev.restype = C.c_int        # ... and the per-item strides behind them: a host array, or None
+        l.trc_planes_split_sbatch_dev.argtypes = [_it, _fl, _fl] + l.trc_planes_split_batch_dev.argtypes[1:]
+        l.trc_planes_join_sbatch_dev.restype = C.c_int
+        l.trc_planes_join_sbatch_dev.argtypes = [_vp, _sz, _it, _fl, _fl] + l.trc_planes_join_batch_dev.argtypes[3:]
+        l.trc_encode_splanes_batch_dev.restype = C.c_int
+        l.trc_encode_splanes_batch_dev.argtypes = [C.c_int, _it, _fl, _fl] + l.trc_encode_planes_batch_dev.argtypes[2:]
+        l.trc_decode_splanes_batch_dev.restype = C.c_int
+        l.trc_decode_splanes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _fl, _fl] + l.trc_decode_planes_batch_dev.argtypes[4:]
+        l.trc_planes_hist_sbatch_dev.restype = C.c_int
+        l.trc_planes_hist_sbatch_dev.argtypes = [C.c_uint, _it, _fl] + l.trc_planes_hist_batch_dev.argtypes[2:]
+        l.trc_planes_advise_sbatch_dev.restype = C.c_int
+        l.trc_planes_advise_sbatch_dev.argtypes = [C.c_uint, _it, _fl] + l.trc_planes_advise_batch_dev.argtypes[2:]
+        l.trc_planes_sbatch_bound.restype = _sz; l.trc_planes_sbatch_bound.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_planes_sbatch_check.restype = C.c_int; l.trc_planes_sbatch_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_sbatch_info.restype = C.c_int
+        l.trc_planes_sbatch_info.argtypes = [_vp, _sz, C.POINTER(PlanesBatchHdr), C.POINTER(C.c_uint64), _fl, _fl, _sz]
+        l.trc_planes_sbatch_pack_dev.restype = C.c_int
+        l.trc_planes_sbatch_pack_dev.argtypes = [C.c_int, _it, _fl, _fl, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]
+        l.trc_decode_splanes_batch_packed_dev.restype = C.c_int
+        l.trc_decode_splanes_batch_packed_dev.argtypes = [C.c_int, _vp, _sz, _it, _fl, _fl, _sz, _sz, _sz, C.c_uint, C.c_uint32, C.c_uint,
+                                                          C.POINTER(C.c_uint64), _vp, _sz, _vp]
+        l.trc_encode_splanes_batch_host.restype = _sz
+        l.trc_encode_splanes_batch_host.argtypes = [C.c_int, _it, _fl, _fl, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz]
+        l.trc_decode_splanes_batch_host.restype = _sz
+        l.trc_decode_splanes_batch_host.argtypes = [_vp, _sz, _it, _sz, _sz, _sz, C.c_int]
         l.trc_planes_batch_auto_chunk.restype = C.c_uint32; l.trc_planes_batch_auto_chunk.argtypes = [C.c_int, _it, _sz, C.c_uint]
         l.trc_planes_batch_bound.restype = _sz; l.trc_planes_batch_bound.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint]
         l.trc_planes_batch_layout_host.restype = C.c_int
@@ -594,6 +619,29 @@ def planes_join_fbatch(d_planes, offset, pitch, items, filters, count, first_ite
                                           item_count, esize, chunk, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
 
 
+def planes_strides(strides, count):
+    """the per-item strides of a batch as the host array the strided batch calls take: None (stride 1), one int for every item, or a
+    sequence of `count` ints.  Values are not judged here: the library does that."""
+    if strides is None:
+        return None
+    s = [strides] * count if isinstance(strides, int) else [int(x) for x in strides]
+    if len(s) != count or any(not 0 <= x <= 255 for x in s):
+        raise TrcError("strides: one byte per item of the batch")
+    return (C.c_uint8 * max(count, 1))(*s)
+
+
+def planes_split_sbatch(items, filters, strides, count, esize, chunk, d_planes, pitch, d_table, table_bytes):
+    """enqueue trc_planes_split_sbatch_dev: planes_split_fbatch with item i predicted from the element strides[i] back"""
+    _chk(lib().trc_planes_split_sbatch_dev(items, planes_filters(filters, count), planes_strides(strides, count), count, esize, chunk,
+                                           d_planes.data_ptr(), pitch, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
+def planes_join_sbatch(d_planes, offset, pitch, items, filters, strides, count, first_item, item_count, esize, chunk, d_table, table_bytes):
+    """enqueue trc_planes_join_sbatch_dev from d_planes[offset:], the inverse of planes_split_sbatch (filters, strides: the whole batch's)"""
+    _chk(lib().trc_planes_join_sbatch_dev(d_planes.data_ptr() + offset, pitch, items, planes_filters(filters, count), planes_strides(strides, count),
+                                          count, first_item, item_count, esize, chunk, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
 class PlanesBatchCoder:
     """The coded buffers of one batch of device tensors of one element size (bf16 / fp16: 2, fp32: 4, fp64 / int64: 8), coded by
     trc_encode_planes_batch_dev as the planes of their virtual buffer: self.clen / payload / total / cdf / status are laid out as
@@ -601,9 +649,12 @@ class PlanesBatchCoder:
     encoded ones by default).  filters (None, one FILTER_* for all items, or one per item) puts a predictor filter in front of
     each item's planes: the trc_*_fplanes_batch_dev calls, and decode() passes the same filters on.  filters="auto": encode() first
     asks the batch advisor (planes_advise_batch_dev, which waits for the stream) about the tensors' current contents, leaves its
-    choice in self.filters and what decided in self.advice, and codes exactly as if that list had been given.  Plumbing only."""
+    choice in self.filters and what decided in self.advice, and codes exactly as if that list had been given.  strides (None, one
+    int for all items, or one per item, each 1 .. 8) predicts a filtered item from the element that many back -- rows of K fields,
+    interleaved channels: the trc_*_splanes_batch_dev calls where an item with a filter has a stride above 1, today's calls
+    otherwise; with filters="auto" the advisor chooses under these strides.  Plumbing only."""
 
-    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None):
+    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None, strides=None):
         """esize: the element size where the tensors do not say it themselves (uint8 tensors of whole elements)"""
         import torch
         self.torch = torch
@@ -616,6 +667,7 @@ class PlanesBatchCoder:
         self.items = self._items(tensors)
         self.auto, self.advice = isinstance(filters, str) and filters == "auto", None
         self.filters = None if self.auto else planes_filters(filters, self.count)
+        self.strides = planes_strides(strides, self.count)
         self.plan, self.first = planes_batch_plan(self.items, self.count, self.esize, chunk)
         self.nch, self.pitch = self.plan["chunks"], self.plan["pitch"]
         self.cdfnum = _cdfnum(codec, cdfnum, prm)
@@ -646,15 +698,22 @@ class PlanesBatchCoder:
 
     def encode(self, flags=0):
         if self.auto:                                          # the advisor on what the tensors hold now; then as if that list had been given
-            chosen, self.advice = planes_advise_batch_dev(self.items, self.esize, self.chunk, 7, self.count, self.dev)
+            chosen, self.advice = planes_advise_batch_dev(self.items, self.esize, self.chunk, 7, self.count, self.dev, strides=self.strides)
             self.filters = planes_filters(chosen, self.count)
         st = self.codec in STATIC
         tail = (self.count, self.esize, self.chunk, self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
                 self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream())
         if self.filters is None:
             _chk(lib().trc_encode_planes_batch_dev(self.codec | flags, self.items, *tail))
+        elif self.strided():
+            _chk(lib().trc_encode_splanes_batch_dev(self.codec | flags, self.items, self.filters, self.strides, *tail))
         else:
             _chk(lib().trc_encode_fplanes_batch_dev(self.codec | flags, self.items, self.filters, *tail))
+
+    def strided(self):
+        """whether an item with a filter has a stride above 1: the strided calls; else today's"""
+        return self.filters is not None and self.strides is not None and \
+            any(f != FILTER_NONE and s > 1 for f, s in zip(self.filters[:self.count], self.strides[:self.count]))
 
     def decode(self, first_item=0, item_count=None, out=None, flags=0):
         """items [first_item, first_item + item_count) into out[i] (a list of count tensors, None outside the range; default: the
@@ -670,24 +729,31 @@ class PlanesBatchCoder:
                 self.range_work.data_ptr(), self.range_work_bytes, self._stream())
         if self.filters is None:
             _chk(lib().trc_decode_planes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, *tail))
+        elif self.strided():
+            _chk(lib().trc_decode_splanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.filters,
+                                                    self.strides, *tail))
         else:
             _chk(lib().trc_decode_fplanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.filters, *tail))
 
     def pack(self, guard=0):
-        """enqueue trc_planes_batch_pack_dev on what encode() left, then synchronise to read the size -> (the TRCB container: a uint8
+        """enqueue trc_planes_batch_pack_dev (strided(): trc_planes_sbatch_pack_dev, the TRCT container, sized by trc_planes_sbatch_bound)
+        on what encode() left, then synchronise to read the size -> (the TRCB container: a uint8
         device tensor trimmed to its size, with what remains of the planes_batch_bound bytes readable behind it; the size).  guard:
         0xA5 from the container's start through to the bound and that many bytes past it; self.pack_guard = the tensor's bytes behind
         the container, which must still be 0xA5.  The full buffer stays in self.packed."""
         st = self.codec in STATIC
-        bound = lib().trc_planes_batch_bound(self.codec, self.items, self.count, self.esize, self.chunk, self.cdfnum)
+        strided = self.strided()
+        bound = (lib().trc_planes_sbatch_bound if strided else lib().trc_planes_batch_bound)(self.codec, self.items, self.count, self.esize, self.chunk, self.cdfnum)
         if bound == 0:
             raise TrcError("bad (codec, tensors, chunk, cdfnum)")
         buf = self.torch.full((bound + guard,), 0xA5 if guard else 0, dtype=self.torch.uint8, device=self.dev)
         d_size = self.torch.zeros(1, dtype=self.torch.int64, device=self.dev)
-        _chk(lib().trc_planes_batch_pack_dev(self.codec, self.items, self.filters, self.count, self.esize, self.chunk,
-                                             self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
-                                             self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(),
-                                             buf.data_ptr(), bound, d_size.data_ptr(), self._stream()))
+        tail = (self.count, self.esize, self.chunk, self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), buf.data_ptr(), bound, d_size.data_ptr(), self._stream())
+        if strided:
+            _chk(lib().trc_planes_sbatch_pack_dev(self.codec, self.items, self.filters, self.strides, *tail))
+        else:
+            _chk(lib().trc_planes_batch_pack_dev(self.codec, self.items, self.filters, *tail))
         size = int(d_size.item())
         self.packed, self.pack_guard = buf, buf[size:]
         return buf[:size], size
@@ -704,10 +770,13 @@ class PlanesBatchCoder:
         if self.range_work is None:
             self.range_work = self._buf(0)
         tot = (C.c_uint64 * 8)(*[int(x) for x in total])
-        _chk(lib().trc_decode_planes_batch_packed_dev(self.codec, d_cont.data_ptr(), d_cont.numel() if cont_bytes is None else cont_bytes,
-                                                      items, self.filters, self.count, first_item, item_count, self.esize, self.chunk,
-                                                      self.cdfnum, tot, self.range_work.data_ptr(),
-                                                      need if work_bytes is None else work_bytes, self._stream()))
+        tail = (self.count, first_item, item_count, self.esize, self.chunk, self.cdfnum, tot, self.range_work.data_ptr(),
+                need if work_bytes is None else work_bytes, self._stream())
+        cont = (self.codec, d_cont.data_ptr(), d_cont.numel() if cont_bytes is None else cont_bytes, items, self.filters)
+        if self.strided():                                     # (d_cont: the TRCT container pack() gave)
+            _chk(lib().trc_decode_splanes_batch_packed_dev(*cont, self.strides, *tail))
+        else:
+            _chk(lib().trc_decode_planes_batch_packed_dev(*cont, *tail))
 
     def stored_bytes(self):
         """Synchronise: payload + directory (+ CDFs of a static coder) of all planes"""
@@ -1001,6 +1070,13 @@ def planes_hist_batch(filters, items, count, first_item, item_count, esize, chun
                                          d_table.data_ptr(), table_bytes, _cur_stream(d_hist)))
 
 
+def planes_hist_sbatch(filters, items, strides, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes):
+    """enqueue trc_planes_hist_sbatch_dev: planes_hist_batch with item i's predicted rows counted against the element strides[i] back
+    (strides: see planes_strides) -- slice j is what planes_hist_stride leaves for item first_item + j alone at its stride"""
+    _chk(lib().trc_planes_hist_sbatch_dev(filters, items, planes_strides(strides, count), count, first_item, item_count, esize, chunk,
+                                          d_hist.data_ptr(), d_table.data_ptr(), table_bytes, _cur_stream(d_hist)))
+
+
 def planes_advise_batch(hist, filters, esize, items, count, advice=True):
     """trc_planes_advise_batch on histograms in host memory (uint64, 3 * esize * 256 per item; needs no device)
     -> (the filter per item: list of ints, the advice per item: list of dicts, or None where advice is False)"""
@@ -1013,10 +1089,11 @@ def planes_advise_batch(hist, filters, esize, items, count, advice=True):
     return [int(x) for x in out[:count]], [_advice_dict(a) for a in adv[:count]] if advice else None
 
 
-def planes_advise_batch_dev(batch, esize=None, chunk=4096, filters=7, count=None, device="cuda", advice=True):
+def planes_advise_batch_dev(batch, esize=None, chunk=4096, filters=7, count=None, device="cuda", advice=True, strides=None):
     """trc_planes_advise_batch_dev on a list of device tensors of one element size, or on a trc_planes_item array (planes_items;
     esize is then required, count defaults to the array's length, the workspace lies on `device`), in a workspace of its own.
-    Waits for the current stream.  -> as planes_advise_batch"""
+    Waits for the current stream.  strides (see planes_strides) given: trc_planes_advise_sbatch_dev, the choice under those strides.
+    -> as planes_advise_batch"""
     import torch
     if isinstance(batch, C.Array):
         items, count = batch, len(batch) if count is None else count
@@ -1031,8 +1108,12 @@ def planes_advise_batch_dev(batch, esize=None, chunk=4096, filters=7, count=None
     work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
     out = (C.c_uint8 * max(count, 1))()
     adv = (PlanesAdvice * max(count, 1))() if advice else None
-    _chk(lib().trc_planes_advise_batch_dev(filters, items, count, esize, chunk, out, adv, work.data_ptr(), need,
-                                           torch.cuda.current_stream(dev).cuda_stream))
+    if strides is None:
+        _chk(lib().trc_planes_advise_batch_dev(filters, items, count, esize, chunk, out, adv, work.data_ptr(), need,
+                                               torch.cuda.current_stream(dev).cuda_stream))
+    else:
+        _chk(lib().trc_planes_advise_sbatch_dev(filters, items, planes_strides(strides, count), count, esize, chunk, out, adv, work.data_ptr(), need,
+                                                torch.cuda.current_stream(dev).cuda_stream))
     return [int(x) for x in out[:count]], [_advice_dict(a) for a in adv[:count]] if advice else None
 
 
@@ -1172,6 +1253,44 @@ def planes_batch_info(buf, cap=None):
     return {k: int(getattr(h, k)) for k, _ in PlanesBatchHdr._fields_}, [int(x) for x in n[:got]], [int(x) for x in f[:got]]
 
 
+SBATCH_MAGIC = 0x54435254                                       # "TRCT"
+
+
+def is_planes_sbatch(buf):
+    """whether the buffer starts like a TRCT container (a TRCB container behind per-item strides)"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    return buf.size >= 4 and int(buf[:4].view("<u4")[0]) == SBATCH_MAGIC
+
+
+def planes_sbatch_prefix(count):
+    """bytes of a TRCT container in front of its TRCB container"""
+    return 16 + ((count + 15) & ~15)
+
+
+def planes_sbatch_bound(codec, sizes, esize, chunk=0, cdfnum=0):
+    return lib().trc_planes_sbatch_bound(codec, planes_items([(None, n) for n in sizes]), len(sizes), esize, chunk, cdfnum)
+
+
+def planes_sbatch_check(buf, count=None):
+    """trc_planes_sbatch_check (needs no device); raises TrcError with the reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_planes_sbatch_check(buf.ctypes.data, buf.size, _sz(-1).value if count is None else count))
+
+
+def planes_sbatch_info(buf, cap=None):
+    """trc_planes_sbatch_info -> (dict of the TRCB header's fields, n: list, filters: list, strides: list) of the first min(cap, count) items"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    h = PlanesBatchHdr()
+    if cap is None:
+        _chk(lib().trc_planes_sbatch_info(buf.ctypes.data, buf.size, C.byref(h), None, None, None, 0))
+        cap = int(h.count)
+    n, f, st = (C.c_uint64 * max(cap, 1))(), (C.c_uint8 * max(cap, 1))(), (C.c_uint8 * max(cap, 1))()
+    _chk(lib().trc_planes_sbatch_info(buf.ctypes.data, buf.size, C.byref(h), n, f, st, cap))
+    got = min(cap, int(h.count))
+    return ({k: int(getattr(h, k)) for k, _ in PlanesBatchHdr._fields_}, [int(x) for x in n[:got]], [int(x) for x in f[:got]],
+            [int(x) for x in st[:got]])
+
+
 def parse_planes_batch(buf):
     """a checked TRCB container -> dict(the header's fields, n: list, filters: list, codec, cdfnum, total: the planes' payload sizes,
     off: the sections' offsets from the TRCB start); the inner TRCP container is buf[inner:size]"""
@@ -1196,12 +1315,22 @@ def _batch_host_items(arrays):
     return planes_items([(a.ctypes.data, a.size) for a in keep]), ITEMS_HOST, keep
 
 
-def host_encode_planes_batch(codec, arrays, esize, chunk=0, filters=None, cdfnum=256, prm=(5, 6)):
+def host_encode_planes_batch(codec, arrays, esize, chunk=0, filters=None, cdfnum=256, prm=(5, 6), strides=None):
     """trc_encode_planes_batch_host on numpy arrays (host items) or device tensors (device items): filters None, one id for all, a
-    list, or "auto" (trc_encode_aplanes_batch_host) -> the TRCB container (np.uint8); with "auto": (container, the filters chosen)"""
+    list, or "auto" (trc_encode_aplanes_batch_host) -> the TRCB container (np.uint8); with "auto": (container, the filters chosen).
+    strides (see planes_strides) under which an item with a filter has a stride above 1: trc_encode_splanes_batch_host -> the TRCT
+    container; other strides change nothing"""
     items, on, keep = _batch_host_items(arrays)
     count = len(keep)
     cn = _cdfnum(codec, cdfnum, prm)
+    if strides is not None and not isinstance(filters, str):
+        f, st = planes_filters(filters, count), planes_strides(strides, count)
+        if f is not None and any(a != FILTER_NONE and b != 1 for a, b in zip(f[:count], st[:count])):      # (a bad stride: the library's to refuse)
+            out = np.zeros(max(lib().trc_planes_sbatch_bound(codec, items, count, esize, chunk, cn), 64), dtype=np.uint8)
+            l = lib().trc_encode_splanes_batch_host(codec, items, f, st, count, esize, chunk, cn, on, out.ctypes.data, out.size)
+            if l == 0:
+                raise TrcError(lib().trc_last_error().decode())
+            return out[:l].copy()
     out = np.zeros(max(lib().trc_planes_batch_bound(codec, items, count, esize, chunk, cn), 64), dtype=np.uint8)
     if isinstance(filters, str) and filters == "auto":
         chosen = (C.c_uint8 * max(count, 1))()
@@ -1215,11 +1344,13 @@ def host_encode_planes_batch(codec, arrays, esize, chunk=0, filters=None, cdfnum
 
 
 def host_decode_planes_batch(comp, first_item=0, item_count=None, out=None, sizes=None):
-    """trc_decode_planes_batch_host: items [first_item, first_item + item_count) of a TRCB container -> a list of np.uint8 arrays, or,
+    """trc_decode_planes_batch_host (trc_decode_splanes_batch_host where comp is a TRCT container): items [first_item, first_item +
+    item_count) of a TRCB container -> a list of np.uint8 arrays, or,
     out given (a list of count device tensors, None outside the range), into those -> the bytes delivered.  sizes: what the call is
     told the items hold instead of the container's own table (the tests' argument errors)"""
     comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    h, n, _ = planes_batch_info(comp)
+    strided = is_planes_sbatch(comp)
+    h, n = planes_sbatch_info(comp)[:2] if strided else planes_batch_info(comp)[:2]
     count = h["count"]
     item_count = count - first_item if item_count is None else item_count
     sizes = n if sizes is None else sizes
@@ -1231,7 +1362,7 @@ def host_decode_planes_batch(comp, first_item=0, item_count=None, out=None, size
     else:
         items = planes_items([(out[i].data_ptr() if out[i] is not None else None, sizes[i]) for i in range(count)])
         on = ITEMS_DEV
-    l = lib().trc_decode_planes_batch_host(comp.ctypes.data, comp.size, items, count, first_item, item_count, on)
+    l = (lib().trc_decode_splanes_batch_host if strided else lib().trc_decode_planes_batch_host)(comp.ctypes.data, comp.size, items, count, first_item, item_count, on)
     if l != sum(n[i] for i in wanted):
         raise TrcError(lib().trc_last_error().decode())
     if out is not None:
