@@ -128,17 +128,22 @@ void trc_launch_range_dir(const uint32_t *d_clen, uint32_t nchunks, size_t n, ui
 // Payload gather: one workgroup per group of 64 chunks moves the group's bytes to payload + base as dst-aligned
 // 16-byte vectors.  A chunk contributes one PIECE (modes 0/1: its scratch region, start- or end-aligned; or the input
 // chunk itself when stored raw) or two (mode 2, the two-stream coders: [4 + len0 bytes at the start of region A]
-// [rest at the start of region B]).  A vector belongs to the piece that holds its FIRST byte and a fixed set of
-// threads walks the vectors of one piece, so nothing is searched: every load address follows from the prefix table
-// in LDS and a thread's loads are independent.  A vector that runs past its piece takes the rest from the next piece
-// (second load, the two spliced); if either piece is shorter than 16 bytes (tiny pieces) it is assembled byte by
-// byte.  (History, 100 MB / chunk 512: chunk-after-chunk copy 55 us, per-vector binary search 54 us, this walk 49 us;
-// the two-part layout went from a per-chunk wave copy, 152 us, to the same walk.)
+// [rest at the start of region B]).  A destination-aligned 64-byte SECTOR belongs to the piece that holds its FIRST byte
+// and a fixed set of threads walks the sectors of one piece, so nothing is searched: every load address follows from the
+// prefix table in LDS and a thread's loads are independent.  The last sector of a piece takes its remaining vectors from
+// the next piece (a second load and a splice, or one load inside the next piece); a vector that needs a third piece or
+// a piece shorter than 16 bytes (tiny pieces) is assembled byte by byte.  The group's first and last partial sector are
+// the neighbours' too and keep partial stores.  (History, 100 MB / chunk 512: chunk-after-chunk copy 55 us, per-vector
+// binary search 54 us, a walk over the vectors of a piece 49 us -- 27.9 with in-piece loads; the two-part layout went
+// from a per-chunk wave copy, 152 us, to the same walk.)
 #ifndef TRC_GATHER_VPT
 #define TRC_GATHER_VPT 6
 #endif
 #ifndef TRC_GATHER_ATTR
 #define TRC_GATHER_ATTR
+#endif
+#ifdef TRC_GATHER_PROF                                           // variant builds only: wall clock (100 MHz) per workgroup: start, table ready, last store issued, stores acknowledged
+__device__ unsigned long long trc_gat_wall[16 * 4096];          // [workgroup][wave][stamp]
 #endif
 template <int PARTS>
 __global__ __launch_bounds__(256) TRC_GATHER_ATTR void trc_gather_kernel(const u8 *__restrict__ in, u64 n, u32 chunk, u32 nchunks,
@@ -155,6 +160,9 @@ __global__ __launch_bounds__(256) TRC_GATHER_ATTR void trc_gather_kernel(const u
     __shared__ u64 src_s[NP];                                  // where piece p's bytes are
     __shared__ u64 base_s;
     const u32 g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+#ifdef TRC_GATHER_PROF
+    const u64 gw0 = wall_clock64();
+#endif
     if (wid == 1 || blockDim.x == 64) {                        // one wave sums, the next builds the table
         const u64 b = trc_group_base(goff, gsum, g);
         if (lane == 0) { base_s = b; if (goff_out) goff_out[g] = b; }      // (kept for a decode of this directory: TrcWork::goff_area)
@@ -183,6 +191,9 @@ __global__ __launch_bounds__(256) TRC_GATHER_ATTR void trc_gather_kernel(const u
         if (lane == 63) ex_s[NP] = inc;
     }
     __syncthreads();
+#ifdef TRC_GATHER_PROF
+    const u64 gw1 = wall_clock64();
+#endif
     const u64 base = base_s;
     const u32 tot = ex_s[NP];
     if (total && g == ngroups - 1 && tid == 0) *total = base + tot;
@@ -193,71 +204,135 @@ __global__ __launch_bounds__(256) TRC_GATHER_ATTR void trc_gather_kernel(const u
     if (head > tot) head = tot;
     const u32 nvec = (tot - head) >> 4;
     const u32 tail0 = head + (nvec << 4);
-    for (u32 b = tid; b < head + (tot - tail0); b += 256) {     // bytes before the first / after the last aligned vector
-        const u32 d = b < head ? b : tail0 + (b - head);
+    // the whole destination-aligned 64-byte sectors of the group: [sh + 64 s, sh + 64 s + 64), s < nsec
+    const u32 sh = (u32)((64u - ((uintptr_t)dst0 & 63u)) & 63u);
+    const u32 nsec = tot > sh ? (tot - sh) >> 6 : 0u;
+    // byte by byte from piece kk on (dv >= ex_s[kk]): three or more pieces inside a vector, or a piece below 16 bytes
+    auto bytewise = [&](u32 dv, u32 kk) {
+        const u8 *p = src_of(kk);
+        for (u32 q = 0; q < 16; q++) {
+            while (dv + q >= ex_s[kk + 1]) { kk++; p = src_of(kk); }
+            dst0[dv + q] = p[dv + q - ex_s[kk]];
+        }
+    };
+    auto piece_of = [&](u32 d) -> u32 {
         u32 lo = 0, hi = NP;
         while (lo + 1 < hi) { const u32 mid = (lo + hi) >> 1; if (ex_s[mid] <= d) lo = mid; else hi = mid; }
+        return lo;
+    };
+    // The group's first and last PARTIAL sector (up to 63 bytes each; the neighbouring groups write the rest of them): whole 16-byte
+    // vectors where they fit, bytes otherwise, nothing outside [0, tot).  These few stores look their pieces up.
+    for (u32 b = tid; b < head + (tot - tail0); b += 256) {     // bytes before the first / after the last aligned vector
+        const u32 d = b < head ? b : tail0 + (b - head);
+        const u32 lo = piece_of(d);
         dst0[d] = src_of(lo)[d - ex_s[lo]];
     }
     {
+        const u32 nv1 = ((tot < sh ? tot : sh) - head) >> 4;    // aligned vectors below the first whole sector (head == sh mod 16)
+        const u32 nv2 = nvec - nv1 - 4u * nsec;                 // ... and behind the last one: at most three each
+        const u32 e = tid - 64u;                                // (the second wave: the first has the bytes above)
+        if (e < nv1 + nv2) {
+            const u32 dv = e < nv1 ? head + (e << 4) : sh + (nsec << 6) + ((e - nv1) << 4);
+            const u32 lo = piece_of(dv);
+            if (dv + 16u <= ex_s[lo + 1]) *(uint4 *)(dst0 + dv) = trc_ld16_a2_global(src_of(lo) + (dv - ex_s[lo]));
+            else bytewise(dv, lo);
+        }
+    }
+    // The whole sectors.  A sector belongs to the piece that holds its FIRST byte, and lane `sub` of the piece's threads writes vector
+    // 4 s + sub (+ TPP, ...) of sector s: with four threads per piece every full-width store instruction of a quad is one whole aligned
+    // sector (with two, an aligned half).  All sectors of a piece but its last lie inside the piece; the last one runs up to 63 bytes
+    // into the next piece, whose own threads start at its first whole sector.
+    {
         const u32 k = tid / TPP, sub = tid % TPP;
         const u32 e0 = ex_s[k], e1 = ex_s[k + 1];
-        // vectors whose first byte lies in [e0, e1): first index = ceil((e0 - head)/16) (0 if e0 <= head), end likewise from e1
-        const u32 v_lo = e0 <= head ? 0u : (e0 - head + 15u) >> 4;
-        u32 v_hi = e1 <= head ? 0u : (e1 - head + 15u) >> 4;
-        if (v_hi > nvec) v_hi = nvec;
-        const u8 *sa = src_of(k);
-        const u8 *sb = k + 1 < NP ? src_of(k + 1) : sa;
-        const u32 e2 = ex_s[k + 2 > NP ? NP : k + 2];
-        // No load leaves the piece it takes bytes from (DESIGN.md "The gather's loads stay inside their pieces"): a vector that
-        // runs past the end of piece k loads the piece's LAST 16 bytes instead (offset pl - 16: its own bytes are the top sp of
-        // them), the next piece gives its FIRST 16 bytes, and trc_splice16 cuts the vector out of the two.  Pieces shorter than
-        // 16 bytes on either side go byte by byte.  Slots past the piece's last vector load nothing.
-        const u32 pl = e1 - e0;
-        const bool a16 = pl >= 16u;                             // piece k can give a 16-byte load
-        const bool b16 = k + 1 < NP && e2 - e1 >= 16u;          // the next piece can
-        auto bytewise = [&](u32 dv) {                           // three or more pieces inside 16 bytes, or a piece below 16 bytes
-            u32 kk = k;
-            const u8 *p = sa;
-            for (u32 q = 0; q < 16; q++) {
-                while (dv + q >= ex_s[kk + 1]) { kk++; p = src_of(kk); }
-                dst0[dv + q] = p[dv + q - ex_s[kk]];
+        // sectors whose first byte lies in [e0, e1): first index = ceil((e0 - sh) / 64) (0 if e0 <= sh), end likewise from e1
+        const u32 s_lo = e0 <= sh ? 0u : (e0 - sh + 63u) >> 6;
+        u32 s_hi = e1 <= sh ? 0u : (e1 - sh + 63u) >> 6;
+        if (s_hi > nsec) s_hi = nsec;
+        if (s_lo < s_hi) {
+            const u8 *sa = src_of(k);
+            const u8 *sb = k + 1 < NP ? src_of(k + 1) : sa;
+            const u32 e2 = ex_s[k + 2 > NP ? NP : k + 2];
+            // No load leaves the piece it takes bytes from (DESIGN.md "The gather's loads stay inside their pieces").  A vector of the
+            // last sector that runs past the end of piece k loads the piece's LAST 16 bytes (offset pl - 16: its own bytes are the top
+            // sp of them), the next piece gives its FIRST 16 bytes, and trc_splice16 cuts the vector out of the two; a vector that lies
+            // in the next piece altogether is one load from there.  One that needs a third piece, or a piece shorter than 16 bytes,
+            // goes byte by byte.  These are at most LV loads of each kind per thread, requested before the trips over the sectors
+            // inside the piece, whose slots are plain loads and stores.
+            const u32 pl = e1 - e0;
+            const bool a16 = pl >= 16u;                         // piece k can give a 16-byte load
+            const bool b16 = k + 1 < NP && e2 - e1 >= 16u;      // the next piece can
+            constexpr u32 LV = 4u / TPP;                        // vectors of one sector per thread
+            enum { WHOLE, SPLICE, BYTES };
+            uint4 la[LV], lb[LV];
+            u32 ld[LV], lk[LV];
+#pragma unroll
+            for (int i = 0; i < (int)LV; i++) {
+                const u32 d = sh + ((4u * (s_hi - 1u) + sub + TPP * (u32)i) << 4);
+                ld[i] = d; lk[i] = BYTES;
+                la[i] = make_uint4(0u, 0u, 0u, 0u); lb[i] = la[i];
+                if (d + 16u <= e1) { la[i] = trc_ld16_a2_global(sa + (d - e0)); lk[i] = WHOLE; }
+                else if (d < e1) { if (a16 && b16) { la[i] = trc_ld16_a2_global(sa + (pl - 16u)); lb[i] = trc_ld16_a2_global(sb); lk[i] = SPLICE; } }
+                else if (d + 16u <= e2) { la[i] = trc_ld16_a2_global(sb + (d - e1)); lk[i] = WHOLE; }
             }
-        };
-        if (!a16) {                                             // at most one vector starts inside a piece this short
-            if (sub == 0 && v_lo < v_hi) bytewise(head + (v_lo << 4));
-            return;
-        }
-        for (u32 v0 = v_lo + sub; v0 < v_hi; v0 += VPT * TPP) {  // VPT vectors per thread per trip
-            uint4 a[VPT], b[VPT];
-            u32 d[VPT];
-            bool ok[VPT];
+            const u32 u_hi = 4u * (s_hi - 1u);
+            for (u32 u0 = 4u * s_lo + sub; u0 < u_hi; u0 += VPT * TPP) {  // VPT vectors per thread per trip
+                uint4 a[VPT];
 #pragma unroll
-            for (int j = 0; j < (int)VPT; j++) {
-                const u32 v = v0 + TPP * (u32)j;
-                ok[j] = v < v_hi;
-                d[j] = head + ((ok[j] ? v : v0) << 4);
-                a[j] = make_uint4(0u, 0u, 0u, 0u);
-                if (ok[j]) a[j] = trc_ld16_a2_global(sa + trc_min(d[j] - e0, pl - 16u));
-                b[j] = a[j];
+                for (int j = 0; j < (int)VPT; j++) {
+                    const u32 u = u0 + TPP * (u32)j;
+                    if (u < u_hi) a[j] = trc_ld16_a2_global(sa + (sh + (u << 4) - e0));
+                }
+                // (These stores stay plain.  Write-through, `global_store_dwordx4 ... sc1` as in StreamOut<.., WT>, cost the gather 11 us
+                // when a quad's four stores straddled two sectors, 29.9 -> 41.0, profiles/r05_notes.md; with whole aligned sectors it
+                // still costs 1.1 us, 26.1 -> 27.2, and the launch ends with its last workgroup: there is no write-back tail to
+                // take away, profiles/edges/edges_notes.md.  The nontemporal hint cost the decoder behind it 9 us.)
+#pragma unroll
+                for (int j = 0; j < (int)VPT; j++) {
+                    const u32 u = u0 + TPP * (u32)j;
+                    if (u < u_hi) *(uint4 *)(dst0 + sh + (u << 4)) = a[j];
+                }
             }
 #pragma unroll
-            for (int j = 0; j < (int)VPT; j++)
-                if (ok[j] && d[j] + 16u > e1 && b16) b[j] = trc_ld16_a2_global(sb);
-#pragma unroll
-            for (int j = 0; j < (int)VPT; j++) {
-                if (!ok[j]) continue;
-                const u32 sp = e1 - d[j];                       // bytes of this vector inside piece k (>= 16: all)
-                // (write-through stores here -- what took 2 us off the encoders' tails, StreamOut<.., WT> -- cost the gather 11 us:
-                // 29.9 -> 41.0; the nontemporal hint 29.8 -> 39.4 and the decoder behind it 60.4 -> 69.5, profiles/r05_notes.md; its
-                // stores stay plain)
-                if (sp >= 16u) { *(uint4 *)(dst0 + d[j]) = a[j]; continue; }
-                if (b16) *(uint4 *)(dst0 + d[j]) = trc_splice16(a[j], b[j], 16u - sp);
-                else bytewise(d[j]);
+            for (int i = 0; i < (int)LV; i++) {
+                if (lk[i] == WHOLE) *(uint4 *)(dst0 + ld[i]) = la[i];
+                else if (lk[i] == SPLICE) *(uint4 *)(dst0 + ld[i]) = trc_splice16(la[i], lb[i], 16u - (e1 - ld[i]));
+                else bytewise(ld[i], k);
             }
         }
     }
+#ifdef TRC_GATHER_PROF
+    {
+        const u64 gw2 = wall_clock64();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const u64 gw3 = wall_clock64();
+        if (lane == 0) { unsigned long long *w = trc_gat_wall + 16u * (g & 4095u) + 4u * (wid & 3u); w[0] = gw0; w[1] = gw1; w[2] = gw2; w[3] = gw3; }
+    }
+#endif
 }
+#ifdef TRC_GATHER_PROF
+#include <stdio.h>
+static void trc_gather_prof_report(u32 ngroups)
+{
+    static int calls = 0;
+    if (++calls % 64 != 0) return;
+    static unsigned long long wl[16 * 4096];
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(wl, HIP_SYMBOL(trc_gat_wall), sizeof wl);
+    const unsigned ng = ngroups < 4096u ? ngroups : 4096u;
+    unsigned long long t0 = ~0ull;
+    for (unsigned i = 0; i < 16 * ng; i += 4) if (wl[i] && wl[i] < t0) t0 = wl[i];
+    double first_ready = 1e9, last_start = 0, sum_ready = 0, last_issue = 0, last_ack = 0, sum_ack = 0; unsigned cnt = 0;
+    for (unsigned i = 0; i < 16 * ng; i += 4) {
+        if (!wl[i]) continue;
+        const double a = (wl[i] - t0) * 0.01, b = (wl[i + 1] - t0) * 0.01, c = (wl[i + 2] - t0) * 0.01, d = (wl[i + 3] - t0) * 0.01;
+        if (a > last_start) last_start = a; if (b < first_ready) first_ready = b; if (c > last_issue) last_issue = c; if (d > last_ack) last_ack = d;
+        sum_ready += b - a; sum_ack += d - a; cnt++;
+    }
+    fprintf(stderr, "[gather wall, us since the first wave's start] waves %u, last start %.2f; first table ready %.2f (mean %.2f after a wave's own start); last store issued %.2f, last store acknowledged %.2f (mean wave life %.2f)\n",
+            cnt, last_start, first_ready, cnt ? sum_ready / cnt : 0.0, last_issue, last_ack, cnt ? sum_ack / cnt : 0.0);
+}
+#endif
 void trc_launch_gather(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcWork &w, TrcGather mode,
                        const uint32_t *d_clen, uint8_t *d_payload, uint64_t *d_total, hipStream_t s)
 {
@@ -270,6 +345,9 @@ void trc_launch_gather(const uint8_t *d_in, size_t n, uint32_t chunk, const TrcW
         TRC_LAUNCH_TIMED((trc_gather_kernel<1>), dim3(w.ngroups), dim3(256), 0, s, d_in, (u64)n, chunk, w.nchunks,
                            w.scratch, w.stride, from_end, w.scratch2, w.stride2, w.aux, d_clen, w.goff, w.gsum, w.ngroups,
                            d_payload, w.goff ? (u64 *)nullptr : d_total, w.goff ? (u64 *)nullptr : w.goff_area);
+#ifdef TRC_GATHER_PROF
+    trc_gather_prof_report(w.ngroups);
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
