@@ -5,7 +5,7 @@ with every lane on one bin; into a dirty buffer; over an item range with every o
 the items lie in ONE allocation with 16 to 48 bytes of 0xA5 between them and no slack of their own, every other device buffer is
 followed by a 512-byte guard of 0xA5 that must survive, and the input image must be unchanged after every call.
 trc_planes_advise_batch_dev must return what the pieces give by hand, whatever the slab; PlanesBatchCoder(filters="auto") must
-code byte for byte what the chosen list codes."""
+code byte for byte what the chosen list codes.  The histogram call and its comparisons are in gpu_planes.py."""
 import ctypes as C
 
 import numpy as np
@@ -16,21 +16,12 @@ import advise_lib as AL
 import fplanes_lib as FL
 import planes_batch_lib as BL
 import trc
-from test_gpu_planes_batch import Packed, assert_same_outputs, guarded
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import E_ARG, E_WORK, GUARD, Packed, assert_hists, assert_same_outputs, decodes_whole_batch, device_hists, guarded
 
 pytestmark = pytest.mark.gpu
-GUARD = BL.GUARD
 ORDERS = (ABL.LENGTHS, ABL.LENGTHS[::-1])
 M_BIG = 65539
-E_ARG, E_WORK = -1, -3
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 _model = {}
@@ -48,47 +39,11 @@ def model(esize, chunk, lengths, kinds=ABL.KINDS, seed=None):
     return _model[key]
 
 
-def device_hists(torch, src, esize, chunk, filters, fi=0, ic=None, null_outside=False, d_hist=None):
-    """one call over items [fi, fi + ic) of the packed batch `src`, into a guarded buffer sized for the range (given, or fresh and
-    dirty) and a guarded table of exactly the range's size -> (uint64 [ic, 3, esize, 256], the buffer); checks guards and input"""
-    count = len(src.sizes)
-    ic = count - fi if ic is None else ic
-    _, first = BL.plan(src.sizes, esize, chunk)
-    tb = trc.lib().trc_planes_batch_table_bytes(ic, first[fi + ic] - first[fi])
-    hb = trc.planes_hist_batch_bytes(ic, esize)
-    assert hb == ic * trc.planes_hist_bytes(esize) and (tb > 0) == (ic > 0)
-    if d_hist is None:
-        d_hist = guarded(torch, hb)
-    d_table = guarded(torch, tb)
-    items = src.items(range(fi, fi + ic)) if null_outside else src.items()
-    trc.planes_hist_batch(filters, items, count, fi, ic, esize, chunk, d_hist, d_table, tb)
-    torch.cuda.synchronize()
-    raw = d_hist.cpu().numpy()
-    assert (raw[hb:] == 0xA5).all(), "the call wrote behind the histograms of its range"
-    assert (d_table.cpu().numpy()[tb:] == 0xA5).all(), "the call wrote behind its table"
-    assert np.array_equal(src.buf.cpu().numpy(), src.img), "the call changed its input, a gap or the guard"
-    return raw[:hb].view("<u8").reshape(ic, 3, esize, 256).copy(), d_hist
-
-
-def assert_hists(got, exp, ms, filters, tag):
-    assert got.shape == exp.shape, tag
-    for i, m in enumerate(ms):
-        for f in range(3):
-            if filters >> f & 1:
-                assert (got[i, f].sum(axis=1) == m).all(), "%s: item %d (%d elements): a row of filter %d does not sum to m" % (tag, i, m, f)
-                if not np.array_equal(got[i, f], exp[i, f]):
-                    k, b = np.argwhere(got[i, f] != exp[i, f])[0]
-                    raise AssertionError("%s: item %d (%d elements) filter %d plane %d bin %d: %d, the model has %d"
-                                         % (tag, i, m, f, k, b, got[i, f, k, b], exp[i, f, k, b]))
-            else:
-                assert not got[i, f].any(), "%s: item %d: rows of filter %d, which was not requested, are not zero" % (tag, i, f)
-
-
 def hist_case(torch, esize, chunk, lengths, filters, fi=0, ic=None, null_outside=False, kinds=ABL.KINDS, seed=None):
     datas, h = model(esize, chunk, lengths, kinds, seed)
     src = Packed(torch, datas, seed=chunk + esize)
     ic = len(datas) - fi if ic is None else ic
-    got, _ = device_hists(torch, src, esize, chunk, filters, fi, ic, null_outside)
+    got, _ = device_hists(torch, esize, chunk, filters, src=src, fi=fi, ic=ic, null_outside=null_outside)
     assert_hists(got, h[fi:fi + ic], list(lengths[fi:fi + ic]), filters,
                  "esize %d chunk %d filters %d items [%d, %d) of %d" % (esize, chunk, filters, fi, fi + ic, len(datas)))
 
@@ -116,8 +71,8 @@ def test_item_count_zero_launches_nothing(torch_cuda):
     torch = torch_cuda
     datas, _ = model(4, 256, ORDERS[0])
     src = Packed(torch, datas)
-    got, d_hist = device_hists(torch, src, 4, 256, 7, 5, 0)
-    assert got.size == 0 and (d_hist.cpu().numpy() == 0xA5).all()
+    got, d_hist = device_hists(torch, 4, 256, 7, src=src, fi=5, ic=0)
+    assert got.size == 0 and (d_hist.whole.cpu().numpy() == 0xA5).all()
     # ... whatever the buffers are
     assert trc.lib().trc_planes_hist_batch_dev(7, src.items(), len(datas), len(datas), 0, 4, 256, None, None, 0, None) == 0
 
@@ -157,7 +112,7 @@ def test_every_lane_on_one_bin(torch_cuda, esize):
     assert exp[0, 0, 0, 0x81] == M_BIG and exp[1, 2, 0, 0] == M_BIG - 257          # (257 chunks open with the element itself)
     src = Packed(torch, const)
     for filters in (1, 7):
-        got, _ = device_hists(torch, src, esize, 256, filters)
+        got, _ = device_hists(torch, esize, 256, filters, src=src)
         assert_hists(got, ABL.masked(exp, filters), [M_BIG] * 2, filters, "equal elements, esize %d, filters %d" % (esize, filters))
     for filters in (1, 7):
         hist_case(torch, esize, 256, (M_BIG, 4097, M_BIG), filters, kinds=("weights",), seed=7)
@@ -175,9 +130,9 @@ def test_the_call_zeroes_a_dirty_buffer(torch_cuda):
     esize, chunk = 4, 256
     d1, h1 = model(esize, chunk, (4097, 513, 2049))
     d2, h2 = model(esize, chunk, (9, 255, 1), seed=5)
-    got, d_hist = device_hists(torch, Packed(torch, d1), esize, chunk, 7)
+    got, d_hist = device_hists(torch, esize, chunk, 7, src=Packed(torch, d1))
     assert_hists(got, h1, [4097, 513, 2049], 7, "first call")
-    got, _ = device_hists(torch, Packed(torch, d2), esize, chunk, 2, d_hist=d_hist)      # fewer elements, fewer filters, the same buffer
+    got, _ = device_hists(torch, esize, chunk, 2, src=Packed(torch, d2), d_hist=d_hist)      # fewer elements, fewer filters, the same buffer
     assert_hists(got, ABL.masked(h2, 2), [9, 255, 1], 2, "second call into the first one's counts")
 
 
@@ -187,7 +142,7 @@ def test_slices_are_the_unbatched_call_per_item(torch_cuda, esize):
     torch = torch_cuda
     chunk = 320
     datas, _ = model(esize, chunk, ORDERS[0])
-    got, _ = device_hists(torch, Packed(torch, datas, seed=3), esize, chunk, 7)
+    got, _ = device_hists(torch, esize, chunk, 7, src=Packed(torch, datas, seed=3))
     hb = trc.planes_hist_bytes(esize)
     for i, d in enumerate(datas):
         d_in = guarded(torch, d.size + trc.PAD, np.concatenate([d, np.zeros(trc.PAD, np.uint8)]))
@@ -271,7 +226,7 @@ def test_advise_batch_dev(torch_cuda, esize, chunk, monkeypatch):
     got, advice = trc.planes_advise_batch_dev(src.views(), esize, chunk)
     ABL.assert_advice(got, advice, want, AL.ALL, esize, ms, tag)
     # the three pieces by hand on the whole batch
-    h, _ = device_hists(torch, src, esize, chunk, AL.ALL)
+    h, _ = device_hists(torch, esize, chunk, AL.ALL, src=src)
     by_hand, by_hand_advice = trc.planes_advise_batch(h, AL.ALL, esize, src.items(), count)
     assert got == by_hand and same_advice(advice, by_hand_advice), tag + ": not what the pieces give"
     # five slabs of 5, 5, 5, 5 and 4 items; and through the item array
@@ -322,10 +277,7 @@ def test_planes_batch_coder_auto(torch_cuda, codec):
     assert_same_outputs(torch, auto, explicit, codec, esize, trc.CODEC_NAMES[codec] + " auto")
     assert auto.stored_bytes() == explicit.stored_bytes()
     assert np.array_equal(src.buf.cpu().numpy(), src.img), "encode changed its input"
-    dst = Packed(torch, datas, seed=9, data=False)
-    auto.decode(out=dst.views())
-    torch.cuda.synchronize()
-    assert np.array_equal(dst.buf.cpu().numpy(), src.img), "decode of all items"
+    decodes_whole_batch(torch, src, auto, trc.CODEC_NAMES[codec] + " auto")
     dst = Packed(torch, datas, seed=9, data=False)
     auto.decode(5, 1, out=dst.views(range(5, 6)))
     torch.cuda.synchronize()

@@ -2,41 +2,21 @@
 advise_lib: at the edges of a thread's vector, a restart segment, a workgroup and the grid; with every lane on one bin; across
 flushes of the 32-bit counters; into a dirty buffer.  trc_encode_aplanes_host must write byte for byte what the explicit call for
 its choice writes, and `trcfile a / d` must round-trip.  Every device buffer is followed by a 512-byte guard of 0xA5 that must
-survive."""
-import os
-import subprocess
-
+survive (the histogram call's have one on both sides); that call and its comparisons are in gpu_planes.py."""
 import numpy as np
 import pytest
 
 import advise_lib as AL
 import fplanes_lib as FL
 import trc
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import CHUNK, assert_hists, device_hists, guarded, trcfile
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 512
 MS = (1, 7, 8, 9, 63, 64, 65, 511, 512, 513, 4095, 4097, 65539)
 SEGS = (256, 320)
 M_BIG = 65539
-CHUNK = 256
 M_AUTO = 200 * CHUNK + 100
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-def guarded(torch, nbytes, data=None):
-    """a device buffer of nbytes (from `data`, else 0xA5 throughout) followed by the guard"""
-    a = np.full(nbytes + GUARD, 0xA5, dtype=np.uint8)
-    if data is not None:
-        a[:nbytes] = data
-    return torch.from_numpy(a).to("cuda:0")
 
 
 _model = {}
@@ -54,36 +34,10 @@ def model(kind, esize, m, t, seg, seed=None):
     return _model[key]
 
 
-def device_hist(torch, d, esize, seg, filters, d_hist=None):
-    """one call into a guarded histogram (given, or fresh and dirty) -> (uint64 [3, esize, 256], the buffer); checks the guards and the input"""
-    n, hb = d.size, trc.planes_hist_bytes(esize)
-    d_in = guarded(torch, n, d)
-    if d_hist is None:
-        d_hist = guarded(torch, hb)
-    trc.planes_hist(filters, d_in, n, esize, seg, d_hist)
-    torch.cuda.synchronize()
-    raw = d_hist.cpu().numpy()
-    assert (raw[hb:] == 0xA5).all(), "the call wrote behind the histograms"
-    back = d_in.cpu().numpy()
-    assert np.array_equal(back[:n], d) and (back[n:] == 0xA5).all(), "the call changed its input"
-    return raw[:hb].view("<u8").reshape(3, esize, 256).copy(), d_hist
-
-
-def assert_hist(got, exp, filters, m, tag):
-    for f in range(3):
-        if filters >> f & 1:
-            assert (got[f].sum(axis=1) == m).all(), tag + ": a row of filter %d does not sum to m" % f
-            if not np.array_equal(got[f], exp[f]):
-                k, b = np.argwhere(got[f] != exp[f])[0]
-                raise AssertionError("%s: filter %d plane %d bin %d: %d, the model has %d" % (tag, f, k, b, got[f, k, b], exp[f, k, b]))
-        else:
-            assert not got[f].any(), tag + ": rows of filter %d, which was not requested, are not zero" % f
-
-
 def hist_case(torch, kind, esize, m, t, seg, filters, seed=None):
     d, exp = model(kind, esize, m, t, seg, seed)
-    got, _ = device_hist(torch, d, esize, seg, filters)
-    assert_hist(got, exp, filters, m, "%s esize %d m %d t %d seg %d filters %d" % (kind, esize, m, t, seg, filters))
+    got, _ = device_hists(torch, esize, seg, filters, d=d)
+    assert_hists(got, exp, [m], filters, "%s esize %d m %d t %d seg %d filters %d" % (kind, esize, m, t, seg, filters))
 
 
 # ---- the kernel ----------------------------------------------------------------------------------------------------------
@@ -112,8 +66,8 @@ def test_every_lane_on_one_bin(torch_cuda, esize):
     d = np.tile(np.arange(0x81, 0x81 + esize, dtype=np.uint8), M_BIG)
     exp = AL.hist(d, esize, 256, AL.ALL)
     for filters in (1, 7):
-        got, _ = device_hist(torch, d, esize, 256, filters)
-        assert_hist(got, exp, filters, M_BIG, "equal elements, esize %d, filters %d" % (esize, filters))
+        got, _ = device_hists(torch, esize, 256, filters, d=d)
+        assert_hists(got, exp, [M_BIG], filters, "equal elements, esize %d, filters %d" % (esize, filters))
     assert exp[0, 0, 0x81] == M_BIG and exp[2, 0, 0] == M_BIG - 257           # (257 segments open with the element itself)
     for filters in (1, 7):
         hist_case(torch, "weights", esize, M_BIG, esize - 1, 256, filters, seed=7)
@@ -146,10 +100,10 @@ def test_the_call_zeroes_a_dirty_buffer(torch_cuda):
     esize = 4
     d1, h1 = model("random", esize, 4097, 0, 256)
     d2, h2 = model("wrap", esize, 513, 3, 256)
-    got, d_hist = device_hist(torch, d1, esize, 256, 7)
-    assert_hist(got, h1, 7, 4097, "first call")
-    got, _ = device_hist(torch, d2, esize, 256, 2, d_hist)          # fewer elements, fewer filters, the same buffer
-    assert_hist(got, h2, 2, 513, "second call into the first one's counts")
+    got, d_hist = device_hists(torch, esize, 256, 7, d=d1)
+    assert_hists(got, h1, [4097], 7, "first call")
+    got, _ = device_hists(torch, esize, 256, 2, d=d2, d_hist=d_hist)          # fewer elements, fewer filters, the same buffer
+    assert_hists(got, h2, [513], 2, "second call into the first one's counts")
 
 
 def test_argument_errors_write_nothing(torch_cuda):
@@ -209,15 +163,12 @@ def test_auto_container_automatic_chunk(torch_cuda):
 
 
 def test_trcfile_auto(torch_cuda, tmp_path):
-    exe = os.path.join(ROOT, "harness", "trcfile")
-    assert os.path.exists(exe), "harness/trcfile is not built"
     d = FL.gen("monotone", 4, 40000, 3, 9)
     src, comp, back, ref = (str(tmp_path / f) for f in ("in.bin", "in.trca", "out.bin", "in.trcf"))
     d.tofile(src)
-    r = subprocess.run([exe, "a", "46", "4", src, comp], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.rstrip().endswith("choice z"), (r.stdout, r.stderr)
-    r = subprocess.run([exe, "d", comp, back], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.stdout, r.stderr)
+    r = trcfile("a", "46", "4", src, comp)
+    assert r.stdout.rstrip().endswith("choice z"), (r.stdout, r.stderr)
+    trcfile("d", comp, back)
     assert np.array_equal(np.fromfile(back, dtype=np.uint8), d)
-    r = subprocess.run([exe, "f", "46", "4", "z", src, ref], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and np.array_equal(np.fromfile(comp, dtype=np.uint8), np.fromfile(ref, dtype=np.uint8))
+    trcfile("f", "46", "4", "z", src, ref)
+    assert np.array_equal(np.fromfile(comp, dtype=np.uint8), np.fromfile(ref, dtype=np.uint8))

@@ -11,15 +11,10 @@ import pytest
 
 import trc
 import trc_testlib as T
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU (and must not silently fall back)"
-    return torch
 
 MB = 10**6
 AUTO_MIN = 512          # TRC_CHUNK_AUTO_MIN (include/trc_hip.h): the smallest chunk the rule picks

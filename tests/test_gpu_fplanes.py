@@ -2,46 +2,23 @@
 the numpy model of fplanes_lib, so every comparison is byte equality: the two kernels alone against the model at the edges of a
 vector, a tile, a restart segment and the grid; the coded calls against the unfiltered calls on the model-filtered input; chunk
 ranges; argument errors; the TRCF container through host pointers and `trcfile f / d / x`; and what it is for: sorted ids store
-fewer bytes.  Every device buffer is followed by a 512-byte guard of 0xA5 that must survive."""
-import os
-import subprocess
-
+fewer bytes.  Every device buffer is followed by a 512-byte guard of 0xA5 that must survive (the kernels' buffers have one on both
+sides).  The device calls and comparisons shared with the other plane files are in gpu_planes.py."""
 import numpy as np
 import pytest
 
 import fplanes_lib as FL
 import planes_lib as PL
 import trc
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import (CHUNK, GUARD, coded_flat, decodes_flat, decodes_ranges_flat, guarded, host_container_filtered, padded, rejected_flat,
+                        split_join_flat, trcfile, trcfile_round_trip)
 from planes_matrix_lib import assert_same_container
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 512
 SEGS = (256, 320, 4096, 65536)
 CODECS = [trc.ANS4S, trc.RCA, trc.RCB, trc.RCSS]
-PRM = (4, 7)
-CHUNK = 256
 M6 = 5 * CHUNK + 3                                              # 6 chunks per plane, the last one of 3 elements
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-def guarded(torch, nbytes, data=None):
-    """a device buffer of nbytes (from `data`, else 0xA5 throughout) followed by the guard"""
-    a = np.full(nbytes + GUARD, 0xA5, dtype=np.uint8)
-    if data is not None:
-        a[:nbytes] = data
-    return torch.from_numpy(a).to("cuda:0")
-
-
-def up256(x):
-    return (x + 255) & ~255
 
 
 def sizes(seg):
@@ -52,30 +29,10 @@ def sizes(seg):
 
 # ---- the two kernels -----------------------------------------------------------------------------------------------------
 def split_join_case(torch, esize, filt, seg, m, t, kind):
-    n = m * esize + t
     d = FL.gen(kind, esize, m, t, 100 * m + 10 * esize + t)
     planes, tail = PL.split(FL.forward(d, esize, filt, seg), esize)
-    pitch = up256(m)                                            # the smallest pitch the call takes
-    d_in = guarded(torch, n, d)
-    d_planes = guarded(torch, esize * pitch)
-    d_tail = guarded(torch, 8)
-    trc.planes_split_filter(filt, d_in, n, esize, seg, d_planes, pitch, d_tail if t else None)
-    d_out = guarded(torch, n)
-    trc.planes_join_filter(filt, d_planes, pitch, d_tail if t else None, n, esize, seg, d_out)
-    torch.cuda.synchronize()
     tag = "esize %d, filter %s, seg %d, m %d, t %d, %s" % (esize, FL.FILTER_NAMES[filt], seg, m, t, kind)
-    exp = np.full(esize * pitch + GUARD, 0xA5, dtype=np.uint8)
-    for k in range(esize):
-        exp[k * pitch:k * pitch + m] = planes[k]
-    got = d_planes.cpu().numpy()
-    assert np.array_equal(got, exp), tag + ": planes or the bytes behind them (first difference at %d)" % int(np.flatnonzero(got != exp)[0])
-    exp_tail = np.full(8 + GUARD, 0xA5, dtype=np.uint8)
-    exp_tail[:t] = tail
-    assert np.array_equal(d_tail.cpu().numpy(), exp_tail), tag + ": tail or the bytes behind it"
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:n], d), tag + ": join(split(x)) != x (first difference at byte %d)" % int(np.flatnonzero(out[:n] != d)[0])
-    assert (out[n:] == 0xA5).all(), tag + ": join wrote behind its output"
-    assert np.array_equal(d_in.cpu().numpy()[:n], d) and (d_in.cpu().numpy()[n:] == 0xA5).all()
+    split_join_flat(torch, d, esize, m, t, planes, tail, tag, filt=filt, seg=seg)
 
 
 @pytest.mark.parametrize("seg", SEGS)
@@ -142,40 +99,11 @@ def test_split_join_argument_errors(torch_cuda):
 
 
 # ---- the coded calls ---------------------------------------------------------------------------------------------------
-_cache = {}
-
-
 def coded(torch, codec, esize, filt, chunk=CHUNK, m=M6):
     """-> (input bytes, FilteredPlanesCoder holding their container, PlanesCoder holding the container of the model-filtered input):
     computed once per key, shared, left unchanged"""
-    key = (codec, esize, filt, chunk, m)
-    if key not in _cache:
-        t = esize - 1
-        d = FL.gen("monotone" if esize > 2 else "walk", esize, m, t, 17 * esize + filt)
-        n = d.size
-        out = []
-        for cls, src, kw in ((trc.FilteredPlanesCoder, d, dict(filter=filt)), (trc.PlanesCoder, FL.forward(d, esize, filt, chunk), {})):
-            pc = cls(codec, n, esize, chunk, "cuda:0", cdfnum=256, prm=PRM, guard=GUARD, **kw)
-            d_in = guarded(torch, n + trc.PAD, np.concatenate([src, np.zeros(trc.PAD, np.uint8)]))
-            pc.payload[:esize * pc.pitch] = 0x5A
-            pc.encode(d_in, n)
-            assert pc.guards_ok(), "encode wrote behind one of its buffers"
-            got = d_in.cpu().numpy()
-            assert np.array_equal(got[:n], src) and (got[n + trc.PAD:] == 0xA5).all()
-            out.append(pc)
-        _cache[key] = (d, out[0], out[1])
-    return _cache[key]
-
-
-def assert_decodes(torch, fc, d, tag):
-    n = d.size
-    d_out = guarded(torch, n + trc.PAD)
-    fc.decode(d_out, n)
-    torch.cuda.synchronize()
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:n], d), tag + ": decode does not return the input"
-    assert (out[n:] == 0xA5).all(), tag + ": decode wrote behind its n bytes"
-    assert fc.guards_ok()
+    d = FL.gen("monotone" if esize > 2 else "walk", esize, m, esize - 1, 17 * esize + filt)
+    return (d,) + coded_flat(torch, codec, esize, chunk, d, trc.FilteredPlanesCoder, lambda: FL.forward(d, esize, filt, chunk), filter=filt)
 
 
 @pytest.mark.parametrize("filt", FL.FILTERS)
@@ -187,19 +115,8 @@ def test_encode_contract_and_every_range(torch_cuda, codec, filt):
     tag = "%s filter %s" % (trc.CODEC_NAMES[codec], FL.FILTER_NAMES[filt])
     assert fc.nch == 6
     assert_same_container(fc, pc, esize, codec, tag)
-    assert_decodes(torch, fc, d, tag)
-    n = d.size
-    for first in range(6):
-        for count in range(1, 6 - first + 1):
-            e0, e1 = first * CHUNK, min(M6, (first + count) * CHUNK)
-            size = (e1 - e0) * esize
-            d_out = guarded(torch, size + trc.PAD)
-            fc.decode_range(d_out, first, count, n)
-            torch.cuda.synchronize()
-            out = d_out.cpu().numpy()
-            assert np.array_equal(out[:size], d[e0 * esize:e1 * esize]), "%s: chunks (%d, %d)" % (tag, first, count)
-            assert (out[size:] == 0xA5).all(), "%s: chunks (%d, %d) wrote behind their elements" % (tag, first, count)
-    assert fc.guards_ok()
+    decodes_flat(torch, fc, d, tag)
+    decodes_ranges_flat(torch, fc, d, esize, CHUNK, [(first, count) for first in range(6) for count in range(1, 6 - first + 1)], tag)
 
 
 @pytest.mark.parametrize("filt", FL.FILTERS)
@@ -210,12 +127,8 @@ def test_encode_contract_other_widths(torch_cuda, esize, codec, filt):
     d, fc, pc = coded(torch, codec, esize, filt, chunk, m)
     tag = "%s esize %d filter %s" % (trc.CODEC_NAMES[codec], esize, FL.FILTER_NAMES[filt])
     assert_same_container(fc, pc, esize, codec, tag)
-    assert_decodes(torch, fc, d, tag)
-    d_out = guarded(torch, (m - chunk) * esize + trc.PAD)
-    fc.decode_range(d_out, 1, 2, d.size)
-    torch.cuda.synchronize()
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:(m - chunk) * esize], d[chunk * esize:m * esize]) and (out[(m - chunk) * esize:] == 0xA5).all()
+    decodes_flat(torch, fc, d, tag)
+    decodes_ranges_flat(torch, fc, d, esize, chunk, [(1, 2)], tag)
 
 
 @pytest.mark.parametrize("codec", (trc.ANS4S, trc.RCA))
@@ -227,18 +140,15 @@ def test_filter_none_is_the_unfiltered_call(torch_cuda, codec):
     fc = trc.FilteredPlanesCoder(codec, n, esize, CHUNK, "cuda:0", cdfnum=256, guard=GUARD)
     assert fc.filter == trc.FILTER_NONE
     pc = trc.PlanesCoder(codec, n, esize, CHUNK, "cuda:0", cdfnum=256, guard=GUARD)
-    d_in = guarded(torch, n + trc.PAD, np.concatenate([d, np.zeros(trc.PAD, np.uint8)]))
+    d_in = padded(torch, d)
     for c in (fc, pc):
         c.payload[:esize * c.pitch] = 0x5A
         c.encode(d_in, n)
     assert_same_container(fc, pc, esize, codec, trc.CODEC_NAMES[codec] + " filter none")
     for name in ("clen", "total", "tail", "cdf", "status"):
         assert torch.equal(getattr(fc, name), getattr(pc, name)), name
-    assert_decodes(torch, fc, d, "filter none")
-    d_out = guarded(torch, 2 * CHUNK * esize + trc.PAD)
-    fc.decode_range(d_out, 2, 2, n)
-    torch.cuda.synchronize()
-    assert np.array_equal(d_out.cpu().numpy()[:2 * CHUNK * esize], d[2 * CHUNK * esize:4 * CHUNK * esize])
+    decodes_flat(torch, fc, d, "filter none")
+    decodes_ranges_flat(torch, fc, d, esize, CHUNK, [(2, 2)], "filter none")
 
 
 @pytest.mark.parametrize("codec", (trc.ANS4S, trc.RCA))
@@ -248,25 +158,12 @@ def test_argument_errors_launch_nothing(torch_cuda, codec):
     d, fc, _ = coded(torch, codec, esize, FL.ZDELTA)
     n = d.size
     d_out = guarded(torch, n + trc.PAD)
-    d_in = guarded(torch, n + trc.PAD, np.concatenate([d, np.zeros(trc.PAD, np.uint8)]))
+    d_in = padded(torch, d)
     names = ("clen", "payload", "total", "tail", "cdf")
     before = [getattr(fc, x).clone() for x in names]
 
-    def rejected(nbytes=n, flags=0, **attrs):
-        """the three calls with some of the coder's attributes replaced: each is TRC_E_ARG"""
-        saved = {k: getattr(fc, k) for k in attrs}
-        for k, v in attrs.items():
-            setattr(fc, k, v)
-        try:
-            with pytest.raises(trc.TrcError, match="rc=-1"):
-                fc.encode(d_in, nbytes, flags=flags)
-            with pytest.raises(trc.TrcError, match="rc=-1"):
-                fc.decode(d_out, nbytes, flags=flags)
-            with pytest.raises(trc.TrcError, match="rc=-1"):
-                fc.decode_range(d_out, 0, 1, nbytes, flags=flags)
-        finally:
-            for k, v in saved.items():
-                setattr(fc, k, v)
+    def rejected(**kw):
+        rejected_flat(fc, d_in, d_out, n, **kw)
 
     for filt in (-1, 3):
         rejected(filter=filt)
@@ -293,31 +190,9 @@ def test_argument_errors_launch_nothing(torch_cuda, codec):
 @pytest.mark.parametrize("codec", (trc.RCA, trc.ANS4S))
 def test_host_container(torch_cuda, codec, filt, chunk):
     esize, m = 4, 9 * 256 + 3
-    t = esize - 1
-    d = FL.gen("monotone", esize, m, t, 23)
-    n = d.size
-    comp = trc.host_encode_fplanes(codec, filt, d, esize, chunk)
-    trc.fplanes_check(comp, n)
-    assert comp[:4].tobytes() == b"TRCF" and (comp[4], comp[5], comp[6], comp[7]) == (filt, 1, 0, 0)
-    assert int(comp[8:16].view("<u8")[0]) == comp.size
-    hdr, _, tail = trc.parse_planes(comp[16:])
-    resolved = hdr["chunk"]
-    assert resolved == (chunk or trc.lib().trc_auto_chunk_codec(codec, m)) and hdr["size"] == comp.size - 16 and hdr["n"] == n
-    exp = trc.host_encode_planes(codec, FL.forward(d, esize, filt, resolved), esize, chunk)
-    assert np.array_equal(comp[16:], exp), "bytes [16:] are not trc_encode_planes_host of the filtered input"
-    assert np.array_equal(tail, d[n - t:])
-    assert np.array_equal(trc.host_decode_fplanes(comp, n), d)
-    c = resolved * esize
-    ranges = [(0, 1), (c - 1, 3), (c // 2, 2 * c), (5, n - 5), (n - t - 1, t + 1), (n - t, t), (n - 1, 1), (0, n)]
-    for offset, length in ranges:
-        if offset + length > n:
-            continue
-        got = trc.host_decode_fplanes_range(comp, offset, length)
-        assert np.array_equal(got, d[offset:offset + length]), "bytes [%d, +%d)" % (offset, length)
-    with pytest.raises(trc.TrcError):
-        trc.host_decode_fplanes_range(comp, n - 1, 2)
-    with pytest.raises(trc.TrcError, match="container"):
-        trc.host_decode_fplanes(comp[:-1], n)
+    d = FL.gen("monotone", esize, m, esize - 1, 23)
+    host_container_filtered(codec, d, esize, m, chunk, b"TRCF", (filt, 1, 0, 0), lambda x, ch: trc.host_encode_fplanes(codec, filt, x, esize, ch),
+                            trc.fplanes_check, trc.host_decode_fplanes, trc.host_decode_fplanes_range, lambda seg: FL.forward(d, esize, filt, seg))
     with pytest.raises(trc.TrcError, match="filter 0"):
         trc.host_encode_fplanes(codec, trc.FILTER_NONE, d, esize, chunk)
 
@@ -337,18 +212,9 @@ def test_sorted_ids_store_fewer_bytes_with_zdelta(torch_cuda):
 
 
 def test_trcfile_fplanes(torch_cuda, tmp_path):
-    exe = os.path.join(ROOT, "harness", "trcfile")
-    assert os.path.exists(exe), "harness/trcfile is not built"
     d = FL.gen("monotone", 4, 40000, 3, 9)
-    src, comp, back, part = (str(tmp_path / f) for f in ("in.bin", "in.trcf", "out.bin", "part.bin"))
-    d.tofile(src)
     for letter, filt in (("z", 1), ("x", 2)):
-        for args in (["f", "46", "4", letter, src, comp], ["d", comp, back], ["x", comp, "70001", "3000", part]):
-            r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120)
-            assert r.returncode == 0, (args, r.stdout, r.stderr)
-        head = np.fromfile(comp, dtype=np.uint8)
+        head = trcfile_round_trip(tmp_path, d, "trcf", ["f", "46", "4", letter], 70001, 3000)
         assert head[:4].tobytes() == b"TRCF" and head[4] == filt and head[16:20].tobytes() == b"TRCP"
-        assert np.array_equal(np.fromfile(back, dtype=np.uint8), d)
-        assert np.array_equal(np.fromfile(part, dtype=np.uint8), d[70001:73001])
-    r = subprocess.run([exe, "f", "46", "4", "q", src, comp], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "filter" in r.stderr
+    r = trcfile("f", "46", "4", "q", tmp_path / "in.bin", tmp_path / "in.trcf", rc=2)
+    assert "filter" in r.stderr

@@ -28,6 +28,7 @@ import pytest
 import trc
 import trc_testlib as T
 from golden.make_golden import gen
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,13 +38,6 @@ KINDS = ("text", "const", "raw", "mixed")
 OFFSETS = (0, 2, 16, 48, 62)
 FRONT = 256                            # poisoned bytes in front of the payload's base
 REFS = {}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU (and must not silently fall back)"
-    return torch
 
 
 def size_of(shape, chunk):

@@ -19,19 +19,13 @@ import pytest
 import trc
 import trc_testlib as T
 from golden.make_golden import gen
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 with open(os.path.join(GOLD, "bench_configs.json")) as _f:
     BENCH_GOLD = {e["name"]: e for e in json.load(_f)}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU (and must not silently fall back)"
-    return torch
 
 
 # (golden entry, bound on container / input in percent -- VERDICT r5 "next" 1: rccdfenc on drift100m <= 28.5 % where one

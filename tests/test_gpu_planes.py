@@ -2,74 +2,30 @@
 loop; the contract of the planar calls (plane k's directory, payload and total are what trc_encode_dev gives for plane k); chunk
 ranges; the TRCP container through host pointers and `trcfile p / d / x`; and what it is for: bf16 weights store fewer bytes as
 planes than flat.  Every comparison is byte equality against planes_lib (numpy) or against the existing per-plane calls, and
-every device buffer is followed by a 512-byte guard of 0xA5 that must survive."""
-import os
-import subprocess
-
+every device buffer is followed by a 512-byte guard of 0xA5 that must survive (the kernels' buffers have one on both sides).  The
+device calls and comparisons shared with the other plane files are in gpu_planes.py."""
 import numpy as np
 import pytest
 
 import planes_lib as PL
 import trc
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import CHUNK, GUARD, PRM, coded_flat, decodes_flat, decodes_ranges_flat, guarded, split_join_flat, trcfile_round_trip
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 512
-CHUNK = 256
 M = 200 * CHUNK + 100                                           # 201 chunks per plane, the last one of 100 bytes
 SIZES = [1, 7, 8, 9, 63, 64, 65, 511, 512, 513, 4095, 4097, 65539]     # elements: around a thread's vector (8), a wave (512), a workgroup (2048) ...
 LOOP_M, LOOP_GRID = 65539, 3                                    # ... and 8192 vectors on a grid capped at 3 workgroups: 11 turns of the loop
 CODECS = [trc.ANS4S, trc.RCA, trc.RCB, trc.RCSS]
-PRM = (4, 7)
 RANGES = [(0, 1), (63, 2), (65, 64), (137, 64), (200, 1), (0, 201)]
 NCH = 201
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-def guarded(torch, nbytes, data=None):
-    """a device buffer of nbytes (from `data`, else 0xA5 throughout) followed by the guard"""
-    a = np.full(nbytes + GUARD, 0xA5, dtype=np.uint8)
-    if data is not None:
-        a[:nbytes] = data
-    return torch.from_numpy(a).to("cuda:0")
-
-
-def up256(x):
-    return (x + 255) & ~255
-
-
 # ---- the two kernels -----------------------------------------------------------------------------------------------------
 def split_join_case(torch, esize, m, t):
-    n = m * esize + t
-    d = np.random.default_rng(100 * m + 10 * esize + t).integers(0, 256, n, dtype=np.uint8)
+    d = np.random.default_rng(100 * m + 10 * esize + t).integers(0, 256, m * esize + t, dtype=np.uint8)
     planes, tail = PL.split(d, esize)
-    pitch = up256(m)                                            # the smallest pitch the call takes: at m = 512 plane k + 1 starts where plane k ends
-    d_in = guarded(torch, n, d)
-    d_planes = guarded(torch, esize * pitch)
-    d_tail = guarded(torch, 8)
-    trc.planes_split(d_in, n, esize, d_planes, pitch, d_tail if t else None)
-    d_out = guarded(torch, n)
-    trc.planes_join(d_planes, pitch, d_tail if t else None, n, esize, d_out)
-    torch.cuda.synchronize()
-    tag = "esize %d, m %d, t %d" % (esize, m, t)
-    exp = np.full(esize * pitch + GUARD, 0xA5, dtype=np.uint8)
-    for k in range(esize):
-        exp[k * pitch:k * pitch + m] = planes[k]
-    assert np.array_equal(d_planes.cpu().numpy(), exp), tag + ": planes or the bytes behind them"
-    exp_tail = np.full(8 + GUARD, 0xA5, dtype=np.uint8)
-    exp_tail[:t] = tail
-    assert np.array_equal(d_tail.cpu().numpy(), exp_tail), tag + ": tail or the bytes behind it"
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:n], d), tag + ": join(split(x)) != x"
-    assert (out[n:] == 0xA5).all(), tag + ": join wrote behind its output"
-    assert np.array_equal(d_in.cpu().numpy()[:n], d) and (d_in.cpu().numpy()[n:] == 0xA5).all()
+    split_join_flat(torch, d, esize, m, t, planes, tail, "esize %d, m %d, t %d" % (esize, m, t))
 
 
 @pytest.mark.parametrize("esize", PL.ESIZES)
@@ -101,24 +57,10 @@ def test_split_join_argument_errors(torch_cuda):
 
 
 # ---- the coded calls ---------------------------------------------------------------------------------------------------
-_cache = {}
-
-
 def coded(torch, codec, esize):
     """-> (input bytes, PlanesCoder holding their planar container): computed once per (codec, esize), shared, left unchanged"""
-    key = (codec, esize)
-    if key not in _cache:
-        t = esize - 1
-        d = PL.mixed_weights(M, esize, CHUNK, t)
-        n = d.size
-        pc = trc.PlanesCoder(codec, n, esize, CHUNK, "cuda:0", cdfnum=256, prm=PRM, guard=GUARD)
-        d_in = guarded(torch, n + trc.PAD, np.concatenate([d, np.zeros(trc.PAD, np.uint8)]))
-        pc.payload[:esize * pc.pitch] = 0x5A
-        pc.encode(d_in, n)
-        assert pc.guards_ok(), "encode wrote behind one of its buffers"
-        assert (d_in.cpu().numpy()[n + trc.PAD:] == 0xA5).all()
-        _cache[key] = (d, pc)
-    return _cache[key]
+    d = PL.mixed_weights(M, esize, CHUNK, esize - 1)
+    return d, coded_flat(torch, codec, esize, CHUNK, d)[0]
 
 
 @pytest.mark.parametrize("esize", (2, 4))
@@ -126,7 +68,6 @@ def coded(torch, codec, esize):
 def test_encode_contract(torch_cuda, codec, esize):
     torch = torch_cuda
     d, pc = coded(torch, codec, esize)
-    n = d.size
     planes, tail = PL.split(d, esize)
     assert np.array_equal(pc.tail[:esize - 1].cpu().numpy(), tail)
     raw = coded_chunks = 0
@@ -149,13 +90,7 @@ def test_encode_contract(torch_cuda, codec, esize):
         lens = np.minimum(CHUNK, M - np.arange(0, M, CHUNK))
         raw += int((clen == lens).sum()); coded_chunks += int((clen < lens).sum())
     assert raw and coded_chunks, "the input is meant to mix raw and coded chunks"
-    d_out = guarded(torch, n + trc.PAD)
-    pc.decode(d_out, n)
-    torch.cuda.synchronize()
-    out = d_out.cpu().numpy()
-    assert np.array_equal(out[:n], d), "decode_planes does not return the input"
-    assert (out[n:] == 0xA5).all(), "decode_planes wrote behind its n bytes"
-    assert pc.guards_ok()
+    decodes_flat(torch, pc, d, "%s esize %d" % (trc.CODEC_NAMES[codec], esize))
 
 
 @pytest.mark.parametrize("esize", (2, 4))
@@ -163,18 +98,8 @@ def test_encode_contract(torch_cuda, codec, esize):
 def test_decode_range(torch_cuda, codec, esize):
     torch = torch_cuda
     d, pc = coded(torch, codec, esize)
-    n = d.size
     assert pc.nch == NCH
-    for first, count in RANGES:
-        e0, e1 = first * CHUNK, min(M, (first + count) * CHUNK)
-        size = (e1 - e0) * esize
-        d_out = guarded(torch, size + trc.PAD)
-        pc.decode_range(d_out, first, count, n)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        assert np.array_equal(out[:size], d[e0 * esize:e1 * esize]), "%s esize %d range (%d, %d)" % (trc.CODEC_NAMES[codec], esize, first, count)
-        assert (out[size:] == 0xA5).all(), "range (%d, %d) wrote behind its elements" % (first, count)
-    assert pc.guards_ok()
+    decodes_ranges_flat(torch, pc, d, esize, CHUNK, RANGES, "%s esize %d" % (trc.CODEC_NAMES[codec], esize))
 
 
 @pytest.mark.parametrize("codec", (trc.ANS4S, trc.RCA))
@@ -244,17 +169,9 @@ def test_host_automatic_chunk(torch_cuda):
 
 
 def test_trcfile_planes(torch_cuda, tmp_path):
-    exe = os.path.join(ROOT, "harness", "trcfile")
-    assert os.path.exists(exe), "harness/trcfile is not built"
     d, _ = coded(torch_cuda, trc.RCA, 2)
-    src, comp, back, part = (str(tmp_path / f) for f in ("in.bin", "in.trcp", "out.bin", "part.bin"))
-    d.tofile(src)
-    for args in (["p", "46", "2", src, comp], ["d", comp, back], ["x", comp, str(2 * CHUNK - 1), "1000", part]):
-        r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (args, r.stdout, r.stderr)
-    assert np.fromfile(comp, dtype=np.uint8)[:4].tobytes() == b"TRCP"
-    assert np.array_equal(np.fromfile(back, dtype=np.uint8), d)
-    assert np.array_equal(np.fromfile(part, dtype=np.uint8), d[2 * CHUNK - 1:2 * CHUNK + 999])
+    comp = trcfile_round_trip(tmp_path, d, "trcp", ["p", "46", "2"], 2 * CHUNK - 1, 1000)
+    assert comp[:4].tobytes() == b"TRCP"
 
 
 # ---- what it is for --------------------------------------------------------------------------------------------------------

@@ -2,64 +2,23 @@
 item and the grid-stride loop; the contract of the coded calls (a batch's outputs are those of trc_encode_planes_dev on the
 virtual buffer, byte for byte); decode of item ranges; and the errors.  The items of a batch lie in ONE allocation with 16 to 48
 bytes of 0xA5 between them and no slack of their own (planes_batch_lib), every other device buffer is followed by a 512-byte guard
-of 0xA5, and every comparison is byte equality against numpy or against the unbatched calls."""
+of 0xA5, and every comparison is byte equality against numpy or against the unbatched calls.  The device calls and comparisons shared
+with the other plane files are in gpu_planes.py."""
 import numpy as np
 import pytest
 
 import planes_batch_lib as BL
 import planes_lib as PL
 import trc
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import (CHUNK, GUARD, PRM, Packed, assert_same_outputs, coded_batch, decode_items_batch, decodes_whole_batch, encode_contract_batch,
+                        guarded, planes_reference, split_join_batch, workspace_one_byte_short)
 
 pytestmark = pytest.mark.gpu
-GUARD = BL.GUARD
 SIZES = [1, 7, 8, 9, 63, 64, 65, 255, 256, 257, 319, 320, 321, 511, 512, 513, 2047, 2049, 4097, 65539]      # m[i], in elements
 CHUNKS = (256, 320, 4096)                                       # 320: 40 vectors per chunk, not a power of two
 CODECS = [trc.ANS4S, trc.RCA, trc.RCB, trc.RCSS]
-PRM = (4, 7)
-CHUNK = 256
 LOOP_GRID = 3
-
-
-def ranges(count):
-    return [(0, 1), (3, 1), (count - 1, 1), (2, 5), (0, count)]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-def guarded(torch, nbytes, data=None):
-    """a device buffer of nbytes (from `data`, else 0xA5 throughout) followed by the guard"""
-    a = np.full(nbytes + GUARD, 0xA5, dtype=np.uint8)
-    if data is not None:
-        a[:nbytes] = data
-    return torch.from_numpy(a).to("cuda:0")
-
-
-class Packed:
-    """the items of a batch in one device allocation (BL.offsets / BL.image), or -- data = False -- their places filled with 0xA5"""
-
-    def __init__(self, torch, datas, seed=0, data=True):
-        self.datas = datas
-        self.sizes = [d.size for d in datas]
-        self.offs, self.total = BL.offsets(self.sizes, seed)
-        self.img = BL.image(datas if data else [None] * len(datas), self.offs, self.total)
-        self.buf = torch.from_numpy(self.img).to("cuda:0")
-        assert self.buf.data_ptr() % 16 == 0
-
-    def views(self, only=None):
-        return BL.views(self.buf, self.offs, self.sizes, only)
-
-    def items(self, only=None):
-        return trc.planes_items([(v.data_ptr() if v is not None else None, n) for v, n in zip(self.views(only), self.sizes)])
-
-    def expect(self, only=None):
-        """the allocation with the items of `only` (default: all) in place and 0xA5 everywhere else"""
-        return BL.image([d if only is None or i in only else None for i, d in enumerate(self.datas)], self.offs, self.total)
 
 
 def batch_data(esize, order, seed):
@@ -68,35 +27,9 @@ def batch_data(esize, order, seed):
 
 
 # ---- the two kernels -----------------------------------------------------------------------------------------------------
-def split_join_case(torch, esize, chunk, order):
+def split_join_case(torch, esize, chunk, order, partial=False):
     datas = batch_data(esize, order, 1000 * esize + chunk)
-    src = Packed(torch, datas, seed=chunk)
-    count = len(datas)
-    pl, first = BL.plan(src.sizes, esize, chunk)
-    got, got_first = trc.planes_batch_plan(src.items(), count, esize, chunk)
-    assert got == pl and got_first == first
-    M = pl["m_total"]
-    pitch = BL.up256(M)                                         # the smallest pitch the call takes
-    planes, _ = PL.split(BL.virtual(datas, esize, chunk), esize)
-    tb = trc.lib().trc_planes_batch_table_bytes(count, pl["chunks"])
-    d_planes, d_table = guarded(torch, esize * pitch), guarded(torch, tb)
-    trc.planes_split_batch(src.items(), count, esize, chunk, d_planes, pitch, d_table, tb)
-    torch.cuda.synchronize()
-    tag = "esize %d, chunk %d" % (esize, chunk)
-    exp = np.full(esize * pitch + GUARD, 0xA5, dtype=np.uint8)
-    for k in range(esize):
-        exp[k * pitch:k * pitch + M] = planes[k]
-    assert np.array_equal(d_planes.cpu().numpy(), exp), tag + ": planes, their pad zeros or the bytes behind them"
-    assert np.array_equal(src.buf.cpu().numpy(), src.img), tag + ": split changed its input"
-    assert (d_table.cpu().numpy()[tb:] == 0xA5).all(), tag + ": split wrote behind its table"
-    # join, whole: every item back, every gap and the guard untouched
-    dst = Packed(torch, datas, seed=chunk, data=False)
-    d_table2 = guarded(torch, tb)
-    trc.planes_join_batch(d_planes, 0, pitch, dst.items(), count, 0, count, esize, chunk, d_table2, tb)
-    torch.cuda.synchronize()
-    assert np.array_equal(dst.buf.cpu().numpy(), src.img), tag + ": join(split(x)) != x, or a gap or the guard was written"
-    assert np.array_equal(d_planes.cpu().numpy(), exp) and (d_table2.cpu().numpy()[tb:] == 0xA5).all()
-    return src, d_planes, pitch, first
+    split_join_batch(torch, datas, esize, chunk, BL.virtual(datas, esize, chunk), "esize %d, chunk %d" % (esize, chunk), partial=partial)
 
 
 @pytest.mark.parametrize("esize", PL.ESIZES)
@@ -116,22 +49,8 @@ def test_split_join_grid_stride_loop(torch_cuda, esize, monkeypatch):
 
 @pytest.mark.parametrize("esize", PL.ESIZES)
 def test_partial_join(torch_cuda, esize):
-    torch = torch_cuda
     for chunk in (256, 320):
-        src, d_planes, pitch, first = split_join_case(torch, esize, chunk, SIZES)
-        count = len(SIZES)
-        for fi, ic in ranges(count):
-            only = range(fi, fi + ic)
-            dst = Packed(torch, src.datas, seed=chunk, data=False)
-            chunks = first[fi + ic] - first[fi]
-            tb = trc.lib().trc_planes_batch_table_bytes(ic, chunks)
-            d_table = guarded(torch, tb)
-            items = dst.items(only)                             # NULL outside the range
-            assert all((items[i].d_ptr is None) == (i not in only) for i in range(count))
-            trc.planes_join_batch(d_planes, first[fi] * chunk, pitch, items, count, fi, ic, esize, chunk, d_table, tb)
-            torch.cuda.synchronize()
-            assert np.array_equal(dst.buf.cpu().numpy(), dst.expect(only)), "esize %d chunk %d items (%d, %d)" % (esize, chunk, fi, ic)
-            assert (d_table.cpu().numpy()[tb:] == 0xA5).all()
+        split_join_case(torch_cuda, esize, chunk, SIZES, partial=True)
 
 
 # ---- the coded calls ---------------------------------------------------------------------------------------------------
@@ -142,45 +61,9 @@ def weights_items(esize, sizes=W_SIZES):
     return [PL.weights(m, esize, seed=11 + i) for i, m in enumerate(sizes)]
 
 
-_cache = {}
-
-
 def coded(torch, codec, esize):
     """-> (Packed source, PlanesBatchCoder holding its coded batch): computed once per (codec, esize), shared, left unchanged"""
-    key = (codec, esize)
-    if key not in _cache:
-        src = Packed(torch, weights_items(esize), seed=esize)
-        bc = trc.PlanesBatchCoder(codec, src.views(), CHUNK, cdfnum=256, prm=PRM, guard=GUARD, esize=esize)
-        bc.payload[:esize * bc.pitch] = 0x5A
-        bc.encode()
-        assert bc.guards_ok(), "encode wrote behind one of its buffers"
-        assert np.array_equal(src.buf.cpu().numpy(), src.img), "encode changed its input"
-        _cache[key] = (src, bc)
-    return _cache[key]
-
-
-def assert_same_outputs(torch, bc, pc, codec, esize, tag):
-    """every output of the batch call against the planes call's: directory, totals, payloads, CDFs, statuses"""
-    assert (bc.nch, bc.pitch) == (pc.nch, pc.pitch), tag
-    assert torch.equal(bc.clen[:4 * esize * bc.nch], pc.clen[:4 * esize * pc.nch]), tag + ": d_clen"
-    assert torch.equal(bc.total[:8 * esize], pc.total[:8 * esize]), tag + ": d_total"
-    for k in range(esize):
-        clen, payload, total = bc.result(k)
-        exp_clen, exp_payload, exp_total = pc.result(k)
-        assert total == exp_total and np.array_equal(clen, exp_clen) and np.array_equal(payload, exp_payload), tag + ": plane %d" % k
-    if codec in trc.STATIC:
-        assert torch.equal(bc.cdf[:2 * esize * trc.PLANES_CDF_STRIDE], pc.cdf[:2 * esize * trc.PLANES_CDF_STRIDE]), tag + ": d_cdf"
-        assert torch.equal(bc.status[:4 * esize], pc.status[:4 * esize]), tag + ": d_status"
-        assert all(bc.cdf_of(k)[1] == bc.plan["m_total"] for k in range(esize))
-
-
-def planes_reference(torch, codec, esize, data):
-    """trc_encode_planes_dev on `data` uploaded as one buffer"""
-    pc = trc.PlanesCoder(codec, data.size, esize, CHUNK, "cuda:0", cdfnum=256, prm=PRM, guard=GUARD)
-    d_in = guarded(torch, data.size + trc.PAD, np.concatenate([data, np.zeros(trc.PAD, np.uint8)]))
-    pc.encode(d_in, data.size)
-    assert pc.guards_ok()
-    return pc
+    return coded_batch(torch, codec, esize, weights_items(esize))
 
 
 @pytest.mark.parametrize("esize", PL.ESIZES)
@@ -188,14 +71,7 @@ def planes_reference(torch, codec, esize, data):
 def test_encode_contract(torch_cuda, codec, esize):
     torch = torch_cuda
     src, bc = coded(torch, codec, esize)
-    v = BL.virtual(src.datas, esize, CHUNK)
-    assert v.size == bc.plan["n_virtual"] and bc.plan["pad_elems"] > 0
-    pc = planes_reference(torch, codec, esize, v)
-    tag = "%s esize %d" % (trc.CODEC_NAMES[codec], esize)
-    assert_same_outputs(torch, bc, pc, codec, esize, tag)
-    for k in range(esize):
-        total = bc.result(k)[2]
-        assert (bc.payload[k * bc.pitch + total:k * bc.pitch + total + 64].cpu().numpy() == 0x5A).all(), tag + ": bytes behind payload %d" % k
+    encode_contract_batch(torch, src, bc, codec, esize, BL.virtual(src.datas, esize, CHUNK), "%s esize %d" % (trc.CODEC_NAMES[codec], esize))
 
 
 @pytest.mark.parametrize("codec", CODECS)
@@ -209,10 +85,7 @@ def test_one_item_is_the_plain_call(torch_cuda, codec):
     bc.encode()
     assert bc.guards_ok()
     assert_same_outputs(torch, bc, planes_reference(torch, codec, esize, d), codec, esize, trc.CODEC_NAMES[codec] + " one item")
-    dst = Packed(torch, [d], data=False)
-    bc.decode(0, 1, out=dst.views())
-    torch.cuda.synchronize()
-    assert np.array_equal(dst.buf.cpu().numpy(), src.img) and bc.guards_ok()
+    decodes_whole_batch(torch, src, bc, trc.CODEC_NAMES[codec] + " one item")
 
 
 @pytest.mark.parametrize("esize", PL.ESIZES)
@@ -220,21 +93,7 @@ def test_one_item_is_the_plain_call(torch_cuda, codec):
 def test_decode_items(torch_cuda, codec, esize):
     torch = torch_cuda
     src, bc = coded(torch, codec, esize)
-    count = bc.count
-    L = trc.lib()
-    for fi, ic in ranges(count):
-        only = range(fi, fi + ic)
-        dst = Packed(torch, src.datas, seed=esize, data=False)
-        out = dst.views(only)
-        need = L.trc_planes_batch_range_work_bytes(codec, dst.items(only), count, esize, CHUNK, fi, ic)
-        bc.range_work, bc.range_work_bytes = None, 0            # a workspace of exactly that size, guarded, for every range
-        bc.decode(fi, ic, out=out)
-        assert bc.range_work_bytes == need > 0
-        torch.cuda.synchronize()
-        tag = "%s esize %d items (%d, %d)" % (trc.CODEC_NAMES[codec], esize, fi, ic)
-        assert np.array_equal(dst.buf.cpu().numpy(), dst.expect(only)), tag
-        assert bc.guards_ok(), tag
-    assert np.array_equal(src.buf.cpu().numpy(), src.img)
+    decode_items_batch(torch, src, bc, codec, esize, "%s esize %d" % (trc.CODEC_NAMES[codec], esize))
 
 
 def test_single_item_of_many_in_a_small_workspace(torch_cuda):
@@ -276,19 +135,15 @@ def test_mixed_raw_and_coded_chunks(torch_cuda, codec):
     for k in range(esize):
         clen = bc.result(k)[0]
         assert int((clen == lens).sum()) and int((clen < lens).sum()), "plane %d is meant to mix raw and coded chunks" % k
-    dst = Packed(torch, datas, seed=4, data=False)
-    bc.decode(out=dst.views())
-    torch.cuda.synchronize()
-    assert np.array_equal(dst.buf.cpu().numpy(), src.img) and bc.guards_ok()
+    decodes_whole_batch(torch, src, bc, "mixed")
 
 
 # ---- errors ------------------------------------------------------------------------------------------------------------
-def raw_encode(bc, codec, items, count, work_bytes=None):
+def raw_encode(bc, codec, items, count):
     st = (codec & 0xff) in trc.STATIC
     return trc.lib().trc_encode_planes_batch_dev(codec, items, count, bc.esize, bc.chunk, bc.cdf.data_ptr() if st else None, bc.cdfnum,
                                                  bc.status.data_ptr() if st else None, bc.clen.data_ptr(), bc.payload.data_ptr(),
-                                                 bc.total.data_ptr(), bc.work.data_ptr(), bc.work_bytes if work_bytes is None else work_bytes,
-                                                 bc._stream())
+                                                 bc.total.data_ptr(), bc.work.data_ptr(), bc.work_bytes, bc._stream())
 
 
 def raw_decode(bc, codec, items, count, fi, ic, d_work, work_bytes):
@@ -303,7 +158,7 @@ def test_argument_errors_launch_nothing(torch_cuda, codec):
     esize = 2
     src, bc = coded(torch, codec, esize)
     count, L = bc.count, trc.lib()
-    E_ARG, E_WORK = -1, -3
+    E_ARG = -1
     outputs = (bc.clen, bc.payload, bc.total, bc.cdf, bc.status, bc.work)
     before = [x.clone() for x in outputs]
     dst = Packed(torch, src.datas, seed=esize, data=False)
@@ -323,10 +178,7 @@ def test_argument_errors_launch_nothing(torch_cuda, codec):
         assert raw_decode(bc, codec, items, cnt, 0, cnt, d_work, need) == E_ARG and text in L.trc_last_error().decode(), text
     assert L.trc_planes_batch_range_work_bytes(codec, items_with(2, ptr=base2 + 8), count, esize, CHUNK, 0, count) == 0
     # a misaligned or NULL pointer outside the requested range is not looked at: checked with a decode that runs, below
-    assert raw_encode(bc, codec, dst.items(), count, bc.work_bytes - 1) == E_WORK
-    assert raw_decode(bc, codec, dst.items(), count, 0, count, d_work, need - 1) == E_WORK
-    one = L.trc_planes_batch_range_work_bytes(codec, dst.items(), count, esize, CHUNK, 3, 1)
-    assert raw_decode(bc, codec, dst.items(), count, 3, 1, d_work, one - 1) == E_WORK
+    workspace_one_byte_short(torch, src, bc, trc.CODEC_NAMES[codec])
     for low4 in (trc.RCA4, trc.RC4):
         assert raw_encode(bc, low4, dst.items(), count) == E_ARG and "low four bits" in L.trc_last_error().decode()
         assert raw_decode(bc, low4, dst.items(), count, 0, count, d_work, need) == E_ARG and "low four bits" in L.trc_last_error().decode()

@@ -2,9 +2,6 @@
 followed by the parent's trc_encode_planes_host on the materialised virtual buffer, the size, the guards), the decode of a packed
 container where it lies, the host-pointer calls with host and device items, and `trcfile b / B / l`.  As in the other batch tests
 the items lie in ONE allocation with 16 to 48 bytes of 0xA5 between them, and every comparison is byte equality."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -12,27 +9,15 @@ import fplanes_lib as FL
 import planes_batch_lib as BL
 import planes_container_lib as CL
 import trc
-from test_gpu_planes_batch import Packed, guarded
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import CHUNK, E_ARG, E_WORK, GUARD, PRM, Packed, guarded, item_ranges, trcfile
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = BL.GUARD
-CHUNK = 256
-PRM = (4, 7)
-E_ARG, E_WORK = -1, -3
 CODECS = (trc.RCA, trc.ANS4S, trc.RCSS)
 ESIZES = (2, 4, 8)
 LENGTHS = [1, 255, 256, 257, 8 * 37 + 3, 2 * 256]              # elements per item: 9 chunks of 256, an odd NC
 ORDERS = {"odd": LENGTHS, "even": LENGTHS + [256], "one": [8 * 37 + 3], "nc1": [255]}
 FILTERS = ("none", "mixed", "zigzag")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 def gen_items(esize, order, seed, turn=0):
@@ -162,10 +147,6 @@ def test_pack_grid_stride_loop_and_argument_errors(torch_cuda, monkeypatch):
 
 
 # ---- decode_packed_dev -----------------------------------------------------------------------------------------------------------
-def item_ranges(count):
-    return [(i, 1) for i in range(count)] + [(i, 2) for i in range(count - 1)] + [(0, count)]
-
-
 @pytest.mark.parametrize("esize", ESIZES)
 @pytest.mark.parametrize("codec", CODECS)
 def test_decode_packed(torch_cuda, codec, esize):
@@ -175,7 +156,7 @@ def test_decode_packed(torch_cuda, codec, esize):
         bc, src = p["bc"], p["src"]
         total = trc.parse_planes_batch(p["cont"])["total"]
         d_cont = bc.packed                                      # the container with what is left of the bound behind it
-        for fi, ic in item_ranges(bc.count):
+        for fi, ic in item_ranges(bc.count, [(i, 2) for i in range(bc.count - 1)]):
             only = range(fi, fi + ic)
             dst = Packed(torch, src.datas, seed=esize, data=False)
             bc.range_work, bc.range_work_bytes = None, 0        # a workspace of exactly the required size, guarded, for every range
@@ -280,16 +261,13 @@ def test_host_calls_at_chunk_4096_with_64_columns(torch_cuda, monkeypatch):
 # ---- the harness ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("letter", ("z", "a"))
 def test_trcfile_batch(torch_cuda, tmp_path, letter):
-    exe = os.path.join(ROOT, "harness", "trcfile")
-    assert os.path.exists(exe), "harness/trcfile is not built"
     datas = gen_items(4, [1000, 299, 5000], 5)
     paths = []
     for i, d in enumerate(datas):
         paths.append(str(tmp_path / ("item%d.bin" % i)))
         d.tofile(paths[-1])
     comp = str(tmp_path / "batch.trcb")
-    r = subprocess.run([exe, "b", "46", "4", "256", letter, comp] + paths, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = trcfile("b", "46", "4", "256", letter, comp, *paths)
     cont = np.fromfile(comp, dtype=np.uint8)
     info = trc.parse_planes_batch(cont)
     assert info["n"] == [d.size for d in datas] and info["codec"] == trc.RCA and info["chunk"] == 256
@@ -298,11 +276,10 @@ def test_trcfile_batch(torch_cuda, tmp_path, letter):
     else:
         assert [l.split("choice ")[1][0] for l in r.stdout.splitlines() if l.startswith("item ")] == ["nzx"[f] for f in info["filters"]]
         assert info["filters"][2] == FL.ZDELTA, "sorted ids are meant to take the zigzag delta"
-    l = subprocess.run([exe, "l", comp], capture_output=True, text=True)
-    assert l.returncode == 0 and l.stdout.startswith("3 items, esize 4, chunk 256")
+    l = trcfile("l", comp)
+    assert l.stdout.startswith("3 items, esize 4, chunk 256")
     assert [x.split(":")[0] for x in l.stdout.splitlines()[1:]] == ["item 0", "item 1", "item 2"]
     for first, cnt in ((0, 3), (1, 2), (2, 1)):
         out = str(tmp_path / "out.bin")
-        x = subprocess.run([exe, "B", comp, str(first), str(cnt), out], capture_output=True, text=True)
-        assert x.returncode == 0, x.stdout + x.stderr
+        trcfile("B", comp, first, cnt, out)
         assert np.array_equal(np.fromfile(out, dtype=np.uint8), np.concatenate(datas[first:first + cnt]))

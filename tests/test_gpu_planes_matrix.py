@@ -20,10 +20,9 @@ import planes_lib as PL
 import planes_matrix_lib as ML
 import trc
 from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import GUARD, PRM, encode_guarded, guarded
 
 pytestmark = pytest.mark.gpu
-GUARD = 512
-PRM = (4, 7)
 NCH, LAST = 67, 100
 RANGES = [(0, 1), (63, 2), (1, 64), (66, 1), (0, 67)]
 MIN_EACH = 10                                                   # raw and coded chunks in every plane's directory, at least
@@ -52,20 +51,6 @@ def esizes(codec):
 
 
 assert CODECS.index(trc.RCC2W32) % 2 == 0 and len(CODECS) == 21 and len(CODECS) + len(MORE) + len(ML.LOW4) == len(ML.ASSIGNED)
-
-
-def guarded(torch, nbytes, data=None, fill=0xA5):
-    """a device buffer of nbytes (from `data`, else `fill` throughout) followed by GUARD bytes of 0xA5"""
-    a = np.full(nbytes + GUARD, 0xA5, dtype=np.uint8)
-    a[:nbytes] = fill if data is None else data
-    t = torch.from_numpy(a).to("cuda:0")
-    assert t.data_ptr() % 256 == 0
-    return t
-
-
-def padded(torch, d):
-    """the input on the device with TRC_PAD zero bytes and the guard behind it"""
-    return guarded(torch, d.size + trc.PAD, np.concatenate([d, np.zeros(trc.PAD, np.uint8)]))
 
 
 class Data:
@@ -169,12 +154,7 @@ def assert_ranges(torch, pc, data, ranges, tag):
 
 
 def encode_into(torch, pc, data, tag):
-    d_in = padded(torch, data.d)
-    pc.payload[:pc.esize * pc.pitch] = 0x5A
-    pc.encode(d_in, data.n)
-    assert pc.guards_ok(), tag + ": encode wrote behind one of its buffers"
-    got = d_in.cpu().numpy()
-    assert np.array_equal(got[:data.n], data.d) and (got[data.n + trc.PAD:] == 0xA5).all(), tag + ": the input or its guard changed"
+    encode_guarded(torch, pc, data.d, data.n, tag)
 
 
 _cache = {}

@@ -3,10 +3,8 @@ in)) with F_S the numpy model of splanes_lib, so every comparison is byte equali
 edges of the stride, a vector, a tile, a restart segment, a span and the grid; stride 1 and TRC_FILTER_NONE against the existing
 calls; the coded calls against the unfiltered calls on the model-filtered input; chunk ranges; argument errors; the histograms of
 trc_planes_hist_stride_dev against numpy bincounts; the TRCS container through host pointers and `trcfile s / d / x`; and what it
-is for: a row-major table stores fewer bytes.  The kernel tests put 512 guard bytes of 0xA5 on both sides of every device buffer."""
-import os
-import subprocess
-
+is for: a row-major table stores fewer bytes.  The kernel tests put 512 guard bytes of 0xA5 on both sides of every device buffer.
+The device calls and comparisons shared with the other plane files are in gpu_planes.py."""
 import numpy as np
 import pytest
 
@@ -14,42 +12,12 @@ import fplanes_lib as FL
 import planes_lib as PL
 import splanes_lib as SL
 import trc
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
+from gpu_planes import (GUARD, Guarded, assert_hists, coded_flat, decodes_flat, decodes_ranges_flat, device_hists, guarded, host_container_filtered,
+                        padded, rejected_flat, split_join_flat, trcfile, trcfile_round_trip, up256)
 from planes_matrix_lib import assert_same_container
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 512
-PRM = (4, 7)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-class Guarded:
-    """a device buffer of nbytes (from `data`, else 0xA5 throughout) with the guard on both sides; .t is the buffer itself"""
-
-    def __init__(self, torch, nbytes, data=None):
-        a = np.full(GUARD + nbytes + GUARD, 0xA5, dtype=np.uint8)
-        if data is not None:
-            a[GUARD:GUARD + nbytes] = data
-        self.nbytes, self.img = nbytes, a
-        self.whole = torch.from_numpy(a).to("cuda:0")
-        self.t = self.whole[GUARD:]
-        assert self.t.data_ptr() % 256 == 0
-
-    def get(self):
-        """-> (the nbytes, True where both guards are intact)"""
-        a = self.whole.cpu().numpy()
-        return a[GUARD:GUARD + self.nbytes], bool((a[:GUARD] == 0xA5).all() and (a[GUARD + self.nbytes:] == 0xA5).all())
-
-
-def up256(x):
-    return (x + 255) & ~255
 
 
 def shapes(stride):
@@ -60,30 +28,10 @@ def shapes(stride):
 
 # ---- the two kernels -----------------------------------------------------------------------------------------------------
 def split_join_case(torch, esize, filt, stride, seg, m, t, kind):
-    n = m * esize + t
     d = SL.gen(kind, esize, m, t, 100 * m + 10 * esize + t + stride, stride)
     planes, tail = PL.split(SL.forward(d, esize, filt, seg, stride), esize)
-    pitch = up256(m)                                            # the smallest pitch the call takes
-    d_in, d_planes, d_tail, d_out = Guarded(torch, n, d), Guarded(torch, esize * pitch), Guarded(torch, 8), Guarded(torch, n)
-    trc.planes_split_sfilter(filt, stride, d_in.t, n, esize, seg, d_planes.t, pitch, d_tail.t if t else None)
-    trc.planes_join_sfilter(filt, stride, d_planes.t, pitch, d_tail.t if t else None, n, esize, seg, d_out.t)
-    torch.cuda.synchronize()
     tag = "esize %d, filter %s, stride %d, seg %d, m %d, t %d, %s" % (esize, FL.FILTER_NAMES[filt], stride, seg, m, t, kind)
-    exp = np.full(esize * pitch, 0xA5, dtype=np.uint8)          # (the pitch gap behind m stays as it was)
-    for k in range(esize):
-        exp[k * pitch:k * pitch + m] = planes[k]
-    got, intact = d_planes.get()
-    assert np.array_equal(got, exp), tag + ": planes or the gaps behind them (first difference at %d)" % int(np.flatnonzero(got != exp)[0])
-    assert intact, tag + ": split wrote outside its planes"
-    exp_tail = np.full(8, 0xA5, dtype=np.uint8)
-    exp_tail[:t] = tail
-    got, intact = d_tail.get()
-    assert np.array_equal(got, exp_tail) and intact, tag + ": tail or the bytes around it"
-    got, intact = d_out.get()
-    assert np.array_equal(got, d), tag + ": join(split(x)) != x (first difference at byte %d)" % int(np.flatnonzero(got != d)[0])
-    assert intact, tag + ": join wrote outside its output"
-    got, intact = d_in.get()
-    assert np.array_equal(got, d) and intact, tag + ": the input changed"
+    split_join_flat(torch, d, esize, m, t, planes, tail, tag, filt=filt, stride=stride, seg=seg)
 
 
 @pytest.mark.parametrize("stride", SL.STRIDES)
@@ -156,18 +104,9 @@ def test_split_join_argument_errors_launch_nothing(torch_cuda):
 
 # ---- the histograms -----------------------------------------------------------------------------------------------------
 def hist_case(torch, esize, stride, seg, m, filters=7):
-    n = m * esize + (esize - 1)
     d = SL.gen("interleaved", esize, m, esize - 1, 31 * m + esize, stride)
-    d_in, d_hist = Guarded(torch, n, d), Guarded(torch, trc.planes_hist_bytes(esize))
-    trc.planes_hist_stride(filters, stride, d_in.t, n, esize, seg, d_hist.t)
-    torch.cuda.synchronize()
-    got, intact = d_hist.get()
-    exp = SL.hist3(d, esize, seg, stride).reshape(3, -1)
-    for f in range(3):
-        if not filters >> f & 1:
-            exp[f] = 0
-    assert intact, "the histogram call wrote outside its counters"
-    assert np.array_equal(got.view("<u8"), exp.reshape(-1)), "esize %d, stride %d, seg %d, m %d, filters %d" % (esize, stride, seg, m, filters)
+    got, _ = device_hists(torch, esize, seg, filters, d=d, strides=stride)
+    assert_hists(got, SL.hist3(d, esize, seg, stride), [m], filters, "esize %d, stride %d, seg %d, m %d, filters %d" % (esize, stride, seg, m, filters))
 
 
 @pytest.mark.parametrize("esize,stride", [(2, 3), (4, 4), (8, 7)])
@@ -191,34 +130,12 @@ def test_hist_stride(torch_cuda, esize, stride, monkeypatch):
 
 
 # ---- the coded calls ---------------------------------------------------------------------------------------------------
-_cache = {}
-
-
 def coded(torch, codec, esize, filt, stride, chunk, m):
     """-> (input bytes, StridedPlanesCoder holding their container, PlanesCoder holding the container of the model-filtered input):
     computed once per key, shared, left unchanged"""
-    key = (codec, esize, filt, stride, chunk, m)
-    if key not in _cache:
-        t = esize - 1
-        d = SL.gen("interleaved", esize, m, t, 17 * esize + filt + stride, stride)
-        n = d.size
-        out = []
-        for cls, src, kw in ((trc.StridedPlanesCoder, d, dict(filter=filt, stride=stride)), (trc.PlanesCoder, SL.forward(d, esize, filt, chunk, stride), {})):
-            pc = cls(codec, n, esize, chunk, "cuda:0", cdfnum=256, prm=PRM, guard=GUARD, **kw)
-            a = np.full(n + trc.PAD + GUARD, 0xA5, dtype=np.uint8)
-            a[:n], a[n:n + trc.PAD] = src, 0
-            d_in = torch.from_numpy(a).to("cuda:0")
-            pc.payload[:esize * pc.pitch] = 0x5A
-            pc.encode(d_in, n)
-            assert pc.guards_ok(), "encode wrote behind one of its buffers"
-            assert np.array_equal(d_in.cpu().numpy(), a), "encode changed its input"
-            out.append(pc)
-        _cache[key] = (d, out[0], out[1])
-    return _cache[key]
-
-
-def tail_guard(torch, nbytes):
-    return torch.full((nbytes + trc.PAD + GUARD,), 0xA5, dtype=torch.uint8, device="cuda:0")
+    d = SL.gen("interleaved", esize, m, esize - 1, 17 * esize + filt + stride, stride)
+    return (d,) + coded_flat(torch, codec, esize, chunk, d, trc.StridedPlanesCoder, lambda: SL.forward(d, esize, filt, chunk, stride),
+                             filter=filt, stride=stride)
 
 
 CODED = [(4, c, chunk) for c in (trc.ANS4S, trc.RCA, trc.RCB) for chunk in (256, 4096)] + [(2, trc.RCA, 256), (8, trc.ANS4S, 256)]
@@ -232,26 +149,12 @@ def test_encode_contract_decode_and_ranges(torch_cuda, esize, codec, chunk, stri
     for filt in SL.FILTERS:
         d, sc, pc = coded(torch, codec, esize, filt, stride, chunk, m)
         tag = "%s esize %d chunk %d filter %s stride %d" % (trc.CODEC_NAMES[codec], esize, chunk, FL.FILTER_NAMES[filt], stride)
-        n, nch = d.size, sc.nch
+        nch = sc.nch
         assert nch == (m + chunk - 1) // chunk
         assert_same_container(sc, pc, esize, codec, tag)
         assert torch.equal(sc.total, pc.total) and torch.equal(sc.clen, pc.clen), tag + ": totals or directory"
-        d_out = tail_guard(torch, n)
-        sc.decode(d_out, n)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        assert np.array_equal(out[:n], d), tag + ": decode does not return the input"
-        assert (out[n:] == 0xA5).all(), tag + ": decode wrote behind its n bytes"
-        for first, count in ((0, 1), (1, 1), (nch - 1, 1), (1, nch - 1)):
-            e0, e1 = first * chunk, min(m, (first + count) * chunk)
-            size = (e1 - e0) * esize
-            d_out = tail_guard(torch, size)
-            sc.decode_range(d_out, first, count, n)
-            torch.cuda.synchronize()
-            out = d_out.cpu().numpy()
-            assert np.array_equal(out[:size], d[e0 * esize:e1 * esize]), "%s: chunks (%d, %d)" % (tag, first, count)
-            assert (out[size:] == 0xA5).all(), "%s: chunks (%d, %d) wrote behind their elements" % (tag, first, count)
-        assert sc.guards_ok()
+        decodes_flat(torch, sc, d, tag)
+        decodes_ranges_flat(torch, sc, d, esize, chunk, ((0, 1), (1, 1), (nch - 1, 1), (1, nch - 1)), tag)
 
 
 @pytest.mark.parametrize("codec", (trc.ANS4S, trc.RCA))
@@ -260,7 +163,7 @@ def test_stride_one_and_filter_none_are_the_existing_calls(torch_cuda, codec):
     esize, chunk, m = 4, 256, 5 * 256 + 3
     d = FL.gen("monotone", esize, m, esize - 1, 3)
     n = d.size
-    d_in = torch.from_numpy(np.concatenate([d, np.zeros(trc.PAD, np.uint8)])).to("cuda:0")
+    d_in = padded(torch, d)
     for filt, stride in ((FL.ZDELTA, 1), (FL.XOR, 1), (FL.NONE, 1), (FL.NONE, 6)):
         sc = trc.StridedPlanesCoder(codec, n, esize, chunk, "cuda:0", cdfnum=256, guard=GUARD, filter=filt, stride=stride)
         fc = trc.FilteredPlanesCoder(codec, n, esize, chunk, "cuda:0", cdfnum=256, guard=GUARD, filter=filt)
@@ -271,15 +174,8 @@ def test_stride_one_and_filter_none_are_the_existing_calls(torch_cuda, codec):
         assert_same_container(sc, fc, esize, codec, tag)
         for name in ("clen", "total", "tail", "cdf", "status"):
             assert torch.equal(getattr(sc, name), getattr(fc, name)), tag + ": " + name
-        d_out = tail_guard(torch, n)
-        sc.decode(d_out, n)
-        torch.cuda.synchronize()
-        assert np.array_equal(d_out.cpu().numpy()[:n], d) and (d_out.cpu().numpy()[n:] == 0xA5).all(), tag
-        d_out = tail_guard(torch, 2 * chunk * esize)
-        sc.decode_range(d_out, 2, 2, n)
-        torch.cuda.synchronize()
-        assert np.array_equal(d_out.cpu().numpy()[:2 * chunk * esize], d[2 * chunk * esize:4 * chunk * esize]), tag
-        assert sc.guards_ok()
+        decodes_flat(torch, sc, d, tag)
+        decodes_ranges_flat(torch, sc, d, esize, chunk, [(2, 2)], tag)
 
 
 @pytest.mark.parametrize("codec", (trc.ANS4S, trc.RCA))
@@ -288,26 +184,13 @@ def test_argument_errors_launch_nothing(torch_cuda, codec):
     esize, chunk, m = 4, 256, 5 * 256 + 3
     d, sc, _ = coded(torch, codec, esize, FL.ZDELTA, 3, chunk, m)
     n = d.size
-    d_out = tail_guard(torch, n)
-    d_in = torch.from_numpy(np.concatenate([d, np.zeros(trc.PAD, np.uint8)])).to("cuda:0")
+    d_out = guarded(torch, n + trc.PAD)
+    d_in = padded(torch, d)
     names = ("clen", "payload", "total", "tail", "cdf")
     before = [getattr(sc, x).clone() for x in names]
 
-    def rejected(nbytes=n, flags=0, **attrs):
-        """the three calls with some of the coder's attributes replaced: each is TRC_E_ARG"""
-        saved = {k: getattr(sc, k) for k in attrs}
-        for k, v in attrs.items():
-            setattr(sc, k, v)
-        try:
-            with pytest.raises(trc.TrcError, match="rc=-1"):
-                sc.encode(d_in, nbytes, flags=flags)
-            with pytest.raises(trc.TrcError, match="rc=-1"):
-                sc.decode(d_out, nbytes, flags=flags)
-            with pytest.raises(trc.TrcError, match="rc=-1"):
-                sc.decode_range(d_out, 0, 1, nbytes, flags=flags)
-        finally:
-            for k, v in saved.items():
-                setattr(sc, k, v)
+    def rejected(**kw):
+        rejected_flat(sc, d_in, d_out, n, **kw)
 
     for stride in (0, 9, -1):
         rejected(stride=stride)
@@ -337,31 +220,13 @@ def test_argument_errors_launch_nothing(torch_cuda, codec):
 @pytest.mark.parametrize("codec", (trc.RCA, trc.ANS4S))
 def test_host_container(torch_cuda, codec, filt, stride, chunk):
     esize, m = 4, 9 * 256 + 3
-    t = esize - 1
-    d = SL.gen("interleaved", esize, m, t, 23, stride)
+    d = SL.gen("interleaved", esize, m, esize - 1, 23, stride)
     n = d.size
-    comp = trc.host_encode_splanes(codec, filt, stride, d, esize, chunk)
-    trc.splanes_check(comp, n)
-    assert comp[:4].tobytes() == b"TRCS" and (comp[4], comp[5], comp[6], comp[7]) == (filt, 1, stride, 0)
-    assert int(comp[8:16].view("<u8")[0]) == comp.size
-    hdr, _, tail = trc.parse_planes(comp[16:])
-    resolved = hdr["chunk"]
-    assert resolved == (chunk or trc.lib().trc_auto_chunk_codec(codec, m)) and hdr["size"] == comp.size - 16 and hdr["n"] == n
-    exp = trc.host_encode_planes(codec, SL.forward(d, esize, filt, resolved, stride), esize, chunk)
-    assert np.array_equal(comp[16:], exp), "bytes [16:] are not trc_encode_planes_host of the filtered input"
-    assert np.array_equal(tail, d[n - t:])
-    assert np.array_equal(trc.host_decode_splanes(comp, n), d)
+    comp, _ = host_container_filtered(codec, d, esize, m, chunk, b"TRCS", (filt, 1, stride, 0),
+                                      lambda x, ch: trc.host_encode_splanes(codec, filt, stride, x, esize, ch), trc.splanes_check,
+                                      trc.host_decode_splanes, trc.host_decode_splanes_range, lambda seg: SL.forward(d, esize, filt, seg, stride),
+                                      more_ranges=lambda c: [(c + 5, 3 * c + 1)])
     assert np.array_equal(trc.host_decode_xplanes(comp, n), d)
-    c = resolved * esize
-    for offset, length in [(0, 1), (c - 1, 3), (c // 2, 2 * c), (c + 5, 3 * c + 1), (5, n - 5), (n - t - 1, t + 1), (n - t, t), (n - 1, 1), (0, n)]:
-        if offset + length > n:
-            continue
-        got = trc.host_decode_splanes_range(comp, offset, length)
-        assert np.array_equal(got, d[offset:offset + length]), "bytes [%d, +%d)" % (offset, length)
-    with pytest.raises(trc.TrcError):
-        trc.host_decode_splanes_range(comp, n - 1, 2)
-    with pytest.raises(trc.TrcError, match="container"):
-        trc.host_decode_splanes(comp[:-1], n)
     with pytest.raises(trc.TrcError, match="trc_encode_fplanes_host"):
         trc.host_encode_splanes(codec, filt, 1, d, esize, chunk)
     with pytest.raises(trc.TrcError, match="magic"):
@@ -382,18 +247,9 @@ def test_a_table_of_four_fields_stores_fewer_bytes_with_stride_four(torch_cuda):
 
 
 def test_trcfile_splanes(torch_cuda, tmp_path):
-    exe = os.path.join(ROOT, "harness", "trcfile")
-    assert os.path.exists(exe), "harness/trcfile is not built"
     d = np.concatenate([SL.table_rows(10000), np.array([1, 2, 3], dtype=np.uint8)])
-    src, comp, back, part = (str(tmp_path / f) for f in ("in.bin", "in.trcs", "out.bin", "part.bin"))
-    d.tofile(src)
     for letter, filt, stride in (("z", 1, 4), ("x", 2, 3)):
-        for args in (["s", "46", "4", letter, str(stride), src, comp], ["d", comp, back], ["x", comp, "70001", "3000", part]):
-            r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120)
-            assert r.returncode == 0, (args, r.stdout, r.stderr)
-        head = np.fromfile(comp, dtype=np.uint8)
+        head = trcfile_round_trip(tmp_path, d, "trcs", ["s", "46", "4", letter, stride], 70001, 3000)
         assert head[:4].tobytes() == b"TRCS" and head[4] == filt and head[6] == stride and head[16:20].tobytes() == b"TRCP"
-        assert np.array_equal(np.fromfile(back, dtype=np.uint8), d)
-        assert np.array_equal(np.fromfile(part, dtype=np.uint8), d[70001:73001])
-    r = subprocess.run([exe, "s", "46", "4", "z", "9", src, comp], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "stride" in r.stderr
+    r = trcfile("s", "46", "4", "z", "9", tmp_path / "in.bin", tmp_path / "in.trcs", rc=2)
+    assert "stride" in r.stderr

@@ -12,16 +12,10 @@ import pytest
 import trc
 import trc_testlib as T
 from golden.make_golden import gen
+from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU (and must not silently fall back)"
-    return torch
 
 
 def host_chunk(codec, chunk):
