@@ -1,0 +1,192 @@
+"""tests/gpu_arena.py without a GPU: the layout arithmetic for every buffer of every case of every coder, the audit on CPU tensors
+(one changed byte in each kind of zone is found and named; what a call may write passes; the allow-list opens writable slack up to
+its recorded offset and no further), and the raw / coded mix of the oracle's directories for the cases of trc.AVAILABLE."""
+import numpy as np
+import pytest
+
+import gpu_arena as GA
+import planes_matrix_lib as PM
+import trc
+
+torch = pytest.importorskip("torch")
+by_name = pytest.mark.parametrize("codec", PM.ASSIGNED, ids=lambda c: trc.CODEC_NAMES[c])
+
+
+def test_every_coder_has_its_cases():
+    assert len(PM.ASSIGNED) == 60
+    assert sorted(PM.ASSIGNED) == sorted(set(trc.AVAILABLE) | set(GA.S.CODECS) | set(GA.B.CODECS))
+    assert len(trc.AVAILABLE) == 27 and len(GA.S.CODECS) == 26 and len(GA.B.CODECS) == 7
+
+
+@by_name
+def test_layout(codec):
+    lib = trc.lib()
+    cases = GA.cases_of(codec)
+    assert [c.nchunks for c in cases] == ([129, 66, 63] if codec in trc.AVAILABLE else [129, 63, 65])
+    for case in cases:
+        for kw in (dict(), dict(rx=False)):
+            specs = case.specs(**kw)
+            L = GA.Layout(specs)
+            stated = dict(specs)
+            assert stated["in"] == stated["out"] == stated["a.payload"] == case.n and stated["a.clen"] == 4 * case.nchunks
+            assert stated["a.total"] == 8 and stated["a.status"] == 4 and stated["a.cdf"] == 514
+            assert stated["a.work"] == lib.trc_work_bytes(codec, case.n, case.chunk) == stated.get("b.work", stated["a.work"])
+            assert stated["a.range_work"] == lib.trc_range_work_bytes(codec, case.n, case.chunk, case.range[1])
+            assert stated["range_out"] == case.range_bytes == (case.n - 63 * case.chunk if case.nchunks == 65 else
+                                                                 2 * case.chunk if case.nchunks > 65 else case.n)
+            assert ("a.cdfini_work" in stated) == (codec in trc.STATIC) and stated.get("a.cdfini_work", 4096) == 4096
+            assert [b.name for b in L.bufs] == [s[0] for s in specs]
+            assert L.bufs[0].start >= GA.MARGIN + GA.ZONE and L.size - L.bufs[-1].end == GA.MARGIN
+            prev_end = None
+            for b in L.bufs:
+                a = GA.ALIGN[b.kind]
+                assert b.size == stated[b.name] and b.end - b.start - b.size == trc.PAD == 256, b.name
+                if b.kind in GA.EXACT:
+                    assert b.start % (2 * a) == a, "%s: aligned to %d and to nothing more" % (b.name, a)
+                else:
+                    assert b.kind in ("cdf", "status") and b.start % 256 == 0, b.name
+                if prev_end is not None:                       # disjoint, a whole guard zone apart, and no further than the alignment asks
+                    assert GA.ZONE <= b.start - prev_end < GA.ZONE + 2 * a, b.name
+                prev_end = b.end
+            kinds = {b.name: (b.kind, GA.ALIGN[b.kind]) for b in L.bufs}
+            assert kinds["in"] == ("in", 16) and kinds["out"] == kinds["range_out"] == ("out", 16) and kinds["a.total"] == ("total", 8)
+            assert kinds["a.work"] == kinds["a.range_work"] == ("work", 256) and kinds["a.clen"] == ("clen", 4)
+            assert kinds["a.payload"] == ("payload", 2)
+            # every byte of the allocation has exactly one name
+            assert L.regions[0][0] == 0 and L.regions[-1][1] == L.size
+            assert all(r[1] == s[0] and r[0] < r[1] for r, s in zip(L.regions, L.regions[1:]))
+
+
+def test_arena_views_keep_the_alignment():
+    case = GA.cases_of(trc.ANS4S)[1]
+    A = GA.Arena(torch, GA.Layout(case.specs()), "cpu", "ff", 0)
+    assert A.buf.data_ptr() % GA.BASE_ALIGN == 0 and A.buf.numel() == A.layout.size
+    dc = GA.ArenaCoder(A, "a", case)
+    rx = GA.ArenaCoder(A, "b", case, rx_of=dc)
+    assert dc.work.data_ptr() % 512 == 256 and rx.work.data_ptr() % 512 == 256 and dc.range_work.data_ptr() % 512 == 256
+    assert dc.work.data_ptr() != rx.work.data_ptr() and dc.work_bytes == A.layout["a.work"].size
+    assert dc.clen.data_ptr() % 8 == 4 and dc.payload.data_ptr() % 4 == 2 and dc.total.data_ptr() % 16 == 8
+    assert A.view("in").data_ptr() % 32 == 16 and A.view("out").data_ptr() % 32 == 16 and A.view("range_out").data_ptr() % 32 == 16
+    assert dc.cdf.data_ptr() % 256 == 0 and dc.status.data_ptr() % 256 == 0 and dc.cdfini_work.data_ptr() % 512 == 256
+    assert rx.clen.data_ptr() == dc.clen.data_ptr() and rx.payload.data_ptr() == dc.payload.data_ptr() and rx.cdf.data_ptr() == dc.cdf.data_ptr()
+    assert dc.clen.numel() == case.nchunks + 64 and dc.total.numel() == 33 and dc.payload.numel() == case.n + 256
+
+
+@pytest.mark.parametrize("poison", GA.POISONS)
+def test_poison_and_inputs(poison):
+    case = GA.cases_of(trc.RCB)[2]
+    L = GA.Layout(case.specs())
+    A = GA.Arena(torch, L, "cpu", poison, 3)
+    d = case.data()["d"]
+    A.put("in", d)
+    img = A.buf.numpy()
+    b = L["in"]
+    assert np.array_equal(img[b.start:b.start + case.n], d)
+    rest = np.concatenate([img[:b.start], img[b.start + b.size:]])
+    if poison == "ff":
+        assert (rest == 0xFF).all()
+    else:                                                      # seeded, every byte value, zeros no more often than any other
+        assert np.array_equal(A.buf.numpy(), _again(L, d, 3)) and len(np.unique(rest)) == 256
+        assert (rest == 0).mean() < 1 / 200
+
+
+def _again(L, d, seed):
+    A = GA.Arena(torch, L, "cpu", "random", seed)
+    A.put("in", d)
+    return A.buf.numpy()
+
+
+def test_audit_names_a_changed_byte_in_every_kind_of_zone():
+    case = GA.cases_of(trc.RCB)[2]
+    L = GA.Layout(case.specs())
+    A = GA.Arena(torch, L, "cpu", "random", 11, record=False)
+    A.snapshot()
+    A.audit("untouched", allow={})
+    i, w, o, last = L["in"], L["a.work"], L["out"], L.bufs[-1]
+    places = [(0, "the front margin (ends %d bytes before in)" % i.start),
+              (i.start - 1, "the front margin (ends 1 bytes before in)"),
+              (i.start + 5, "in, byte 5 of its stated %d" % case.n),
+              (i.start + i.size, "the slack of in, stated size + 0"),
+              (i.end - 1, "the slack of in, stated size + 255"),
+              (i.end, "the guard zone between in and a.work, byte 0 of it"),
+              (w.start - 1, "the guard zone between in and a.work, byte %d of it" % (w.start - i.end - 1)),
+              (w.start + w.size + 3, "the slack of a.work, stated size + 3"),
+              (o.start + o.size, "the slack of out, stated size + 0"),
+              (last.end, "the rear margin, byte 0 behind the slack of b.work"),
+              (L.size - 1, "the rear margin, byte %d behind the slack of b.work" % (GA.MARGIN - 1))]
+    for off, text in places:
+        A.buf[off] ^= 0x80
+        with pytest.raises(AssertionError) as e:
+            A.audit("tag", allow={})
+        assert str(e.value) == "tag: 1 byte(s) changed in " + text, off
+        A.buf[off] ^= 0x80
+        A.audit("restored", allow={})
+    A.buf[i.start + 5] ^= 1                                     # two places, first and last of each
+    A.buf[w.start + w.size + 3] ^= 1
+    A.buf[w.start + w.size + 9] ^= 1
+    with pytest.raises(AssertionError) as e:
+        A.audit("tag", allow={})
+    assert str(e.value) == ("tag: 1 byte(s) changed in in, byte 5 of its stated %d; 2 byte(s) changed in the slack of a.work, "
+                            "stated size + 3 .. the slack of a.work, stated size + 9" % case.n)
+
+
+def test_audit_rules():
+    """what a call may write passes and nothing next to it; writable slack is open up to the allow-list's offset only; recording
+    mode records the furthest offset and judges nothing there, but still judges everything else"""
+    case = GA.cases_of(trc.RCB)[2]
+    L = GA.Layout(case.specs())
+    A = GA.Arena(torch, L, "cpu", "ff", 0, record=False)
+    w, p = L["a.work"], L["a.payload"]
+    total = 1000
+    writes = [("a.work", 0, w.size), ("a.payload", 0, total)]
+    soft = [GA.slack(A, "a.work"), ("a.payload", total + 64, case.n + GA.PAD, total)]
+    A.snapshot()
+    A.buf[w.start:w.start + w.size] = 1
+    A.buf[p.start:p.start + total] = 2
+    A.audit("allowed", writes, soft, "rcs", {})
+    for off, text in ((p.start + total, "a.payload, byte 1000 of its stated"), (p.start + total + 63, "a.payload, byte 1063 of its stated"),
+                      (p.start + total + 64, "a.payload, byte 1064"), (p.start + p.size + 255, "the slack of a.payload, stated size + 255"),
+                      (p.end, "the guard zone between a.payload and a.total"), (w.start + w.size, "the slack of a.work, stated size + 0")):
+        A.buf[off] = 3
+        with pytest.raises(AssertionError, match=text.replace("+", r"\+")):
+            A.audit("tag", writes, soft, "rcs", {})
+        A.buf[off] = 0xFF
+    A.buf[w.start + w.size + 15] = 3                            # the allow-list: open up to its offset, for its coder, and no further
+    A.buf[p.start + total + 64] = 3
+    allow = {("rcs", "work"): 15, ("rcs", "payload"): 64}
+    A.audit("listed", writes, soft, "rcs", allow)
+    with pytest.raises(AssertionError, match="slack of a.work"):
+        A.audit("another coder", writes, soft, "rccdf", allow)
+    with pytest.raises(AssertionError, match=r"slack of a.work, stated size \+ 15"):
+        A.audit("one less", writes, soft, "rcs", {("rcs", "work"): 14, ("rcs", "payload"): 64})
+    with pytest.raises(AssertionError, match="a.payload, byte 1064"):
+        A.audit("one less", writes, soft, "rcs", {("rcs", "work"): 15, ("rcs", "payload"): 63})
+    rec = {}
+    A.record = rec
+    A.audit("recording", writes, soft, "rcs", {})
+    assert rec[("rcs", "work")] == 15 and rec[("rcs", "payload")] == 64
+    A.buf[w.start - 1] = 3
+    with pytest.raises(AssertionError, match="guard zone between in and a.work"):
+        A.audit("recording still judges the hard rules", writes, soft, "rcs", {})
+
+
+def test_allow_list_stays_inside_the_slack():
+    names = set(trc.CODEC_NAMES.values())
+    for (coder, kind), far in GA.ALLOW.items():
+        assert coder in names and kind in ("work", "range_work", "cdfini_work", "clen", "total", "status", "payload"), (coder, kind)
+        assert 0 <= far < trc.PAD, (coder, kind, far)
+
+
+@pytest.mark.parametrize("codec", trc.AVAILABLE, ids=lambda c: trc.CODEC_NAMES[c])
+def test_raw_and_coded_mix(codec):
+    """the mix test_gpu_arena.py asserts holds for the oracle alone: at (129, 100) at least 30 raw and 30 coded chunks, except for
+    the three nibble coders, which never store a chunk raw; every case has a ragged or full last chunk as its shape says"""
+    cases = GA.cases_of(codec)
+    raw, coded = GA.mix_of(cases[0])
+    if codec in trc.NIBBLE_CODECS:
+        assert (raw, coded) == (0, 129)
+    else:
+        assert raw >= GA.MIX_MIN and coded >= GA.MIX_MIN and raw + coded == 129, (raw, coded)
+    assert [c.n % c.chunk for c in cases] == [100, 37, 0]
+    x = cases[1].data()
+    assert x["clen"].size == 66 and int(x["clen"].sum()) == x["payload"].size
