@@ -17,6 +17,13 @@
  *                                 pairs): the filter predicts from the element <stride> back, 2 .. 8.  The file is the library's
  *                                 strided planes container: 16 bytes "TRCS" | u8 filter | u8 1 | u16 stride | u64 size, then the TRCP
  *                                 container of the filtered data
+ *   trcfile r <id> <esize> <z|x> <base> <in> <out>   as f, with the filter RELATIVE TO A BASE FILE: z = zigzag delta, x = xor of every
+ *                                 element against the element at the same place in <base> (the previous checkpoint, the base model of
+ *                                 a fine-tune, a page before its update), which holds at least the whole elements of <in>.  The file
+ *                                 is the library's TRCD container: 32 bytes "TRCD" | u8 filter | u8 1 | u16 0 | u64 size | u64 base
+ *                                 bytes | u64 base fingerprint, then the TRCP container of the filtered data
+ *   trcfile R <in> <base> <out>   decompress a file of r against its base; a base with another fingerprint is refused.  d and x do
+ *                                 not read such a file: they have no base to give
  *   trcfile a <id> <esize> <in> <out>   as p or f, whichever the library's planes advisor chooses from the order-0 histograms of the
  *                                 planes under no filter, z and x (trc_encode_aplanes_host): the file is what p or f would have
  *                                 written; prints the three estimates and the choice (n, z or x)
@@ -121,6 +128,8 @@ static int is_planes(const unsigned char *fb, size_t fl) { return fl >= 4 && !me
 static int is_fplanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCF", 4) && fb[5] == 1 && !memcmp(fb + 16, "TRCP", 4); }
 /* a file of `trcfile s` */
 static int is_splanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCS", 4) && !memcmp(fb + 16, "TRCP", 4); }
+/* a file of `trcfile r` */
+static int is_bplanes(const unsigned char *fb, size_t fl) { return fl >= 36 && !memcmp(fb, "TRCD", 4) && !memcmp(fb + 32, "TRCP", 4); }
 static int write_file(const char *path, const unsigned char *p, size_t n)
 {
     FILE *f = fopen(path, "wb");
@@ -261,6 +270,39 @@ int main(int argc, char **argv)
         printf("%zu -> %zu bytes (%.2f%%)  %u planes, filter %s, stride %d\n", n, l, 100.0 * l / n, esize, argv[4], stride);
         return 0;
     }
+    if (argc == 8 && !strcmp(argv[1], "r")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        const int filter = !strcmp(argv[4], "z") ? TRC_FILTER_ZDELTA : !strcmp(argv[4], "x") ? TRC_FILTER_XOR : TRC_FILTER_NONE;
+        size_t n, bn;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (filter == TRC_FILTER_NONE) { fprintf(stderr, "filter %s: z (zigzag delta) or x (xor)\n", argv[4]); return 2; }
+        unsigned char *base = slurp(argv[5], &bn), *in = base ? slurp(argv[6], &n) : 0;
+        if (!in) return 2;
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_bplanes_bound(n, esize, 0, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u with %zu bytes: esize is 2, 4 or 8 and the file holds at least one element\n", esize, n); return 2; }
+        if (bn < n - n % esize) { fprintf(stderr, "the base holds %zu bytes, the elements of the input take %zu\n", bn, n - n % esize); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        const size_t l = trc_encode_bplanes_host(codec, filter, in, base, n, esize, 0, out, cap, cdfnum);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[7], out, l)) return 2;
+        printf("%zu -> %zu bytes (%.2f%%)  %u planes, filter %s against the base\n", n, l, 100.0 * l / n, esize, argv[4]);
+        return 0;
+    }
+    if (argc == 5 && !strcmp(argv[1], "R")) {
+        size_t fl, bn;
+        unsigned char *fb = slurp(argv[2], &fl), *base = fb ? slurp(argv[3], &bn) : 0;
+        if (!base) return 2;
+        trc_planes_hdr ph;
+        if (trc_bplanes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        memcpy(&ph, fb + sizeof(trc_bplanes_hdr), sizeof ph);
+        unsigned char *out = malloc((size_t)ph.n + 1024);
+        if (!out) { perror("malloc"); return 2; }
+        if (trc_decode_bplanes_host(fb, fl, base, bn, out, (size_t)ph.n) != ph.n) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+        return write_file(argv[4], out, (size_t)ph.n);
+    }
     if (argc == 6 && !strcmp(argv[1], "a")) {
         const int id = atoi(argv[2]), codec = lib_codec(id);
         const unsigned esize = (unsigned)atoi(argv[3]);
@@ -358,6 +400,7 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        if (is_bplanes(fb, fl)) { fprintf(stderr, "a file of trcfile r, coded against a base: trcfile R <in> <base> <out> decodes it\n"); return 2; }
         /* a file of `trcfile p`, f, s or a: untrusted, so checked against what was read; the library looks at the magic itself
          * (trc_decode_xplanes_host = trc_decode_planes_host, trc_decode_fplanes_host or trc_decode_splanes_host) */
         if (is_fplanes(fb, fl) || is_splanes(fb, fl) || is_planes(fb, fl)) {
@@ -401,6 +444,7 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
+        if (is_bplanes(fb, fl)) { fprintf(stderr, "a file of trcfile r, coded against a base: trcfile R <in> <base> <out> decodes it\n"); return 2; }
         if (is_splanes(fb, fl)) {
             const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
             trc_planes_hdr ph;
@@ -571,6 +615,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in>\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in> | trcfile r <id> <esize> <z|x> <base> <in> <out> | trcfile R <in> <base> <out>\n");
     return 2;
 }

@@ -582,6 +582,91 @@ size_t trc_decode_splanes_host(const void *in, size_t inlen, void *out, size_t o
 size_t trc_decode_splanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
 int    trc_splanes_check(const void *buf, size_t buflen, size_t outlen);
 
+/* ---- byte planes relative to a BASE buffer: checkpoint and page deltas ------------------------------------------------
+ * The filters above predict from inside the buffer.  A checkpoint, a fine-tuned model or an updated KV-cache page has a better
+ * predictor: the same buffer one version earlier, already on the device.  With a base of the same element layout:
+ *        x[i], b[i] = the m = n / esize elements of `in` and of `base`, little-endian unsigned words of w = 8 * esize bits
+ *        TRC_FILTER_ZDELTA   d = x[i] - b[i] mod 2^w;   y[i] = zigzag(d)        inverse: x[i] = b[i] + unzigzag(y[i]) mod 2^w
+ *        TRC_FILTER_XOR      y[i] = x[i] ^ b[i]                                  inverse: x[i] = y[i] ^ b[i]
+ *        D(filter, esize, in, base) = the y's followed by the t = n % esize tail bytes of `in`, untouched
+ * The filter enum is untouched; the base is an argument of calls of their own.  There is no restart and no `seg`: element i
+ * depends on element i of the base only, so the inverse is elementwise.  The calls read bytes [0, m * esize) of the base and
+ * nothing else: the base needs no TRC_PAD slack and no tail.
+ *
+ * The whole contract:  bplanes(filter, ..., in, base)  ==  planes(..., D(filter, esize, in, base))  byte for byte -- directory,
+ * payload, totals, per-plane CDFs and statuses, tail, the host container's body.  Arguments, alignment, flags and workspace are
+ * those of the unfiltered call (trc_planes_work_bytes / trc_planes_range_work_bytes serve unchanged).  A filter outside {0, 1, 2}
+ * is TRC_E_ARG ahead of everything else.  With TRC_FILTER_NONE a device call IS its unfiltered counterpart, launches its kernels
+ * and does not look at d_base (which may be NULL); with filter 1 or 2, d_base NULL or not 16-byte aligned is TRC_E_ARG.  The seven
+ * low-nibble coders, TRC_TABLES_READY and TRC_DIR_READY are refused as everywhere in the family.
+ *
+ * Decoding IN PLACE is part of the contract: the d_out of the join and of the decoders may be exactly the address the call reads
+ * the base from, which applies a delta to a resident base.  Any other overlap of [base, base + m * esize) with [d_out, d_out + n)
+ * is TRC_E_ARG, before anything is enqueued.  trc_decode_bplanes_range_dev takes the WHOLE base and reads its elements
+ * [first_chunk * chunk, ...) (that offset is a multiple of 128 bytes, so the alignment holds); d_out[0] is the range's first
+ * element, and in place means d_out == (char *)d_base + first_chunk * chunk * esize.
+ *
+ * trc_planes_hist_base_dev has the layout and the rules of trc_planes_hist_dev (no seg), with the rows of filters 1 and 2 counted
+ * under D and row 0 the unfiltered one, so trc_planes_advise serves on its output as it stands.  Without bit 1 or 2 in `filters`
+ * it is trc_planes_hist_dev's unfiltered row and ignores d_base.
+ *
+ * The fingerprint lets a container name its base.  With W = ceil(nbytes / 8) little-endian u64 words w_j of the nbytes bytes,
+ * zero-padded to 8:      fp = sum_j (2j + 1) * w_j + nbytes * 0x9E3779B97F4A7C15   mod 2^64
+ * A change confined to one 8-byte word is always detected (the multiplier is odd), and so is another length of zeros.  It is an
+ * IDENTITY check against mixing up files, not a cryptographic one: bases that collide are easy to construct.
+ * trc_base_fingerprint_dev (d_base 16-byte aligned, read in [0, nbytes) only; d_fp 8-byte aligned, overwritten; only enqueues
+ * work) and trc_base_fingerprint_host (host only, no GPU needed) give the same value. */
+int trc_planes_split_base_dev(int filter, const void *d_in, const void *d_base, size_t n, unsigned esize,
+                              void *d_planes, size_t pitch, void *d_tail, void *stream);
+int trc_planes_join_base_dev(int filter, const void *d_planes, size_t pitch, const void *d_tail, const void *d_base,
+                             size_t n, unsigned esize, void *d_out, void *stream);
+int trc_encode_bplanes_dev(int codec, int filter, const void *d_in, const void *d_base, size_t n, unsigned esize, uint32_t chunk,
+                           uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                           uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                           void *d_work, size_t work_bytes, void *stream);
+int trc_decode_bplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                           const void *d_base, size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                           void *d_out, void *d_work, size_t work_bytes, void *stream);
+int trc_decode_bplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_base,
+                                 size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                 const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_out, void *d_work, size_t work_bytes, void *stream);
+int trc_planes_hist_base_dev(unsigned filters, const void *d_in, const void *d_base, size_t n, unsigned esize,
+                             uint64_t *d_hist, void *stream);
+int      trc_base_fingerprint_dev(const void *d_base, size_t nbytes, uint64_t *d_fp, void *stream);
+uint64_t trc_base_fingerprint_host(const void *base, size_t nbytes);
+
+/* Planes against a base through host pointers: the TRCD container = a 32-byte prefix in front of an ordinary TRCP container of
+ * D(filter, esize, in, base).  Bytes [32, size) are byte-identical to trc_encode_planes_host(codec, D(in, base), ...) at the same
+ * resolved chunk, so trc_planes_check, trc_container_check and trc_container_range work on the inner part as they stand.
+ * trc_encode_bplanes_host takes filter 1 or 2 (TRC_FILTER_NONE returns 0: trc_encode_planes_host writes that content, one layout
+ * per content) and reads m * esize bytes of `base`; out must hold trc_bplanes_bound = trc_planes_bound + 32 bytes.  The base is
+ * uploaded next to the input and fingerprinted on the device.  trc_decode_bplanes_host requires base_len >= base_bytes, uploads
+ * and fingerprints base_bytes bytes of the base, and where the fingerprint differs from the header's returns 0 BEFORE decoding,
+ * with "base fingerprint" and both values in trc_last_error().  trc_decode_bplanes_range_host uploads only the covering elements
+ * of the base and the covering chunks, takes tail bytes from the container and does NOT verify the fingerprint: it never sees the
+ * whole base; a caller who needs the check calls trc_base_fingerprint_host once.  All return the size, 0 on error.
+ * trc_bplanes_check (host only, no GPU needed) validates, in this order, magic and version 1, filter 1 or 2, zero == 0,
+ * 32 < size <= buflen, the inner container with trc_planes_check(buf + 32, size - 32, outlen), base_bytes == n - tail; both
+ * decoders call it first.  trc_decode_xplanes_host returns 0 for this magic and names trc_decode_bplanes_host: it has no base. */
+#define TRC_BPLANES_MAGIC 0x44435254u   /* "TRCD" */
+typedef struct trc_bplanes_hdr {
+    uint32_t magic;      /* TRC_BPLANES_MAGIC */
+    uint8_t  filter;     /* TRC_FILTER_ZDELTA or TRC_FILTER_XOR */
+    uint8_t  version;    /* 1 */
+    uint16_t zero;
+    uint64_t size;       /* 32 + the inner TRCP container's size */
+    uint64_t base_bytes; /* m * esize: the bytes of the base the filter read */
+    uint64_t base_fp;    /* the fingerprint of those bytes */
+} trc_bplanes_hdr;       /* 32 bytes, little endian */
+size_t trc_bplanes_bound(size_t n, unsigned esize, uint32_t chunk, unsigned cdfnum);
+size_t trc_encode_bplanes_host(int codec, int filter, const void *in, const void *base, size_t n, unsigned esize, uint32_t chunk,
+                               void *out, size_t outcap, unsigned cdfnum);
+size_t trc_decode_bplanes_host(const void *in, size_t inlen, const void *base, size_t base_len, void *out, size_t outlen);
+size_t trc_decode_bplanes_range_host(const void *in, size_t inlen, const void *base, size_t base_len,
+                                     size_t offset, size_t len, void *out);
+int    trc_bplanes_check(const void *buf, size_t buflen, size_t outlen);
+
 /* ---- batched byte planes: many separate allocations in one coded call, any one of them decodable ------------------------
  * A checkpoint is hundreds of tensors of one dtype, a KV-cache a pool of pages, a table a set of columns: many allocations, each
  * too small to fill the device and too many to launch the planes calls once apiece.  A batch codes them as ONE planes call over
@@ -687,6 +772,40 @@ int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *items, const 
                                  void *d_work, size_t work_bytes, void *stream);
 int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
                                  const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
+                                 unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_work, size_t work_bytes, void *stream);
+
+/* ---- batched byte planes against a base per item ------------------------------------------------------------------------------
+ * A checkpoint against the previous one is hundreds of tensors, each with its own base.  `bases` and `filters` are HOST arrays of
+ * `count` entries with the lifetime rule of `items`; in THESE calls a filter id always means "against bases[i]" (the predecessor
+ * filters are not available here; mixing the two is out of scope):
+ *        G(i)  = item i                                   where filters[i] == TRC_FILTER_NONE   (bases[i] is not looked at)
+ *                D(filters[i], esize, item i, bases[i])   otherwise                             (the filters against a base, above)
+ * The whole contract:  encode  ==  trc_encode_planes_dev(codec, V([G(0) .. G(count - 1)], esize, chunk), ...)  byte for byte; the pad
+ * stays zero; plan, M, NC, first[] and pitch are the unfiltered batch's.  filters == NULL or all TRC_FILTER_NONE IS the unfiltered
+ * batched call and launches its kernels.  For an item the call touches with filter 1 or 2, bases[i] must be non-NULL and 16-byte
+ * aligned; the kernels read [0, n[i]) of it and nothing else (no slack needed; its last partial vector is moved element by
+ * element).  On decode bases[i] == items[i].d_ptr is the in-place case and is allowed; any OTHER overlap of a base with an item is
+ * not checked and gives undefined results.  Order of checks: the plan (host only), the filters (the item's index in the message),
+ * then pointers and buffers.  The base pointers travel as a uint64 array behind the chunk map of the table:
+ * trc_planes_bbatch_table_bytes = trc_planes_batch_table_bytes + 8 * count rounded up to 256, and the work-bytes functions are the
+ * unfiltered batch's plus that.  The join is elementwise (no scan).  The TRCB container has no place for a base: these batches
+ * have no host-pointer container yet. */
+int trc_planes_split_bbatch_dev(const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
+                                unsigned esize, uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream);
+int trc_planes_join_bbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const void *const *bases,
+                               const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
+                               unsigned esize, uint32_t chunk, void *d_table, size_t table_bytes, void *stream);
+size_t trc_planes_bbatch_table_bytes(size_t count, uint64_t chunks);
+size_t trc_planes_bbatch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk);
+size_t trc_planes_bbatch_range_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                          size_t first_item, size_t item_count);
+int trc_encode_bplanes_batch_dev(int codec, const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
+                                 unsigned esize, uint32_t chunk, uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                 uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                 void *d_work, size_t work_bytes, void *stream);
+int trc_decode_bplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload, const trc_planes_item *items,
+                                 const void *const *bases, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
                                  unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                  void *d_work, size_t work_bytes, void *stream);
 

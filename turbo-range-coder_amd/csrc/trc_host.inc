@@ -131,6 +131,7 @@ struct HostCtx {
     hipStream_t s_in = nullptr, s_out = nullptr, s_k[TRC_NKS_MAX] = {};
     uint8_t *d_in = nullptr;   size_t cap_in = 0;      // plain bytes (encode input / decode output) of the shard
     uint8_t *d_cont = nullptr; size_t cap_cont = 0;    // directory slice | payload regions of the shard
+    uint8_t *d_base = nullptr; size_t cap_base = 0;    // the base of a planes call against one (trc_bplanes.inc)
     uint8_t *d_work[TRC_NKS_MAX] = {}; size_t cap_work[TRC_NKS_MAX] = {};   // one workspace per coder stream
     uint8_t *d_small = nullptr;                        // cdf (1 KiB) | totals (8 B x 4096 slices at 2048) | status
     // pageable caller buffers travel in PIECES (host_piece(): 8 MB) through three pinned slots per direction -- the unit of the
@@ -357,7 +358,8 @@ int ctx_init(HostCtx &c, int dev)
         if (c.d_in) (void)hipFree(c.d_in);
         if (c.d_cont) (void)hipFree(c.d_cont);
         if (c.d_small) (void)hipFree(c.d_small);
-        c.d_in = c.d_cont = c.d_small = nullptr; c.cap_in = c.cap_cont = 0;
+        if (c.d_base) (void)hipFree(c.d_base);
+        c.d_in = c.d_cont = c.d_small = c.d_base = nullptr; c.cap_in = c.cap_cont = c.cap_base = 0;
         if (c.out) c.out->drain();
         for (int i = 0; i < TRC_NSLOT; i++) {
             if (c.pin_in[i]) (void)hipHostFree(c.pin_in[i]);

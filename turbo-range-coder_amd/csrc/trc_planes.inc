@@ -66,13 +66,20 @@ int trc_planes_filter_arg(const char *who, int filter);     // trc_fplanes.hip: 
 
 // The strided forms (trc_fplanes.hip, trc_splanes.inc) are the same three calls with another split / join: stride 1 is the fplanes
 // call, whose kernels it launches.  The stride itself is vetted by trc_splanes.inc before it gets here.
-static int split_any(int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg, void *d_planes, size_t pitch, void *d_tail, void *stream)
+// A filter against a BASE buffer (trc_bplanes.hip) travels the same way, as the "stride" PLANES_VS_BASE with the base next to it: its
+// split and join are elementwise and have no restart.  What can be said about the base is said before anything is enqueued.
+#define PLANES_VS_BASE 0
+int trc_bplanes_base_arg(const char *who, const void *d_base);          // trc_bplanes.hip
+int trc_bplanes_overlap_arg(const char *who, const void *d_base, size_t base_bytes, const void *d_out, size_t n);
+static int split_any(int filter, int stride, const void *d_in, const void *d_base, size_t n, unsigned esize, uint32_t seg, void *d_planes, size_t pitch, void *d_tail, void *stream)
 {
+    if (stride == PLANES_VS_BASE) return trc_planes_split_base_dev(filter, d_in, d_base, n, esize, d_planes, pitch, d_tail, stream);
     return stride == 1 ? trc_planes_split_filter_dev(filter, d_in, n, esize, seg, d_planes, pitch, d_tail, stream)
                        : trc_planes_split_sfilter_dev(filter, stride, d_in, n, esize, seg, d_planes, pitch, d_tail, stream);
 }
-static int join_any(int filter, int stride, const void *d_planes, size_t pitch, const void *d_tail, size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream)
+static int join_any(int filter, int stride, const void *d_planes, size_t pitch, const void *d_tail, const void *d_base, size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream)
 {
+    if (stride == PLANES_VS_BASE) return trc_planes_join_base_dev(filter, d_planes, pitch, d_tail, d_base, n, esize, d_out, stream);
     return stride == 1 ? trc_planes_join_filter_dev(filter, d_planes, pitch, d_tail, n, esize, seg, d_out, stream)
                        : trc_planes_join_sfilter_dev(filter, stride, d_planes, pitch, d_tail, n, esize, seg, d_out, stream);
 }
@@ -80,10 +87,11 @@ static int join_any(int filter, int stride, const void *d_planes, size_t pitch, 
 static int planes_encode_dev(int codec, int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
                              uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
                              uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
-                             void *d_work, size_t work_bytes, void *stream)
+                             void *d_work, size_t work_bytes, void *stream, const void *d_base = nullptr)
 {
     int rc = trc_planes_filter_arg("encode_planes", filter);
     if (rc) return rc;
+    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_base_arg("encode_planes", d_base))) return rc;
     if ((rc = planes_common("encode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
@@ -95,7 +103,7 @@ static int planes_encode_dev(int codec, int filter, int stride, const void *d_in
     if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
         return fail(TRC_E_ARG, "encode_planes: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned");
     uint8_t *w = (uint8_t *)d_work;
-    if ((rc = split_any(filter, stride, d_in, n, esize, chunk, w, P.slice, d_tail, stream))) return rc;
+    if ((rc = split_any(filter, stride, d_in, d_base, n, esize, chunk, w, P.slice, d_tail, stream))) return rc;
     for (unsigned k = 0; k < esize; k++) {
         uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
         uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
@@ -124,10 +132,11 @@ extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsi
 
 static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
                              size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
-                             void *d_out, void *d_work, size_t work_bytes, void *stream)
+                             void *d_out, void *d_work, size_t work_bytes, void *stream, const void *d_base = nullptr)
 {
     int rc = trc_planes_filter_arg("decode_planes", filter);
     if (rc) return rc;
+    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_base_arg("decode_planes", d_base))) return rc;
     if ((rc = planes_common("decode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
@@ -135,6 +144,7 @@ static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *
     if (work_bytes < esize * P.slice) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, esize * P.slice);
     if (!d_out || ((uintptr_t)d_out & 15)) return fail(TRC_E_ARG, "decode_planes: d_out must be 16-byte aligned");
     if (n % esize && !d_tail) return fail(TRC_E_ARG, "decode_planes: %zu tail bytes and no tail buffer", n % esize);
+    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_overlap_arg("decode_planes", d_base, P.m * esize, d_out, n))) return rc;
     const TrcCodec &r = codec_row(codec);
     uint8_t *w = (uint8_t *)d_work;
     for (unsigned k = 0; k < esize; k++) {
@@ -142,7 +152,7 @@ static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *
         if ((rc = trc_decode_dev(codec, d_clen + k * P.nc, (const uint8_t *)d_payload + k * P.buf, P.m, chunk,
                                  r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return join_any(filter, stride, w, P.slice, d_tail, n, esize, chunk, d_out, stream);
+    return join_any(filter, stride, w, P.slice, d_tail, d_base, n, esize, chunk, d_out, stream);
 }
 extern "C" int trc_decode_fplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
                                       size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
@@ -160,10 +170,11 @@ extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const vo
 static int planes_decode_range_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload,
                                    size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
                                    const uint16_t *d_cdf, unsigned cdfnum,
-                                   void *d_out, void *d_work, size_t work_bytes, void *stream)
+                                   void *d_out, void *d_work, size_t work_bytes, void *stream, const void *d_base = nullptr)
 {
     int rc = trc_planes_filter_arg("decode_planes_range", filter);
     if (rc) return rc;
+    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_base_arg("decode_planes_range", d_base))) return rc;
     if ((rc = planes_common("decode_planes_range", codec, n, esize, d_work))) return rc;
     const size_t m = n / esize;
     if ((rc = check_common(codec, m, chunk, d_cdf, cdfnum))) return rc;
@@ -179,13 +190,15 @@ static int planes_decode_range_dev(int codec, int filter, int stride, const uint
     const size_t pitch = trc_planes_pitch(n, esize);                     // the payload areas of the WHOLE container lie this far apart
     const size_t e0 = first_chunk * (size_t)chunk, e1 = (first_chunk + count) * (size_t)chunk;
     const size_t elems = (e1 < m ? e1 : m) - e0;
+    if (d_base) d_base = (const uint8_t *)d_base + e0 * esize;          // (the whole base is given: the range's part of it)
+    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_overlap_arg("decode_planes_range", d_base, elems * esize, d_out, elems * esize))) return rc;
     uint8_t *w = (uint8_t *)d_work;
     for (unsigned k = 0; k < esize; k++) {
         uint8_t *plane = w + k * P.slice;
         if ((rc = trc_decode_range_dev(codec, d_clen + k * nc, (const uint8_t *)d_payload + k * pitch, m, chunk, first_chunk, count,
                                        r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return join_any(filter, stride, w, P.slice, nullptr, elems * esize, esize, chunk, d_out, stream);       // (the range opens a segment)
+    return join_any(filter, stride, w, P.slice, nullptr, d_base, elems * esize, esize, chunk, d_out, stream);       // (the range opens a segment)
 }
 extern "C" int trc_decode_fplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload,
                                             size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
@@ -272,10 +285,11 @@ extern "C" int trc_planes_check(const void *buf, size_t buflen, size_t outlen)
 // ---- host pointers: plain calls on the caller's current device ---------------------------------------------------------------------
 // One context (the one of the host-pointer calls: its buffers, its first coder stream), one copy up, the planar device call, the
 // results back: no slices, no staging threads, no device list.
-//   d_small: CDFs of the planes at 0 (8 x 528 B) | totals at 8192 | cdfini status at 8448 | tail bytes at 8704
+//   d_small: CDFs of the planes at 0 (8 x 528 B) | totals at 8192 | cdfini status at 8448 | tail bytes at 8704 | a base's fingerprint at 8960
 #define PLANES_SMALL_TOT 8192
 #define PLANES_SMALL_STATUS 8448
 #define PLANES_SMALL_TAIL 8704
+#define PLANES_SMALL_FP 8960                        // the fingerprint of a base (the calls against a base, trc_bplanes.inc)
 #define PCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fail(TRC_E_HIP, "%s -> %s", #x, hipGetErrorString(e_)); (void)hipStreamSynchronize(s); return 0; } } while (0)
 
 // the context of the calling thread's current device, locked by the caller through `lk`
@@ -326,9 +340,12 @@ extern "C" int trc_planes_advise(const uint64_t *hist, unsigned filters, unsigne
 // the TRCP container of F(filter, chunk, esize, in) -- of `in` itself with TRC_FILTER_NONE.  filter = PLANES_FILTER_AUTO: the advisor
 // chooses from the bytes on the device (*advice, where given, says how), and `out` receives what the explicit host call writes for
 // that choice: the TRCP container, behind the 16-byte TRCF prefix where the choice is a filter.
+// stride = PLANES_VS_BASE: the container of D(filter, esize, in, base); the m * esize bytes of `base` go to the context's second
+// buffer, and *base_fp receives their fingerprint, computed on the device.
 #define PLANES_FILTER_AUTO (-1)
 static size_t planes_host_encode(int codec, int filter, const void *in, size_t n, unsigned esize, uint32_t chunk,
-                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice = nullptr, int stride = 1)
+                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice = nullptr, int stride = 1,
+                                 const void *base = nullptr, uint64_t *base_fp = nullptr)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
     if (codec_row(codec).low4) { fail(TRC_E_ARG, "encode_planes_host: " PLANES_LOW4, codec); return 0; }      // before anything is uploaded
@@ -357,6 +374,12 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
     int32_t *d_status = (int32_t *)(c.d_small + PLANES_SMALL_STATUS);
     uint8_t *d_tail = c.d_small + PLANES_SMALL_TAIL;
     PCHK(hipMemcpyAsync(c.d_in, in, n, hipMemcpyHostToDevice, s));
+    uint64_t *d_fp = (uint64_t *)(c.d_small + PLANES_SMALL_FP);
+    if (stride == PLANES_VS_BASE) {
+        if (grow(&c.d_base, &c.cap_base, m * esize)) return 0;
+        PCHK(hipMemcpyAsync(c.d_base, base, m * esize, hipMemcpyHostToDevice, s));
+        if (trc_base_fingerprint_dev(c.d_base, m * esize, d_fp, s)) { (void)hipStreamSynchronize(s); return 0; }
+    }
     size_t lead = 0;                                                     // bytes of TRCF prefix in front of the container
     if (filter == PLANES_FILTER_AUTO) {
         std::vector<uint64_t> hist(histb / sizeof(uint64_t));
@@ -374,7 +397,8 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
         }
     }
     if (planes_encode_dev(codec, filter, stride, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
-                              d_clen, d_payload, d_total, d_tail, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
+                              d_clen, d_payload, d_total, d_tail, c.d_work[0], c.cap_work[0], s, stride == PLANES_VS_BASE ? c.d_base : nullptr)) { (void)hipStreamSynchronize(s); return 0; }
+    if (stride == PLANES_VS_BASE) PCHK(hipMemcpyAsync(base_fp, d_fp, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     uint64_t total[8];
     int32_t status[8];
     uint16_t cdf[8 * TRC_PLANES_CDF_STRIDE];
@@ -447,9 +471,11 @@ static void planes_sections(const uint8_t *b, const trc_planes_hdr &h, PlanesSec
     }
 }
 
-// elements [first_chunk * chunk, ...) of `count` chunks -- or, whole = true, everything with the tail -- decoded to c.d_in
+// elements [first_chunk * chunk, ...) of `count` chunks -- or, whole = true, everything with the tail -- decoded to c.d_in.
+// stride = PLANES_VS_BASE: `base` = those elements of the base, in host memory; they go to the context's second buffer.  fp, where
+// given, is what their fingerprint must be: it is computed on the device and compared before anything is decoded.
 static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const trc_planes_hdr &h, bool whole, size_t first_chunk, size_t count, size_t elems,
-                                 int stride = 1)
+                                 int stride = 1, const void *base = nullptr, const uint64_t *fp = nullptr)
 {
     const TrcCodec &r = codec_row(h.codec);
     const unsigned esize = h.esize;
@@ -466,6 +492,21 @@ static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const
     uint8_t *d_payload = c.d_cont + up256(esize * 4 * count + 256);
     uint16_t *d_cdf = (uint16_t *)c.d_small;
     uint8_t *d_tail = c.d_small + PLANES_SMALL_TAIL;
+    if (stride == PLANES_VS_BASE) {
+        uint64_t *d_fp = (uint64_t *)(c.d_small + PLANES_SMALL_FP), got = 0;
+        if (grow(&c.d_base, &c.cap_base, elems * esize)) return 0;
+        PCHK(hipMemcpyAsync(c.d_base, base, elems * esize, hipMemcpyHostToDevice, s));
+        if (fp) {
+            if (trc_base_fingerprint_dev(c.d_base, elems * esize, d_fp, s)) { (void)hipStreamSynchronize(s); return 0; }
+            PCHK(hipMemcpyAsync(&got, d_fp, sizeof got, hipMemcpyDeviceToHost, s));
+            PCHK(hipStreamSynchronize(s));
+            if (got != *fp) {
+                fail(TRC_E_ARG, "decode_planes_host: base fingerprint %016llx, the container was made against %016llx: this is not its base",
+                     (unsigned long long)got, (unsigned long long)*fp);
+                return 0;
+            }
+        }
+    }
     for (unsigned k = 0; k < esize; k++) {
         trc_container_hdr sh;
         memcpy(&sh, S[k].cont, sizeof sh);
@@ -478,12 +519,13 @@ static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const
     }
     if (whole && h.tail) PCHK(hipMemcpyAsync(d_tail, b + h.size - h.tail, h.tail, hipMemcpyHostToDevice, s));
     if (planes_decode_dev(h.codec, filter, stride, d_clen, d_payload, d_tail, nsub, esize, h.chunk, r.cdf ? d_cdf : nullptr, h.cdfnum,
-                              c.d_in, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
+                              c.d_in, c.d_work[0], c.cap_work[0], s, stride == PLANES_VS_BASE ? c.d_base : nullptr)) { (void)hipStreamSynchronize(s); return 0; }
     return nsub;
 }
 
 // the two decoders of a TRCP container whose content is F(filter, chunk, esize, original)
-static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, void *out, size_t outlen, int stride = 1)
+static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, void *out, size_t outlen, int stride = 1,
+                                     const void *base = nullptr, const uint64_t *fp = nullptr)
 {
     if (trc_planes_check(in, inlen, outlen)) return 0;
     trc_planes_hdr h;
@@ -492,7 +534,7 @@ static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, v
     std::unique_lock<std::mutex> lk;
     if (planes_ctx(cp, lk)) return 0;
     const size_t m = (size_t)(h.n / h.esize);
-    if (!planes_host_decode(*cp, filter, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m, stride)) return 0;
+    if (!planes_host_decode(*cp, filter, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m, stride, base, fp)) return 0;
     hipStream_t s = cp->s_k[0];
     PCHK(hipMemcpyAsync(out, cp->d_in, (size_t)h.n, hipMemcpyDeviceToHost, s));
     PCHK(hipStreamSynchronize(s));
@@ -505,7 +547,8 @@ extern "C" size_t trc_decode_planes_host(const void *in, size_t inlen, void *out
     return planes_host_decode_all(TRC_FILTER_NONE, in, inlen, out, outlen);
 }
 
-static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen, size_t offset, size_t len, void *out, int stride = 1)
+static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen, size_t offset, size_t len, void *out, int stride = 1,
+                                       const void *base = nullptr)
 {
     if (trc_planes_check(in, inlen, (size_t)-1)) return 0;
     trc_planes_hdr h;
@@ -521,7 +564,8 @@ static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen,
         HostCtx *cp = nullptr;
         std::unique_lock<std::mutex> lk;
         if (planes_ctx(cp, lk)) return 0;
-        if (!planes_host_decode(*cp, filter, b, h, false, c0, c1 - c0 + 1, elems, stride)) return 0;
+        if (!planes_host_decode(*cp, filter, b, h, false, c0, c1 - c0 + 1, elems, stride,
+                                base ? (const uint8_t *)base + c0 * (size_t)h.chunk * h.esize : nullptr)) return 0;
         hipStream_t s = cp->s_k[0];
         PCHK(hipMemcpyAsync(out, cp->d_in + (offset - c0 * (size_t)h.chunk * h.esize), lb, hipMemcpyDeviceToHost, s));
         PCHK(hipStreamSynchronize(s));
@@ -611,6 +655,10 @@ extern "C" size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *ou
     if (magic == TRC_PLANES_MAGIC) return trc_decode_planes_host(in, inlen, out, outlen);
     if (magic == TRC_FPLANES_MAGIC) return trc_decode_fplanes_host(in, inlen, out, outlen);
     if (magic == TRC_SPLANES_MAGIC) return trc_decode_splanes_host(in, inlen, out, outlen);
+    if (magic == TRC_BPLANES_MAGIC) {
+        fail(TRC_E_ARG, "decode_xplanes_host: a planes container against a base (TRCD): trc_decode_bplanes_host decodes it, given the base");
+        return 0;
+    }
     fail(TRC_E_ARG, "decode_xplanes_host: neither a planes (TRCP) nor a filtered planes (TRCF, TRCS) container");
     return 0;
 }

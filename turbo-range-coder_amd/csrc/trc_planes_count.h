@@ -118,6 +118,26 @@ template <int ESIZE, int S> __device__ __forceinline__ void count_filtered(u32 *
         count_vec<ESIZE>(sm, R.row_x, cshift, w);
     }
 }
+// the same with the predictor of every element given, not derived from the vector: p[j] predicts element j (trc_bplanes.hip)
+template <int ESIZE> __device__ __forceinline__ void count_predicted(u32 *sm, const HistRows &R, u32 cshift, u32 *w, const typename Elem<ESIZE>::T *p)
+{
+    typedef typename Elem<ESIZE>::T T;
+    if (R.with_n) count_vec<ESIZE>(sm, R.row_n, cshift, w);
+    T e[TRC_PLANES_VEC], y[TRC_PLANES_VEC];
+    unpack<ESIZE>(w, e);
+    if (R.with_z) {
+#pragma unroll
+        for (int j = 0; j < TRC_PLANES_VEC; j++) y[j] = fwd<ESIZE, TRC_FILTER_ZDELTA>(e[j], p[j]);
+        pack<ESIZE>(y, w);
+        count_vec<ESIZE>(sm, R.row_z, cshift, w);
+    }
+    if (R.with_x) {
+#pragma unroll
+        for (int j = 0; j < TRC_PLANES_VEC; j++) y[j] = fwd<ESIZE, TRC_FILTER_XOR>(e[j], p[j]);
+        pack<ESIZE>(y, w);
+        count_vec<ESIZE>(sm, R.row_x, cshift, w);
+    }
+}
 // one element x with its predecessor p (0 where it has none)
 template <int ESIZE> __device__ __forceinline__ void count_filtered_elem(u32 *sm, const HistRows &R, u32 cshift, typename Elem<ESIZE>::T x, typename Elem<ESIZE>::T p)
 {

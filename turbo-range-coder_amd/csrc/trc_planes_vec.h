@@ -2,9 +2,12 @@
 // filters' forward step over a vector, the launch shape, the kernel tables' row and the argument rules.
 //   trc_planes.hip              split / join
 //   trc_fplanes.hip             the same behind a zigzag-delta or xor filter, of every stride (join: trc_planes_scan.h)
+//   trc_bplanes.hip             the same behind a zigzag-delta or xor filter against a BASE buffer (elementwise both ways), the
+//                               advisor's histograms against a base, the base's fingerprint
 //   trc_planes_hist.hip         the advisor's histograms of the filtered planes, of every stride (trc_planes_count.h)
 //   trc_planes_batch.hip        split / join over a table of separate allocations; includes
 //     trc_fplanes_batch.inc       the same with a filter per item (join: trc_planes_scan.h)
+//     trc_bplanes_batch.inc       the same with a filter against a base per item (join: elementwise)
 //     trc_splanes_batch.inc       the same with a filter and a stride per item: split, join, histograms
 //     trc_planes_hist_batch.inc   the advisor's histograms per item (trc_planes_count.h)
 //   trc_planes_pack.hip         the batch container's packing (trc_planes_pack.h)
@@ -102,6 +105,16 @@ template <int ESIZE, int FILTER> __device__ __forceinline__ typename Elem<ESIZE>
     if constexpr (FILTER == TRC_FILTER_XOR) return x ^ p;
     const T d = (x - p) & MASK;
     return ((d << 1) ^ ((T)0 - (d >> (W - 1)))) & MASK;
+}
+
+// x of y and the predictor, where the predictor is at hand and no scan is needed (trc_bplanes.hip): clean in the element's width
+template <int ESIZE, int FILTER> __device__ __forceinline__ typename Elem<ESIZE>::T inv(typename Elem<ESIZE>::T y, typename Elem<ESIZE>::T p)
+{
+    typedef typename Elem<ESIZE>::T T;
+    constexpr int W = 8 * ESIZE;
+    constexpr T MASK = (T)~(T)0 >> (8 * sizeof(T) - W);
+    if constexpr (FILTER == TRC_FILTER_XOR) return y ^ p;
+    return (p + ((y >> 1) ^ ((T)0 - (y & 1)))) & MASK;
 }
 
 // the last S elements of the vector in front of vector v, at pe[8 - S .. 7]; only the 16-byte words that hold them are loaded

@@ -3,6 +3,8 @@
 // is the TRCF container with the stride where that one has its reserved field.  Nothing here knows a coder or a kernel.
 
 // the stride is looked at ahead of everything else, pointers included
+// (it also keeps PLANES_VS_BASE, which travels where a stride does inside trc_planes.inc, from ever arriving through a strided call)
+static_assert(PLANES_VS_BASE < 1, "stride_common must refuse the value that selects the kernels against a base");
 static int stride_common(const char *who, int stride)
 {
     if (stride < 1 || stride > TRC_STRIDE_MAX) return fail(TRC_E_ARG, "%s: stride %d (1 .. %d)", who, stride, TRC_STRIDE_MAX);

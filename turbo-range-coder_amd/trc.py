@@ -197,6 +197,25 @@ def lib():
         l.trc_decode_splanes_host.restype = _sz; l.trc_decode_splanes_host.argtypes = [_vp, _sz, _vp, _sz]
         l.trc_decode_splanes_range_host.restype = _sz; l.trc_decode_splanes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
         l.trc_splanes_check.restype = C.c_int; l.trc_splanes_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_split_base_dev.restype = C.c_int
+        l.trc_planes_split_base_dev.argtypes = [C.c_int, _vp, _vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]
+        l.trc_planes_join_base_dev.restype = C.c_int
+        l.trc_planes_join_base_dev.argtypes = [C.c_int, _vp, _sz, _vp, _vp, _sz, C.c_uint, _vp, _vp]
+        l.trc_encode_bplanes_dev.restype = C.c_int
+        l.trc_encode_bplanes_dev.argtypes = [C.c_int, C.c_int, _vp, _vp] + l.trc_encode_planes_dev.argtypes[2:]
+        l.trc_decode_bplanes_dev.restype = C.c_int
+        l.trc_decode_bplanes_dev.argtypes = [C.c_int, C.c_int, _vp, _vp, _vp, _vp] + l.trc_decode_planes_dev.argtypes[4:]
+        l.trc_decode_bplanes_range_dev.restype = C.c_int
+        l.trc_decode_bplanes_range_dev.argtypes = [C.c_int, C.c_int, _vp, _vp, _vp] + l.trc_decode_planes_range_dev.argtypes[3:]
+        l.trc_planes_hist_base_dev.restype = C.c_int; l.trc_planes_hist_base_dev.argtypes = [C.c_uint, _vp, _vp, _sz, C.c_uint, _vp, _vp]
+        l.trc_base_fingerprint_dev.restype = C.c_int; l.trc_base_fingerprint_dev.argtypes = [_vp, _sz, _vp, _vp]
+        l.trc_base_fingerprint_host.restype = C.c_uint64; l.trc_base_fingerprint_host.argtypes = [_vp, _sz]
+        l.trc_bplanes_bound.restype = _sz; l.trc_bplanes_bound.argtypes = [_sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_encode_bplanes_host.restype = _sz
+        l.trc_encode_bplanes_host.argtypes = [C.c_int, C.c_int, _vp, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint]
+        l.trc_decode_bplanes_host.restype = _sz; l.trc_decode_bplanes_host.argtypes = [_vp, _sz, _vp, _sz, _vp, _sz]
+        l.trc_decode_bplanes_range_host.restype = _sz; l.trc_decode_bplanes_range_host.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _vp]
+        l.trc_bplanes_check.restype = C.c_int; l.trc_bplanes_check.argtypes = [_vp, _sz, _sz]
         _it = C.POINTER(PlanesItem)
         l.trc_planes_batch_plan_host.restype = C.c_int
         l.trc_planes_batch_plan_host.argtypes = [_it, _sz, C.c_uint, C.c_uint32, C.POINTER(PlanesBatchPlan), C.POINTER(C.c_uint64)]
@@ -221,6 +240,19 @@ def lib():
         l.trc_encode_fplanes_batch_dev.argtypes = [C.c_int, _it, _fl] + l.trc_encode_planes_batch_dev.argtypes[2:]
         l.trc_decode_fplanes_batch_dev.restype = C.c_int
         l.trc_decode_fplanes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _fl] + l.trc_decode_planes_batch_dev.argtypes[4:]
+        _bs = C.POINTER(C.c_void_p)                 # the per-item bases of the batch calls against a base: a host array, or None
+        l.trc_planes_split_bbatch_dev.restype = C.c_int
+        l.trc_planes_split_bbatch_dev.argtypes = [_it, _bs, _fl] + l.trc_planes_split_batch_dev.argtypes[1:]
+        l.trc_planes_join_bbatch_dev.restype = C.c_int
+        l.trc_planes_join_bbatch_dev.argtypes = [_vp, _sz, _it, _bs, _fl] + l.trc_planes_join_batch_dev.argtypes[3:]
+        l.trc_planes_bbatch_table_bytes.restype = _sz; l.trc_planes_bbatch_table_bytes.argtypes = [_sz, C.c_uint64]
+        l.trc_planes_bbatch_work_bytes.restype = _sz; l.trc_planes_bbatch_work_bytes.argtypes = l.trc_planes_batch_work_bytes.argtypes
+        l.trc_planes_bbatch_range_work_bytes.restype = _sz
+        l.trc_planes_bbatch_range_work_bytes.argtypes = l.trc_planes_batch_range_work_bytes.argtypes
+        l.trc_encode_bplanes_batch_dev.restype = C.c_int
+        l.trc_encode_bplanes_batch_dev.argtypes = [C.c_int, _it, _bs, _fl] + l.trc_encode_planes_batch_dev.argtypes[2:]
+        l.trc_decode_bplanes_batch_dev.restype = C.c_int
+        l.trc_decode_bplanes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _bs, _fl] + l.trc_decode_planes_batch_dev.argtypes[4:]
         _ad = C.POINTER(PlanesAdvice)               # the batch advisor: advice per item, or None
         l.trc_planes_hist_batch_bytes.restype = _sz; l.trc_planes_hist_batch_bytes.argtypes = [_sz, C.c_uint]
         l.trc_planes_hist_batch_dev.restype = C.c_int
@@ -642,6 +674,29 @@ def planes_join_sbatch(d_planes, offset, pitch, items, filters, strides, count, 
                                           count, first_item, item_count, esize, chunk, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
 
 
+def planes_bases(bases, count):
+    """the per-item bases of a batch as the host array the bbatch calls take: None, or a sequence of `count` device tensors,
+    addresses or None.  Values are not judged here: the library does that."""
+    if bases is None:
+        return None
+    b = [x.data_ptr() if hasattr(x, "data_ptr") else x for x in bases]
+    if len(b) != count:
+        raise TrcError("bases: one entry per item of the batch")
+    return (C.c_void_p * max(count, 1))(*b)
+
+
+def planes_split_bbatch(items, bases, filters, count, esize, chunk, d_planes, pitch, d_table, table_bytes):
+    """enqueue trc_planes_split_bbatch_dev: planes_split_batch of the items, item i filtered against bases[i] (see planes_bases)"""
+    _chk(lib().trc_planes_split_bbatch_dev(items, planes_bases(bases, count), planes_filters(filters, count), count, esize, chunk,
+                                           d_planes.data_ptr(), pitch, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
+def planes_join_bbatch(d_planes, offset, pitch, items, bases, filters, count, first_item, item_count, esize, chunk, d_table, table_bytes):
+    """enqueue trc_planes_join_bbatch_dev from d_planes[offset:], the inverse of planes_split_bbatch (bases, filters: the whole batch's)"""
+    _chk(lib().trc_planes_join_bbatch_dev(d_planes.data_ptr() + offset, pitch, items, planes_bases(bases, count), planes_filters(filters, count),
+                                          count, first_item, item_count, esize, chunk, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
 class PlanesBatchCoder:
     """The coded buffers of one batch of device tensors of one element size (bf16 / fp16: 2, fp32: 4, fp64 / int64: 8), coded by
     trc_encode_planes_batch_dev as the planes of their virtual buffer: self.clen / payload / total / cdf / status are laid out as
@@ -652,9 +707,12 @@ class PlanesBatchCoder:
     choice in self.filters and what decided in self.advice, and codes exactly as if that list had been given.  strides (None, one
     int for all items, or one per item, each 1 .. 8) predicts a filtered item from the element that many back -- rows of K fields,
     interleaved channels: the trc_*_splanes_batch_dev calls where an item with a filter has a stride above 1, today's calls
-    otherwise; with filters="auto" the advisor chooses under these strides.  Plumbing only."""
+    otherwise; with filters="auto" the advisor chooses under these strides.  bases (a list of one tensor or None per item):
+    filters[i] then means "against bases[i]" -- the trc_*_bplanes_batch_dev calls; decode(bases=...) may be given other bases (the
+    output tensors themselves: in place).  It cannot be combined with strides or filters="auto", and pack() raises: the TRCB
+    container has no place for a base.  Plumbing only."""
 
-    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None, strides=None):
+    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None, strides=None, bases=None):
         """esize: the element size where the tensors do not say it themselves (uint8 tensors of whole elements)"""
         import torch
         self.torch = torch
@@ -668,10 +726,15 @@ class PlanesBatchCoder:
         self.auto, self.advice = isinstance(filters, str) and filters == "auto", None
         self.filters = None if self.auto else planes_filters(filters, self.count)
         self.strides = planes_strides(strides, self.count)
+        if bases is not None and (strides is not None or self.auto):
+            raise ValueError("bases cannot be combined with strides or filters=\"auto\": a filter id then means \"against bases[i]\"")
+        self._bases = None if bases is None else list(bases)   # (kept alive: the array below holds addresses only)
+        self.bases = planes_bases(self._bases, self.count)
         self.plan, self.first = planes_batch_plan(self.items, self.count, self.esize, chunk)
         self.nch, self.pitch = self.plan["chunks"], self.plan["pitch"]
         self.cdfnum = _cdfnum(codec, cdfnum, prm)
-        self.work_bytes = lib().trc_planes_batch_work_bytes(codec, self.items, self.count, self.esize, chunk)
+        self.work_bytes = (lib().trc_planes_bbatch_work_bytes if self.bases is not None else lib().trc_planes_batch_work_bytes)(
+            codec, self.items, self.count, self.esize, chunk)
         if self.work_bytes == 0:
             raise TrcError("bad (codec, tensors, chunk)")
         self.guard, self._guards = guard, []
@@ -703,7 +766,9 @@ class PlanesBatchCoder:
         st = self.codec in STATIC
         tail = (self.count, self.esize, self.chunk, self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
                 self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream())
-        if self.filters is None:
+        if self.bases is not None:
+            _chk(lib().trc_encode_bplanes_batch_dev(self.codec | flags, self.items, self.bases, self.filters, *tail))
+        elif self.filters is None:
             _chk(lib().trc_encode_planes_batch_dev(self.codec | flags, self.items, *tail))
         elif self.strided():
             _chk(lib().trc_encode_splanes_batch_dev(self.codec | flags, self.items, self.filters, self.strides, *tail))
@@ -715,19 +780,24 @@ class PlanesBatchCoder:
         return self.filters is not None and self.strides is not None and \
             any(f != FILTER_NONE and s > 1 for f, s in zip(self.filters[:self.count], self.strides[:self.count]))
 
-    def decode(self, first_item=0, item_count=None, out=None, flags=0):
+    def decode(self, first_item=0, item_count=None, out=None, flags=0, bases=None):
         """items [first_item, first_item + item_count) into out[i] (a list of count tensors, None outside the range; default: the
-        encoded tensors), in a workspace of its own that grows with the requested chunks"""
+        encoded tensors), in a workspace of its own that grows with the requested chunks.  bases (a coder with bases): the bases
+        to decode against instead of the coder's own, one per item, None outside the range"""
         item_count = self.count - first_item if item_count is None else item_count
         items = self.items if out is None else self._items(list(out))
-        need = lib().trc_planes_batch_range_work_bytes(self.codec, items, self.count, self.esize, self.chunk, first_item, item_count)
+        range_bytes = lib().trc_planes_bbatch_range_work_bytes if self.bases is not None else lib().trc_planes_batch_range_work_bytes
+        need = range_bytes(self.codec, items, self.count, self.esize, self.chunk, first_item, item_count)
         if need > self.range_work_bytes:
             self.range_work, self.range_work_bytes = self._buf(need), need
         if self.range_work is None:                            # nothing to size a workspace by: the call rejects or ignores these arguments itself
             self.range_work = self._buf(0)
         tail = (self.count, first_item, item_count, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
                 self.range_work.data_ptr(), self.range_work_bytes, self._stream())
-        if self.filters is None:
+        if self.bases is not None:
+            _chk(lib().trc_decode_bplanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items,
+                                                    self.bases if bases is None else planes_bases(list(bases), self.count), self.filters, *tail))
+        elif self.filters is None:
             _chk(lib().trc_decode_planes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, *tail))
         elif self.strided():
             _chk(lib().trc_decode_splanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.filters,
@@ -741,6 +811,8 @@ class PlanesBatchCoder:
         device tensor trimmed to its size, with what remains of the planes_batch_bound bytes readable behind it; the size).  guard:
         0xA5 from the container's start through to the bound and that many bytes past it; self.pack_guard = the tensor's bytes behind
         the container, which must still be 0xA5.  The full buffer stays in self.packed."""
+        if self.bases is not None:
+            raise TrcError("pack: the TRCB container has no place for a base; a batch against bases has no container")
         st = self.codec in STATIC
         strided = self.strided()
         bound = (lib().trc_planes_sbatch_bound if strided else lib().trc_planes_batch_bound)(self.codec, self.items, self.count, self.esize, self.chunk, self.cdfnum)
@@ -1196,6 +1268,133 @@ def splanes_check(buf, outlen=None):
     """trc_splanes_check on a TRCS container in host memory (needs no device); raises TrcError with the library's reason"""
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
     _chk(lib().trc_splanes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
+
+
+# ------------------------------------------------ byte planes relative to a base buffer (include/trc_hip.h) ---
+BPLANES_MAGIC = 0x44435254                                     # "TRCD"
+BPLANES_HDR = 32
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def planes_split_base(filt, d_in, d_base, n, esize, d_planes, pitch, d_tail=None):
+    """enqueue trc_planes_split_base_dev: planes_split of the elements filtered against those of d_base (None with FILTER_NONE)"""
+    _chk(lib().trc_planes_split_base_dev(filt, d_in.data_ptr(), _ptr(d_base), n, esize, d_planes.data_ptr(), pitch, _ptr(d_tail), _cur_stream(d_in)))
+
+
+def planes_join_base(filt, d_planes, pitch, d_tail, d_base, n, esize, d_out):
+    """enqueue trc_planes_join_base_dev, the inverse of planes_split_base; d_out may be d_base itself (in place)"""
+    _chk(lib().trc_planes_join_base_dev(filt, d_planes.data_ptr(), pitch, _ptr(d_tail), _ptr(d_base), n, esize, d_out.data_ptr(), _cur_stream(d_out)))
+
+
+class BasePlanesCoder(PlanesCoder):
+    """PlanesCoder through the trc_*_bplanes_dev calls: the same buffers and results, of the elements filtered against a base that
+    every call is given.  filter=FILTER_NONE is the unfiltered coder, and d_base may then be None."""
+
+    def __init__(self, codec, n, esize, chunk=4096, device="cuda", cdfnum=256, prm=(5, 6), guard=0, filter=FILTER_NONE):
+        super().__init__(codec, n, esize, chunk, device, cdfnum=cdfnum, prm=prm, guard=guard)
+        self.filter = filter
+
+    def encode(self, d_in, d_base, n=None, flags=0):
+        n = self.n if n is None else n
+        st = self.codec in STATIC
+        _chk(lib().trc_encode_bplanes_dev(self.codec | flags, self.filter, d_in.data_ptr(), _ptr(d_base), n, self.esize, self.chunk,
+                                          self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                                          self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.tail.data_ptr(),
+                                          self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode(self, d_out, d_base, n=None, flags=0):
+        """d_out may be d_base itself: the delta is then applied in place"""
+        n = self.n if n is None else n
+        _chk(lib().trc_decode_bplanes_dev(self.codec | flags, self.filter, self.clen.data_ptr(), self.payload.data_ptr(), self.tail.data_ptr(),
+                                          _ptr(d_base), n, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None,
+                                          self.cdfnum, d_out.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream()))
+
+    def decode_range(self, d_out, d_base, first, count, n=None, flags=0):
+        """elements [first * chunk, min(m, (first + count) * chunk)) to d_out[0:]; d_base is the WHOLE base"""
+        n = self.n if n is None else n
+        need = lib().trc_planes_range_work_bytes(self.codec, n, self.esize, self.chunk, count)
+        if need > self.range_work_bytes:
+            self.range_work, self.range_work_bytes = self._buf(need), need
+        if self.range_work is None:
+            self.range_work = self._buf(0)
+        _chk(lib().trc_decode_bplanes_range_dev(self.codec | flags, self.filter, self.clen.data_ptr(), self.payload.data_ptr(), _ptr(d_base),
+                                                n, self.esize, self.chunk, first, count,
+                                                self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
+                                                d_out.data_ptr(), self.range_work.data_ptr(), self.range_work_bytes, self._stream()))
+
+
+def planes_hist_base(filters, d_in, d_base, n, esize, d_hist):
+    """enqueue trc_planes_hist_base_dev: planes_hist with the rows of filters 1 and 2 counted against d_base"""
+    _chk(lib().trc_planes_hist_base_dev(filters, d_in.data_ptr(), _ptr(d_base), n, esize, d_hist.data_ptr(), _cur_stream(d_in)))
+
+
+def base_fingerprint_enqueue(d_base, nbytes, d_fp):
+    """enqueue trc_base_fingerprint_dev: the fingerprint of d_base[:nbytes] into the 8 bytes of d_fp (device tensors); does not wait"""
+    _chk(lib().trc_base_fingerprint_dev(d_base.data_ptr(), nbytes, d_fp.data_ptr(), _cur_stream(d_base)))
+
+
+def base_fingerprint(d_base, nbytes=None):
+    """trc_base_fingerprint_dev on a uint8 device tensor -> the fingerprint (synchronises)"""
+    import torch
+    nbytes = d_base.numel() if nbytes is None else nbytes
+    d_fp = torch.full((8,), 0xA5, dtype=torch.uint8, device=d_base.device)
+    base_fingerprint_enqueue(d_base, nbytes, d_fp)
+    return int(d_fp.cpu().numpy().view("<u8")[0])
+
+
+def base_fingerprint_host(data):
+    """trc_base_fingerprint_host (needs no device)"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    return int(lib().trc_base_fingerprint_host(data.ctypes.data, data.size))
+
+
+def bplanes_bound(n, esize, chunk=0, cdfnum=0):
+    return lib().trc_bplanes_bound(n, esize, chunk, cdfnum)
+
+
+def host_encode_bplanes(codec, filt, data, base, esize, chunk=0, cdfnum=256, prm=(5, 6)):
+    """trc_encode_bplanes_host -> the TRCD container (np.uint8): 32 bytes, then the TRCP container of the data filtered against base"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    base = np.ascontiguousarray(base, dtype=np.uint8)
+    if base.size < data.size - data.size % esize:
+        raise ValueError("the base holds %d bytes, the elements take %d" % (base.size, data.size - data.size % esize))
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(bplanes_bound(data.size, esize, chunk, cn), 64), dtype=np.uint8)
+    l = lib().trc_encode_bplanes_host(codec, filt, data.ctypes.data, base.ctypes.data, data.size, esize, chunk, out.ctypes.data, out.size, cn)
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy()
+
+
+def _host_decode_base_guarded(name, comp, base, length, offset=None):
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    base = np.ascontiguousarray(base, dtype=np.uint8)
+    out = np.full(length + 64, 0xA5, dtype=np.uint8)
+    f = getattr(lib(), name)
+    if offset is None:
+        l = f(comp.ctypes.data, comp.size, base.ctypes.data, base.size, out.ctypes.data, length)
+    else:
+        l = f(comp.ctypes.data, comp.size, base.ctypes.data, base.size, offset, length, out.ctypes.data)
+    if l != length or not (out[length:] == 0xA5).all():
+        raise TrcError(lib().trc_last_error().decode() if l != length else name + " wrote past its output")
+    return out[:length].copy()
+
+
+def host_decode_bplanes(comp, base, n):
+    return _host_decode_base_guarded("trc_decode_bplanes_host", comp, base, n)
+
+
+def host_decode_bplanes_range(comp, base, offset, length):
+    return _host_decode_base_guarded("trc_decode_bplanes_range_host", comp, base, length, offset)
+
+
+def bplanes_check(buf, outlen=None):
+    """trc_bplanes_check on a TRCD container in host memory (needs no device); raises TrcError with the library's reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_bplanes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
 
 
 def encode_host_container(codec, data, chunk, cdf=None, cdfnum=256, prm=(5, 6)):
