@@ -12,7 +12,10 @@ the sequence tests/test_gpu_arena.py runs per case and poison.
 The slack of an output is "readable/writable" in the header.  What the kernels do to the slack of d_work, d_clen, d_total, d_status
 and to d_payload[total + 64, n + TRC_PAD) was recorded once over all cases (TRC_ARENA_RECORD=<file> makes the audit record instead
 of judge; profiles/arena/arena_notes.md holds the result): ALLOW lists every such write, everything else is a hard rule.  No coder
-wrote any of it, so ALLOW is empty and every rule is hard."""
+wrote any of it, so ALLOW is empty and every rule is hard.
+
+The byte-plane calls use the same Layout and Arena from tests/gpu_planes_arena.py: further buffer kinds with their own alignment,
+a slack per kind (none behind a base or a batch item), an alias for the two names of an in-place decode, and PLANES_ALLOW."""
 import hashlib
 import os
 
@@ -32,6 +35,15 @@ BASE_ALIGN = 512                                               # layout offsets 
 ALIGN = {"in": 16, "out": 16, "work": 256, "total": 8, "clen": 4, "payload": 2, "cdf": 256, "status": 256}
 EXACT = ("in", "out", "work", "total", "clen", "payload")      # the header states nothing for d_cdf and d_status: they stay 256-aligned
 KIND = {"range_out": "out", "range_work": "work", "cdfini_work": "work"}
+# the byte-plane calls (tests/gpu_planes_arena.py): a base and a batch item are read in their stated bytes only, so they get NO slack
+# and end where the poison of the guard zone begins; planes and tables are 256-byte aligned, the planes a batched join reads 64;
+# payload4: d_payload of the pack / packed-decode calls (4); histograms, fingerprint, container and its size 8; the 8-byte tail
+# buffer has no stated alignment and lies at an odd address
+ALIGN.update({"base": 16, "item": 16, "planes": 256, "table": 256, "jplanes": 64, "payload4": 4, "hist": 8, "fp": 8, "cont": 8,
+              "size": 8, "tail": 1})
+EXACT += ("base", "item", "planes", "table", "jplanes", "payload4", "hist", "fp", "cont", "size")
+ODD = ("tail",)
+SLACK = {"base": 0, "item": 0}                                 # bytes of slack behind the stated size; every other kind: TRC_PAD
 POISONS = ("random", "ff")
 TRC_E_WORK = -3
 AVAILABLE_SHAPES = ((129, 100), (66, 37), (63, None))          # (nchunks, tail); None: a full last chunk -- less than one wave
@@ -41,6 +53,9 @@ MIX_MIN = 30                                                   # raw and coded c
 # (coder name, buffer kind) -> the furthest byte a call writes behind the stated size (d_payload on the encode side: behind
 # `total`), as recorded on the MI355X over all cases and both poisons; a pair that is not listed must not be written at all
 ALLOW = {}
+# the same for the byte-plane calls (tests/gpu_planes_arena.py), keyed ("<call family>:<coder>", buffer kind), as recorded over
+# tests/test_gpu_planes_arena.py (profiles/arena/planes_arena_notes.md): nothing was written there either
+PLANES_ALLOW = {}
 
 RECORDING = bool(os.environ.get("TRC_ARENA_RECORD"))
 RECORD = {}                                                    # filled in recording mode: (coder, kind) -> furthest offset
@@ -55,19 +70,23 @@ class Buf:
     def __init__(self, name, size, start):
         self.name, self.size, self.start = name, size, start
         self.kind = kind_of(name)
-        self.end = start + size + PAD                          # the slack is exactly TRC_PAD
+        self.slack = SLACK.get(self.kind, PAD)                 # exactly TRC_PAD; none behind a base or a batch item
+        self.end = start + size + self.slack
 
 
 class Layout:
-    """where the buffers of `specs` = [(name, stated size), ...] lie, as offsets from an address that is a multiple of BASE_ALIGN"""
+    """where the buffers of `specs` = [(name, stated size), ...] lie, as offsets from an address that is a multiple of BASE_ALIGN.
+    alias = {second name: buffer}: two names for one extent (an in-place decode: `out` is `base`); the second name has no region"""
 
-    def __init__(self, specs):
+    def __init__(self, specs, alias=None):
         self.bufs, self.by_name = [], {}
         pos = MARGIN
         for name, size in specs:
             a = ALIGN[kind_of(name)]
             pos += ZONE
-            if kind_of(name) in EXACT:                         # the next address = a (mod 2 a): aligned to a, and to nothing more
+            if kind_of(name) in ODD:
+                start = pos | 1
+            elif kind_of(name) in EXACT:                       # the next address = a (mod 2 a): aligned to a, and to nothing more
                 start = pos + (a - pos) % (2 * a)
             else:
                 start = pos + (-pos) % a
@@ -76,6 +95,9 @@ class Layout:
             self.bufs.append(b)
             self.by_name[name] = b
             pos = b.end
+        for second, name in (alias or {}).items():
+            assert second not in self.by_name
+            self.by_name[second] = self.by_name[name]
         self.size = pos + MARGIN
         self.regions = []                                      # (lo, hi, text of the place, offset the reported number counts from)
         prev = None
@@ -85,7 +107,8 @@ class Layout:
             else:
                 self.regions.append((prev.end, b.start, "the guard zone between %s and %s, byte %%d of it" % (prev.name, b.name), prev.end))
             self.regions.append((b.start, b.start + b.size, "%s, byte %%d of its stated %d" % (b.name, b.size), b.start))
-            self.regions.append((b.start + b.size, b.end, "the slack of %s, stated size + %%d" % b.name, b.start + b.size))
+            if b.slack:
+                self.regions.append((b.start + b.size, b.end, "the slack of %s, stated size + %%d" % b.name, b.start + b.size))
             prev = b
         self.regions.append((prev.end, self.size, "the rear margin, byte %%d behind the slack of %s" % prev.name, prev.end))
         self.starts = np.array([r[0] for r in self.regions], dtype=np.int64)
@@ -347,8 +370,8 @@ class ArenaCoder(trc.DeviceCoder):
 
 def slack(arena, name):
     """the soft rule of a buffer's whole slack"""
-    size = arena.layout[name].size
-    return (name, size, size + PAD, size)
+    b = arena.layout[name]
+    return (name, b.size, b.size + b.slack, b.size)
 
 
 def run_case(torch, case, poison, seed, short=None, allow=None, record=None, device="cuda:0"):

@@ -190,3 +190,106 @@ def test_raw_and_coded_mix(codec):
     assert [c.n % c.chunk for c in cases] == [100, 37, 0]
     x = cases[1].data()
     assert x["clen"].size == 66 and int(x["clen"].sum()) == x["payload"].size
+
+
+# ---- the byte-plane calls in the arena (tests/gpu_planes_arena.py) -----------------------------------------------------------
+import gpu_planes_arena as P  # noqa: E402
+
+RESIDUE = {"in": (32, 16), "out": (32, 16), "base": (32, 16), "item": (32, 16), "planes": (512, 256), "work": (512, 256), "table": (512, 256),
+           "jplanes": (128, 64), "payload": (4, 2), "payload4": (8, 4), "clen": (8, 4), "total": (16, 8), "hist": (16, 8), "fp": (16, 8),
+           "cont": (16, 8), "size": (16, 8), "tail": (2, 1), "cdf": (256, 0), "status": (256, 0)}       # kind -> start = r (mod q)
+EVERY_KIND = [("in", 1001), ("i0.item", 2), ("i1.item", 512), ("b0.base", 0), ("b1.base", 33), ("planes", 4 * 256), ("work", 4096),
+              ("table", 256), ("r0.jplanes", 4 * 256), ("payload", 77), ("c.payload4", 78), ("clen", 12), ("total", 32), ("hist", 3 * 2 * 256 * 8),
+              ("fp", 8), ("cont", 1000), ("size", 8), ("tail", 8), ("cdf", 2 * 4 * 264), ("status", 16), ("out", 1001), ("range_out", 24),
+              ("range_work", 8192)]
+
+
+def planes_layouts():
+    """(specs, alias) of one layout with every kind and of the layouts of sections A, B and C"""
+    yield EVERY_KIND, {"io.out": "b1.base"}
+    for fam in P.FLAT_FAMILIES:
+        for esize in P.ESIZES:
+            for m, t in P.flat_shapes(esize):
+                yield P.flat_specs(fam, esize, m, t)
+    for case in P.coded_cases():
+        yield P.coded(*case).specs()
+    b = P.Batch("bbatch", 8)
+    yield b.item_specs() + b.base_specs() + [("planes", 8 * P.up256(b.M)), ("table", 256)] + b.item_specs("o") + [("r0.jplanes", 8 * 256)], None
+
+
+def test_planes_layouts():
+    """every kind lands at its residue and nowhere better; a base and an item end at start + size, every other buffer TRC_PAD
+    later; an alias is a second name of the same buffer and adds no region; no two regions overlap, every byte has one name"""
+    count = 0
+    for specs, alias in planes_layouts():
+        L = GA.Layout(specs, alias)
+        count += 1
+        assert [b.name for b in L.bufs] == [s[0] for s in specs]
+        prev_end = GA.MARGIN
+        for b, (name, size) in zip(L.bufs, specs):
+            q, r = RESIDUE[b.kind]
+            assert b.start % q == r, "%s (%s) at %d: not %d (mod %d)" % (name, b.kind, b.start, r, q)
+            assert b.size == size and b.end == b.start + size + (0 if b.kind in ("base", "item") else trc.PAD), name
+            assert GA.ZONE <= b.start - prev_end < GA.ZONE + q + (256 if b.kind in ("cdf", "status") else 0), name
+            prev_end = b.end
+        assert L.size - prev_end == GA.MARGIN
+        for second, name in (alias or {}).items():
+            assert L[second] is L[name] and second not in [b.name for b in L.bufs] and all(second not in r[2] for r in L.regions)
+        assert L.regions[0][0] == 0 and L.regions[-1][1] == L.size
+        assert all(r[1] == s[0] and r[0] <= r[1] for r, s in zip(L.regions, L.regions[1:]))
+        assert all(r[0] < r[1] or "stated 0" in r[2] for r in L.regions), "an empty region that is not a buffer of 0 bytes"
+    assert count > 200
+    A = GA.Arena(torch, GA.Layout(EVERY_KIND, {"io.out": "b1.base"}), "cpu", "ff", 0)
+    assert A.ptr("tail") % 2 == 1 and A.ptr("cont") % 16 == 8 and A.ptr("r0.jplanes") % 128 == 64 and A.ptr("c.payload4") % 8 == 4
+    assert A.ptr("io.out") == A.ptr("b1.base") and A.ptr("b1.base") % 32 == 16 and A.view("b1.base").numel() == 33 and A.view("i0.item").numel() == 2
+
+
+def test_planes_audit_names_the_byte_behind_an_item_a_pitch_gap_and_the_tail_buffer():
+    """what the byte-plane audits rest on, on CPU tensors: with a split's writes permitted ([0, m) of each plane, [0, t) of the
+    tail), one changed byte directly behind an item or a base, in a pitch gap and in bytes 1 .. 7 of the tail buffer is named"""
+    esize, m, t, pitch = 4, 300, 1, 512
+    specs = [("i0.item", 64), ("b0.base", 48), ("planes", esize * pitch), ("tail", 8), ("out", m * esize + t)]
+    L = GA.Layout(specs)
+    A = GA.Arena(torch, L, "cpu", "random", 2, record=False)
+    writes = P.plane_writes("planes", esize, pitch, m) + [("tail", 0, t)]
+    A.snapshot()
+    for k in range(esize):
+        A.buf[L["planes"].start + k * pitch:L["planes"].start + k * pitch + m] ^= 0x11
+    A.buf[L["tail"].start] ^= 0x11
+    A.audit("a split's own writes", writes, allow={})
+    it, ba, pl, tl = L["i0.item"], L["b0.base"], L["planes"], L["tail"]
+    assert it.end == it.start + 64 and ba.end == ba.start + 48
+    places = [(it.start + 64, "the guard zone between i0.item and b0.base, byte 0 of it"),
+              (ba.start + 48, "the guard zone between b0.base and planes, byte 0 of it"),
+              (pl.start + m, "planes, byte 300 of its stated 2048"), (pl.start + pitch - 1, "planes, byte 511 of its stated 2048"),
+              (pl.start + 3 * pitch + m, "planes, byte %d of its stated 2048" % (3 * pitch + m)),
+              (pl.start + esize * pitch, "the slack of planes, stated size + 0")]
+    places += [(tl.start + i, "tail, byte %d of its stated 8" % i) for i in range(1, 8)]
+    for off, text in places:
+        A.buf[off] ^= 0x80
+        with pytest.raises(AssertionError) as e:
+            A.audit("tag", writes, allow={})
+        assert str(e.value) == "tag: 1 byte(s) changed in " + text, off
+        A.buf[off] ^= 0x80
+    A.audit("restored", writes, allow={})
+
+
+@pytest.mark.parametrize("case", P.coded_cases(), ids=P.case_id)
+def test_coded_planes_inputs_mix_raw_and_coded_chunks(case):
+    """for every input of the coded flat calls the oracle alone gives at least one raw and one coded chunk in every plane; the
+    call's input is the family's inverse filter of the joined planes"""
+    c = P.coded(*case)
+    assert c.planes.shape == (c.esize, c.m) and c.n == c.m * c.esize + c.t and c.nc == trc.nchunks(c.m, c.chunk)
+    assert (c.nc, c.m % c.chunk, c.t, c.range) in ((66, 37, c.esize - 1, (63, 2)), (3, 3, 0, (0, 1)))
+    for k, (raw, coded) in enumerate(c.mix()):
+        assert raw >= 1 and coded >= 1 and raw + coded == c.nc, "%s: plane %d has %d raw and %d coded chunks" % (c.tag, k, raw, coded)
+    assert np.array_equal(P.PL.split(P.forward(c.model, c.d, c.base, c.esize, c.chunk), c.esize)[0], c.planes)
+
+
+def test_planes_allow_list_stays_inside_the_slack():
+    names = set(trc.CODEC_NAMES.values())
+    fams = set(P.CODED_FAMILIES) | set(P.BATCH_FAMILIES)
+    for (key, kind), far in GA.PLANES_ALLOW.items():
+        fam, coder = key.split(":")
+        assert fam in fams and coder in names and kind in ("work", "range_work", "clen", "total", "status", "payload", "payload4", "cdf"), (key, kind)
+        assert 0 <= far < trc.PAD, (key, kind, far)
