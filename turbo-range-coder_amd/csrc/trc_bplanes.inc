@@ -9,18 +9,16 @@ extern "C" int trc_encode_bplanes_dev(int codec, int filter, const void *d_in, c
                                       uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
                                       void *d_work, size_t work_bytes, void *stream)
 {
-    const bool none = filter == TRC_FILTER_NONE;
-    return planes_encode_dev(codec, filter, none ? 1 : PLANES_VS_BASE, d_in, n, esize, chunk, d_cdf, cdfnum, d_status,
-                             d_clen, d_payload, d_total, d_tail, d_work, work_bytes, stream, none ? nullptr : d_base);
+    return planes_encode_dev(codec, pred_base(filter, d_base), d_in, n, esize, chunk, d_cdf, cdfnum, d_status,
+                             d_clen, d_payload, d_total, d_tail, d_work, work_bytes, stream);
 }
 
 extern "C" int trc_decode_bplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
                                       const void *d_base, size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                       void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    const bool none = filter == TRC_FILTER_NONE;
-    return planes_decode_dev(codec, filter, none ? 1 : PLANES_VS_BASE, d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum,
-                             d_out, d_work, work_bytes, stream, none ? nullptr : d_base);
+    return planes_decode_dev(codec, pred_base(filter, d_base), d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum,
+                             d_out, d_work, work_bytes, stream);
 }
 
 extern "C" int trc_decode_bplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_base,
@@ -28,9 +26,8 @@ extern "C" int trc_decode_bplanes_range_dev(int codec, int filter, const uint32_
                                             const uint16_t *d_cdf, unsigned cdfnum,
                                             void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    const bool none = filter == TRC_FILTER_NONE;
-    return planes_decode_range_dev(codec, filter, none ? 1 : PLANES_VS_BASE, d_clen, d_payload, n, esize, chunk, first_chunk, count,
-                                   d_cdf, cdfnum, d_out, d_work, work_bytes, stream, none ? nullptr : d_base);
+    return planes_decode_range_dev(codec, pred_base(filter, d_base), d_clen, d_payload, n, esize, chunk, first_chunk, count,
+                                   d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 
 // ---- the TRCD container: trc_bplanes_hdr (32 B) | the TRCP container of the data filtered against the base -------------------------
@@ -43,14 +40,10 @@ extern "C" size_t trc_bplanes_bound(size_t n, unsigned esize, uint32_t chunk, un
 // the whole check: 0 and the prefix, or TRC_E_ARG with the reason set
 static int bplanes_verdict(const void *buf, size_t buflen, size_t outlen, trc_bplanes_hdr &h)
 {
-    if (!buf || buflen < sizeof h) return fail(TRC_E_ARG, "base planes container: %zu bytes is shorter than the header", buflen);
-    memcpy(&h, buf, sizeof h);
-    if (h.magic != TRC_BPLANES_MAGIC || h.version != 1) return fail(TRC_E_ARG, "base planes container: bad magic/version");
-    if (h.filter != TRC_FILTER_ZDELTA && h.filter != TRC_FILTER_XOR) return fail(TRC_E_ARG, "base planes container: filter %u (1 zigzag delta, 2 xor)", h.filter);
-    if (h.zero) return fail(TRC_E_ARG, "base planes container: reserved field is 0x%x, must be 0", h.zero);
-    if (h.size > buflen) return fail(TRC_E_ARG, "base planes container: states %llu bytes, the buffer holds %zu", (unsigned long long)h.size, buflen);
-    if (h.size <= sizeof h) return fail(TRC_E_ARG, "base planes container: size %llu leaves no room behind the header", (unsigned long long)h.size);
-    const int rc = trc_planes_check((const uint8_t *)buf + sizeof h, (size_t)h.size - sizeof h, outlen);
+    int rc = planes_prefix("base planes container", TRC_BPLANES_MAGIC, buf, buflen, h, [](const trc_bplanes_hdr &d) {
+        return d.zero ? fail(TRC_E_ARG, "base planes container: reserved field is 0x%x, must be 0", d.zero) : (int)TRC_OK; });
+    if (rc) return rc;
+    rc = trc_planes_check((const uint8_t *)buf + sizeof h, (size_t)h.size - sizeof h, outlen);
     if (rc) return rc;
     trc_planes_hdr p;
     memcpy(&p, (const uint8_t *)buf + sizeof h, sizeof p);
@@ -74,8 +67,7 @@ extern "C" size_t trc_encode_bplanes_host(int codec, int filter, const void *in,
     if (!base) { fail(TRC_E_ARG, "encode_bplanes_host: no base"); return 0; }
     if (!out || outcap <= sizeof(trc_bplanes_hdr)) { fail(TRC_E_ARG, "encode_bplanes_host: out holds %zu bytes (trc_bplanes_bound)", outcap); return 0; }
     uint64_t fp = 0;
-    const size_t inner = planes_host_encode(codec, filter, in, n, esize, chunk, (uint8_t *)out + sizeof(trc_bplanes_hdr), outcap - sizeof(trc_bplanes_hdr), cdfnum,
-                                            nullptr, PLANES_VS_BASE, base, &fp);
+    const size_t inner = planes_host_encode(codec, pred_base(filter, base), false, in, n, esize, chunk, (uint8_t *)out + sizeof(trc_bplanes_hdr), outcap - sizeof(trc_bplanes_hdr), cdfnum, nullptr, &fp);
     if (!inner) return 0;
     trc_bplanes_hdr h;
     memset(&h, 0, sizeof h);
@@ -100,7 +92,7 @@ extern "C" size_t trc_decode_bplanes_host(const void *in, size_t inlen, const vo
 {
     trc_bplanes_hdr h;
     if (bplanes_decode_args("decode_bplanes_host", in, inlen, base, base_len, out, outlen, h)) return 0;
-    return planes_host_decode_all(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, out, outlen, PLANES_VS_BASE, base, &h.base_fp);
+    return planes_host_decode_all(pred_base(h.filter, base), (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, out, outlen, &h.base_fp);
 }
 
 // (no fingerprint here: the call uploads the covering elements of the base and never sees the rest)
@@ -109,5 +101,5 @@ extern "C" size_t trc_decode_bplanes_range_host(const void *in, size_t inlen, co
 {
     trc_bplanes_hdr h;
     if (bplanes_decode_args("decode_bplanes_range_host", in, inlen, base, base_len, out, (size_t)-1, h)) return 0;
-    return planes_host_decode_bytes(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out, PLANES_VS_BASE, base);
+    return planes_host_decode_bytes(pred_base(h.filter, base), (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out);
 }

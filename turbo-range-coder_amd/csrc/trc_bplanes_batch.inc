@@ -135,8 +135,7 @@ void trc_bplanes_join_batch_kernel(const uint8_t *__restrict__ planes, size_t pi
 // the batch table with the base pointers behind the chunk map
 extern "C" size_t trc_planes_bbatch_table_bytes(size_t count, uint64_t chunks)
 {
-    const size_t t = trc_planes_batch_table_bytes(count, chunks);
-    return t ? t + up256(8 * count) : 0;
+    return batch_pred_table_bytes(BATCH_PRED_BASED, count, chunks);
 }
 
 // the bases of items [first_item, first_item + item_count) whose filter is 1 or 2 (also the coded calls' check, trc_bplanes.inc)

@@ -64,34 +64,45 @@ static int planes_common(const char *who, int codec, size_t n, unsigned esize, c
 // and join are the plain ones.  The restart length is the chunk, which check_common has vetted by the time split or join see it.
 int trc_planes_filter_arg(const char *who, int filter);     // trc_fplanes.hip: the filter id, with the text of the split / join calls
 
-// The strided forms (trc_fplanes.hip, trc_splanes.inc) are the same three calls with another split / join: stride 1 is the fplanes
-// call, whose kernels it launches.  The stride itself is vetted by trc_splanes.inc before it gets here.
-// A filter against a BASE buffer (trc_bplanes.hip) travels the same way, as the "stride" PLANES_VS_BASE with the base next to it: its
-// split and join are elementwise and have no restart.  What can be said about the base is said before anything is enqueued.
-#define PLANES_VS_BASE 0
+// How a flat call predicts its elements.  The strided forms (trc_fplanes.hip, trc_splanes.inc) are the same three calls with another
+// split / join: stride 1 is the fplanes call, whose kernels it launches, and the stride itself is vetted by trc_splanes.inc before it
+// gets here.  based: the filter is against a BASE buffer (trc_bplanes.hip), whose split and join are elementwise and have no restart;
+// what can be said about the base is said before anything is enqueued.  `base` is a device pointer for the *_dev calls and a host
+// pointer for the host-pointer calls, which upload it.  An unfiltered call is told nothing of stride or base.
+struct PlanesPred { int filter, stride; const void *base; bool based; };
+static PlanesPred pred_none() { return PlanesPred{ TRC_FILTER_NONE, 1, nullptr, false }; }
+static PlanesPred pred_stride(int filter, int stride) { return PlanesPred{ filter, filter == TRC_FILTER_NONE ? 1 : stride, nullptr, false }; }
+static PlanesPred pred_base(int filter, const void *base)
+{
+    const bool none = filter == TRC_FILTER_NONE;
+    return PlanesPred{ filter, 1, none ? nullptr : base, !none };
+}
+// the same predictor for the elements that start `bytes` into the buffer
+static PlanesPred pred_from(PlanesPred p, size_t bytes) { if (p.base) p.base = (const uint8_t *)p.base + bytes; return p; }
+
 int trc_bplanes_base_arg(const char *who, const void *d_base);          // trc_bplanes.hip
 int trc_bplanes_overlap_arg(const char *who, const void *d_base, size_t base_bytes, const void *d_out, size_t n);
-static int split_any(int filter, int stride, const void *d_in, const void *d_base, size_t n, unsigned esize, uint32_t seg, void *d_planes, size_t pitch, void *d_tail, void *stream)
+static int split_any(PlanesPred p, const void *d_in, size_t n, unsigned esize, uint32_t seg, void *d_planes, size_t pitch, void *d_tail, void *stream)
 {
-    if (stride == PLANES_VS_BASE) return trc_planes_split_base_dev(filter, d_in, d_base, n, esize, d_planes, pitch, d_tail, stream);
-    return stride == 1 ? trc_planes_split_filter_dev(filter, d_in, n, esize, seg, d_planes, pitch, d_tail, stream)
-                       : trc_planes_split_sfilter_dev(filter, stride, d_in, n, esize, seg, d_planes, pitch, d_tail, stream);
+    if (p.based) return trc_planes_split_base_dev(p.filter, d_in, p.base, n, esize, d_planes, pitch, d_tail, stream);
+    return p.stride == 1 ? trc_planes_split_filter_dev(p.filter, d_in, n, esize, seg, d_planes, pitch, d_tail, stream)
+                         : trc_planes_split_sfilter_dev(p.filter, p.stride, d_in, n, esize, seg, d_planes, pitch, d_tail, stream);
 }
-static int join_any(int filter, int stride, const void *d_planes, size_t pitch, const void *d_tail, const void *d_base, size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream)
+static int join_any(PlanesPred p, const void *d_planes, size_t pitch, const void *d_tail, size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream)
 {
-    if (stride == PLANES_VS_BASE) return trc_planes_join_base_dev(filter, d_planes, pitch, d_tail, d_base, n, esize, d_out, stream);
-    return stride == 1 ? trc_planes_join_filter_dev(filter, d_planes, pitch, d_tail, n, esize, seg, d_out, stream)
-                       : trc_planes_join_sfilter_dev(filter, stride, d_planes, pitch, d_tail, n, esize, seg, d_out, stream);
+    if (p.based) return trc_planes_join_base_dev(p.filter, d_planes, pitch, d_tail, p.base, n, esize, d_out, stream);
+    return p.stride == 1 ? trc_planes_join_filter_dev(p.filter, d_planes, pitch, d_tail, n, esize, seg, d_out, stream)
+                         : trc_planes_join_sfilter_dev(p.filter, p.stride, d_planes, pitch, d_tail, n, esize, seg, d_out, stream);
 }
 
-static int planes_encode_dev(int codec, int filter, int stride, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+static int planes_encode_dev(int codec, PlanesPred pred, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
                              uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
                              uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
-                             void *d_work, size_t work_bytes, void *stream, const void *d_base = nullptr)
+                             void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = trc_planes_filter_arg("encode_planes", filter);
+    int rc = trc_planes_filter_arg("encode_planes", pred.filter);
     if (rc) return rc;
-    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_base_arg("encode_planes", d_base))) return rc;
+    if (pred.based && (rc = trc_bplanes_base_arg("encode_planes", pred.base))) return rc;
     if ((rc = planes_common("encode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
@@ -103,7 +114,7 @@ static int planes_encode_dev(int codec, int filter, int stride, const void *d_in
     if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
         return fail(TRC_E_ARG, "encode_planes: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned");
     uint8_t *w = (uint8_t *)d_work;
-    if ((rc = split_any(filter, stride, d_in, d_base, n, esize, chunk, w, P.slice, d_tail, stream))) return rc;
+    if ((rc = split_any(pred, d_in, n, esize, chunk, w, P.slice, d_tail, stream))) return rc;
     for (unsigned k = 0; k < esize; k++) {
         uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
         uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
@@ -118,7 +129,7 @@ extern "C" int trc_encode_fplanes_dev(int codec, int filter, const void *d_in, s
                                       uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
                                       void *d_work, size_t work_bytes, void *stream)
 {
-    return planes_encode_dev(codec, filter, 1, d_in, n, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total, d_tail, d_work, work_bytes, stream);
+    return planes_encode_dev(codec, pred_stride(filter, 1), d_in, n, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total, d_tail, d_work, work_bytes, stream);
 }
 
 extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
@@ -130,13 +141,13 @@ extern "C" int trc_encode_planes_dev(int codec, const void *d_in, size_t n, unsi
                                   d_work, work_bytes, stream);
 }
 
-static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+static int planes_decode_dev(int codec, PlanesPred pred, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
                              size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
-                             void *d_out, void *d_work, size_t work_bytes, void *stream, const void *d_base = nullptr)
+                             void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = trc_planes_filter_arg("decode_planes", filter);
+    int rc = trc_planes_filter_arg("decode_planes", pred.filter);
     if (rc) return rc;
-    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_base_arg("decode_planes", d_base))) return rc;
+    if (pred.based && (rc = trc_bplanes_base_arg("decode_planes", pred.base))) return rc;
     if ((rc = planes_common("decode_planes", codec, n, esize, d_work))) return rc;
     PlanesMap P;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
@@ -144,7 +155,7 @@ static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *
     if (work_bytes < esize * P.slice) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, esize * P.slice);
     if (!d_out || ((uintptr_t)d_out & 15)) return fail(TRC_E_ARG, "decode_planes: d_out must be 16-byte aligned");
     if (n % esize && !d_tail) return fail(TRC_E_ARG, "decode_planes: %zu tail bytes and no tail buffer", n % esize);
-    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_overlap_arg("decode_planes", d_base, P.m * esize, d_out, n))) return rc;
+    if (pred.based && (rc = trc_bplanes_overlap_arg("decode_planes", pred.base, P.m * esize, d_out, n))) return rc;
     const TrcCodec &r = codec_row(codec);
     uint8_t *w = (uint8_t *)d_work;
     for (unsigned k = 0; k < esize; k++) {
@@ -152,13 +163,13 @@ static int planes_decode_dev(int codec, int filter, int stride, const uint32_t *
         if ((rc = trc_decode_dev(codec, d_clen + k * P.nc, (const uint8_t *)d_payload + k * P.buf, P.m, chunk,
                                  r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return join_any(filter, stride, w, P.slice, d_tail, d_base, n, esize, chunk, d_out, stream);
+    return join_any(pred, w, P.slice, d_tail, n, esize, chunk, d_out, stream);
 }
 extern "C" int trc_decode_fplanes_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
                                       size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                       void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    return planes_decode_dev(codec, filter, 1, d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
+    return planes_decode_dev(codec, pred_stride(filter, 1), d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
                                      size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
@@ -167,14 +178,14 @@ extern "C" int trc_decode_planes_dev(int codec, const uint32_t *d_clen, const vo
     return trc_decode_fplanes_dev(codec, TRC_FILTER_NONE, d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 
-static int planes_decode_range_dev(int codec, int filter, int stride, const uint32_t *d_clen, const void *d_payload,
+static int planes_decode_range_dev(int codec, PlanesPred pred, const uint32_t *d_clen, const void *d_payload,
                                    size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
                                    const uint16_t *d_cdf, unsigned cdfnum,
-                                   void *d_out, void *d_work, size_t work_bytes, void *stream, const void *d_base = nullptr)
+                                   void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    int rc = trc_planes_filter_arg("decode_planes_range", filter);
+    int rc = trc_planes_filter_arg("decode_planes_range", pred.filter);
     if (rc) return rc;
-    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_base_arg("decode_planes_range", d_base))) return rc;
+    if (pred.based && (rc = trc_bplanes_base_arg("decode_planes_range", pred.base))) return rc;
     if ((rc = planes_common("decode_planes_range", codec, n, esize, d_work))) return rc;
     const size_t m = n / esize;
     if ((rc = check_common(codec, m, chunk, d_cdf, cdfnum))) return rc;
@@ -190,22 +201,22 @@ static int planes_decode_range_dev(int codec, int filter, int stride, const uint
     const size_t pitch = trc_planes_pitch(n, esize);                     // the payload areas of the WHOLE container lie this far apart
     const size_t e0 = first_chunk * (size_t)chunk, e1 = (first_chunk + count) * (size_t)chunk;
     const size_t elems = (e1 < m ? e1 : m) - e0;
-    if (d_base) d_base = (const uint8_t *)d_base + e0 * esize;          // (the whole base is given: the range's part of it)
-    if (stride == PLANES_VS_BASE && (rc = trc_bplanes_overlap_arg("decode_planes_range", d_base, elems * esize, d_out, elems * esize))) return rc;
+    const PlanesPred part = pred_from(pred, e0 * esize);                 // (the whole base is given: the range's part of it)
+    if (part.based && (rc = trc_bplanes_overlap_arg("decode_planes_range", part.base, elems * esize, d_out, elems * esize))) return rc;
     uint8_t *w = (uint8_t *)d_work;
     for (unsigned k = 0; k < esize; k++) {
         uint8_t *plane = w + k * P.slice;
         if ((rc = trc_decode_range_dev(codec, d_clen + k * nc, (const uint8_t *)d_payload + k * pitch, m, chunk, first_chunk, count,
                                        r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    return join_any(filter, stride, w, P.slice, nullptr, d_base, elems * esize, esize, chunk, d_out, stream);       // (the range opens a segment)
+    return join_any(part, w, P.slice, nullptr, elems * esize, esize, chunk, d_out, stream);       // (the range opens a segment)
 }
 extern "C" int trc_decode_fplanes_range_dev(int codec, int filter, const uint32_t *d_clen, const void *d_payload,
                                             size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
                                             const uint16_t *d_cdf, unsigned cdfnum,
                                             void *d_out, void *d_work, size_t work_bytes, void *stream)
 {
-    return planes_decode_range_dev(codec, filter, 1, d_clen, d_payload, n, esize, chunk, first_chunk, count, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
+    return planes_decode_range_dev(codec, pred_stride(filter, 1), d_clen, d_payload, n, esize, chunk, first_chunk, count, d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_planes_range_dev(int codec, const uint32_t *d_clen, const void *d_payload,
                                            size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
@@ -337,15 +348,13 @@ extern "C" int trc_planes_advise(const uint64_t *hist, unsigned filters, unsigne
     return TRC_OK;
 }
 
-// the TRCP container of F(filter, chunk, esize, in) -- of `in` itself with TRC_FILTER_NONE.  filter = PLANES_FILTER_AUTO: the advisor
-// chooses from the bytes on the device (*advice, where given, says how), and `out` receives what the explicit host call writes for
+// the TRCP container of F(pred, chunk, esize, in) -- of `in` itself with TRC_FILTER_NONE.  choose: the advisor sets the filter
+// from the bytes on the device (*advice, where given, says how), and `out` receives what the explicit host call writes for
 // that choice: the TRCP container, behind the 16-byte TRCF prefix where the choice is a filter.
-// stride = PLANES_VS_BASE: the container of D(filter, esize, in, base); the m * esize bytes of `base` go to the context's second
-// buffer, and *base_fp receives their fingerprint, computed on the device.
-#define PLANES_FILTER_AUTO (-1)
-static size_t planes_host_encode(int codec, int filter, const void *in, size_t n, unsigned esize, uint32_t chunk,
-                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice = nullptr, int stride = 1,
-                                 const void *base = nullptr, uint64_t *base_fp = nullptr)
+// pred.based: the container of D(filter, esize, in, base); the m * esize bytes of the host buffer pred.base go to the context's
+// second buffer, and *base_fp receives their fingerprint, computed on the device.
+static size_t planes_host_encode(int codec, PlanesPred pred, bool choose, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice, uint64_t *base_fp)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
     if (codec_row(codec).low4) { fail(TRC_E_ARG, "encode_planes_host: " PLANES_LOW4, codec); return 0; }      // before anything is uploaded
@@ -363,7 +372,7 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
     if (planes_ctx(cp, lk)) return 0;
     HostCtx &c = *cp;
     const size_t dirsz = up256(4 * P.nc + 256);
-    const size_t histb = filter == PLANES_FILTER_AUTO ? trc_planes_hist_bytes(esize) : 0;        // (in the workspace, ahead of the encode)
+    const size_t histb = choose ? trc_planes_hist_bytes(esize) : 0;        // (in the workspace, ahead of the encode)
     if (grow(&c.d_in, &c.cap_in, n) || grow(&c.d_cont, &c.cap_cont, esize * (dirsz + P.buf)) ||
         grow(&c.d_work[0], &c.cap_work[0], esize * P.slice > histb ? esize * P.slice : histb)) return 0;
     hipStream_t s = c.s_k[0];
@@ -375,13 +384,14 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
     uint8_t *d_tail = c.d_small + PLANES_SMALL_TAIL;
     PCHK(hipMemcpyAsync(c.d_in, in, n, hipMemcpyHostToDevice, s));
     uint64_t *d_fp = (uint64_t *)(c.d_small + PLANES_SMALL_FP);
-    if (stride == PLANES_VS_BASE) {
+    if (pred.based) {
         if (grow(&c.d_base, &c.cap_base, m * esize)) return 0;
-        PCHK(hipMemcpyAsync(c.d_base, base, m * esize, hipMemcpyHostToDevice, s));
+        PCHK(hipMemcpyAsync(c.d_base, pred.base, m * esize, hipMemcpyHostToDevice, s));
         if (trc_base_fingerprint_dev(c.d_base, m * esize, d_fp, s)) { (void)hipStreamSynchronize(s); return 0; }
+        pred.base = c.d_base;
     }
     size_t lead = 0;                                                     // bytes of TRCF prefix in front of the container
-    if (filter == PLANES_FILTER_AUTO) {
+    if (choose) {
         std::vector<uint64_t> hist(histb / sizeof(uint64_t));
         trc_planes_advice adv;
         if (trc_planes_hist_dev(7, c.d_in, n, esize, chunk, (uint64_t *)c.d_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
@@ -389,16 +399,16 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
         PCHK(hipStreamSynchronize(s));
         if (trc_planes_advise(hist.data(), 7, esize, m, &adv)) return 0;
         if (advice) *advice = adv;
-        filter = adv.filter;
-        if (filter != TRC_FILTER_NONE) {
+        pred.filter = adv.filter;
+        if (pred.filter != TRC_FILTER_NONE) {
             lead = sizeof(trc_fplanes_hdr);
             if (outcap <= lead) { fail(TRC_E_ARG, "encode_aplanes_host: out holds %zu bytes (trc_fplanes_bound)", outcap); return 0; }
             out = (uint8_t *)out + lead; outcap -= lead;
         }
     }
-    if (planes_encode_dev(codec, filter, stride, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
-                              d_clen, d_payload, d_total, d_tail, c.d_work[0], c.cap_work[0], s, stride == PLANES_VS_BASE ? c.d_base : nullptr)) { (void)hipStreamSynchronize(s); return 0; }
-    if (stride == PLANES_VS_BASE) PCHK(hipMemcpyAsync(base_fp, d_fp, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (planes_encode_dev(codec, pred, c.d_in, n, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+                          d_clen, d_payload, d_total, d_tail, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
+    if (pred.based) PCHK(hipMemcpyAsync(base_fp, d_fp, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     uint64_t total[8];
     int32_t status[8];
     uint16_t cdf[8 * TRC_PLANES_CDF_STRIDE];
@@ -447,7 +457,7 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
     if (lead) {
         trc_fplanes_hdr fh;
         memset(&fh, 0, sizeof fh);
-        fh.magic = TRC_FPLANES_MAGIC; fh.filter = (uint8_t)filter; fh.version = 1; fh.size = lead + size;
+        fh.magic = TRC_FPLANES_MAGIC; fh.filter = (uint8_t)pred.filter; fh.version = 1; fh.size = lead + size;
         memcpy(o - lead, &fh, sizeof fh);
     }
     return lead + size;
@@ -455,7 +465,7 @@ static size_t planes_host_encode(int codec, int filter, const void *in, size_t n
 extern "C" size_t trc_encode_planes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
                                          void *out, size_t outcap, unsigned cdfnum)
 {
-    return planes_host_encode(codec, TRC_FILTER_NONE, in, n, esize, chunk, out, outcap, cdfnum);
+    return planes_host_encode(codec, pred_none(), false, in, n, esize, chunk, out, outcap, cdfnum, nullptr, nullptr);
 }
 
 // sections of a container that planes_verdict has accepted: where plane k's CDF and TRC1 container lie and how far the latter may reach
@@ -472,10 +482,10 @@ static void planes_sections(const uint8_t *b, const trc_planes_hdr &h, PlanesSec
 }
 
 // elements [first_chunk * chunk, ...) of `count` chunks -- or, whole = true, everything with the tail -- decoded to c.d_in.
-// stride = PLANES_VS_BASE: `base` = those elements of the base, in host memory; they go to the context's second buffer.  fp, where
+// pred.based: pred.base = those elements of the base, in host memory; they go to the context's second buffer.  fp, where
 // given, is what their fingerprint must be: it is computed on the device and compared before anything is decoded.
-static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const trc_planes_hdr &h, bool whole, size_t first_chunk, size_t count, size_t elems,
-                                 int stride = 1, const void *base = nullptr, const uint64_t *fp = nullptr)
+static size_t planes_host_decode(HostCtx &c, PlanesPred pred, const uint8_t *b, const trc_planes_hdr &h, bool whole, size_t first_chunk, size_t count, size_t elems,
+                                 const uint64_t *fp)
 {
     const TrcCodec &r = codec_row(h.codec);
     const unsigned esize = h.esize;
@@ -492,10 +502,11 @@ static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const
     uint8_t *d_payload = c.d_cont + up256(esize * 4 * count + 256);
     uint16_t *d_cdf = (uint16_t *)c.d_small;
     uint8_t *d_tail = c.d_small + PLANES_SMALL_TAIL;
-    if (stride == PLANES_VS_BASE) {
+    if (pred.based) {
         uint64_t *d_fp = (uint64_t *)(c.d_small + PLANES_SMALL_FP), got = 0;
         if (grow(&c.d_base, &c.cap_base, elems * esize)) return 0;
-        PCHK(hipMemcpyAsync(c.d_base, base, elems * esize, hipMemcpyHostToDevice, s));
+        PCHK(hipMemcpyAsync(c.d_base, pred.base, elems * esize, hipMemcpyHostToDevice, s));
+        pred.base = c.d_base;
         if (fp) {
             if (trc_base_fingerprint_dev(c.d_base, elems * esize, d_fp, s)) { (void)hipStreamSynchronize(s); return 0; }
             PCHK(hipMemcpyAsync(&got, d_fp, sizeof got, hipMemcpyDeviceToHost, s));
@@ -518,14 +529,14 @@ static size_t planes_host_decode(HostCtx &c, int filter, const uint8_t *b, const
         if (R.payload_len) PCHK(hipMemcpyAsync(d_payload + k * P.buf, pay + R.payload_off, (size_t)R.payload_len, hipMemcpyHostToDevice, s));
     }
     if (whole && h.tail) PCHK(hipMemcpyAsync(d_tail, b + h.size - h.tail, h.tail, hipMemcpyHostToDevice, s));
-    if (planes_decode_dev(h.codec, filter, stride, d_clen, d_payload, d_tail, nsub, esize, h.chunk, r.cdf ? d_cdf : nullptr, h.cdfnum,
-                              c.d_in, c.d_work[0], c.cap_work[0], s, stride == PLANES_VS_BASE ? c.d_base : nullptr)) { (void)hipStreamSynchronize(s); return 0; }
+    if (planes_decode_dev(h.codec, pred, d_clen, d_payload, d_tail, nsub, esize, h.chunk, r.cdf ? d_cdf : nullptr, h.cdfnum,
+                          c.d_in, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
     return nsub;
 }
 
-// the two decoders of a TRCP container whose content is F(filter, chunk, esize, original)
-static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, void *out, size_t outlen, int stride = 1,
-                                     const void *base = nullptr, const uint64_t *fp = nullptr)
+// the two decoders of a TRCP container whose content is F(pred, chunk, esize, original); pred.base and fp as planes_host_decode, for
+// the whole buffer
+static size_t planes_host_decode_all(PlanesPred pred, const void *in, size_t inlen, void *out, size_t outlen, const uint64_t *fp)
 {
     if (trc_planes_check(in, inlen, outlen)) return 0;
     trc_planes_hdr h;
@@ -534,7 +545,7 @@ static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, v
     std::unique_lock<std::mutex> lk;
     if (planes_ctx(cp, lk)) return 0;
     const size_t m = (size_t)(h.n / h.esize);
-    if (!planes_host_decode(*cp, filter, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m, stride, base, fp)) return 0;
+    if (!planes_host_decode(*cp, pred, (const uint8_t *)in, h, true, 0, (m + h.chunk - 1) / h.chunk, m, fp)) return 0;
     hipStream_t s = cp->s_k[0];
     PCHK(hipMemcpyAsync(out, cp->d_in, (size_t)h.n, hipMemcpyDeviceToHost, s));
     PCHK(hipStreamSynchronize(s));
@@ -544,11 +555,10 @@ static size_t planes_host_decode_all(int filter, const void *in, size_t inlen, v
 extern "C" size_t trc_decode_planes_host(const void *in, size_t inlen, void *out, size_t outlen)
 {
     if (!in || !out) { fail(TRC_E_ARG, "decode_planes_host: bad arguments"); return 0; }
-    return planes_host_decode_all(TRC_FILTER_NONE, in, inlen, out, outlen);
+    return planes_host_decode_all(pred_none(), in, inlen, out, outlen, nullptr);
 }
 
-static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen, size_t offset, size_t len, void *out, int stride = 1,
-                                       const void *base = nullptr)
+static size_t planes_host_decode_bytes(PlanesPred pred, const void *in, size_t inlen, size_t offset, size_t len, void *out)
 {
     if (trc_planes_check(in, inlen, (size_t)-1)) return 0;
     trc_planes_hdr h;
@@ -564,8 +574,7 @@ static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen,
         HostCtx *cp = nullptr;
         std::unique_lock<std::mutex> lk;
         if (planes_ctx(cp, lk)) return 0;
-        if (!planes_host_decode(*cp, filter, b, h, false, c0, c1 - c0 + 1, elems, stride,
-                                base ? (const uint8_t *)base + c0 * (size_t)h.chunk * h.esize : nullptr)) return 0;
+        if (!planes_host_decode(*cp, pred_from(pred, c0 * (size_t)h.chunk * h.esize), b, h, false, c0, c1 - c0 + 1, elems, nullptr)) return 0;
         hipStream_t s = cp->s_k[0];
         PCHK(hipMemcpyAsync(out, cp->d_in + (offset - c0 * (size_t)h.chunk * h.esize), lb, hipMemcpyDeviceToHost, s));
         PCHK(hipStreamSynchronize(s));
@@ -576,7 +585,7 @@ static size_t planes_host_decode_bytes(int filter, const void *in, size_t inlen,
 extern "C" size_t trc_decode_planes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out)
 {
     if (!in || !out) { fail(TRC_E_ARG, "decode_planes_range_host: bad arguments"); return 0; }
-    return planes_host_decode_bytes(TRC_FILTER_NONE, in, inlen, offset, len, out);
+    return planes_host_decode_bytes(pred_none(), in, inlen, offset, len, out);
 }
 #undef PCHK
 
@@ -587,17 +596,25 @@ extern "C" size_t trc_fplanes_bound(size_t n, unsigned esize, uint32_t chunk, un
     return b ? b + sizeof(trc_fplanes_hdr) : 0;
 }
 
-// the prefix alone: 0 and the header, or TRC_E_ARG with the reason set
+// What the prefixes of the TRCF, TRCS and TRCD containers have in common -- magic, filter, version and size lie alike in all three
+// headers -- in the order they are looked at; `own` is the container's check of its 16-bit field, between the filter and the size.
+// 0 and the header, or TRC_E_ARG with the reason set.
+template <class Hdr, class Own> static int planes_prefix(const char *noun, uint32_t magic, const void *buf, size_t buflen, Hdr &h, Own own)
+{
+    if (!buf || buflen < sizeof h) return fail(TRC_E_ARG, "%s: %zu bytes is shorter than the header", noun, buflen);
+    memcpy(&h, buf, sizeof h);
+    if (h.magic != magic || h.version != 1) return fail(TRC_E_ARG, "%s: bad magic/version", noun);
+    if (h.filter != TRC_FILTER_ZDELTA && h.filter != TRC_FILTER_XOR) return fail(TRC_E_ARG, "%s: filter %u (1 zigzag delta, 2 xor)", noun, h.filter);
+    const int rc = own(h);
+    if (rc) return rc;
+    if (h.size > buflen) return fail(TRC_E_ARG, "%s: states %llu bytes, the buffer holds %zu", noun, (unsigned long long)h.size, buflen);
+    if (h.size <= sizeof h) return fail(TRC_E_ARG, "%s: size %llu leaves no room behind the header", noun, (unsigned long long)h.size);
+    return TRC_OK;
+}
 static int fplanes_prefix(const void *buf, size_t buflen, trc_fplanes_hdr &h)
 {
-    if (!buf || buflen < sizeof h) return fail(TRC_E_ARG, "filtered planes container: %zu bytes is shorter than the header", buflen);
-    memcpy(&h, buf, sizeof h);
-    if (h.magic != TRC_FPLANES_MAGIC || h.version != 1) return fail(TRC_E_ARG, "filtered planes container: bad magic/version");
-    if (h.filter != TRC_FILTER_ZDELTA && h.filter != TRC_FILTER_XOR) return fail(TRC_E_ARG, "filtered planes container: filter %u (1 zigzag delta, 2 xor)", h.filter);
-    if (h.zero) return fail(TRC_E_ARG, "filtered planes container: reserved field is 0x%x, must be 0", h.zero);
-    if (h.size > buflen) return fail(TRC_E_ARG, "filtered planes container: states %llu bytes, the buffer holds %zu", (unsigned long long)h.size, buflen);
-    if (h.size <= sizeof h) return fail(TRC_E_ARG, "filtered planes container: size %llu leaves no room behind the header", (unsigned long long)h.size);
-    return TRC_OK;
+    return planes_prefix("filtered planes container", TRC_FPLANES_MAGIC, buf, buflen, h, [](const trc_fplanes_hdr &f) {
+        return f.zero ? fail(TRC_E_ARG, "filtered planes container: reserved field is 0x%x, must be 0", f.zero) : (int)TRC_OK; });
 }
 extern "C" int trc_fplanes_check(const void *buf, size_t buflen, size_t outlen)
 {
@@ -614,7 +631,8 @@ extern "C" size_t trc_encode_fplanes_host(int codec, int filter, const void *in,
         return 0;
     }
     if (!out || outcap <= sizeof(trc_fplanes_hdr)) { fail(TRC_E_ARG, "encode_fplanes_host: out holds %zu bytes (trc_fplanes_bound)", outcap); return 0; }
-    const size_t inner = planes_host_encode(codec, filter, in, n, esize, chunk, (uint8_t *)out + sizeof(trc_fplanes_hdr), outcap - sizeof(trc_fplanes_hdr), cdfnum);
+    const size_t inner = planes_host_encode(codec, pred_stride(filter, 1), false, in, n, esize, chunk, (uint8_t *)out + sizeof(trc_fplanes_hdr), outcap - sizeof(trc_fplanes_hdr), cdfnum,
+                                            nullptr, nullptr);
     if (!inner) return 0;
     trc_fplanes_hdr h;
     memset(&h, 0, sizeof h);
@@ -629,7 +647,7 @@ extern "C" size_t trc_decode_fplanes_host(const void *in, size_t inlen, void *ou
     trc_fplanes_hdr h;
     if (!in || !out) { fail(TRC_E_ARG, "decode_fplanes_host: bad arguments"); return 0; }
     if (fplanes_prefix(in, inlen, h)) return 0;
-    return planes_host_decode_all(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, out, outlen);
+    return planes_host_decode_all(pred_stride(h.filter, 1), (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, out, outlen, nullptr);
 }
 
 extern "C" size_t trc_decode_fplanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out)
@@ -637,14 +655,14 @@ extern "C" size_t trc_decode_fplanes_range_host(const void *in, size_t inlen, si
     trc_fplanes_hdr h;
     if (!in || !out) { fail(TRC_E_ARG, "decode_fplanes_range_host: bad arguments"); return 0; }
     if (fplanes_prefix(in, inlen, h)) return 0;
-    return planes_host_decode_bytes(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out);
+    return planes_host_decode_bytes(pred_stride(h.filter, 1), (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out);
 }
 
 // ---- either container, and the encoder that chooses between them ------------------------------------------------------------------
 extern "C" size_t trc_encode_aplanes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
                                           void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice)
 {
-    return planes_host_encode(codec, PLANES_FILTER_AUTO, in, n, esize, chunk, out, outcap, cdfnum, advice);
+    return planes_host_encode(codec, pred_none(), true, in, n, esize, chunk, out, outcap, cdfnum, advice, nullptr);
 }
 
 extern "C" size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *out, size_t outlen)

@@ -26,6 +26,7 @@
 
 #include "trc_planes_scan.h"                      // the scanning join (trc_fplanes_batch.inc)
 #include "trc_planes_count.h"                     // the advisor's LDS counters (trc_planes_hist_batch.inc)
+#include "trc_planes_pred.h"                      // the predictors of a batch, shared with trc_planes_batch.inc
 
 // one item as the kernels see it; `first` and `v0` count from the first chunk of the call's chunk range
 struct BatchRec { uint64_t ptr, m, v0, first; };        // base address, elements, first vector (first * chunk / 8), first chunk
@@ -229,10 +230,9 @@ static int batch_table(const char *who, const std::vector<BatchRec> &recs, uint6
     return TRC_OK;
 }
 
-static int batch_table_args(const char *who, size_t count, uint64_t chunks, const void *d_table, size_t table_bytes)
+static int batch_table_args(const char *who, size_t need, const void *d_table, size_t table_bytes)
 {
     if (!d_table || ((uintptr_t)d_table & 255)) return trc_fail(TRC_E_ARG, "%s: the table must be 256-byte aligned", who);
-    const size_t need = trc_planes_batch_table_bytes(count, chunks);
     if (table_bytes < need) return trc_fail(TRC_E_WORK, "%s: table %zu B < required %zu B", who, table_bytes, need);
     return TRC_OK;
 }
@@ -246,80 +246,95 @@ static int batch_table_args(const char *who, size_t count, uint64_t chunks, cons
 // ---- the kernels with a filter against a base per item ----------------------------------------------------------------------------
 #include "trc_bplanes_batch.inc"
 
-// ---- split and join: plain, with filters, with filters and strides -----------------------------------------------------------------
+// ---- split and join: plain, with filters, with filters and strides, with filters against bases ------------------------------------
 typedef void (*split_batch_fn)(const BatchRec *, const u32 *, u32, u32, size_t, size_t, uint8_t *, size_t);
 static const split_batch_fn split_batch_kernels[3][3] = { TRC_BY_ESIZE(trc_planes_split_batch_kernel), TRC_BY_ESIZE(trc_fplanes_split_batch_kernel),
                                                           TRC_BY_ESIZE(trc_splanes_split_batch_kernel) };     // [none, any filter, a stride above 1][esize_row]
 static void (*const join_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t) = TRC_BY_ESIZE(trc_planes_join_batch_kernel);
 typedef void (*fjoin_batch_fn)(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t, u32, u32, size_t);
 static const fjoin_batch_fn fjoin_batch_kernels[2][3] = { TRC_BY_ESIZE(trc_fplanes_join_batch_kernel), TRC_BY_ESIZE(trc_splanes_join_batch_kernel) };     // [a stride above 1][esize_row]
+static void (*const bsplit_batch_kernels[3])(const BatchRec *, const u32 *, const uint64_t *, u32, u32, size_t, size_t, uint8_t *, size_t) = TRC_BY_ESIZE(trc_bplanes_split_batch_kernel);
+static void (*const bjoin_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, const uint64_t *, u32, u32, size_t) = TRC_BY_ESIZE(trc_bplanes_join_batch_kernel);
 
-// filters == NULL: the batch call; a batch whose filters are all TRC_FILTER_NONE is that call too, and says so in its messages.
-// strides == NULL: the filtered batch call; a batch in which no item with a filter has a stride above 1 is that call too, likewise
-static int split_batch(const char *who, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize, uint32_t chunk,
-                       void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+// Every kind of batch (BatchPred, trc_planes_pred.h).  Checks: the plan, the filters, the strides, then pointers and buffers.
+// filters == NULL: the batch call; a batch whose filters are all TRC_FILTER_NONE is that call too -- whatever else the descriptor
+// holds -- and says so in its messages.  strides == NULL: the filtered batch call; a batch in which no item with a filter has a
+// stride above 1 is that call too, likewise.  A base that overlaps its item in any other way than being it (join) is NOT checked.
+int split_batch(const char *who, const trc_planes_item *items, BatchPred pred, size_t count, unsigned esize, uint32_t chunk,
+                void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
     trc_planes_batch_plan P;
     int rc = batch_plan(who, items, count, esize, chunk, &P, nullptr);
     if (rc) return rc;
     bool any, strided;
-    if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
-    if ((rc = trc_planes_batch_strides(who, filters, strides, count, &strided))) return rc;
-    if (!strided && strides) who = "planes_split_fbatch";
-    if (!any) who = "planes_split_batch";
+    if ((rc = trc_planes_batch_filters(who, pred.filters, count, &any))) return rc;
+    if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, &strided))) return rc;
+    if (!strided && pred.strides) who = "planes_split_fbatch";
+    if (!any) { who = "planes_split_batch"; pred = batch_pred_none(); }
     if (!d_planes || ((uintptr_t)d_planes & 255)) return trc_fail(TRC_E_ARG, "%s: the planes must be 256-byte aligned", who);
     if ((pitch & 255) || pitch < P.m_total) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)P.m_total);
-    if ((rc = batch_table_args(who, count, P.chunks, d_table, table_bytes))) return rc;
+    if ((rc = batch_table_args(who, batch_pred_table_bytes(pred, count, P.chunks), d_table, table_bytes))) return rc;
     std::vector<BatchRec> recs;
     uint64_t chunks, elems;
     if ((rc = batch_range(who, items, 0, count, esize, chunk, chunks, elems, &recs))) return rc;
-    if (any) fbatch_pack(recs, filters);
-    if (strided) sbatch_pack(recs, filters, strides);
+    if (pred.based && (rc = trc_planes_bbatch_bases(who, pred.bases, pred.filters, 0, count))) return rc;
+    if (any) fbatch_pack(recs, pred.filters);
+    if (strided) sbatch_pack(recs, pred.filters, pred.strides);
     hipStream_t s = (hipStream_t)stream;
     const BatchRec *d_rec;
     const u32 *d_map;
+    const uint64_t *d_base = nullptr;
     if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
+    if (pred.based && (rc = bbatch_bases_up(who, pred.bases, pred.filters, 0, count, chunks, d_table, s, d_base))) return rc;
     const size_t M = (size_t)elems, nv = (M + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
     const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    hipLaunchKernelGGL(split_batch_kernels[strided ? 2 : any][esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
+    if (pred.based)
+        hipLaunchKernelGGL(bsplit_batch_kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, d_base, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
+    else
+        hipLaunchKernelGGL(split_batch_kernels[strided ? 2 : any][esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(e));
 }
 
-static int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
-                      size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, void *d_table, size_t table_bytes, void *stream)
+int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_planes_item *items, BatchPred pred, size_t count, size_t first_item, size_t item_count,
+               unsigned esize, uint32_t chunk, void *d_table, size_t table_bytes, void *stream)
 {
     int rc = batch_plan(who, items, count, esize, chunk, nullptr, nullptr);
     if (rc) return rc;
     bool any, strided;
-    if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
-    if ((rc = trc_planes_batch_strides(who, filters, strides, count, &strided))) return rc;
-    if (!strided && strides) who = "planes_join_fbatch";
-    if (!any) who = "planes_join_batch";
+    if ((rc = trc_planes_batch_filters(who, pred.filters, count, &any))) return rc;
+    if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, &strided))) return rc;
+    if (!strided && pred.strides) who = "planes_join_fbatch";
+    if (!any) { who = "planes_join_batch"; pred = batch_pred_none(); }
     if (first_item > count || item_count > count - first_item)
         return trc_fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
     if (item_count == 0) return TRC_OK;
     std::vector<BatchRec> recs;
     uint64_t chunks, elems;
     if ((rc = batch_range(who, items, first_item, item_count, esize, chunk, chunks, elems, &recs))) return rc;
-    if (any) fbatch_pack(recs, filters + first_item);
-    if (strided) sbatch_pack(recs, filters + first_item, strides + first_item);
+    if (pred.based && (rc = trc_planes_bbatch_bases(who, pred.bases, pred.filters, first_item, item_count))) return rc;
+    if (any) fbatch_pack(recs, pred.filters + first_item);
+    if (strided) sbatch_pack(recs, pred.filters + first_item, pred.strides + first_item);
     if (!d_planes || ((uintptr_t)d_planes & 63)) return trc_fail(TRC_E_ARG, "%s: the planes must be 64-byte aligned", who);
     if ((pitch & 255) || pitch < elems) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)elems);
-    if ((rc = batch_table_args(who, item_count, chunks, d_table, table_bytes))) return rc;
+    if ((rc = batch_table_args(who, batch_pred_table_bytes(pred, item_count, chunks), d_table, table_bytes))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const BatchRec *d_rec;
     const u32 *d_map;
+    const uint64_t *d_base = nullptr;
     if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
+    if (pred.based && (rc = bbatch_bases_up(who, pred.bases, pred.filters, first_item, item_count, chunks, d_table, s, d_base))) return rc;
     const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    if (any) {                                     // the scanning join: a wave per span
+    const size_t nv = ((size_t)elems + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
+    if (pred.based) {                              // elementwise, as the plain join
+        hipLaunchKernelGGL(bjoin_batch_kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, d_base, vpc, rcp, nv);
+    } else if (any) {                              // the scanning join: a wave per span
         u32 span;
         size_t nspan;
         const unsigned grid = join_grid((size_t)elems, chunk, span, nspan);
         hipLaunchKernelGGL(fjoin_batch_kernels[strided][esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp,
                            (size_t)elems, chunk, span, nspan);
     } else {
-        const size_t nv = ((size_t)elems + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
         hipLaunchKernelGGL(join_batch_kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, nv);
     }
     const hipError_t e = hipGetLastError();
@@ -329,109 +344,46 @@ static int join_batch(const char *who, const void *d_planes, size_t pitch, const
 extern "C" int trc_planes_split_batch_dev(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
                                           void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
-    return split_batch("planes_split_batch", items, nullptr, nullptr, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+    return split_batch("planes_split_batch", items, batch_pred_none(), count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_split_fbatch_dev(const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
                                            void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
-    return split_batch("planes_split_fbatch", items, filters, nullptr, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+    return split_batch("planes_split_fbatch", items, batch_pred_strides(filters, nullptr), count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+}
+extern "C" int trc_planes_split_sbatch_dev(const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize,
+                                           uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+{
+    return split_batch("planes_split_sbatch", items, batch_pred_strides(filters, strides), count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+}
+extern "C" int trc_planes_split_bbatch_dev(const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
+                                           unsigned esize, uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+{
+    return split_batch("planes_split_bbatch", items, batch_pred_bases(filters, bases), count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_join_batch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, size_t count,
                                          size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
                                          void *d_table, size_t table_bytes, void *stream)
 {
-    return join_batch("planes_join_batch", d_planes, pitch, items, nullptr, nullptr, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
+    return join_batch("planes_join_batch", d_planes, pitch, items, batch_pred_none(), count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_join_fbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, size_t count,
                                           size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
                                           void *d_table, size_t table_bytes, void *stream)
 {
-    return join_batch("planes_join_fbatch", d_planes, pitch, items, filters, nullptr, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
-}
-extern "C" int trc_planes_split_sbatch_dev(const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize,
-                                           uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
-{
-    return split_batch("planes_split_sbatch", items, filters, strides, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+    return join_batch("planes_join_fbatch", d_planes, pitch, items, batch_pred_strides(filters, nullptr), count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_join_sbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
                                           size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
                                           void *d_table, size_t table_bytes, void *stream)
 {
-    return join_batch("planes_join_sbatch", d_planes, pitch, items, filters, strides, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
+    return join_batch("planes_join_sbatch", d_planes, pitch, items, batch_pred_strides(filters, strides), count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
 }
-
-// ---- split and join against a base per item: a filter id here always means "against bases[i]".  filters == NULL or all
-// TRC_FILTER_NONE IS the unfiltered batched call.  Checks: the plan, the filters, then pointers and buffers.  A base that overlaps
-// its item in any other way than being it (join) is NOT checked.
-extern "C" int trc_planes_split_bbatch_dev(const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
-                                           unsigned esize, uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
-{
-    const char *who = "planes_split_bbatch";
-    trc_planes_batch_plan P;
-    int rc = batch_plan(who, items, count, esize, chunk, &P, nullptr);
-    if (rc) return rc;
-    bool any;
-    if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
-    if (!any) return split_batch("planes_split_batch", items, nullptr, nullptr, count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
-    if (!d_planes || ((uintptr_t)d_planes & 255)) return trc_fail(TRC_E_ARG, "%s: the planes must be 256-byte aligned", who);
-    if ((pitch & 255) || pitch < P.m_total) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)P.m_total);
-    if (!d_table || ((uintptr_t)d_table & 255)) return trc_fail(TRC_E_ARG, "%s: the table must be 256-byte aligned", who);
-    const size_t need = trc_planes_bbatch_table_bytes(count, P.chunks);
-    if (table_bytes < need) return trc_fail(TRC_E_WORK, "%s: table %zu B < required %zu B", who, table_bytes, need);
-    std::vector<BatchRec> recs;
-    uint64_t chunks, elems;
-    if ((rc = batch_range(who, items, 0, count, esize, chunk, chunks, elems, &recs))) return rc;
-    if ((rc = trc_planes_bbatch_bases(who, bases, filters, 0, count))) return rc;
-    fbatch_pack(recs, filters);
-    hipStream_t s = (hipStream_t)stream;
-    const BatchRec *d_rec;
-    const u32 *d_map;
-    const uint64_t *d_base;
-    if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
-    if ((rc = bbatch_bases_up(who, bases, filters, 0, count, chunks, d_table, s, d_base))) return rc;
-    const size_t M = (size_t)elems, nv = (M + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
-    const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    static void (*const kernels[3])(const BatchRec *, const u32 *, const uint64_t *, u32, u32, size_t, size_t, uint8_t *, size_t) = TRC_BY_ESIZE(trc_bplanes_split_batch_kernel);
-    hipLaunchKernelGGL(kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, d_base, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(e));
-}
-
 extern "C" int trc_planes_join_bbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const void *const *bases,
                                           const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
                                           unsigned esize, uint32_t chunk, void *d_table, size_t table_bytes, void *stream)
 {
-    const char *who = "planes_join_bbatch";
-    int rc = batch_plan(who, items, count, esize, chunk, nullptr, nullptr);
-    if (rc) return rc;
-    bool any;
-    if ((rc = trc_planes_batch_filters(who, filters, count, &any))) return rc;
-    if (!any) return join_batch("planes_join_batch", d_planes, pitch, items, nullptr, nullptr, count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
-    if (first_item > count || item_count > count - first_item)
-        return trc_fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
-    if (item_count == 0) return TRC_OK;
-    std::vector<BatchRec> recs;
-    uint64_t chunks, elems;
-    if ((rc = batch_range(who, items, first_item, item_count, esize, chunk, chunks, elems, &recs))) return rc;
-    if ((rc = trc_planes_bbatch_bases(who, bases, filters, first_item, item_count))) return rc;
-    fbatch_pack(recs, filters + first_item);
-    if (!d_planes || ((uintptr_t)d_planes & 63)) return trc_fail(TRC_E_ARG, "%s: the planes must be 64-byte aligned", who);
-    if ((pitch & 255) || pitch < elems) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)elems);
-    if (!d_table || ((uintptr_t)d_table & 255)) return trc_fail(TRC_E_ARG, "%s: the table must be 256-byte aligned", who);
-    const size_t need = trc_planes_bbatch_table_bytes(item_count, chunks);
-    if (table_bytes < need) return trc_fail(TRC_E_WORK, "%s: table %zu B < required %zu B", who, table_bytes, need);
-    hipStream_t s = (hipStream_t)stream;
-    const BatchRec *d_rec;
-    const u32 *d_map;
-    const uint64_t *d_base;
-    if ((rc = batch_table(who, recs, chunks, d_table, s, d_rec, d_map))) return rc;
-    if ((rc = bbatch_bases_up(who, bases, filters, first_item, item_count, chunks, d_table, s, d_base))) return rc;
-    const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
-    const size_t nv = ((size_t)elems + TRC_PLANES_VEC - 1) / TRC_PLANES_VEC;
-    static void (*const kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, const uint64_t *, u32, u32, size_t) = TRC_BY_ESIZE(trc_bplanes_join_batch_kernel);
-    hipLaunchKernelGGL(kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, d_base, vpc, rcp, nv);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TRC_OK : trc_fail(TRC_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return join_batch("planes_join_bbatch", d_planes, pitch, items, batch_pred_bases(filters, bases), count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
 }
 
 // ---- the advisor's histograms, per item ---------------------------------------------------------------------------------------

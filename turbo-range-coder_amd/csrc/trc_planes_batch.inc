@@ -5,19 +5,25 @@
 // is the unbatched call on (M * esize, esize, chunk) with another split in front or another join behind; item i is the chunk range
 // [first[i], first[i] + nc[i]) of every plane.  Nothing here knows a coder.
 //   workspace: the planes workspace of (M * esize, esize, chunk) -- planes_map / planes_range_map -- followed by the table
+#include "trc_planes_pred.h"                      // BatchPred, its table, split_batch / join_batch (trc_planes_batch.hip)
 int trc_planes_batch_plan_quiet(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, trc_planes_batch_plan *plan, uint64_t *first_chunk);
 int trc_planes_batch_ptrs_ok(const trc_planes_item *items, size_t first_item, size_t item_count);
 int trc_planes_batch_filters(const char *who, const uint8_t *filters, size_t count, bool *any);      // trc_fplanes_batch.inc
 int trc_planes_batch_strides(const char *who, const uint8_t *filters, const uint8_t *strides, size_t count, bool *strided);      // trc_splanes_batch.inc
 int trc_planes_bbatch_bases(const char *who, const void *const *bases, const uint8_t *filters, size_t first_item, size_t item_count);      // trc_bplanes_batch.inc
 
-extern "C" size_t trc_planes_batch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+// the workspaces of a call whose table is `pred`'s
+static size_t batch_work_bytes(const BatchPred &pred, int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
 {
     trc_planes_batch_plan B;
     PlanesMap P;
     if (trc_planes_batch_plan_quiet(items, count, esize, chunk, &B, nullptr) || !trc_planes_batch_ptrs_ok(items, 0, count)) return 0;
     if (!planes_map(codec, (size_t)B.n_virtual, esize, chunk, P)) return 0;
-    return esize * P.slice + trc_planes_batch_table_bytes(count, B.chunks);
+    return esize * P.slice + batch_pred_table_bytes(pred, count, B.chunks);
+}
+extern "C" size_t trc_planes_batch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+{
+    return batch_work_bytes(batch_pred_none(), codec, items, count, esize, chunk);
 }
 
 // the chunk range of items [first_item, first_item + item_count) of a planned batch
@@ -29,8 +35,8 @@ static void batch_chunk_range(const trc_planes_item *items, size_t first_item, s
         if (i < first_item) c0 += nc; else cnt += nc;
     }
 }
-extern "C" size_t trc_planes_batch_range_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
-                                                    size_t first_item, size_t item_count)
+static size_t batch_range_work_bytes(const BatchPred &pred, int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                     size_t first_item, size_t item_count)
 {
     trc_planes_batch_plan B;
     PlanesMap P;
@@ -39,21 +45,25 @@ extern "C" size_t trc_planes_batch_range_work_bytes(int codec, const trc_planes_
     size_t c0, cnt;
     batch_chunk_range(items, first_item, item_count, esize, chunk, c0, cnt);
     if (!planes_range_map(codec, (size_t)B.n_virtual, esize, chunk, cnt, P)) return 0;
-    return esize * P.slice + trc_planes_batch_table_bytes(item_count, cnt);
+    return esize * P.slice + batch_pred_table_bytes(pred, item_count, cnt);
+}
+extern "C" size_t trc_planes_batch_range_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
+                                                    size_t first_item, size_t item_count)
+{
+    return batch_range_work_bytes(batch_pred_none(), codec, items, count, esize, chunk, first_item, item_count);
 }
 
-// the encoders: filters == NULL is the unfiltered batch, strides == NULL the filtered one (the split hands an all-NONE batch to the
-// unfiltered kernels and a batch without a stride above 1 to the filtered ones).  vs_base: the filters are against bases[i]
-// (trc_bplanes_batch.inc), and the table holds the base pointers behind the map
-static int encode_batch(const char *who, int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, unsigned esize, uint32_t chunk,
+// the encoders of every kind of batch (BatchPred, trc_planes_pred.h): the split hands an all-NONE batch to the unfiltered kernels and
+// a batch without a stride above 1 to the filtered ones; against bases the table holds the base pointers behind the map
+static int encode_batch(const char *who, int codec, const trc_planes_item *items, const BatchPred pred, size_t count, unsigned esize, uint32_t chunk,
                         uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status, uint32_t *d_clen, void *d_payload, uint64_t *d_total,
-                        void *d_work, size_t work_bytes, void *stream, bool vs_base = false, const void *const *bases = nullptr)
+                        void *d_work, size_t work_bytes, void *stream)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
-    if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
-    if ((rc = trc_planes_batch_strides(who, filters, strides, count, nullptr))) return rc;      // then a bad stride
+    if ((rc = trc_planes_batch_filters(who, pred.filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
+    if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, nullptr))) return rc;      // then a bad stride
     const size_t n = (size_t)B.n_virtual;
     if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
@@ -63,14 +73,13 @@ static int encode_batch(const char *who, int codec, const trc_planes_item *items
     PlanesMap P;
     if (!planes_map(codec, n, esize, chunk, P)) return fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk)", who);
     if (!trc_planes_batch_ptrs_ok(items, 0, count)) return fail(TRC_E_ARG, "%s: every item's pointer must be non-null and 16-byte aligned", who);
-    if (vs_base && (rc = trc_planes_bbatch_bases(who, bases, filters, 0, count))) return rc;
-    const size_t table = vs_base ? trc_planes_bbatch_table_bytes(count, B.chunks) : trc_planes_batch_table_bytes(count, B.chunks), need = esize * P.slice + table;
+    if (pred.based && (rc = trc_planes_bbatch_bases(who, pred.bases, pred.filters, 0, count))) return rc;
+    const size_t table = batch_pred_table_bytes(pred, count, B.chunks), need = esize * P.slice + table;
     if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
     if (!d_clen || !d_payload || !d_total || ((uintptr_t)d_payload & 1) || ((uintptr_t)d_clen & 3) || ((uintptr_t)d_total & 7))
         return fail(TRC_E_ARG, "%s: d_clen must be 4-byte, d_payload 2-byte, d_total 8-byte aligned", who);
     uint8_t *w = (uint8_t *)d_work;
-    if ((rc = vs_base ? trc_planes_split_bbatch_dev(items, bases, filters, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream)
-                    : trc_planes_split_sbatch_dev(items, filters, strides, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream))) return rc;
+    if ((rc = split_batch(pred.based ? "planes_split_bbatch" : "planes_split_sbatch", items, pred, count, esize, chunk, w, P.slice, w + esize * P.slice, table, stream))) return rc;
     for (unsigned k = 0; k < esize; k++) {         // as trc_encode_fplanes_dev
         uint8_t *plane = w + k * P.slice, *pw = plane + P.buf;
         uint16_t *cdf = r.cdf ? d_cdf + k * TRC_PLANES_CDF_STRIDE : nullptr;
@@ -86,7 +95,7 @@ extern "C" int trc_encode_planes_batch_dev(int codec, const trc_planes_item *ite
                                            uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                                            void *d_work, size_t work_bytes, void *stream)
 {
-    return encode_batch("encode_planes_batch", codec, items, nullptr, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+    return encode_batch("encode_planes_batch", codec, items, batch_pred_none(), count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
                         d_work, work_bytes, stream);
 }
 extern "C" int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize, uint32_t chunk,
@@ -94,7 +103,7 @@ extern "C" int trc_encode_fplanes_batch_dev(int codec, const trc_planes_item *it
                                             uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    return encode_batch("encode_fplanes_batch", codec, items, filters, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+    return encode_batch("encode_fplanes_batch", codec, items, batch_pred_strides(filters, nullptr), count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
                         d_work, work_bytes, stream);
 }
 extern "C" int trc_encode_splanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
@@ -102,7 +111,7 @@ extern "C" int trc_encode_splanes_batch_dev(int codec, const trc_planes_item *it
                                             uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    return encode_batch("encode_splanes_batch", codec, items, filters, strides, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
+    return encode_batch("encode_splanes_batch", codec, items, batch_pred_strides(filters, strides), count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
                         d_work, work_bytes, stream);
 }
 
@@ -127,17 +136,15 @@ static BatchCoded coded_flat(const uint32_t *d_clen, const void *d_payload, cons
 
 // sub_m != 0: the coded buffers hold the covering chunks of the requested items alone, as a coded buffer of sub_m elements (the
 // host-pointer decoder, trc_planes_container.inc); else they hold the whole batch
-static int decode_batch(const char *who, int codec, const BatchCoded &S,
-                        const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
-                        unsigned esize, uint32_t chunk, unsigned cdfnum,
-                        void *d_work, size_t work_bytes, void *stream, size_t sub_m = 0, const uint8_t *strides = nullptr,
-                        bool vs_base = false, const void *const *bases = nullptr)
+static int decode_batch(const char *who, int codec, const BatchCoded &S, size_t sub_m,
+                        const trc_planes_item *items, const BatchPred pred, size_t count, size_t first_item, size_t item_count,
+                        unsigned esize, uint32_t chunk, unsigned cdfnum, void *d_work, size_t work_bytes, void *stream)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
-    if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
-    if ((rc = trc_planes_batch_strides(who, filters, strides, count, nullptr))) return rc;      // then a bad stride
+    if ((rc = trc_planes_batch_filters(who, pred.filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
+    if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, nullptr))) return rc;      // then a bad stride
     const size_t m = sub_m ? sub_m : (size_t)B.m_total, n = m * esize;
     if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, m, chunk, S.cdf[0], cdfnum))) return rc;
@@ -149,8 +156,8 @@ static int decode_batch(const char *who, int codec, const BatchCoded &S,
     batch_chunk_range(items, first_item, item_count, esize, chunk, c0, cnt);
     PlanesMap P;
     if (!planes_range_map(codec, n, esize, chunk, cnt, P)) return fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk)", who);
-    if (vs_base && (rc = trc_planes_bbatch_bases(who, bases, filters, first_item, item_count))) return rc;
-    const size_t table = vs_base ? trc_planes_bbatch_table_bytes(item_count, cnt) : trc_planes_batch_table_bytes(item_count, cnt), need = esize * P.slice + table;
+    if (pred.based && (rc = trc_planes_bbatch_bases(who, pred.bases, pred.filters, first_item, item_count))) return rc;
+    const size_t table = batch_pred_table_bytes(pred, item_count, cnt), need = esize * P.slice + table;
     if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
     if (!S.clen[0] || !S.payload[0] || ((uintptr_t)S.payload[0] & 1) || ((uintptr_t)S.clen[0] & 3))
         return fail(TRC_E_ARG, "%s: d_clen must be 4-byte, d_payload 2-byte aligned", who);
@@ -161,8 +168,8 @@ static int decode_batch(const char *who, int codec, const BatchCoded &S,
         if ((rc = trc_decode_range_dev(codec, S.clen[k], S.payload[k], m, chunk, sub_m ? 0 : c0, cnt,
                                        r.cdf ? S.cdf[k] : nullptr, cdfnum, plane, plane + P.buf, P.work, stream))) return rc;
     }
-    if (vs_base) return trc_planes_join_bbatch_dev(w, P.slice, items, bases, filters, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
-    return trc_planes_join_sbatch_dev(w, P.slice, items, filters, strides, count, first_item, item_count, esize, chunk, w + esize * P.slice, table, stream);
+    return join_batch(pred.based ? "planes_join_bbatch" : "planes_join_sbatch", w, P.slice, items, pred, count, first_item, item_count, esize, chunk,
+                      w + esize * P.slice, table, stream);
 }
 
 extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
@@ -170,7 +177,7 @@ extern "C" int trc_decode_planes_batch_dev(int codec, const uint32_t *d_clen, co
                                            unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                            void *d_work, size_t work_bytes, void *stream)
 {
-    return decode_batch("decode_planes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), items, nullptr, count,
+    return decode_batch("decode_planes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), 0, items, batch_pred_none(), count,
                         first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
@@ -178,50 +185,44 @@ extern "C" int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, c
                                             unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    return decode_batch("decode_fplanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), items, filters, count,
-                        first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
+    return decode_batch("decode_fplanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), 0, items, batch_pred_strides(filters, nullptr),
+                        count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_splanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
                                             const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count,
                                             size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    return decode_batch("decode_splanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), items, filters, count,
-                        first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream, 0, strides);
+    return decode_batch("decode_splanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), 0, items, batch_pred_strides(filters, strides),
+                        count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 
 // ---- a base per item: the filters are against bases[i] (trc_bplanes_batch.inc); the workspace holds the base pointers as well ------
-static size_t bbatch_extra(size_t count) { return up256(8 * count); }
+// (filters == NULL: the unfiltered call, under its own name)
 extern "C" size_t trc_planes_bbatch_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
 {
-    const size_t w = trc_planes_batch_work_bytes(codec, items, count, esize, chunk);
-    return w ? w + bbatch_extra(count) : 0;
+    return batch_work_bytes(BATCH_PRED_BASED, codec, items, count, esize, chunk);
 }
 extern "C" size_t trc_planes_bbatch_range_work_bytes(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
                                                      size_t first_item, size_t item_count)
 {
-    const size_t w = trc_planes_batch_range_work_bytes(codec, items, count, esize, chunk, first_item, item_count);
-    return w ? w + bbatch_extra(item_count) : 0;
+    return batch_range_work_bytes(BATCH_PRED_BASED, codec, items, count, esize, chunk, first_item, item_count);
 }
 extern "C" int trc_encode_bplanes_batch_dev(int codec, const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
                                             unsigned esize, uint32_t chunk, uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
                                             uint32_t *d_clen, void *d_payload, uint64_t *d_total,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    if (!filters) return encode_batch("encode_planes_batch", codec, items, nullptr, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload,
-                                      d_total, d_work, work_bytes, stream);
-    return encode_batch("encode_bplanes_batch", codec, items, filters, nullptr, count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload, d_total,
-                        d_work, work_bytes, stream, true, bases);
+    return encode_batch(filters ? "encode_bplanes_batch" : "encode_planes_batch", codec, items, batch_pred_bases(filters, bases), count, esize, chunk,
+                        d_cdf, cdfnum, d_status, d_clen, d_payload, d_total, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_bplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload, const trc_planes_item *items,
                                             const void *const *bases, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
                                             unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
                                             void *d_work, size_t work_bytes, void *stream)
 {
-    const BatchCoded S = coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk);
-    if (!filters) return decode_batch("decode_planes_batch", codec, S, items, nullptr, count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
-    return decode_batch("decode_bplanes_batch", codec, S, items, filters, count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream,
-                        0, nullptr, true, bases);
+    return decode_batch(filters ? "decode_bplanes_batch" : "decode_planes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), 0,
+                        items, batch_pred_bases(filters, bases), count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 
 // ---- the batch advisor: a filter per item from the histograms of trc_planes_hist_batch_dev ---------------------------------------

@@ -7,6 +7,7 @@
 #include "trc_planes_pack.h"
 
 static inline size_t batch_front_bytes(size_t count) { return sizeof(trc_planes_batch_hdr) + 8 * count + up8(count); }
+static inline const uint8_t *batch_filters(const void *trcb, size_t count) { return (const uint8_t *)trcb + sizeof(trc_planes_batch_hdr) + 8 * count; }
 
 // chunk 0 -> the automatic chunk, a chunk above the coder's largest -> that one: what planes_host_encode does for n = sum n[i].
 // 0 for a batch whose sizes cannot be added up (the plan says why).
@@ -212,15 +213,15 @@ extern "C" int trc_planes_batch_pack_dev(int codec, const trc_planes_item *items
 // ---- decoding a packed container where it lies ------------------------------------------------------------------------------------
 // both packed decoders: d_cont = the TRCB container, `lead` bytes into the buffer of cont_bytes the caller named (the TRCT prefix, or 0)
 static int packed_decode(const char *who, int codec, const void *d_cont, size_t lead, size_t cont_bytes,
-                         const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, size_t count, size_t first_item, size_t item_count,
+                         const trc_planes_item *items, const BatchPred pred, size_t count, size_t first_item, size_t item_count,
                          unsigned esize, uint32_t chunk, unsigned cdfnum, const uint64_t *total,
                          void *d_work, size_t work_bytes, void *stream)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
     if (rc) return rc;
-    if ((rc = trc_planes_batch_filters(who, filters, count, nullptr))) return rc;
-    if ((rc = trc_planes_batch_strides(who, filters, strides, count, nullptr))) return rc;
+    if ((rc = trc_planes_batch_filters(who, pred.filters, count, nullptr))) return rc;
+    if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, nullptr))) return rc;
     if ((rc = container_common(who, codec & ~(TRC_TABLES_READY | TRC_DIR_READY), esize))) return rc;
     if (!d_cont || ((uintptr_t)d_cont & 7) || !total) return fail(TRC_E_ARG, "%s: d_cont must be 8-byte aligned, total a host array of %u entries", who, esize);
     const TrcCodec &r = codec_row(codec);
@@ -236,14 +237,14 @@ static int packed_decode(const char *who, int codec, const void *d_cont, size_t 
         S.clen[k] = (const uint32_t *)(sec + cdfb + sizeof(trc_container_hdr));
         S.payload[k] = sec + cdfb + sizeof(trc_container_hdr) + 4 * (size_t)B.chunks;
     }
-    return decode_batch(who, codec, S, items, filters, count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream, 0, strides);
+    return decode_batch(who, codec, S, 0, items, pred, count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 extern "C" int trc_decode_planes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
                                                   const trc_planes_item *items, const uint8_t *filters, size_t count, size_t first_item, size_t item_count,
                                                   unsigned esize, uint32_t chunk, unsigned cdfnum, const uint64_t *total,
                                                   void *d_work, size_t work_bytes, void *stream)
 {
-    return packed_decode("decode_planes_batch_packed", codec, d_cont, 0, cont_bytes, items, filters, nullptr, count, first_item, item_count,
+    return packed_decode("decode_planes_batch_packed", codec, d_cont, 0, cont_bytes, items, batch_pred_strides(filters, nullptr), count, first_item, item_count,
                          esize, chunk, cdfnum, total, d_work, work_bytes, stream);
 }
 
@@ -290,8 +291,9 @@ static int batch_items_up(HostCtx &c, hipStream_t s, const trc_planes_item *item
     return flush();
 }
 
-// strides given: the TRCT container (trc_encode_splanes_batch_host); it refuses a batch that is a TRCB container's
-static size_t batch_host_encode(const char *who, int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, bool choose, uint8_t *filters_out,
+// strides given: the TRCT container (trc_encode_splanes_batch_host); it refuses a batch that is a TRCB container's.
+// choose: the batch advisor sets the filters (to filters_out as well, where given)
+static size_t batch_host_encode(const char *who, int codec, const trc_planes_item *items, BatchPred pred, bool choose, uint8_t *filters_out,
                                 size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
@@ -301,12 +303,12 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     chunk = batch_resolve_chunk(r, items, count, esize, chunk);
     trc_planes_batch_plan B;
     if (trc_planes_batch_plan_host(items, count, esize, chunk ? chunk : TRC_CHUNK_AUTO_MIN, &B, nullptr)) return 0;     // (chunk 0 here: a bad batch, and the plan says why)
-    if (trc_planes_batch_filters(who, filters, count, nullptr)) return 0;
+    if (trc_planes_batch_filters(who, pred.filters, count, nullptr)) return 0;
     bool strided = false;
-    if (trc_planes_batch_strides(who, filters, strides, count, &strided)) return 0;
-    if (strides && !strided) { fail(TRC_E_ARG, "%s: no item with a filter has a stride above 1: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
+    if (trc_planes_batch_strides(who, pred.filters, pred.strides, count, &strided)) return 0;
+    if (pred.strides && !strided) { fail(TRC_E_ARG, "%s: no item with a filter has a stride above 1: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
     if (!r.cdf && !r.ss) cdfnum = 0;
-    const size_t bound = strides ? trc_planes_sbatch_bound(codec, items, count, esize, chunk, cdfnum) : trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
+    const size_t bound = pred.strides ? trc_planes_sbatch_bound(codec, items, count, esize, chunk, cdfnum) : trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
     PlanesMap P;
     if (!bound || !planes_map(codec, (size_t)B.n_virtual, esize, chunk, P)) { fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk %u, cdfnum 0x%x)", who, chunk, cdfnum); return 0; }
     for (size_t i = 0; i < count; i++)
@@ -326,7 +328,7 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
         for (size_t i = 0; i < count; i++) dev[i].d_ptr = c.d_in + off[i];
         if (batch_items_up(c, s, items, count, off)) { (void)hipStreamSynchronize(s); return 0; }
     }
-    const size_t table = trc_planes_batch_table_bytes(count, B.chunks), work = esize * P.slice + table;
+    const size_t work = esize * P.slice + batch_pred_table_bytes(pred, count, B.chunks);
     const size_t awork = choose ? TRC_PLANES_ADVISE_SLAB_BYTES + advise_table_bytes(dev.data(), count, esize, chunk) : 0;
     const size_t dirsz = up256(esize * 4 * P.nc + 256);
     if (grow(&c.d_cont, &c.cap_cont, dirsz + esize * P.buf) || grow(&c.d_work[0], &c.cap_work[0], work > awork ? work : awork) ||
@@ -341,13 +343,13 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     if (choose) {
         chosen.resize(count);
         if (trc_planes_advise_batch_dev(7, dev.data(), count, esize, chunk, chosen.data(), nullptr, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
-        filters = chosen.data();
+        pred.filters = chosen.data();
     }
-    if (trc_encode_splanes_batch_dev(codec, dev.data(), filters, strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
-                                     d_clen, d_payload, d_total, c.d_work[0], c.cap_work[0], s) ||
-        (strides ? trc_planes_sbatch_pack_dev(codec, dev.data(), filters, strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+    if (encode_batch("encode_splanes_batch", codec, dev.data(), pred, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+                     d_clen, d_payload, d_total, c.d_work[0], c.cap_work[0], s) ||
+        (pred.strides ? trc_planes_sbatch_pack_dev(codec, dev.data(), pred.filters, pred.strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                                               d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s)
-                 : trc_planes_batch_pack_dev(codec, dev.data(), filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+                 : trc_planes_batch_pack_dev(codec, dev.data(), pred.filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                                              d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s))) { (void)hipStreamSynchronize(s); return 0; }
     uint64_t size = 0;
     BCHK(hipMemcpyAsync(&size, d_size, sizeof size, hipMemcpyDeviceToHost, s));
@@ -363,22 +365,21 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
 extern "C" size_t trc_encode_planes_batch_host(int codec, const trc_planes_item *items, const uint8_t *filters, size_t count, unsigned esize,
                                                uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap)
 {
-    return batch_host_encode("encode_planes_batch_host", codec, items, filters, nullptr, false, nullptr, count, esize, chunk, cdfnum, items_on, out, outcap);
+    return batch_host_encode("encode_planes_batch_host", codec, items, batch_pred_strides(filters, nullptr), false, nullptr, count, esize, chunk, cdfnum, items_on, out, outcap);
 }
 extern "C" size_t trc_encode_aplanes_batch_host(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk,
                                                 unsigned cdfnum, int items_on, void *out, size_t outcap, uint8_t *filters_out)
 {
-    return batch_host_encode("encode_aplanes_batch_host", codec, items, nullptr, nullptr, true, filters_out, count, esize, chunk, cdfnum, items_on, out, outcap);
+    return batch_host_encode("encode_aplanes_batch_host", codec, items, batch_pred_none(), true, filters_out, count, esize, chunk, cdfnum, items_on, out, outcap);
 }
 
-// both host decoders behind their checks: in = a checked TRCB container; strides = the TRCT prefix's (NULL: a TRCB container alone)
-static size_t batch_host_decode(const char *who, const void *in, const uint8_t *strides, const trc_planes_item *items, size_t count,
+// both host decoders behind their checks: in = a checked TRCB container; pred = its filters, with the TRCT prefix's strides where it has one
+static size_t batch_host_decode(const char *who, const void *in, const BatchPred pred, const trc_planes_item *items, size_t count,
                                 size_t first_item, size_t item_count, int items_on)
 {
     const uint8_t *b = (const uint8_t *)in;
     trc_planes_batch_hdr h;
     memcpy(&h, b, sizeof h);
-    const uint8_t *filters = b + sizeof h + 8 * count;
     for (size_t i = 0; i < count; i++) {
         uint64_t n;
         memcpy(&n, b + sizeof h + 8 * i, 8);
@@ -417,8 +418,8 @@ static size_t batch_host_decode(const char *who, const void *in, const uint8_t *
         if (grow(&c.d_in, &c.cap_in, bytes)) return 0;
         for (size_t i = 0; i < count; i++) dev[i].d_ptr = i >= first_item && i < first_item + item_count ? c.d_in + off[i - first_item] : nullptr;
     }
-    const size_t dirsz = up256(esize * 4 * cnt + 256), table = trc_planes_batch_table_bytes(item_count, cnt);
-    if (grow(&c.d_cont, &c.cap_cont, dirsz + esize * P.buf) || grow(&c.d_work[0], &c.cap_work[0], esize * P.slice + table)) return 0;
+    const size_t dirsz = up256(esize * 4 * cnt + 256);
+    if (grow(&c.d_cont, &c.cap_cont, dirsz + esize * P.buf) || grow(&c.d_work[0], &c.cap_work[0], esize * P.slice + batch_pred_table_bytes(pred, item_count, cnt))) return 0;
     uint32_t *d_clen = (uint32_t *)c.d_cont;
     uint8_t *d_payload = c.d_cont + dirsz;
     uint16_t *d_cdf = (uint16_t *)c.d_small;
@@ -439,7 +440,7 @@ static size_t batch_host_decode(const char *who, const void *in, const uint8_t *
         D.clen[k] = d_clen + k * cnt;
         D.payload[k] = d_payload + k * P.buf;
     }
-    if (decode_batch(who, p.codec, D, dev.data(), filters, count, first_item, item_count, esize, chunk, p.cdfnum, c.d_work[0], c.cap_work[0], s, elems, strides)) {
+    if (decode_batch(who, p.codec, D, elems, dev.data(), pred, count, first_item, item_count, esize, chunk, p.cdfnum, c.d_work[0], c.cap_work[0], s)) {
         (void)hipStreamSynchronize(s);
         return 0;
     }
@@ -459,7 +460,7 @@ extern "C" size_t trc_decode_planes_batch_host(const void *in, size_t inlen, con
     const char *who = "decode_planes_batch_host";
     if (!in || !items || (items_on != TRC_ITEMS_HOST && items_on != TRC_ITEMS_DEV)) { fail(TRC_E_ARG, "%s: bad arguments", who); return 0; }
     if (trc_planes_batch_check(in, inlen, count)) return 0;
-    return batch_host_decode(who, in, nullptr, items, count, first_item, item_count, items_on);
+    return batch_host_decode(who, in, batch_pred_strides(batch_filters(in, count), nullptr), items, count, first_item, item_count, items_on);
 }
 
 // ---- the TRCT container: the strides of a batch in front of its TRCB container ---------------------------------------------------
@@ -559,8 +560,8 @@ extern "C" int trc_decode_splanes_batch_packed_dev(int codec, const void *d_cont
                                                    const uint64_t *total, void *d_work, size_t work_bytes, void *stream)
 {
     const size_t prefix = sbatch_prefix_bytes(count <= TRC_PLANES_BATCH_MAX ? count : 0);     // (a bad count: the plan says so before d_cont is looked at)
-    return packed_decode("decode_splanes_batch_packed", codec, d_cont ? (const uint8_t *)d_cont + prefix : nullptr, prefix, cont_bytes, items, filters,
-                         strides, count, first_item, item_count, esize, chunk, cdfnum, total, d_work, work_bytes, stream);
+    return packed_decode("decode_splanes_batch_packed", codec, d_cont ? (const uint8_t *)d_cont + prefix : nullptr, prefix, cont_bytes, items,
+                         batch_pred_strides(filters, strides), count, first_item, item_count, esize, chunk, cdfnum, total, d_work, work_bytes, stream);
 }
 
 extern "C" size_t trc_encode_splanes_batch_host(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
@@ -569,7 +570,7 @@ extern "C" size_t trc_encode_splanes_batch_host(int codec, const trc_planes_item
 {
     const char *who = "encode_splanes_batch_host";
     if (!strides) { fail(TRC_E_ARG, "%s: no strides: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
-    return batch_host_encode(who, codec, items, filters, strides, false, nullptr, count, esize, chunk, cdfnum, items_on, out, outcap);
+    return batch_host_encode(who, codec, items, batch_pred_strides(filters, strides), false, nullptr, count, esize, chunk, cdfnum, items_on, out, outcap);
 }
 
 extern "C" size_t trc_decode_splanes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
@@ -579,5 +580,6 @@ extern "C" size_t trc_decode_splanes_batch_host(const void *in, size_t inlen, co
     if (!in || !items || (items_on != TRC_ITEMS_HOST && items_on != TRC_ITEMS_DEV)) { fail(TRC_E_ARG, "%s: bad arguments", who); return 0; }
     if (trc_planes_sbatch_check(in, inlen, count)) return 0;
     const size_t prefix = sbatch_prefix_bytes(count);
-    return batch_host_decode(who, (const uint8_t *)in + prefix, (const uint8_t *)in + sizeof(trc_planes_sbatch_hdr), items, count, first_item, item_count, items_on);
+    const uint8_t *trcb = (const uint8_t *)in + prefix;
+    return batch_host_decode(who, trcb, batch_pred_strides(batch_filters(trcb, count), (const uint8_t *)in + sizeof(trc_planes_sbatch_hdr)), items, count, first_item, item_count, items_on);
 }

@@ -100,7 +100,7 @@ int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, co
     if (strided)
         for (size_t i = 0; i < item_count; i++) recs[i].v0 |= (uint64_t)(strides[first_item + i] - 1) << SBATCH_SHIFT;
     if (!d_hist || ((uintptr_t)d_hist & 7)) return trc_fail(TRC_E_ARG, "%s: the histograms must be 8-byte aligned", who);
-    if ((rc = batch_table_args(who, item_count, chunks, d_table, table_bytes))) return rc;
+    if ((rc = batch_table_args(who, trc_planes_batch_table_bytes(item_count, chunks), d_table, table_bytes))) return rc;
     const HistShape hs = hist_shape(filters, esize);
     // a workgroup per 256 vectors of the range under the caps of trc_planes_hist_dev, then whole chunks per workgroup
     unsigned grid = batch_grid((size_t)chunks * (chunk / TRC_PLANES_VEC));

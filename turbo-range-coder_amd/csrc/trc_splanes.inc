@@ -3,8 +3,6 @@
 // is the TRCF container with the stride where that one has its reserved field.  Nothing here knows a coder or a kernel.
 
 // the stride is looked at ahead of everything else, pointers included
-// (it also keeps PLANES_VS_BASE, which travels where a stride does inside trc_planes.inc, from ever arriving through a strided call)
-static_assert(PLANES_VS_BASE < 1, "stride_common must refuse the value that selects the kernels against a base");
 static int stride_common(const char *who, int stride)
 {
     if (stride < 1 || stride > TRC_STRIDE_MAX) return fail(TRC_E_ARG, "%s: stride %d (1 .. %d)", who, stride, TRC_STRIDE_MAX);
@@ -18,7 +16,7 @@ extern "C" int trc_encode_splanes_dev(int codec, int filter, int stride, const v
 {
     const int rc = stride_common("encode_splanes", stride);
     if (rc) return rc;
-    return planes_encode_dev(codec, filter, filter == TRC_FILTER_NONE ? 1 : stride, d_in, n, esize, chunk, d_cdf, cdfnum, d_status,
+    return planes_encode_dev(codec, pred_stride(filter, stride), d_in, n, esize, chunk, d_cdf, cdfnum, d_status,
                              d_clen, d_payload, d_total, d_tail, d_work, work_bytes, stream);
 }
 
@@ -28,7 +26,7 @@ extern "C" int trc_decode_splanes_dev(int codec, int filter, int stride, const u
 {
     const int rc = stride_common("decode_splanes", stride);
     if (rc) return rc;
-    return planes_decode_dev(codec, filter, filter == TRC_FILTER_NONE ? 1 : stride, d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum,
+    return planes_decode_dev(codec, pred_stride(filter, stride), d_clen, d_payload, d_tail, n, esize, chunk, d_cdf, cdfnum,
                              d_out, d_work, work_bytes, stream);
 }
 
@@ -39,7 +37,7 @@ extern "C" int trc_decode_splanes_range_dev(int codec, int filter, int stride, c
 {
     const int rc = stride_common("decode_splanes_range", stride);
     if (rc) return rc;
-    return planes_decode_range_dev(codec, filter, filter == TRC_FILTER_NONE ? 1 : stride, d_clen, d_payload, n, esize, chunk, first_chunk, count,
+    return planes_decode_range_dev(codec, pred_stride(filter, stride), d_clen, d_payload, n, esize, chunk, first_chunk, count,
                                    d_cdf, cdfnum, d_out, d_work, work_bytes, stream);
 }
 
@@ -53,14 +51,8 @@ extern "C" size_t trc_splanes_bound(size_t n, unsigned esize, uint32_t chunk, un
 // the prefix alone: 0 and the header, or TRC_E_ARG with the reason set
 static int splanes_prefix(const void *buf, size_t buflen, trc_splanes_hdr &h)
 {
-    if (!buf || buflen < sizeof h) return fail(TRC_E_ARG, "strided planes container: %zu bytes is shorter than the header", buflen);
-    memcpy(&h, buf, sizeof h);
-    if (h.magic != TRC_SPLANES_MAGIC || h.version != 1) return fail(TRC_E_ARG, "strided planes container: bad magic/version");
-    if (h.filter != TRC_FILTER_ZDELTA && h.filter != TRC_FILTER_XOR) return fail(TRC_E_ARG, "strided planes container: filter %u (1 zigzag delta, 2 xor)", h.filter);
-    if (h.stride < 2 || h.stride > TRC_STRIDE_MAX) return fail(TRC_E_ARG, "strided planes container: stride %u (2 .. %d)", h.stride, TRC_STRIDE_MAX);
-    if (h.size > buflen) return fail(TRC_E_ARG, "strided planes container: states %llu bytes, the buffer holds %zu", (unsigned long long)h.size, buflen);
-    if (h.size <= sizeof h) return fail(TRC_E_ARG, "strided planes container: size %llu leaves no room behind the header", (unsigned long long)h.size);
-    return TRC_OK;
+    return planes_prefix("strided planes container", TRC_SPLANES_MAGIC, buf, buflen, h, [](const trc_splanes_hdr &t) {
+        return t.stride < 2 || t.stride > TRC_STRIDE_MAX ? fail(TRC_E_ARG, "strided planes container: stride %u (2 .. %d)", t.stride, TRC_STRIDE_MAX) : (int)TRC_OK; });
 }
 extern "C" int trc_splanes_check(const void *buf, size_t buflen, size_t outlen)
 {
@@ -79,8 +71,7 @@ extern "C" size_t trc_encode_splanes_host(int codec, int filter, int stride, con
     }
     if (stride == 1) { fail(TRC_E_ARG, "encode_splanes_host: stride 1 goes through trc_encode_fplanes_host (one layout per content)"); return 0; }
     if (!out || outcap <= sizeof(trc_splanes_hdr)) { fail(TRC_E_ARG, "encode_splanes_host: out holds %zu bytes (trc_splanes_bound)", outcap); return 0; }
-    const size_t inner = planes_host_encode(codec, filter, in, n, esize, chunk, (uint8_t *)out + sizeof(trc_splanes_hdr), outcap - sizeof(trc_splanes_hdr), cdfnum,
-                                            nullptr, stride);
+    const size_t inner = planes_host_encode(codec, pred_stride(filter, stride), false, in, n, esize, chunk, (uint8_t *)out + sizeof(trc_splanes_hdr), outcap - sizeof(trc_splanes_hdr), cdfnum, nullptr, nullptr);
     if (!inner) return 0;
     trc_splanes_hdr h;
     memset(&h, 0, sizeof h);
@@ -95,7 +86,7 @@ extern "C" size_t trc_decode_splanes_host(const void *in, size_t inlen, void *ou
     trc_splanes_hdr h;
     if (!in || !out) { fail(TRC_E_ARG, "decode_splanes_host: bad arguments"); return 0; }
     if (splanes_prefix(in, inlen, h)) return 0;
-    return planes_host_decode_all(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, out, outlen, h.stride);
+    return planes_host_decode_all(pred_stride(h.filter, h.stride), (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, out, outlen, nullptr);
 }
 
 extern "C" size_t trc_decode_splanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out)
@@ -103,5 +94,5 @@ extern "C" size_t trc_decode_splanes_range_host(const void *in, size_t inlen, si
     trc_splanes_hdr h;
     if (!in || !out) { fail(TRC_E_ARG, "decode_splanes_range_host: bad arguments"); return 0; }
     if (splanes_prefix(in, inlen, h)) return 0;
-    return planes_host_decode_bytes(h.filter, (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out, h.stride);
+    return planes_host_decode_bytes(pred_stride(h.filter, h.stride), (const uint8_t *)in + sizeof h, (size_t)h.size - sizeof h, offset, len, out);
 }

@@ -628,15 +628,20 @@ def planes_join_batch(d_planes, offset, pitch, items, count, first_item, item_co
                                          d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
 
 
+def _byte_per_item(what, values, count):
+    """None, one int for every item or a sequence of `count` ints as the host array of bytes the batch calls take"""
+    if values is None:
+        return None
+    v = [values] * count if isinstance(values, int) else [int(x) for x in values]
+    if len(v) != count or any(not 0 <= x <= 255 for x in v):
+        raise TrcError("%s: one byte per item of the batch" % what)
+    return (C.c_uint8 * max(count, 1))(*v)
+
+
 def planes_filters(filters, count):
     """the per-item filters of a batch as the host array the filtered batch calls take: None (no filter), one int for every item,
     or a sequence of `count` ints.  Values are not judged here: the library does that."""
-    if filters is None:
-        return None
-    f = [filters] * count if isinstance(filters, int) else [int(x) for x in filters]
-    if len(f) != count or any(not 0 <= x <= 255 for x in f):
-        raise TrcError("filters: one byte per item of the batch")
-    return (C.c_uint8 * max(count, 1))(*f)
+    return _byte_per_item("filters", filters, count)
 
 
 def planes_split_fbatch(items, filters, count, esize, chunk, d_planes, pitch, d_table, table_bytes):
@@ -654,12 +659,7 @@ def planes_join_fbatch(d_planes, offset, pitch, items, filters, count, first_ite
 def planes_strides(strides, count):
     """the per-item strides of a batch as the host array the strided batch calls take: None (stride 1), one int for every item, or a
     sequence of `count` ints.  Values are not judged here: the library does that."""
-    if strides is None:
-        return None
-    s = [strides] * count if isinstance(strides, int) else [int(x) for x in strides]
-    if len(s) != count or any(not 0 <= x <= 255 for x in s):
-        raise TrcError("strides: one byte per item of the batch")
-    return (C.c_uint8 * max(count, 1))(*s)
+    return _byte_per_item("strides", strides, count)
 
 
 def planes_split_sbatch(items, filters, strides, count, esize, chunk, d_planes, pitch, d_table, table_bytes):
@@ -766,14 +766,21 @@ class PlanesBatchCoder:
         st = self.codec in STATIC
         tail = (self.count, self.esize, self.chunk, self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
                 self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), self.work.data_ptr(), self.work_bytes, self._stream())
+        fam, lead = self._family()
+        _chk(getattr(lib(), "trc_encode_%splanes_batch_dev" % fam)(self.codec | flags, self.items, *lead, *tail))
+
+    def _family(self, bases=None):
+        """which calls the coder's bases, filters and strides select as they stand -- "b", "" (no filter), "s" or "f", the letter in
+        front of "planes" in their names -- and what those take between the items and `count`.  bases: others than the coder's"""
         if self.bases is not None:
-            _chk(lib().trc_encode_bplanes_batch_dev(self.codec | flags, self.items, self.bases, self.filters, *tail))
-        elif self.filters is None:
-            _chk(lib().trc_encode_planes_batch_dev(self.codec | flags, self.items, *tail))
-        elif self.strided():
-            _chk(lib().trc_encode_splanes_batch_dev(self.codec | flags, self.items, self.filters, self.strides, *tail))
-        else:
-            _chk(lib().trc_encode_fplanes_batch_dev(self.codec | flags, self.items, self.filters, *tail))
+            return "b", (self.bases if bases is None else planes_bases(list(bases), self.count), self.filters)
+        if self.filters is None:
+            return "", ()
+        return ("s", (self.filters, self.strides)) if self.strided() else ("f", (self.filters,))
+
+    def _packed_family(self):
+        """the same for the container calls, which come strided ("s") or not ("") and always take the filters, None included"""
+        return ("s", (self.filters, self.strides)) if self.strided() else ("", (self.filters,))
 
     def strided(self):
         """whether an item with a filter has a stride above 1: the strided calls; else today's"""
@@ -794,16 +801,8 @@ class PlanesBatchCoder:
             self.range_work = self._buf(0)
         tail = (self.count, first_item, item_count, self.esize, self.chunk, self.cdf.data_ptr() if self.codec in STATIC else None, self.cdfnum,
                 self.range_work.data_ptr(), self.range_work_bytes, self._stream())
-        if self.bases is not None:
-            _chk(lib().trc_decode_bplanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items,
-                                                    self.bases if bases is None else planes_bases(list(bases), self.count), self.filters, *tail))
-        elif self.filters is None:
-            _chk(lib().trc_decode_planes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, *tail))
-        elif self.strided():
-            _chk(lib().trc_decode_splanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.filters,
-                                                    self.strides, *tail))
-        else:
-            _chk(lib().trc_decode_fplanes_batch_dev(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, self.filters, *tail))
+        fam, lead = self._family(bases)
+        _chk(getattr(lib(), "trc_decode_%splanes_batch_dev" % fam)(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, *lead, *tail))
 
     def pack(self, guard=0):
         """enqueue trc_planes_batch_pack_dev (strided(): trc_planes_sbatch_pack_dev, the TRCT container, sized by trc_planes_sbatch_bound)
@@ -814,18 +813,15 @@ class PlanesBatchCoder:
         if self.bases is not None:
             raise TrcError("pack: the TRCB container has no place for a base; a batch against bases has no container")
         st = self.codec in STATIC
-        strided = self.strided()
-        bound = (lib().trc_planes_sbatch_bound if strided else lib().trc_planes_batch_bound)(self.codec, self.items, self.count, self.esize, self.chunk, self.cdfnum)
+        fam, lead = self._packed_family()
+        bound = getattr(lib(), "trc_planes_%sbatch_bound" % fam)(self.codec, self.items, self.count, self.esize, self.chunk, self.cdfnum)
         if bound == 0:
             raise TrcError("bad (codec, tensors, chunk, cdfnum)")
         buf = self.torch.full((bound + guard,), 0xA5 if guard else 0, dtype=self.torch.uint8, device=self.dev)
         d_size = self.torch.zeros(1, dtype=self.torch.int64, device=self.dev)
         tail = (self.count, self.esize, self.chunk, self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
                 self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), buf.data_ptr(), bound, d_size.data_ptr(), self._stream())
-        if strided:
-            _chk(lib().trc_planes_sbatch_pack_dev(self.codec, self.items, self.filters, self.strides, *tail))
-        else:
-            _chk(lib().trc_planes_batch_pack_dev(self.codec, self.items, self.filters, *tail))
+        _chk(getattr(lib(), "trc_planes_%sbatch_pack_dev" % fam)(self.codec, self.items, *lead, *tail))
         size = int(d_size.item())
         self.packed, self.pack_guard = buf, buf[size:]
         return buf[:size], size
@@ -844,11 +840,9 @@ class PlanesBatchCoder:
         tot = (C.c_uint64 * 8)(*[int(x) for x in total])
         tail = (self.count, first_item, item_count, self.esize, self.chunk, self.cdfnum, tot, self.range_work.data_ptr(),
                 need if work_bytes is None else work_bytes, self._stream())
-        cont = (self.codec, d_cont.data_ptr(), d_cont.numel() if cont_bytes is None else cont_bytes, items, self.filters)
-        if self.strided():                                     # (d_cont: the TRCT container pack() gave)
-            _chk(lib().trc_decode_splanes_batch_packed_dev(*cont, self.strides, *tail))
-        else:
-            _chk(lib().trc_decode_planes_batch_packed_dev(*cont, *tail))
+        fam, lead = self._packed_family()                      # ("s": d_cont is the TRCT container pack() gave)
+        _chk(getattr(lib(), "trc_decode_%splanes_batch_packed_dev" % fam)(self.codec, d_cont.data_ptr(), d_cont.numel() if cont_bytes is None else cont_bytes,
+                                                                         items, *lead, *tail))
 
     def stored_bytes(self):
         """Synchronise: payload + directory (+ CDFs of a static coder) of all planes"""
