@@ -36,6 +36,16 @@
  *   trcfile l <in>                list a file of b: count, esize, chunk, coder and every item's bytes and filter (needs no GPU).  B and l
  *                                 also read the library's TRCT container (a TRCB container behind a stride per item, which this
  *                                 tool does not write); l then adds a stride column
+ *   trcfile e <id> <esize> <chunk|0> <z|x|a> <out> <in> <base|-> [<in> <base|-> ...]   compress a BATCH AGAINST BASES: every input file is
+ *                                 one item and is followed by its base file (the same tensor of the previous checkpoint; at least the
+ *                                 item's bytes), or by - for an item without one, which is coded unfiltered.  z / x: that filter for
+ *                                 every item with a base; a = the library's advisor against the bases chooses per item
+ *                                 (trc_encode_abplanes_batch_host) and every choice is printed.  The file is the library's TRCE
+ *                                 container: a fingerprint per base in front of a TRCB container -- or, where no item ends up with a
+ *                                 filter, a plain TRCB container, which B reads
+ *   trcfile E <in> <item> <base|-> <out>   item <item> of a file of e against its base file (- where it has no filter): only the chunks
+ *                                 that cover it are sent to the GPU; a base with another fingerprint is refused.  l lists such a file
+ *                                 with every item's base fingerprint (needs no GPU); B does not read it: it has no bases to give
  *   trcfile d <in> <out>          decompress (files of c, p, f, s and a)
  *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p, f or s: only the
  *                                 chunks that cover them are sent to the GPU and decoded (trc_decode_range_host)
@@ -354,6 +364,91 @@ int main(int argc, char **argv)
         printf("%zu items, %zu -> %zu bytes (%.2f%%)  %u planes\n", count, total, l, 100.0 * l / total, esize);
         return 0;
     }
+    if (argc >= 9 && !((argc - 7) & 1) && !strcmp(argv[1], "e")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        const uint32_t chunk = (uint32_t)strtoul(argv[4], 0, 10);
+        const char *fl = argv[5];
+        const size_t count = (size_t)(argc - 7) / 2;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (strlen(fl) != 1 || !strchr("zxa", fl[0])) { fprintf(stderr, "filter %s: z (zigzag delta), x (xor) or a (the advisor, per item)\n", fl); return 2; }
+        trc_planes_item *items = calloc(count, sizeof *items);
+        const void **bases = calloc(count, sizeof *bases);
+        uint8_t *filters = calloc(count, 1);
+        if (!items || !bases || !filters) { perror("malloc"); return 2; }
+        size_t total = 0;
+        for (size_t i = 0; i < count; i++) {
+            size_t n, bn;
+            if (!(items[i].d_ptr = slurp(argv[7 + 2 * i], &n))) return 2;
+            items[i].n = n; total += n;
+            if (strcmp(argv[8 + 2 * i], "-")) {
+                if (!(bases[i] = slurp(argv[8 + 2 * i], &bn))) return 2;
+                if (bn < n) { fprintf(stderr, "%s holds %zu bytes, its item %zu\n", argv[8 + 2 * i], bn, n); return 2; }
+                filters[i] = fl[0] == 'z' ? TRC_FILTER_ZDELTA : TRC_FILTER_XOR;
+            }
+        }
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_planes_bbatch_bound(codec, items, count, esize, chunk, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u, chunk %u: esize is 2, 4 or 8, the chunk 0 or a multiple of 64, and every file holds whole elements, at least one\n", esize, chunk); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        const size_t l = fl[0] == 'a' ? trc_encode_abplanes_batch_host(codec, items, bases, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap, filters)
+                                      : trc_encode_bplanes_batch_host(codec, items, bases, filters, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[6], out, l)) return 2;
+        if (fl[0] == 'a') for (size_t i = 0; i < count; i++) printf("item %zu: %llu bytes, choice %c  %s\n", i, (unsigned long long)items[i].n, "nzx"[filters[i]], argv[7 + 2 * i]);
+        printf("%zu items, %zu -> %zu bytes (%.2f%%)  %u planes, %.4s\n", count, total, l, 100.0 * l / total, esize, (const char *)out);
+        return 0;
+    }
+    if (argc == 6 && !strcmp(argv[1], "E")) {
+        size_t fl, bn = 0;
+        unsigned char *fb = slurp(argv[2], &fl);
+        if (!fb) return 2;
+        const int based = fl >= 4 && !memcmp(fb, "TRCE", 4);
+        trc_planes_batch_hdr h;
+        if (based ? trc_planes_bbatch_info(fb, fl, &h, 0, 0, 0, 0) : trc_planes_batch_info(fb, fl, &h, 0, 0, 0)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        const size_t count = (size_t)h.count, item = (size_t)strtoull(argv[3], 0, 10);
+        if (item >= count) { fprintf(stderr, "item %zu of %zu\n", item, count); return 2; }
+        uint64_t *n = calloc(count, sizeof *n);
+        trc_planes_item *items = calloc(count, sizeof *items);
+        const void **bases = calloc(count, sizeof *bases);
+        if (!n || !items || !bases) { perror("malloc"); return 2; }
+        if (based ? trc_planes_bbatch_info(fb, fl, &h, n, 0, 0, count) : trc_planes_batch_info(fb, fl, &h, n, 0, count)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        for (size_t i = 0; i < count; i++) items[i].n = n[i];
+        unsigned char *out = malloc((size_t)n[item] + 1024);
+        if (!out) { perror("malloc"); return 2; }
+        items[item].d_ptr = out;
+        if (strcmp(argv[4], "-")) {
+            if (!(bases[item] = slurp(argv[4], &bn))) return 2;
+            if (bn < n[item]) { fprintf(stderr, "%s holds %zu bytes, the item %llu\n", argv[4], bn, (unsigned long long)n[item]); return 2; }
+        }
+        if (trc_decode_bplanes_batch_host(fb, fl, items, bases, count, item, 1, TRC_ITEMS_HOST) != n[item]) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+        return write_file(argv[5], out, (size_t)n[item]);
+    }
+    if (argc == 3 && !strcmp(argv[1], "l")) {          /* a file of e: the TRCB listing with the bases' fingerprints */
+        size_t fl;
+        unsigned char *fb = slurp(argv[2], &fl);
+        if (!fb) return 2;
+        if (fl >= 4 && !memcmp(fb, "TRCE", 4)) {
+            trc_planes_batch_hdr h;
+            if (trc_planes_bbatch_info(fb, fl, &h, 0, 0, 0, 0)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            const size_t count = (size_t)h.count, lead = sizeof(trc_planes_bbatch_hdr) + ((8 * count + 15) & ~(size_t)15);
+            uint64_t *n = calloc(count, sizeof *n), *fp = calloc(count, sizeof *fp);
+            uint8_t *filters = calloc(count, 1);
+            if (!n || !fp || !filters) { perror("malloc"); return 2; }
+            if (trc_planes_bbatch_info(fb, fl, &h, n, filters, fp, count)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            trc_planes_hdr ph;
+            memcpy(&ph, fb + lead + h.inner, sizeof ph);
+            printf("%llu items, esize %u, chunk %u, codec %u, %llu -> %llu bytes, against bases\n", (unsigned long long)h.count, h.esize, h.chunk, ph.codec,
+                   (unsigned long long)h.bytes, (unsigned long long)(lead + h.size));
+            for (size_t i = 0; i < count; i++) {
+                if (filters[i]) printf("item %zu: %llu bytes, filter %c, base %016llx\n", i, (unsigned long long)n[i], "nzx"[filters[i]], (unsigned long long)fp[i]);
+                else printf("item %zu: %llu bytes, filter n\n", i, (unsigned long long)n[i]);
+            }
+            return 0;
+        }
+        free(fb);
+    }
     if ((argc == 6 && !strcmp(argv[1], "B")) || (argc == 3 && !strcmp(argv[1], "l"))) {
         const int list = argv[1][0] == 'l';
         size_t fl;
@@ -615,6 +710,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in> | trcfile r <id> <esize> <z|x> <base> <in> <out> | trcfile R <in> <base> <out>\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in> | trcfile r <id> <esize> <z|x> <base> <in> <out> | trcfile R <in> <base> <out> | trcfile e <id> <esize> <chunk|0> <z|x|a> <out> <in> <base|-> ... | trcfile E <in> <item> <base|-> <out>\n");
     return 2;
 }

@@ -789,8 +789,8 @@ int trc_decode_fplanes_batch_dev(int codec, const uint32_t *d_clen, const void *
  * not checked and gives undefined results.  Order of checks: the plan (host only), the filters (the item's index in the message),
  * then pointers and buffers.  The base pointers travel as a uint64 array behind the chunk map of the table:
  * trc_planes_bbatch_table_bytes = trc_planes_batch_table_bytes + 8 * count rounded up to 256, and the work-bytes functions are the
- * unfiltered batch's plus that.  The join is elementwise (no scan).  The TRCB container has no place for a base: these batches
- * have no host-pointer container yet. */
+ * unfiltered batch's plus that.  The join is elementwise (no scan).  The TRCB container has no place for a base: the TRCE
+ * container below carries these batches. */
 int trc_planes_split_bbatch_dev(const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
                                 unsigned esize, uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream);
 int trc_planes_join_bbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const void *const *bases,
@@ -1046,6 +1046,120 @@ int trc_planes_hist_sbatch_dev(unsigned filters, const trc_planes_item *items, c
 int trc_planes_advise_sbatch_dev(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize,
                                  uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice,
                                  void *d_work, size_t work_bytes, void *stream);
+
+/* ---- batched byte planes against a base per item: fingerprints per base, the TRCE container --------------------------------------
+ * A batch coded against bases decodes silently wrong against any other base, and in place it destroys that base.  So a container of
+ * such a batch names every base by its fingerprint (trc_base_fingerprint_host, above), and the fingerprints of a whole batch come
+ * from ONE launch.
+ *
+ * trc_base_fingerprint_batch_dev: for j in [0, item_count), i = first_item + j:
+ *        d_fp[j] = trc_base_fingerprint_host(bases[i], items[i].n)   where filters[i] != TRC_FILTER_NONE
+ *                = 0                                                 otherwise (bases[i] is not looked at and may be NULL)
+ * exactly: the sum wraps mod 2^64, so every order of addition gives the same value.  The call zeroes d_fp[0, item_count) on the
+ * stream first.  It reads bytes [0, n[i]) of a requested base and nothing else (whole 16-byte words, the bytes behind them one by
+ * one: no slack needed); no d_ptr is looked at.  The work is cut by bytes, not by items: a 200 MB base is shared by many workgroups,
+ * thousands of 4 KiB bases share a few.  Checks, in this order: the items (1 .. TRC_PLANES_BATCH_MAX of them, none empty), the
+ * filters, the range, the pointers (a requested base non-NULL and 16-byte aligned, d_fp 8-byte aligned), the table: 256-byte
+ * aligned, trc_base_fingerprint_batch_table_bytes(item_count) bytes (32 per item for the records and 8 per item that
+ * trc_base_verify_batch_dev uses, each rounded up to 256; 0 for 0 or too many items), TRC_E_WORK where it is smaller.
+ * item_count == 0 is TRC_OK with nothing enqueued.  `items`, `bases` and `filters` are free again when the call returns; apart from
+ * that upload the call only enqueues work.  TRC_PLANES_GRID caps the grid as it does the other plane kernels'.
+ *
+ * The TRCE container, little endian, mirrors TRCT -- a prefix in front of an unchanged TRCB container:
+ *   trc_planes_bbatch_hdr (16 B) | uint64 base_fp[count], zero-padded so that the prefix is a multiple of 16 | the TRCB container
+ * The TRCB part is that of (items, filters) with the inner TRCP container of V([G(0) .. G(count - 1)]), G as above: byte for byte
+ * what trc_planes_batch_pack_dev writes for the outputs of trc_encode_bplanes_batch_dev, its header's `size` its own -- so
+ * trc_planes_batch_check, trc_planes_batch_info and trc_planes_check work on that part as they stand.  base_fp[i] is the
+ * fingerprint of bases[i] over n[i] bytes (a base's length is its item's and is not stored), 0 for an item without a filter.  One
+ * layout per content: a batch in which every filter is NONE is a TRCB container, and trc_planes_bbatch_pack_dev refuses it
+ * (TRC_E_ARG, naming trc_planes_batch_pack_dev).
+ * Host only, no GPU needed:
+ *   trc_planes_bbatch_bound   trc_planes_batch_bound + prefix, prefix = 16 + up16(8 count); 0 for what the calls reject.
+ *   trc_planes_bbatch_check   in this order: magic, version, the zero fields, count in 1 .. TRC_PLANES_BATCH_MAX (and == count_expected
+ *                             unless that is (size_t)-1), the prefix within buflen, zero padding, trc_planes_batch_check on the rest,
+ *                             its count equal to the prefix's, base_fp[i] == 0 wherever filter[i] is NONE, at least one filter set.
+ *                             A failure leaves the reason in trc_last_error(), prefixed "based batch container:", naming the item.
+ *   trc_planes_bbatch_info    trc_planes_batch_info (the TRCB header, n, filters) plus the first min(cap, count) fingerprints
+ *                             (n, filters, base_fp: may be NULL), nothing behind them.
+ * trc_planes_bbatch_pack_dev writes the container in device memory without a host round trip: the 16-byte header (an upload), the
+ * zero padding, trc_base_fingerprint_batch_dev with d_fp = d_out + 16, trc_planes_batch_pack_dev on d_out + prefix (a multiple of
+ * 16, so that call's alignment holds); *d_size comes out as the WHOLE size (0 as there).  out_bytes >= trc_planes_bbatch_bound, the
+ * table that of the fingerprint call for `count` items; nothing at or behind d_out + size is written.  Checks: the plan, the
+ * filters, the all-NONE refusal, the bases, the table, then those of trc_planes_batch_pack_dev; nothing is enqueued unless all pass.
+ * trc_decode_bplanes_batch_packed_dev is trc_decode_planes_batch_packed_dev on a TRCE container: d_cont is its start (16-byte
+ * aligned), cont_bytes and TRC_PAD count from there, `bases` stand next to `filters` (bases[i] == items[i].d_ptr: in place), the
+ * workspace is trc_planes_bbatch_range_work_bytes.  It trusts its buffers as every _dev call does and does NOT verify the bases.
+ * trc_base_verify_batch_dev fingerprints the bases of items [first_item, first_item + item_count) (the call above, into the
+ * table's second part) and a small kernel writes *d_bad (8-byte aligned, device): the lowest item index whose fingerprint differs
+ * from the base_fp of the container at d_cont (device, 8-byte aligned; only its prefix is read), or -1.  A batch range holds whole items, so every requested base is seen whole.  It only enqueues
+ * work (but for the table upload): the caller decides whether to wait for *d_bad before a decode in place.  The decode does not
+ * gate on it because that would put a flag read into every join kernel, or a host round trip into a call that only enqueues: the
+ * join kernels stay as they are, and a caller who cannot afford a wrong base reads *d_bad first.
+ *
+ * Through host pointers (TRC_ITEMS_HOST / TRC_ITEMS_DEV as for TRCB; the BASES lie where the items lie): trc_encode_bplanes_batch_host
+ * is the batched encode against the bases and trc_planes_bbatch_pack_dev, one synchronise to read the size, one copy; it returns the
+ * size, 0 on error, and refuses an all-NONE batch (naming trc_encode_planes_batch_host), a bad filter id and the low-nibble coders
+ * before any device is needed.  trc_decode_bplanes_batch_host checks the container, wants items[i].n == n[i] for ALL entries, uploads
+ * (or uses) only the requested items' bases and compares their fingerprints with the container's BEFORE anything is decoded: on a
+ * mismatch it returns 0 with "base fingerprint", the item's index and both values in trc_last_error(), and no output is touched.  A
+ * wrong base outside the range is not looked at.  bases[i] == items[i].d_ptr is the in-place case.  It also reads a plain TRCB
+ * container (no item has a base: `bases` is ignored and may be NULL).
+ *
+ * The advisor against bases, per item.  trc_planes_hist_bbatch_dev is trc_planes_hist_batch_dev with item i predicted from
+ * bases[i]: slice j is exactly what trc_planes_hist_base_dev(filters, item, base, n, esize, ...) writes for item first_item + j
+ * alone -- no restart, no seg (`chunk` shapes the plan and the walk only), pad elements counted nowhere.  An item whose base is NULL
+ * (or bases == NULL) gets the unfiltered row alone: rows 1 and 2 of its slice stay zero.  A base is 16-byte aligned, and bytes
+ * [0, n[i]) of it are read, nothing else.  Same d_hist, table (trc_planes_batch_table_bytes: the base's address travels in the
+ * item's record), checks and order as trc_planes_hist_batch_dev.  trc_planes_advise_bbatch (host only) gives per item what
+ * trc_planes_advise gives on the item's slice under the bit set filters & (bases[i] ? 7 : 1) -- same estimates, ties and 1/64 rule --
+ * so an item with no base is never given a filter (and is TRC_E_ARG, naming the item, where `filters` lacks the unfiltered row).
+ * trc_planes_advise_bbatch_dev does both, with the slabs, the workspace function (trc_planes_advise_batch_work_bytes) and the single
+ * synchronise per slab of trc_planes_advise_batch_dev.  trc_encode_abplanes_batch_host asks it first (all three filters) and writes
+ * exactly the container the explicit call writes for the chosen list, which filters_out (count bytes, may be NULL) receives: TRCE,
+ * or TRCB where no filter was chosen anywhere. */
+#define TRC_PLANES_BBATCH_MAGIC 0x45435254u   /* "TRCE" */
+typedef struct trc_planes_bbatch_hdr {
+    uint32_t magic;      /* TRC_PLANES_BBATCH_MAGIC */
+    uint8_t  version;    /* 1 */
+    uint8_t  zero;
+    uint16_t zero2;
+    uint64_t count;      /* items: that of the TRCB container behind the fingerprints */
+} trc_planes_bbatch_hdr; /* 16 bytes, little endian */
+size_t trc_base_fingerprint_batch_table_bytes(size_t item_count);
+int    trc_base_fingerprint_batch_dev(const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
+                                      size_t first_item, size_t item_count, uint64_t *d_fp,
+                                      void *d_table, size_t table_bytes, void *stream);
+size_t trc_planes_bbatch_bound(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum);
+int    trc_planes_bbatch_check(const void *buf, size_t buflen, size_t count_expected);
+int    trc_planes_bbatch_info(const void *buf, size_t buflen, trc_planes_batch_hdr *h, uint64_t *n, uint8_t *filters, uint64_t *base_fp, size_t cap);
+int trc_planes_bbatch_pack_dev(int codec, const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
+                               unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                               const int32_t *d_status, const uint32_t *d_clen, const void *d_payload,
+                               const uint64_t *d_total, void *d_out, size_t out_bytes, uint64_t *d_size,
+                               void *d_table, size_t table_bytes, void *stream);
+int trc_decode_bplanes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
+                                        const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
+                                        size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, unsigned cdfnum,
+                                        const uint64_t *total /* host, esize entries */, void *d_work, size_t work_bytes, void *stream);
+size_t trc_encode_bplanes_batch_host(int codec, const trc_planes_item *items, const void *const *bases, const uint8_t *filters,
+                                     size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on,
+                                     void *out, size_t outcap);
+size_t trc_encode_abplanes_batch_host(int codec, const trc_planes_item *items, const void *const *bases, size_t count, unsigned esize,
+                                      uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap,
+                                      uint8_t *filters_out /* may be NULL */);
+size_t trc_decode_bplanes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, const void *const *bases, size_t count,
+                                     size_t first_item, size_t item_count, int items_on);
+int trc_planes_hist_bbatch_dev(unsigned filters, const trc_planes_item *items, const void *const *bases, size_t count,
+                               size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                               uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);
+int trc_planes_advise_bbatch(const uint64_t *hist, unsigned filters, unsigned esize, const trc_planes_item *items,
+                             const void *const *bases, size_t count, uint8_t *filters_out, trc_planes_advice *advice /* may be NULL */);
+int trc_planes_advise_bbatch_dev(unsigned filters, const trc_planes_item *items, const void *const *bases, size_t count, unsigned esize,
+                                 uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice,
+                                 void *d_work, size_t work_bytes, void *stream);
+int trc_base_verify_batch_dev(const void *d_cont, const trc_planes_item *items, const void *const *bases, const uint8_t *filters,
+                              size_t count, size_t first_item, size_t item_count, int64_t *d_bad,
+                              void *d_table, size_t table_bytes, void *stream);
 
 /* Optional timing of the coder kernels: every coder launch of a call carries a HIP event pair (hipExtLaunchKernel
  * start/stop events on the caller's stream), so the durations are the kernels' own -- BOTH passes of the two-pass

@@ -152,13 +152,8 @@ void trc_bplanes_hist_kernel(const uint8_t *__restrict__ in, const uint8_t *__re
 // of the nbytes bytes, zero-padded to 8.  A sum, so its terms are added in any order: a partial sum per thread over the whole
 // 16-byte pairs of words, the bytes behind them (at most 15, read one by one: nothing at or behind p + nbytes is touched) and the
 // length term by one lane, a reduction across the wave and the workgroup, one 64-bit atomicAdd per workgroup into *fp, which the
-// call has zeroed on the stream.
-#define TRC_FP_LEN_MUL 0x9E3779B97F4A7C15ull
-// the terms of words 2i and 2i + 1, the 16-byte pair x
-__device__ __forceinline__ uint64_t fp_pair(size_t i, uint4 x)
-{
-    return (4 * (uint64_t)i + 1) * ((uint64_t)x.x | (uint64_t)x.y << 32) + (4 * (uint64_t)i + 3) * ((uint64_t)x.z | (uint64_t)x.w << 32);
-}
+// call has zeroed on the stream.  (A base per item of a batch, from one launch: trc_fp_batch.inc.)
+#include "trc_fp.h"                               // TRC_FP_LEN_MUL, fp_pair
 __global__ __launch_bounds__(TRC_PLANES_BLOCK)
 void trc_base_fingerprint_kernel(const uint8_t *__restrict__ p, size_t nbytes, u64a *__restrict__ fp)
 {

@@ -388,3 +388,6 @@ extern "C" int trc_planes_join_bbatch_dev(const void *d_planes, size_t pitch, co
 
 // ---- the advisor's histograms, per item ---------------------------------------------------------------------------------------
 #include "trc_planes_hist_batch.inc"
+
+// ---- the fingerprints of a batch's bases, per item ------------------------------------------------------------------------------
+#include "trc_fp_batch.inc"

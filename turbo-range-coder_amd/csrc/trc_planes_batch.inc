@@ -228,11 +228,14 @@ extern "C" int trc_decode_bplanes_batch_dev(int codec, const uint32_t *d_clen, c
 // ---- the batch advisor: a filter per item from the histograms of trc_planes_hist_batch_dev ---------------------------------------
 int trc_planes_hist_batch_run(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t first_item, size_t item_count,
                               unsigned esize, uint32_t chunk, uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);      // trc_planes_hist_batch.inc
+int trc_planes_hist_bbatch_run(unsigned filters, const trc_planes_item *items, const void *const *bases, size_t first_item, size_t item_count,
+                               unsigned esize, uint32_t chunk, uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);     // likewise
 
 // trc_planes_advise on items [base, base + count) of a batch, hist = the first one's slice: choice[i] and advice[i] (may be NULL)
-// count from `base` as well; the index in an error's text is the item's index in the batch
+// count from `base` as well; the index in an error's text is the item's index in the batch.  based: the filters are against
+// bases[i] (of the whole batch), and an item without a base is judged under the unfiltered row alone
 static int advise_items(const uint64_t *hist, unsigned filters, unsigned esize, const trc_planes_item *items, size_t base, size_t count,
-                        uint8_t *choice, trc_planes_advice *advice)
+                        uint8_t *choice, trc_planes_advice *advice, bool based = false, const void *const *bases = nullptr)
 {
     const size_t slice = (size_t)3 * esize * 256;
     for (size_t i = 0; i < count; i++) {
@@ -240,7 +243,7 @@ static int advise_items(const uint64_t *hist, unsigned filters, unsigned esize, 
         if (n < esize || n % esize)
             return fail(TRC_E_ARG, "planes_advise_batch: item %zu has %llu bytes: not a whole number (at least one) of %u-byte elements", base + i, (unsigned long long)n, esize);
         trc_planes_advice a;
-        if (trc_planes_advise(hist + i * slice, filters, esize, (size_t)(n / esize), &a)) {
+        if (trc_planes_advise(hist + i * slice, based && !(bases && bases[base + i]) ? filters & 1u : filters, esize, (size_t)(n / esize), &a)) {
             char why[400];
             snprintf(why, sizeof why, "%s", g_err);
             return fail(TRC_E_ARG, "planes_advise_batch: item %zu: %s", base + i, why);
@@ -261,6 +264,22 @@ extern "C" int trc_planes_advise_batch(const uint64_t *hist, unsigned filters, u
     if (!planes_esize_ok(esize)) return fail(TRC_E_ARG, "planes_advise_batch: esize %u (2, 4 or 8)", esize);
     std::vector<uint8_t> choice(count);
     const int rc = advise_items(hist, filters, esize, items, 0, count, choice.data(), advice);
+    if (rc) return rc;
+    memcpy(filters_out, choice.data(), count);
+    return TRC_OK;
+}
+
+// the same against a base per item: item i under the bit set filters & (bases[i] ? 7 : 1), so an item without a base is never given a
+// filter (and is an error where `filters` does not hold the unfiltered row)
+extern "C" int trc_planes_advise_bbatch(const uint64_t *hist, unsigned filters, unsigned esize, const trc_planes_item *items,
+                                        const void *const *bases, size_t count, uint8_t *filters_out, trc_planes_advice *advice)
+{
+    if (!hist || !items || !filters_out) return fail(TRC_E_ARG, "planes_advise_batch: null histograms, items or filters_out");
+    if (count == 0 || count > TRC_PLANES_BATCH_MAX) return fail(TRC_E_ARG, "planes_advise_batch: %zu items (1 .. %u)", count, TRC_PLANES_BATCH_MAX);
+    if (filters < 1 || filters > 7) return fail(TRC_E_ARG, "planes_advise_batch: filters 0x%x (a bit set of filter ids: 1 none, 2 zigzag delta, 4 xor)", filters);
+    if (!planes_esize_ok(esize)) return fail(TRC_E_ARG, "planes_advise_batch: esize %u (2, 4 or 8)", esize);
+    std::vector<uint8_t> choice(count);
+    const int rc = advise_items(hist, filters, esize, items, 0, count, choice.data(), advice, true, bases);
     if (rc) return rc;
     memcpy(filters_out, choice.data(), count);
     return TRC_OK;
@@ -296,9 +315,10 @@ extern "C" size_t trc_planes_advise_batch_work_bytes(const trc_planes_item *item
     return TRC_PLANES_ADVISE_SLAB_BYTES + advise_table_bytes(items, count, esize, chunk);
 }
 
-// both advisors: strides == NULL is trc_planes_advise_batch_dev
+// all three advisors: strides == NULL and !based is trc_planes_advise_batch_dev; based: against bases[i] (NULL entries, or bases NULL: no base)
 static int advise_batch_dev(unsigned filters, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize, uint32_t chunk,
-                            uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
+                            uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream,
+                            bool based = false, const void *const *bases = nullptr)
 {
     trc_planes_batch_plan B;
     int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
@@ -317,13 +337,14 @@ static int advise_batch_dev(unsigned filters, const trc_planes_item *items, cons
     std::vector<uint8_t> choice(count);
     for (size_t i0 = 0; i0 < count; i0 += slab) {
         const size_t cnt = count - i0 < slab ? count - i0 : slab;
-        if ((rc = trc_planes_hist_batch_run(filters, items, strides, i0, cnt, esize, chunk, d_hist, (uint8_t *)d_work + TRC_PLANES_ADVISE_SLAB_BYTES, table, s))) {
+        if ((rc = based ? trc_planes_hist_bbatch_run(filters, items, bases, i0, cnt, esize, chunk, d_hist, (uint8_t *)d_work + TRC_PLANES_ADVISE_SLAB_BYTES, table, s)
+                        : trc_planes_hist_batch_run(filters, items, strides, i0, cnt, esize, chunk, d_hist, (uint8_t *)d_work + TRC_PLANES_ADVISE_SLAB_BYTES, table, s))) {
             (void)hipStreamSynchronize(s);
             return rc;
         }
         HIPCHK(hipMemcpyAsync(hist.data(), d_hist, cnt * slice * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if ((rc = advise_items(hist.data(), filters, esize, items, i0, cnt, choice.data(), advice))) return rc;
+        if ((rc = advise_items(hist.data(), filters, esize, items, i0, cnt, choice.data(), advice, based, bases))) return rc;
     }
     memcpy(filters_out, choice.data(), count);
     return TRC_OK;
@@ -339,4 +360,10 @@ extern "C" int trc_planes_advise_sbatch_dev(unsigned filters, const trc_planes_i
                                             uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
 {
     return advise_batch_dev(filters, items, strides, count, esize, chunk, filters_out, advice, d_work, work_bytes, stream);
+}
+// the filter per item against bases[i]: the slab walk above over trc_planes_hist_bbatch_dev's histograms, same workspace function
+extern "C" int trc_planes_advise_bbatch_dev(unsigned filters, const trc_planes_item *items, const void *const *bases, size_t count, unsigned esize,
+                                            uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
+{
+    return advise_batch_dev(filters, items, nullptr, count, esize, chunk, filters_out, advice, d_work, work_bytes, stream, true, bases);
 }

@@ -254,11 +254,11 @@ extern "C" int trc_decode_planes_batch_packed_dev(int codec, const void *d_cont,
 #define BCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fail(TRC_E_HIP, "%s -> %s", #x, hipGetErrorString(e_)); (void)hipStreamSynchronize(s); return 0; } } while (0)
 static inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-// Host items to c.d_in, item i at offset off[i] (multiples of 16, increasing).  A pageable hipMemcpyAsync per item costs the
+// Host items to d_dst (c.d_in, or c.d_base for the bases of a batch), item i at offset off[i] (multiples of 16, increasing).  A pageable hipMemcpyAsync per item costs the
 // runtime's staging and a round of its bookkeeping per call, whatever the item's size (profiles/planes/container_notes.md), so the
 // items are gathered into the context's page-locked staging slots at the same mutual offsets and a slot is sent when the next
 // item does not fit: one copy per slot's worth.  An item larger than a slot goes by a copy of its own.
-static int batch_items_up(HostCtx &c, hipStream_t s, const trc_planes_item *items, size_t count, const std::vector<size_t> &off)
+static int batch_items_up(HostCtx &c, hipStream_t s, uint8_t *d_dst, const trc_planes_item *items, size_t count, const std::vector<size_t> &off)
 {
     if (grow_pins(c, true)) return TRC_E_HIP;
     const size_t cap = c.cap_pin;
@@ -267,7 +267,7 @@ static int batch_items_up(HostCtx &c, hipStream_t s, const trc_planes_item *item
     size_t base = 0, fill = 0;                     // the slot holds device bytes [base, base + fill)
     auto flush = [&]() -> int {
         if (!fill) return TRC_OK;
-        HIPCHK(hipMemcpyAsync(c.d_in + base, c.pin_in[slot], fill, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_dst + base, c.pin_in[slot], fill, hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(c.ev_in[slot], s));
         used[slot] = true;
         slot = (slot + 1) % TRC_NSLOT;
@@ -279,7 +279,7 @@ static int batch_items_up(HostCtx &c, hipStream_t s, const trc_planes_item *item
         const size_t n = (size_t)items[i].n;
         if (n > cap) {
             if (flush()) return TRC_E_HIP;
-            HIPCHK(hipMemcpyAsync(c.d_in + off[i], items[i].d_ptr, n, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_dst + off[i], items[i].d_ptr, n, hipMemcpyHostToDevice, s));
             continue;
         }
         if (fill && off[i] + n - base > cap && flush()) return TRC_E_HIP;
@@ -291,7 +291,35 @@ static int batch_items_up(HostCtx &c, hipStream_t s, const trc_planes_item *item
     return flush();
 }
 
+// The bases of items [first_item, first_item + item_count) that want[i] asks for, to c.d_base (host bases) -> dev[i], NULL elsewhere.
+// items_on == TRC_ITEMS_DEV: the caller's pointers as they are.  The staging slots are the items': the stream is drained first.
+static int batch_bases_up(HostCtx &c, hipStream_t s, const trc_planes_item *items, const void *const *bases, const std::vector<bool> &want,
+                          size_t count, size_t first_item, size_t item_count, int items_on, std::vector<const void *> &dev)
+{
+    dev.assign(count, nullptr);
+    std::vector<trc_planes_item> up;
+    std::vector<size_t> off, idx;
+    size_t pos = 0;
+    for (size_t i = first_item; i < first_item + item_count; i++) {
+        if (!want[i]) continue;
+        if (items_on == TRC_ITEMS_DEV) { dev[i] = bases[i]; continue; }
+        up.push_back(trc_planes_item{ const_cast<void *>(bases[i]), items[i].n });
+        off.push_back(pos);
+        idx.push_back(i);
+        pos += up16((size_t)items[i].n);
+    }
+    if (up.empty()) return TRC_OK;
+    if (grow(&c.d_base, &c.cap_base, pos)) return TRC_E_HIP;
+    HIPCHK(hipStreamSynchronize(s));
+    if (batch_items_up(c, s, c.d_base, up.data(), up.size(), off)) return TRC_E_HIP;
+    for (size_t k = 0; k < idx.size(); k++) dev[idx[k]] = c.d_base + off[k];
+    return TRC_OK;
+}
+extern "C" size_t trc_planes_bbatch_bound(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum);      // trc_planes_bcontainer.inc
+
 // strides given: the TRCT container (trc_encode_splanes_batch_host); it refuses a batch that is a TRCB container's.
+// based: the TRCE container (trc_encode_bplanes_batch_host, trc_planes_bcontainer.inc), the bases lying where the items lie; it refuses an
+// all-NONE batch likewise, and with `choose` an item without a base is never given a filter and an all-NONE choice is a TRCB container.
 // choose: the batch advisor sets the filters (to filters_out as well, where given)
 static size_t batch_host_encode(const char *who, int codec, const trc_planes_item *items, BatchPred pred, bool choose, uint8_t *filters_out,
                                 size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap)
@@ -303,12 +331,19 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     chunk = batch_resolve_chunk(r, items, count, esize, chunk);
     trc_planes_batch_plan B;
     if (trc_planes_batch_plan_host(items, count, esize, chunk ? chunk : TRC_CHUNK_AUTO_MIN, &B, nullptr)) return 0;     // (chunk 0 here: a bad batch, and the plan says why)
-    if (trc_planes_batch_filters(who, pred.filters, count, nullptr)) return 0;
+    bool any = false;
+    if (trc_planes_batch_filters(who, pred.filters, count, &any)) return 0;
+    if (pred.based && !choose) {
+        if (!any) { fail(TRC_E_ARG, "%s: no item has a filter: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
+        for (size_t i = 0; i < count; i++)
+            if (pred.filters[i] != TRC_FILTER_NONE && (!pred.bases || !pred.bases[i])) { fail(TRC_E_ARG, "%s: item %zu: a filter against a base needs the base", who, i); return 0; }
+    }
     bool strided = false;
     if (trc_planes_batch_strides(who, pred.filters, pred.strides, count, &strided)) return 0;
     if (pred.strides && !strided) { fail(TRC_E_ARG, "%s: no item with a filter has a stride above 1: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
     if (!r.cdf && !r.ss) cdfnum = 0;
-    const size_t bound = pred.strides ? trc_planes_sbatch_bound(codec, items, count, esize, chunk, cdfnum) : trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
+    const size_t bound = pred.based ? trc_planes_bbatch_bound(codec, items, count, esize, chunk, cdfnum) :
+                         pred.strides ? trc_planes_sbatch_bound(codec, items, count, esize, chunk, cdfnum) : trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
     PlanesMap P;
     if (!bound || !planes_map(codec, (size_t)B.n_virtual, esize, chunk, P)) { fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk %u, cdfnum 0x%x)", who, chunk, cdfnum); return 0; }
     for (size_t i = 0; i < count; i++)
@@ -326,13 +361,21 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
         for (size_t i = 0; i < count; i++) { off[i] = pos; pos += up16((size_t)items[i].n); }
         if (grow(&c.d_in, &c.cap_in, pos)) return 0;
         for (size_t i = 0; i < count; i++) dev[i].d_ptr = c.d_in + off[i];
-        if (batch_items_up(c, s, items, count, off)) { (void)hipStreamSynchronize(s); return 0; }
+        if (batch_items_up(c, s, c.d_in, items, count, off)) { (void)hipStreamSynchronize(s); return 0; }
     }
+    std::vector<const void *> devb;
+    if (pred.based) {
+        std::vector<bool> want(count);
+        for (size_t i = 0; i < count; i++) want[i] = choose ? pred.bases && pred.bases[i] : pred.filters[i] != TRC_FILTER_NONE;
+        if (batch_bases_up(c, s, items, pred.bases, want, count, 0, count, items_on, devb)) { (void)hipStreamSynchronize(s); return 0; }
+        pred.bases = devb.data();
+    }
+    const size_t fp_table = pred.based ? trc_base_fingerprint_batch_table_bytes(count) : 0;
     const size_t work = esize * P.slice + batch_pred_table_bytes(pred, count, B.chunks);
     const size_t awork = choose ? TRC_PLANES_ADVISE_SLAB_BYTES + advise_table_bytes(dev.data(), count, esize, chunk) : 0;
     const size_t dirsz = up256(esize * 4 * P.nc + 256);
     if (grow(&c.d_cont, &c.cap_cont, dirsz + esize * P.buf) || grow(&c.d_work[0], &c.cap_work[0], work > awork ? work : awork) ||
-        grow(&c.d_work[1], &c.cap_work[1], bound)) { (void)hipStreamSynchronize(s); return 0; }
+        grow(&c.d_work[1], &c.cap_work[1], up256(bound) + fp_table)) { (void)hipStreamSynchronize(s); return 0; }
     uint32_t *d_clen = (uint32_t *)c.d_cont;
     uint8_t *d_payload = c.d_cont + dirsz;
     uint16_t *d_cdf = (uint16_t *)c.d_small;
@@ -342,12 +385,18 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     std::vector<uint8_t> chosen;
     if (choose) {
         chosen.resize(count);
-        if (trc_planes_advise_batch_dev(7, dev.data(), count, esize, chunk, chosen.data(), nullptr, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
+        if (pred.based ? trc_planes_advise_bbatch_dev(7, dev.data(), pred.bases, count, esize, chunk, chosen.data(), nullptr, c.d_work[0], c.cap_work[0], s)
+                       : trc_planes_advise_batch_dev(7, dev.data(), count, esize, chunk, chosen.data(), nullptr, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
         pred.filters = chosen.data();
+        any = false;
+        for (size_t i = 0; i < count; i++) any |= chosen[i] != TRC_FILTER_NONE;
+        if (pred.based && !any) pred = batch_pred_strides(chosen.data(), nullptr);      // no filter anywhere: the TRCB container
     }
-    if (encode_batch("encode_splanes_batch", codec, dev.data(), pred, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+    if (encode_batch(pred.based ? "encode_bplanes_batch" : "encode_splanes_batch", codec, dev.data(), pred, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                      d_clen, d_payload, d_total, c.d_work[0], c.cap_work[0], s) ||
-        (pred.strides ? trc_planes_sbatch_pack_dev(codec, dev.data(), pred.filters, pred.strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+        (pred.based ? trc_planes_bbatch_pack_dev(codec, dev.data(), pred.bases, pred.filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+                                                d_clen, d_payload, d_total, c.d_work[1], up256(bound), d_size, c.d_work[1] + up256(bound), fp_table, s) :
+         pred.strides ? trc_planes_sbatch_pack_dev(codec, dev.data(), pred.filters, pred.strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                                               d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s)
                  : trc_planes_batch_pack_dev(codec, dev.data(), pred.filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                                              d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s))) { (void)hipStreamSynchronize(s); return 0; }
@@ -373,9 +422,11 @@ extern "C" size_t trc_encode_aplanes_batch_host(int codec, const trc_planes_item
     return batch_host_encode("encode_aplanes_batch_host", codec, items, batch_pred_none(), true, filters_out, count, esize, chunk, cdfnum, items_on, out, outcap);
 }
 
-// both host decoders behind their checks: in = a checked TRCB container; pred = its filters, with the TRCT prefix's strides where it has one
-static size_t batch_host_decode(const char *who, const void *in, const BatchPred pred, const trc_planes_item *items, size_t count,
-                                size_t first_item, size_t item_count, int items_on)
+// the host decoders behind their checks: in = a checked TRCB container; pred = its filters, with the TRCT prefix's strides where it has one,
+// or -- based -- the caller's bases, lying where the items lie, and want_fp = the TRCE prefix's fingerprints: the requested items' bases
+// are fingerprinted and compared BEFORE anything is decoded (a batch range holds whole items, so each is seen whole)
+static size_t batch_host_decode(const char *who, const void *in, BatchPred pred, const trc_planes_item *items, size_t count,
+                                size_t first_item, size_t item_count, int items_on, const uint8_t *want_fp = nullptr)
 {
     const uint8_t *b = (const uint8_t *)in;
     trc_planes_batch_hdr h;
@@ -417,6 +468,31 @@ static size_t batch_host_decode(const char *who, const void *in, const BatchPred
     if (items_on == TRC_ITEMS_HOST) {
         if (grow(&c.d_in, &c.cap_in, bytes)) return 0;
         for (size_t i = 0; i < count; i++) dev[i].d_ptr = i >= first_item && i < first_item + item_count ? c.d_in + off[i - first_item] : nullptr;
+    }
+    std::vector<const void *> devb;
+    if (pred.based) {
+        std::vector<bool> want(count);
+        for (size_t i = 0; i < count; i++) want[i] = pred.filters[i] != TRC_FILTER_NONE;
+        for (size_t i = first_item; i < first_item + item_count; i++)
+            if (want[i] && (!pred.bases || !pred.bases[i])) { fail(TRC_E_ARG, "%s: item %zu: a filter against a base needs the base", who, i); return 0; }
+        if (batch_bases_up(c, s, items, pred.bases, want, count, first_item, item_count, items_on, devb)) { (void)hipStreamSynchronize(s); return 0; }
+        pred.bases = devb.data();
+        const size_t tb = trc_base_fingerprint_batch_table_bytes(item_count);
+        if (grow(&c.d_work[1], &c.cap_work[1], tb + 8 * item_count)) return 0;
+        uint64_t *d_fp = (uint64_t *)(c.d_work[1] + tb);
+        if (trc_base_fingerprint_batch_dev(items, pred.bases, pred.filters, count, first_item, item_count, d_fp, c.d_work[1], tb, s)) { (void)hipStreamSynchronize(s); return 0; }
+        std::vector<uint64_t> got(item_count);
+        BCHK(hipMemcpyAsync(got.data(), d_fp, 8 * item_count, hipMemcpyDeviceToHost, s));
+        BCHK(hipStreamSynchronize(s));
+        for (size_t j = 0; j < item_count; j++) {
+            uint64_t stored;
+            memcpy(&stored, want_fp + 8 * (first_item + j), 8);
+            if (got[j] != stored) {
+                fail(TRC_E_ARG, "%s: item %zu: base fingerprint 0x%016llx, the container was coded against 0x%016llx", who, first_item + j,
+                     (unsigned long long)got[j], (unsigned long long)stored);
+                return 0;
+            }
+        }
     }
     const size_t dirsz = up256(esize * 4 * cnt + 256);
     if (grow(&c.d_cont, &c.cap_cont, dirsz + esize * P.buf) || grow(&c.d_work[0], &c.cap_work[0], esize * P.slice + batch_pred_table_bytes(pred, item_count, cnt))) return 0;

@@ -287,6 +287,32 @@ def lib():
         l.trc_encode_splanes_batch_host.argtypes = [C.c_int, _it, _fl, _fl, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz]
         l.trc_decode_splanes_batch_host.restype = _sz
         l.trc_decode_splanes_batch_host.argtypes = [_vp, _sz, _it, _sz, _sz, _sz, C.c_int]
+        l.trc_base_fingerprint_batch_table_bytes.restype = _sz; l.trc_base_fingerprint_batch_table_bytes.argtypes = [_sz]
+        l.trc_base_fingerprint_batch_dev.restype = C.c_int
+        l.trc_base_fingerprint_batch_dev.argtypes = [_it, _bs, _fl, _sz, _sz, _sz, _vp, _vp, _sz, _vp]
+        l.trc_base_verify_batch_dev.restype = C.c_int
+        l.trc_base_verify_batch_dev.argtypes = [_vp, _it, _bs, _fl, _sz, _sz, _sz, _vp, _vp, _sz, _vp]
+        l.trc_planes_bbatch_bound.restype = _sz; l.trc_planes_bbatch_bound.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_planes_bbatch_check.restype = C.c_int; l.trc_planes_bbatch_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_bbatch_info.restype = C.c_int
+        l.trc_planes_bbatch_info.argtypes = [_vp, _sz, C.POINTER(PlanesBatchHdr), C.POINTER(C.c_uint64), _fl, C.POINTER(C.c_uint64), _sz]
+        l.trc_planes_bbatch_pack_dev.restype = C.c_int
+        l.trc_planes_bbatch_pack_dev.argtypes = [C.c_int, _it, _bs, _fl, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
+        l.trc_decode_bplanes_batch_packed_dev.restype = C.c_int
+        l.trc_decode_bplanes_batch_packed_dev.argtypes = [C.c_int, _vp, _sz, _it, _bs, _fl, _sz, _sz, _sz, C.c_uint, C.c_uint32, C.c_uint,
+                                                          C.POINTER(C.c_uint64), _vp, _sz, _vp]
+        l.trc_planes_hist_bbatch_dev.restype = C.c_int
+        l.trc_planes_hist_bbatch_dev.argtypes = [C.c_uint, _it, _bs] + l.trc_planes_hist_batch_dev.argtypes[2:]
+        l.trc_planes_advise_bbatch.restype = C.c_int
+        l.trc_planes_advise_bbatch.argtypes = [_vp, C.c_uint, C.c_uint, _it, _bs, _sz, _fl, _ad]
+        l.trc_planes_advise_bbatch_dev.restype = C.c_int
+        l.trc_planes_advise_bbatch_dev.argtypes = [C.c_uint, _it, _bs] + l.trc_planes_advise_batch_dev.argtypes[2:]
+        l.trc_encode_bplanes_batch_host.restype = _sz
+        l.trc_encode_bplanes_batch_host.argtypes = [C.c_int, _it, _bs, _fl, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz]
+        l.trc_encode_abplanes_batch_host.restype = _sz
+        l.trc_encode_abplanes_batch_host.argtypes = [C.c_int, _it, _bs, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz, _fl]
+        l.trc_decode_bplanes_batch_host.restype = _sz
+        l.trc_decode_bplanes_batch_host.argtypes = [_vp, _sz, _it, _bs, _sz, _sz, _sz, C.c_int]
         l.trc_planes_batch_auto_chunk.restype = C.c_uint32; l.trc_planes_batch_auto_chunk.argtypes = [C.c_int, _it, _sz, C.c_uint]
         l.trc_planes_batch_bound.restype = _sz; l.trc_planes_batch_bound.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint]
         l.trc_planes_batch_layout_host.restype = C.c_int
@@ -851,6 +877,79 @@ class PlanesBatchCoder:
         return int(tot.sum()) + self.esize * (4 * self.nch + (2 * (self.cdfnum + 1) if self.codec in STATIC else 0))
 
 
+class BasePlanesBatchCoder(PlanesBatchCoder):
+    """PlanesBatchCoder for a batch against bases (required: one tensor or None per item) with the TRCE container, which names every
+    base by its fingerprint: pack() -> the container, decode_packed(..., bases=None) decodes from it against the coder's bases or the
+    ones given (the output tensors themselves: in place), verify(d_cont, bases=None) -> the lowest item index whose base does not
+    have the container's fingerprint, or -1.  filters="auto": encode() first asks the advisor against the bases
+    (planes_advise_batch_dev(bases=...), which waits for the stream; an item without a base is never given a filter) and leaves
+    self.filters / self.advice as the parent does.  Where no filter is chosen anywhere the batch is a TRCB container: pack() raises
+    as the library does.  No strides."""
+
+    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None, bases=None):
+        if bases is None:
+            raise ValueError("BasePlanesBatchCoder codes against bases: one tensor or None per item")
+        auto = isinstance(filters, str) and filters == "auto"
+        super().__init__(codec, tensors, chunk, cdfnum=cdfnum, prm=prm, guard=guard, esize=esize, filters=None if auto else filters, bases=bases)
+        self.auto_bases = auto                                 # (self.auto stays False: the parent's advisor knows no bases)
+        self.table_bytes = lib().trc_base_fingerprint_batch_table_bytes(self.count)
+        self.table = self._buf(self.table_bytes)
+
+    def encode(self, flags=0):
+        if self.auto_bases:                                    # the advisor against the bases on what the tensors hold now
+            chosen, self.advice = planes_advise_batch_dev(self.items, self.esize, self.chunk, 7, self.count, self.dev, bases=self._bases)
+            self.filters = planes_filters(chosen, self.count)
+        super().encode(flags)
+
+    def pack(self, guard=0):
+        """enqueue trc_planes_bbatch_pack_dev on what encode() left, then synchronise to read the size -> (the TRCE container: a uint8
+        device tensor trimmed to its size; the size).  guard, self.packed and self.pack_guard as in the parent"""
+        st = self.codec in STATIC
+        bound = lib().trc_planes_bbatch_bound(self.codec, self.items, self.count, self.esize, self.chunk, self.cdfnum)
+        if bound == 0:
+            raise TrcError("bad (codec, tensors, chunk, cdfnum)")
+        buf = self.torch.full((bound + guard,), 0xA5 if guard else 0, dtype=self.torch.uint8, device=self.dev)
+        d_size = self.torch.zeros(1, dtype=self.torch.int64, device=self.dev)
+        _chk(lib().trc_planes_bbatch_pack_dev(self.codec, self.items, self.bases, self.filters, self.count, self.esize, self.chunk,
+                                              self.cdf.data_ptr() if st else None, self.cdfnum, self.status.data_ptr() if st else None,
+                                              self.clen.data_ptr(), self.payload.data_ptr(), self.total.data_ptr(), buf.data_ptr(), bound,
+                                              d_size.data_ptr(), self.table.data_ptr(), self.table_bytes, self._stream()))
+        size = int(d_size.item())
+        self.packed, self.pack_guard = buf, buf[size:]
+        return buf[:size], size
+
+    def decode_packed(self, d_cont, total, first_item=0, item_count=None, out=None, cont_bytes=None, work_bytes=None, bases=None):
+        """the inverse of pack(): trc_decode_bplanes_batch_packed_dev from the TRCE container d_cont (`total` as parse_planes_bbatch
+        gives it) into out[i] (default: the encoded tensors) against `bases` (default: the coder's); it does not verify them"""
+        item_count = self.count - first_item if item_count is None else item_count
+        items = self.items if out is None else self._items(list(out))
+        need = lib().trc_planes_bbatch_range_work_bytes(self.codec, items, self.count, self.esize, self.chunk, first_item, item_count)
+        if need > self.range_work_bytes:
+            self.range_work, self.range_work_bytes = self._buf(need), need
+        if self.range_work is None:
+            self.range_work = self._buf(0)
+        tot = (C.c_uint64 * 8)(*[int(x) for x in total])
+        _chk(lib().trc_decode_bplanes_batch_packed_dev(self.codec, d_cont.data_ptr(), d_cont.numel() if cont_bytes is None else cont_bytes, items,
+                                                       *self._family(bases)[1], self.count, first_item, item_count, self.esize, self.chunk, self.cdfnum, tot,
+                                                       self.range_work.data_ptr(), need if work_bytes is None else work_bytes, self._stream()))
+
+    def verify(self, d_cont, bases=None, first_item=0, item_count=None):
+        """trc_base_verify_batch_dev, then synchronise -> the lowest index in [first_item, first_item + item_count) whose base (the
+        coder's, or the one given) does not have the fingerprint the container holds, or -1"""
+        item_count = self.count - first_item if item_count is None else item_count
+        d_bad = self.torch.full((1,), -2, dtype=self.torch.int64, device=self.dev)
+        _chk(lib().trc_base_verify_batch_dev(d_cont.data_ptr(), self.items, *self._family(bases)[1], self.count, first_item, item_count,
+                                             d_bad.data_ptr(), self.table.data_ptr(), self.table_bytes, self._stream()))
+        return int(d_bad.item())
+
+
+def base_fingerprint_batch(items, bases, filters, count, first_item, item_count, d_fp, d_table, table_bytes):
+    """enqueue trc_base_fingerprint_batch_dev: the fingerprints of the bases of items [first_item, first_item + item_count) with a
+    filter into d_fp (8 bytes per item of the range, 0 where the filter is NONE); does not wait"""
+    _chk(lib().trc_base_fingerprint_batch_dev(items, planes_bases(bases, count), planes_filters(filters, count), count, first_item, item_count,
+                                              d_fp.data_ptr(), d_table.data_ptr(), table_bytes, _cur_stream(d_fp)))
+
+
 # ------------------------------------------------------ reference-signature layer (host pointers) ---
 _HOST_ENC = {ANS4S: "anscdf4senc", RCS1: "rccdfsenc", RCS2: "rccdfs2enc", RCA: "rccdfenc", ANSA: "anscdfenc", RCB: "rcsenc", RCAI: "rccdfienc",
              RCA4: "rccdf4enc", RCAI4: "rccdf4ienc", ANSA4: "anscdf4enc", RCSM: "rccdfsmenc", ANSO1: "anscdf1enc", ANSB: "ansbc",
@@ -1143,23 +1242,34 @@ def planes_hist_sbatch(filters, items, strides, count, first_item, item_count, e
                                           d_hist.data_ptr(), d_table.data_ptr(), table_bytes, _cur_stream(d_hist)))
 
 
-def planes_advise_batch(hist, filters, esize, items, count, advice=True):
+def planes_hist_bbatch(filters, items, bases, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes):
+    """enqueue trc_planes_hist_bbatch_dev: planes_hist_batch with item i's predicted rows counted against bases[i] (see planes_bases; an
+    item without a base gets the unfiltered row alone) -- slice j is what planes_hist_base leaves for item first_item + j alone"""
+    _chk(lib().trc_planes_hist_bbatch_dev(filters, items, planes_bases(bases, count), count, first_item, item_count, esize, chunk,
+                                          d_hist.data_ptr(), d_table.data_ptr(), table_bytes, _cur_stream(d_hist)))
+
+
+def planes_advise_batch(hist, filters, esize, items, count, advice=True, bases=False):
     """trc_planes_advise_batch on histograms in host memory (uint64, 3 * esize * 256 per item; needs no device)
-    -> (the filter per item: list of ints, the advice per item: list of dicts, or None where advice is False)"""
+    -> (the filter per item: list of ints, the advice per item: list of dicts, or None where advice is False).  bases (None, or a
+    list of addresses / tensors / None per item): trc_planes_advise_bbatch, an item without a base under the unfiltered row alone"""
     hist = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
     if esize in (2, 4, 8) and hist.size < count * 3 * esize * 256:
         raise TrcError("planes_advise_batch: %d histogram words for %d items" % (hist.size, count))
     out = (C.c_uint8 * max(count, 1))()
     adv = (PlanesAdvice * max(count, 1))() if advice else None
-    _chk(lib().trc_planes_advise_batch(hist.ctypes.data, filters, esize, items, count, out, adv))
+    if bases is False:
+        _chk(lib().trc_planes_advise_batch(hist.ctypes.data, filters, esize, items, count, out, adv))
+    else:
+        _chk(lib().trc_planes_advise_bbatch(hist.ctypes.data, filters, esize, items, planes_bases(bases, count), count, out, adv))
     return [int(x) for x in out[:count]], [_advice_dict(a) for a in adv[:count]] if advice else None
 
 
-def planes_advise_batch_dev(batch, esize=None, chunk=4096, filters=7, count=None, device="cuda", advice=True, strides=None):
+def planes_advise_batch_dev(batch, esize=None, chunk=4096, filters=7, count=None, device="cuda", advice=True, strides=None, bases=False):
     """trc_planes_advise_batch_dev on a list of device tensors of one element size, or on a trc_planes_item array (planes_items;
     esize is then required, count defaults to the array's length, the workspace lies on `device`), in a workspace of its own.
     Waits for the current stream.  strides (see planes_strides) given: trc_planes_advise_sbatch_dev, the choice under those strides.
-    -> as planes_advise_batch"""
+    bases (None or see planes_bases) given: trc_planes_advise_bbatch_dev, the choice against those bases.  -> as planes_advise_batch"""
     import torch
     if isinstance(batch, C.Array):
         items, count = batch, len(batch) if count is None else count
@@ -1174,7 +1284,10 @@ def planes_advise_batch_dev(batch, esize=None, chunk=4096, filters=7, count=None
     work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
     out = (C.c_uint8 * max(count, 1))()
     adv = (PlanesAdvice * max(count, 1))() if advice else None
-    if strides is None:
+    if bases is not False:
+        _chk(lib().trc_planes_advise_bbatch_dev(filters, items, planes_bases(bases, count), count, esize, chunk, out, adv, work.data_ptr(), need,
+                                                torch.cuda.current_stream(dev).cuda_stream))
+    elif strides is None:
         _chk(lib().trc_planes_advise_batch_dev(filters, items, count, esize, chunk, out, adv, work.data_ptr(), need,
                                                torch.cuda.current_stream(dev).cuda_stream))
     else:
@@ -1484,6 +1597,46 @@ def planes_sbatch_info(buf, cap=None):
             [int(x) for x in st[:got]])
 
 
+BBATCH_MAGIC = 0x45435254                                       # "TRCE"
+
+
+def planes_bbatch_prefix(count):
+    """bytes of a TRCE container in front of its TRCB container"""
+    return 16 + ((8 * count + 15) & ~15)
+
+
+def planes_bbatch_bound(codec, sizes, esize, chunk=0, cdfnum=0):
+    return lib().trc_planes_bbatch_bound(codec, planes_items([(None, n) for n in sizes]), len(sizes), esize, chunk, cdfnum)
+
+
+def planes_bbatch_check(buf, count=None):
+    """trc_planes_bbatch_check (needs no device); raises TrcError with the reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_planes_bbatch_check(buf.ctypes.data, buf.size, _sz(-1).value if count is None else count))
+
+
+def planes_bbatch_info(buf, cap=None):
+    """trc_planes_bbatch_info -> (dict of the TRCB header's fields, n: list, filters: list, base_fp: list) of the first min(cap, count) items"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    h = PlanesBatchHdr()
+    if cap is None:
+        _chk(lib().trc_planes_bbatch_info(buf.ctypes.data, buf.size, C.byref(h), None, None, None, 0))
+        cap = int(h.count)
+    n, f, fp = (C.c_uint64 * max(cap, 1))(), (C.c_uint8 * max(cap, 1))(), (C.c_uint64 * max(cap, 1))()
+    _chk(lib().trc_planes_bbatch_info(buf.ctypes.data, buf.size, C.byref(h), n, f, fp, cap))
+    got = min(cap, int(h.count))
+    return ({k: int(getattr(h, k)) for k, _ in PlanesBatchHdr._fields_}, [int(x) for x in n[:got]], [int(x) for x in f[:got]],
+            [int(x) for x in fp[:got]])
+
+
+def parse_planes_bbatch(buf):
+    """a checked TRCE container -> parse_planes_batch of its TRCB part (offsets from the TRCB start) with prefix and base_fp: list"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    h, _, _, fp = planes_bbatch_info(buf)
+    prefix = planes_bbatch_prefix(h["count"])
+    return dict(parse_planes_batch(buf[prefix:]), prefix=prefix, base_fp=fp)
+
+
 def parse_planes_batch(buf):
     """a checked TRCB container -> dict(the header's fields, n: list, filters: list, codec, cdfnum, total: the planes' payload sizes,
     off: the sections' offsets from the TRCB start); the inner TRCP container is buf[inner:size]"""
@@ -1534,6 +1687,62 @@ def host_encode_planes_batch(codec, arrays, esize, chunk=0, filters=None, cdfnum
     if l == 0:
         raise TrcError(lib().trc_last_error().decode())
     return out[:l].copy() if chosen is None else (out[:l].copy(), [int(x) for x in chosen[:count]])
+
+
+def _host_bases(bases, on, count):
+    """-> (the host array of base addresses the host calls take, what keeps the memory alive): numpy arrays where the items are
+    host arrays, device tensors where they are tensors, None for no base"""
+    if bases is None:
+        return None, []
+    keep = [None if b is None else (np.ascontiguousarray(b).reshape(-1).view(np.uint8) if on == ITEMS_HOST else b.contiguous()) for b in bases]
+    return planes_bases([None if b is None else (b.ctypes.data if on == ITEMS_HOST else b.data_ptr()) for b in keep], count), keep
+
+
+def host_encode_bplanes_batch(codec, arrays, bases, esize, chunk=0, filters=None, cdfnum=256, prm=(5, 6)):
+    """trc_encode_bplanes_batch_host on numpy arrays (host items and bases) or device tensors: filters one id for all, a list, or "auto"
+    (trc_encode_abplanes_batch_host) -> the TRCE container (np.uint8); with "auto": (the TRCE or TRCB container, the filters chosen)"""
+    items, on, keep = _batch_host_items(arrays)
+    count = len(keep)
+    b, keep_b = _host_bases(bases, on, count)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(lib().trc_planes_bbatch_bound(codec, items, count, esize, chunk, cn), 64), dtype=np.uint8)
+    if isinstance(filters, str) and filters == "auto":
+        chosen = (C.c_uint8 * max(count, 1))()
+        l = lib().trc_encode_abplanes_batch_host(codec, items, b, count, esize, chunk, cn, on, out.ctypes.data, out.size, chosen)
+    else:
+        chosen = None
+        l = lib().trc_encode_bplanes_batch_host(codec, items, b, planes_filters(filters, count), count, esize, chunk, cn, on, out.ctypes.data, out.size)
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy() if chosen is None else (out[:l].copy(), [int(x) for x in chosen[:count]])
+
+
+def host_decode_bplanes_batch(comp, bases, first_item=0, item_count=None, out=None):
+    """trc_decode_bplanes_batch_host: items [first_item, first_item + item_count) of a TRCE (or TRCB) container against `bases` (numpy
+    arrays, or device tensors with `out`; None where an item has none or outside the range) -> a list of np.uint8 arrays, or, out given
+    (a list of count device tensors, None outside the range), into those -> the bytes delivered.  The bases are verified first"""
+    comp = np.ascontiguousarray(comp, dtype=np.uint8)
+    based = comp.size >= 4 and int(comp[:4].view("<u4")[0]) == BBATCH_MAGIC
+    h, n = planes_bbatch_info(comp)[:2] if based else planes_batch_info(comp)[:2]
+    count = h["count"]
+    item_count = count - first_item if item_count is None else item_count
+    wanted = range(first_item, first_item + item_count)
+    if out is None:
+        res = [np.full(n[i] + 64, 0xA5, dtype=np.uint8) if i in wanted else None for i in range(count)]
+        items = planes_items([(res[i].ctypes.data if i in wanted else None, n[i]) for i in range(count)])
+        on = ITEMS_HOST
+    else:
+        items = planes_items([(out[i].data_ptr() if out[i] is not None else None, n[i]) for i in range(count)])
+        on = ITEMS_DEV
+    b, keep_b = _host_bases(bases, on, count)
+    l = lib().trc_decode_bplanes_batch_host(comp.ctypes.data, comp.size, items, b, count, first_item, item_count, on)
+    if l != sum(n[i] for i in wanted):
+        raise TrcError(lib().trc_last_error().decode())
+    if out is not None:
+        return l
+    if any((res[i][n[i]:] != 0xA5).any() for i in wanted):
+        raise TrcError("trc_decode_bplanes_batch_host wrote past an item")
+    return [res[i][:n[i]].copy() for i in wanted]
 
 
 def host_decode_planes_batch(comp, first_item=0, item_count=None, out=None, sizes=None):
