@@ -17,6 +17,13 @@
  *                                 pairs): the filter predicts from the element <stride> back, 2 .. 8.  The file is the library's
  *                                 strided planes container: 16 bytes "TRCS" | u8 filter | u8 1 | u16 stride | u64 size, then the TRCP
  *                                 container of the filtered data
+ *   trcfile o <id> <esize> <order> <stride> <in> <out>   as s for SMOOTH series (sampled signals, PCM, sensor readings): the zigzag delta
+ *                                 taken <order> times, 2 or 3 (the fixed polynomial predictors of the lossless audio coders), against
+ *                                 the element <stride> back, 1 .. 8.  The file is the library's order planes container: 16 bytes "TRCO"
+ *                                 | u8 order | u8 1 | u16 stride | u64 size, then the TRCP container of the filtered data
+ *   trcfile O <id> <esize> <stride> <in> <out>   as p, f, s or o, whichever the library's order advisor chooses from the order-0
+ *                                 histograms of the planes under orders 0 .. 3 at <stride> (trc_encode_aoplanes_host): the file is
+ *                                 what that command would have written; prints the four estimates and the chosen order
  *   trcfile r <id> <esize> <z|x> <base> <in> <out>   as f, with the filter RELATIVE TO A BASE FILE: z = zigzag delta, x = xor of every
  *                                 element against the element at the same place in <base> (the previous checkpoint, the base model of
  *                                 a fine-tune, a page before its update), which holds at least the whole elements of <in>.  The file
@@ -46,8 +53,8 @@
  *   trcfile E <in> <item> <base|-> <out>   item <item> of a file of e against its base file (- where it has no filter): only the chunks
  *                                 that cover it are sent to the GPU; a base with another fingerprint is refused.  l lists such a file
  *                                 with every item's base fingerprint (needs no GPU); B does not read it: it has no bases to give
- *   trcfile d <in> <out>          decompress (files of c, p, f, s and a)
- *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p, f or s: only the
+ *   trcfile d <in> <out>          decompress (files of c, p, f, s, o, a and O)
+ *   trcfile x <in> <offset> <len> <out>   extract bytes [offset, offset + len) of a file written by `trcfile c`, p, f, s or o: only the
  *                                 chunks that cover them are sent to the GPU and decoded (trc_decode_range_host)
  *
  * File = "TRCF" | u8 id | u8 cdfnum-1 | u16 0 | u64 raw length | u64 stored length | [cdf: (cdfnum+1) x u16, static coders]
@@ -138,6 +145,8 @@ static int is_planes(const unsigned char *fb, size_t fl) { return fl >= 4 && !me
 static int is_fplanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCF", 4) && fb[5] == 1 && !memcmp(fb + 16, "TRCP", 4); }
 /* a file of `trcfile s` */
 static int is_splanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCS", 4) && !memcmp(fb + 16, "TRCP", 4); }
+/* a file of `trcfile o` */
+static int is_oplanes(const unsigned char *fb, size_t fl) { return fl >= 20 && !memcmp(fb, "TRCO", 4) && !memcmp(fb + 16, "TRCP", 4); }
 /* a file of `trcfile r` */
 static int is_bplanes(const unsigned char *fb, size_t fl) { return fl >= 36 && !memcmp(fb, "TRCD", 4) && !memcmp(fb + 32, "TRCP", 4); }
 static int write_file(const char *path, const unsigned char *p, size_t n)
@@ -278,6 +287,47 @@ int main(int argc, char **argv)
         if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
         if (write_file(argv[7], out, l)) return 2;
         printf("%zu -> %zu bytes (%.2f%%)  %u planes, filter %s, stride %d\n", n, l, 100.0 * l / n, esize, argv[4], stride);
+        return 0;
+    }
+    if (argc == 8 && !strcmp(argv[1], "o")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id), order = atoi(argv[4]), stride = atoi(argv[5]);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        size_t n;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (order < 2 || order > TRC_ORDER_MAX) { fprintf(stderr, "order %s: 2 .. %d (order 1 is trcfile f or s, order 0 trcfile p)\n", argv[4], TRC_ORDER_MAX); return 2; }
+        if (stride < 1 || stride > TRC_STRIDE_MAX) { fprintf(stderr, "stride %s: 1 .. %d\n", argv[5], TRC_STRIDE_MAX); return 2; }
+        unsigned char *in = slurp(argv[6], &n);
+        if (!in) return 2;
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_oplanes_bound(n, esize, 0, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u with %zu bytes: esize is 2, 4 or 8 and the file holds at least one element\n", esize, n); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        const size_t l = trc_encode_oplanes_host(codec, order, stride, in, n, esize, 0, out, cap, cdfnum);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[7], out, l)) return 2;
+        printf("%zu -> %zu bytes (%.2f%%)  %u planes, order %d, stride %d\n", n, l, 100.0 * l / n, esize, order, stride);
+        return 0;
+    }
+    if (argc == 7 && !strcmp(argv[1], "O")) {
+        const int id = atoi(argv[2]), codec = lib_codec(id), stride = atoi(argv[4]);
+        const unsigned esize = (unsigned)atoi(argv[3]);
+        size_t n;
+        if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
+        if (stride < 1 || stride > TRC_STRIDE_MAX) { fprintf(stderr, "stride %s: 1 .. %d\n", argv[4], TRC_STRIDE_MAX); return 2; }
+        unsigned char *in = slurp(argv[5], &n);
+        if (!in) return 2;
+        const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
+        const size_t cap = trc_oplanes_bound(n, esize, 0, cdfnum);
+        if (!cap) { fprintf(stderr, "esize %u with %zu bytes: esize is 2, 4 or 8 and the file holds at least one element\n", esize, n); return 2; }
+        unsigned char *out = malloc(cap);
+        if (!out) { perror("malloc"); return 2; }
+        trc_planes_order_advice adv;
+        const size_t l = trc_encode_aoplanes_host(codec, stride, in, n, esize, 0, out, cap, cdfnum, &adv);
+        if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
+        if (write_file(argv[6], out, l)) return 2;
+        printf("%zu -> %zu bytes (%.2f%%)  %u planes, stride %d, order-0 estimate of orders 0 .. 3: %.0f %.0f %.0f %.0f bytes, choice order %d\n", n, l, 100.0 * l / n, esize,
+               stride, adv.total_bits[0] / 8, adv.total_bits[1] / 8, adv.total_bits[2] / 8, adv.total_bits[3] / 8, adv.order);
         return 0;
     }
     if (argc == 8 && !strcmp(argv[1], "r")) {
@@ -498,10 +548,10 @@ int main(int argc, char **argv)
         if (is_bplanes(fb, fl)) { fprintf(stderr, "a file of trcfile r, coded against a base: trcfile R <in> <base> <out> decodes it\n"); return 2; }
         /* a file of `trcfile p`, f, s or a: untrusted, so checked against what was read; the library looks at the magic itself
          * (trc_decode_xplanes_host = trc_decode_planes_host, trc_decode_fplanes_host or trc_decode_splanes_host) */
-        if (is_fplanes(fb, fl) || is_splanes(fb, fl) || is_planes(fb, fl)) {
-            const size_t lead = is_planes(fb, fl) ? 0 : sizeof(trc_fplanes_hdr);     /* (the TRCS prefix has the TRCF prefix's size) */
+        if (is_fplanes(fb, fl) || is_splanes(fb, fl) || is_oplanes(fb, fl) || is_planes(fb, fl)) {
+            const size_t lead = is_planes(fb, fl) ? 0 : sizeof(trc_fplanes_hdr);     /* (the TRCS and TRCO prefixes have the TRCF prefix's size) */
             trc_planes_hdr ph;
-            if (is_splanes(fb, fl) ? trc_splanes_check(fb, fl, (size_t)-1) : lead ? trc_fplanes_check(fb, fl, (size_t)-1) : trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            if (is_oplanes(fb, fl) ? trc_oplanes_check(fb, fl, (size_t)-1) : is_splanes(fb, fl) ? trc_splanes_check(fb, fl, (size_t)-1) : lead ? trc_fplanes_check(fb, fl, (size_t)-1) : trc_planes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
             memcpy(&ph, fb + lead, sizeof ph);
             unsigned char *out = malloc((size_t)ph.n + 1024);
             if (!out) { perror("malloc"); return 2; }
@@ -549,6 +599,17 @@ int main(int argc, char **argv)
             unsigned char *out = malloc((size_t)len + 1024);
             if (!out) { perror("malloc"); return 2; }
             if (trc_decode_splanes_range_host(fb, fl, (size_t)off, (size_t)len, out) != len) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
+            return write_file(argv[5], out, (size_t)len);
+        }
+        if (is_oplanes(fb, fl)) {
+            const uint64_t off = strtoull(argv[3], 0, 10), len = strtoull(argv[4], 0, 10);
+            trc_planes_hdr ph;
+            if (trc_oplanes_check(fb, fl, (size_t)-1)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+            memcpy(&ph, fb + sizeof(trc_oplanes_hdr), sizeof ph);
+            if (!len || off > ph.n || len > ph.n - off) { fprintf(stderr, "range outside the file's %llu bytes\n", (unsigned long long)ph.n); return 2; }
+            unsigned char *out = malloc((size_t)len + 1024);
+            if (!out) { perror("malloc"); return 2; }
+            if (trc_decode_oplanes_range_host(fb, fl, (size_t)off, (size_t)len, out) != len) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
             return write_file(argv[5], out, (size_t)len);
         }
         if (is_fplanes(fb, fl)) {
@@ -710,6 +771,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in> | trcfile r <id> <esize> <z|x> <base> <in> <out> | trcfile R <in> <base> <out> | trcfile e <id> <esize> <chunk|0> <z|x|a> <out> <in> <base|-> ... | trcfile E <in> <item> <base|-> <out>\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile o <id> <esize> <order> <stride> <in> <out> | trcfile O <id> <esize> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in> | trcfile r <id> <esize> <z|x> <base> <in> <out> | trcfile R <in> <base> <out> | trcfile e <id> <esize> <chunk|0> <z|x|a> <out> <in> <base|-> ... | trcfile E <in> <item> <base|-> <out>\n");
     return 2;
 }

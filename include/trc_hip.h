@@ -582,6 +582,88 @@ size_t trc_decode_splanes_host(const void *in, size_t inlen, void *out, size_t o
 size_t trc_decode_splanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
 int    trc_splanes_check(const void *buf, size_t buflen, size_t outlen);
 
+/* ---- byte planes behind a predictor of ORDER 2 or 3: smooth series ---------------------------------------------------
+ * Sampled signals, PCM and sensor series are smooth, and the first difference of a smooth series is smooth again: the filters
+ * above leave most of its structure in place.  The fixed polynomial predictors of the lossless audio coders take the difference
+ * K times.  With the names above, S the stride in 1 .. TRC_STRIDE_MAX and K the order in 0 .. TRC_ORDER_MAX:
+ *        D_S(a)[i] = a[i] where i % seg < S,  a[i] - a[i - S] mod 2^w elsewhere
+ *        y[i]      = zigzag(D_S applied K times to x, at i)                               (zigzag once, at the end)
+ *        O(K, S, seg, esize, in) = the y's followed by the t untouched tail bytes
+ * or, with x taken as zero in front of its segment, D^K[i] = sum_j (-1)^j C(K, j) x[i - j S]:  x[i] - 2 x[i - S] + x[i - 2S]  for
+ * K = 2,  x[i] - 3 x[i - S] + 3 x[i - 2S] - x[i - 3S]  for K = 3.  The inverse undoes the zigzag and runs K class-wise segmented
+ * prefix sums mod 2^w from a zero state (a class = the place in the segment mod S).  K = 1 is F_S(TRC_FILTER_ZDELTA, ...), K = 0 is
+ * no filter; there is no xor form.  The filter enum is untouched: the order is an argument of calls of its own, as the stride is.
+ * An order is an option, never a default: on integer columns that the first difference already flattens, order 2 stores MORE.
+ *
+ * The whole contract:  oplanes(K, S, ..., in)  ==  planes(..., O(K, S, chunk, esize, in))  byte for byte -- directory, payload,
+ * tail, totals, statuses and per-plane CDFs; a chunk range decodes from its own bytes alone.  Arguments, alignment, flags and
+ * workspace are those of the planes calls (the filter needs no workspace), with `int order, int stride` where the splanes calls
+ * have `int filter, int stride`.  An order outside 0 .. TRC_ORDER_MAX is TRC_E_ARG ahead of everything else, pointers included, so
+ * without a device; the stride is looked at next; everything else as in the planes calls.  With order 0 a device call IS the
+ * unfiltered call, with order 1 it IS the splanes call with TRC_FILTER_ZDELTA, and launches those kernels.
+ *
+ * trc_planes_hist_order_dev counts the planes under orders 0 .. 3 at one stride in one read of the input: orders is a bit set, bit
+ * k = order k (1 .. 15, anything else is TRC_E_ARG, then the stride), d_hist[(k * esize + p) * 256 + b] as trc_planes_hist_dev has
+ * it; the call zeroes all trc_planes_hist_order_bytes(esize) = 4 * esize * 256 * 8 bytes first, rows not requested stay zero,
+ * nothing behind them is written.  Rows 0 and 1 are rows 0 and 1 of trc_planes_hist_stride_dev(3, stride, ...).
+ * trc_planes_advise_order (host only) gives the estimates of trc_planes_advise and the requested order with the smallest total,
+ * ties to the lower order -- but order 0 where it was requested and the winner saves less than 1/64 of its total (the same
+ * policy).  Every requested row must sum to m; that, orders outside 1 .. 15, a bad esize, m == 0 or a NULL pointer is TRC_E_ARG.
+ *
+ * Host pointers: the TRCO container = trc_oplanes_hdr (16 bytes) in front of the TRCP container of O(K, S, chunk, esize, in);
+ * bytes [16, size) are byte-identical to trc_encode_planes_host(codec, O(in), ...) at the same resolved chunk.
+ * trc_encode_oplanes_host takes order 2 or 3: order 0 returns 0 and names trc_encode_planes_host, order 1 names
+ * trc_encode_fplanes_host / trc_encode_splanes_host (one layout per content); out must hold trc_oplanes_bound = trc_planes_bound
+ * + 16 bytes.  trc_oplanes_check (host only) validates magic, version 1, order 2 .. 3, stride 1 .. TRC_STRIDE_MAX, 16 < size <=
+ * buflen, then trc_planes_check(buf + 16, size - 16, outlen); the decoders call it first.  trc_decode_xplanes_host reads a TRCO
+ * container too.  trc_encode_aoplanes_host: upload once, trc_planes_hist_order_dev(15, stride, ..., seg = the resolved chunk),
+ * trc_planes_advise_order, then the coded call on the bytes already on the device; the output is byte for byte what the explicit
+ * call writes for that choice -- TRCP for order 0, TRCF for order 1 at stride 1, TRCS for order 1 at a stride above 1, TRCO for
+ * order 2 or 3; out must hold trc_oplanes_bound bytes; *advice (may be NULL) receives what decided. */
+#define TRC_ORDER_MAX 3
+int trc_planes_split_ofilter_dev(int order, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg,
+                                 void *d_planes, size_t pitch, void *d_tail, void *stream);
+int trc_planes_join_ofilter_dev(int order, int stride, const void *d_planes, size_t pitch, const void *d_tail,
+                                size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream);
+int trc_encode_oplanes_dev(int codec, int order, int stride, const void *d_in, size_t n, unsigned esize, uint32_t chunk,
+                           uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                           uint32_t *d_clen, void *d_payload, uint64_t *d_total, void *d_tail,
+                           void *d_work, size_t work_bytes, void *stream);
+int trc_decode_oplanes_dev(int codec, int order, int stride, const uint32_t *d_clen, const void *d_payload, const void *d_tail,
+                           size_t n, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                           void *d_out, void *d_work, size_t work_bytes, void *stream);
+int trc_decode_oplanes_range_dev(int codec, int order, int stride, const uint32_t *d_clen, const void *d_payload,
+                                 size_t n, unsigned esize, uint32_t chunk, size_t first_chunk, size_t count,
+                                 const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_out, void *d_work, size_t work_bytes, void *stream);
+typedef struct trc_planes_order_advice {
+    int      order;              /* the choice: 0 .. TRC_ORDER_MAX */
+    unsigned esize, orders;      /* as given */
+    uint64_t m;
+    double   bits[4][8];         /* order-0 model estimate of plane p under predictor order k, in bits */
+    double   total_bits[4];      /* sum over the planes */
+} trc_planes_order_advice;
+size_t trc_planes_hist_order_bytes(unsigned esize);
+int    trc_planes_hist_order_dev(unsigned orders, int stride, const void *d_in, size_t n, unsigned esize, uint32_t seg,
+                                 uint64_t *d_hist, void *stream);
+int    trc_planes_advise_order(const uint64_t *hist, unsigned orders, unsigned esize, size_t m, trc_planes_order_advice *a);
+#define TRC_OPLANES_MAGIC 0x4f435254u   /* "TRCO" */
+typedef struct trc_oplanes_hdr {
+    uint32_t magic;      /* TRC_OPLANES_MAGIC */
+    uint8_t  order;      /* 2 .. TRC_ORDER_MAX */
+    uint8_t  version;    /* 1 */
+    uint16_t stride;     /* 1 .. TRC_STRIDE_MAX */
+    uint64_t size;       /* 16 + the inner TRCP container's size */
+} trc_oplanes_hdr;       /* 16 bytes, little endian */
+size_t trc_oplanes_bound(size_t n, unsigned esize, uint32_t chunk, unsigned cdfnum);
+size_t trc_encode_oplanes_host(int codec, int order, int stride, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                               void *out, size_t outcap, unsigned cdfnum);
+size_t trc_decode_oplanes_host(const void *in, size_t inlen, void *out, size_t outlen);
+size_t trc_decode_oplanes_range_host(const void *in, size_t inlen, size_t offset, size_t len, void *out);
+int    trc_oplanes_check(const void *buf, size_t buflen, size_t outlen);
+size_t trc_encode_aoplanes_host(int codec, int stride, const void *in, size_t n, unsigned esize, uint32_t chunk,
+                                void *out, size_t outcap, unsigned cdfnum, trc_planes_order_advice *advice);
+
 /* ---- byte planes relative to a BASE buffer: checkpoint and page deltas ------------------------------------------------
  * The filters above predict from inside the buffer.  A checkpoint, a fine-tuned model or an updated KV-cache page has a better
  * predictor: the same buffer one version earlier, already on the device.  With a base of the same element layout:

@@ -700,6 +700,7 @@ extern "C" int trc_container_check(const void *buf, size_t buflen, int codec, si
 // ---- byte planes of 16 / 32 / 64-bit elements: device wrappers, the TRCP container, its host calls ----------------
 #include "trc_planes.inc"
 #include "trc_splanes.inc"
+#include "trc_oplanes.inc"
 #include "trc_bplanes.inc"
 #include "trc_planes_batch.inc"
 #include "trc_planes_container.inc"

@@ -68,8 +68,9 @@ int trc_planes_filter_arg(const char *who, int filter);     // trc_fplanes.hip: 
 // split / join: stride 1 is the fplanes call, whose kernels it launches, and the stride itself is vetted by trc_splanes.inc before it
 // gets here.  based: the filter is against a BASE buffer (trc_bplanes.hip), whose split and join are elementwise and have no restart;
 // what can be said about the base is said before anything is enqueued.  `base` is a device pointer for the *_dev calls and a host
-// pointer for the host-pointer calls, which upload it.  An unfiltered call is told nothing of stride or base.
-struct PlanesPred { int filter, stride; const void *base; bool based; };
+// pointer for the host-pointer calls, which upload it.  An unfiltered call is told nothing of stride or base.  order: how many times
+// the strided zigzag delta is taken (trc_oplanes.hip has the kernels of orders 2 and 3); every filter above is of order 1.
+struct PlanesPred { int filter, stride; const void *base; bool based; int order = 1; };
 static PlanesPred pred_none() { return PlanesPred{ TRC_FILTER_NONE, 1, nullptr, false }; }
 static PlanesPred pred_stride(int filter, int stride) { return PlanesPred{ filter, filter == TRC_FILTER_NONE ? 1 : stride, nullptr, false }; }
 static PlanesPred pred_base(int filter, const void *base)
@@ -85,12 +86,14 @@ int trc_bplanes_overlap_arg(const char *who, const void *d_base, size_t base_byt
 static int split_any(PlanesPred p, const void *d_in, size_t n, unsigned esize, uint32_t seg, void *d_planes, size_t pitch, void *d_tail, void *stream)
 {
     if (p.based) return trc_planes_split_base_dev(p.filter, d_in, p.base, n, esize, d_planes, pitch, d_tail, stream);
+    if (p.order >= 2) return trc_planes_split_ofilter_dev(p.order, p.stride, d_in, n, esize, seg, d_planes, pitch, d_tail, stream);
     return p.stride == 1 ? trc_planes_split_filter_dev(p.filter, d_in, n, esize, seg, d_planes, pitch, d_tail, stream)
                          : trc_planes_split_sfilter_dev(p.filter, p.stride, d_in, n, esize, seg, d_planes, pitch, d_tail, stream);
 }
 static int join_any(PlanesPred p, const void *d_planes, size_t pitch, const void *d_tail, size_t n, unsigned esize, uint32_t seg, void *d_out, void *stream)
 {
     if (p.based) return trc_planes_join_base_dev(p.filter, d_planes, pitch, d_tail, p.base, n, esize, d_out, stream);
+    if (p.order >= 2) return trc_planes_join_ofilter_dev(p.order, p.stride, d_planes, pitch, d_tail, n, esize, seg, d_out, stream);
     return p.stride == 1 ? trc_planes_join_filter_dev(p.filter, d_planes, pitch, d_tail, n, esize, seg, d_out, stream)
                          : trc_planes_join_sfilter_dev(p.filter, p.stride, d_planes, pitch, d_tail, n, esize, seg, d_out, stream);
 }
@@ -348,13 +351,43 @@ extern "C" int trc_planes_advise(const uint64_t *hist, unsigned filters, unsigne
     return TRC_OK;
 }
 
+// the prefix that the explicit host call for a predictor puts in front of the TRCP container: none for unfiltered data, else the 16
+// bytes of TRCF (stride 1), TRCS (a stride above 1) or TRCO (an order above 1)
+static size_t planes_lead(PlanesPred pred)
+{
+    return pred.filter == TRC_FILTER_NONE ? 0 : sizeof(trc_fplanes_hdr);
+}
+static void planes_lead_write(PlanesPred pred, uint8_t *at, size_t size)
+{
+    if (pred.order >= 2) {
+        trc_oplanes_hdr oh;
+        memset(&oh, 0, sizeof oh);
+        oh.magic = TRC_OPLANES_MAGIC; oh.order = (uint8_t)pred.order; oh.version = 1; oh.stride = (uint16_t)pred.stride; oh.size = size;
+        memcpy(at, &oh, sizeof oh);
+    } else if (pred.stride > 1) {
+        trc_splanes_hdr sh;
+        memset(&sh, 0, sizeof sh);
+        sh.magic = TRC_SPLANES_MAGIC; sh.filter = (uint8_t)pred.filter; sh.version = 1; sh.stride = (uint16_t)pred.stride; sh.size = size;
+        memcpy(at, &sh, sizeof sh);
+    } else {
+        trc_fplanes_hdr fh;
+        memset(&fh, 0, sizeof fh);
+        fh.magic = TRC_FPLANES_MAGIC; fh.filter = (uint8_t)pred.filter; fh.version = 1; fh.size = size;
+        memcpy(at, &fh, sizeof fh);
+    }
+}
+
 // the TRCP container of F(pred, chunk, esize, in) -- of `in` itself with TRC_FILTER_NONE.  choose: the advisor sets the filter
 // from the bytes on the device (*advice, where given, says how), and `out` receives what the explicit host call writes for
 // that choice: the TRCP container, behind the 16-byte TRCF prefix where the choice is a filter.
 // pred.based: the container of D(filter, esize, in, base); the m * esize bytes of the host buffer pred.base go to the context's
 // second buffer, and *base_fp receives their fingerprint, computed on the device.
+// by_order (trc_encode_aoplanes_host, with choose): the choice is among the predictor orders 0 .. 3 at pred.stride, not among the
+// filters; *oadvice, where given, says how, and the prefix is the one of the explicit call for that choice (planes_lead_write).
+static PlanesPred pred_order(int order, int stride);                     // trc_oplanes.inc
 static size_t planes_host_encode(int codec, PlanesPred pred, bool choose, const void *in, size_t n, unsigned esize, uint32_t chunk,
-                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice, uint64_t *base_fp)
+                                 void *out, size_t outcap, unsigned cdfnum, trc_planes_advice *advice, uint64_t *base_fp,
+                                 trc_planes_order_advice *oadvice = nullptr, bool by_order = false)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
     if (codec_row(codec).low4) { fail(TRC_E_ARG, "encode_planes_host: " PLANES_LOW4, codec); return 0; }      // before anything is uploaded
@@ -372,7 +405,7 @@ static size_t planes_host_encode(int codec, PlanesPred pred, bool choose, const 
     if (planes_ctx(cp, lk)) return 0;
     HostCtx &c = *cp;
     const size_t dirsz = up256(4 * P.nc + 256);
-    const size_t histb = choose ? trc_planes_hist_bytes(esize) : 0;        // (in the workspace, ahead of the encode)
+    const size_t histb = !choose ? 0 : by_order ? trc_planes_hist_order_bytes(esize) : trc_planes_hist_bytes(esize);       // (in the workspace, ahead of the encode)
     if (grow(&c.d_in, &c.cap_in, n) || grow(&c.d_cont, &c.cap_cont, esize * (dirsz + P.buf)) ||
         grow(&c.d_work[0], &c.cap_work[0], esize * P.slice > histb ? esize * P.slice : histb)) return 0;
     hipStream_t s = c.s_k[0];
@@ -393,16 +426,23 @@ static size_t planes_host_encode(int codec, PlanesPred pred, bool choose, const 
     size_t lead = 0;                                                     // bytes of TRCF prefix in front of the container
     if (choose) {
         std::vector<uint64_t> hist(histb / sizeof(uint64_t));
-        trc_planes_advice adv;
-        if (trc_planes_hist_dev(7, c.d_in, n, esize, chunk, (uint64_t *)c.d_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
+        if (by_order ? trc_planes_hist_order_dev(15, pred.stride, c.d_in, n, esize, chunk, (uint64_t *)c.d_work[0], s)
+                     : trc_planes_hist_dev(7, c.d_in, n, esize, chunk, (uint64_t *)c.d_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
         PCHK(hipMemcpyAsync(hist.data(), c.d_work[0], histb, hipMemcpyDeviceToHost, s));
         PCHK(hipStreamSynchronize(s));
-        if (trc_planes_advise(hist.data(), 7, esize, m, &adv)) return 0;
-        if (advice) *advice = adv;
-        pred.filter = adv.filter;
-        if (pred.filter != TRC_FILTER_NONE) {
-            lead = sizeof(trc_fplanes_hdr);
-            if (outcap <= lead) { fail(TRC_E_ARG, "encode_aplanes_host: out holds %zu bytes (trc_fplanes_bound)", outcap); return 0; }
+        if (by_order) {
+            trc_planes_order_advice adv;
+            if (trc_planes_advise_order(hist.data(), 15, esize, m, &adv)) return 0;
+            if (oadvice) *oadvice = adv;
+            pred = pred_order(adv.order, pred.stride);
+        } else {
+            trc_planes_advice adv;
+            if (trc_planes_advise(hist.data(), 7, esize, m, &adv)) return 0;
+            if (advice) *advice = adv;
+            pred.filter = adv.filter;
+        }
+        if ((lead = planes_lead(pred))) {
+            if (outcap <= lead) { fail(TRC_E_ARG, "%s: out holds %zu bytes (%s)", by_order ? "encode_aoplanes_host" : "encode_aplanes_host", outcap, by_order ? "trc_oplanes_bound" : "trc_fplanes_bound"); return 0; }
             out = (uint8_t *)out + lead; outcap -= lead;
         }
     }
@@ -454,12 +494,7 @@ static size_t planes_host_encode(int codec, PlanesPred pred, bool choose, const 
     }
     if (t) PCHK(hipMemcpyAsync(o + pos, d_tail, t, hipMemcpyDeviceToHost, s));
     PCHK(hipStreamSynchronize(s));
-    if (lead) {
-        trc_fplanes_hdr fh;
-        memset(&fh, 0, sizeof fh);
-        fh.magic = TRC_FPLANES_MAGIC; fh.filter = (uint8_t)pred.filter; fh.version = 1; fh.size = lead + size;
-        memcpy(o - lead, &fh, sizeof fh);
-    }
+    if (lead) planes_lead_write(pred, o - lead, lead + size);
     return lead + size;
 }
 extern "C" size_t trc_encode_planes_host(int codec, const void *in, size_t n, unsigned esize, uint32_t chunk,
@@ -673,6 +708,7 @@ extern "C" size_t trc_decode_xplanes_host(const void *in, size_t inlen, void *ou
     if (magic == TRC_PLANES_MAGIC) return trc_decode_planes_host(in, inlen, out, outlen);
     if (magic == TRC_FPLANES_MAGIC) return trc_decode_fplanes_host(in, inlen, out, outlen);
     if (magic == TRC_SPLANES_MAGIC) return trc_decode_splanes_host(in, inlen, out, outlen);
+    if (magic == TRC_OPLANES_MAGIC) return trc_decode_oplanes_host(in, inlen, out, outlen);
     if (magic == TRC_BPLANES_MAGIC) {
         fail(TRC_E_ARG, "decode_xplanes_host: a planes container against a base (TRCD): trc_decode_bplanes_host decodes it, given the base");
         return 0;

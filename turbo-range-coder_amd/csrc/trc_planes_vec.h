@@ -5,6 +5,8 @@
 //   trc_bplanes.hip             the same behind a zigzag-delta or xor filter against a BASE buffer (elementwise both ways), the
 //                               advisor's histograms against a base, the base's fingerprint
 //   trc_planes_hist.hip         the advisor's histograms of the filtered planes, of every stride (trc_planes_count.h)
+//   trc_oplanes.hip             split / join behind a predictor of order 2 or 3, of every stride (join: trc_planes_scan.h), and the
+//                               advisor's histograms of orders 0 .. 3
 //   trc_planes_batch.hip        split / join over a table of separate allocations; includes
 //     trc_fplanes_batch.inc       the same with a filter per item (join: trc_planes_scan.h)
 //     trc_bplanes_batch.inc       the same with a filter against a base per item (join: elementwise)

@@ -96,6 +96,12 @@ class PlanesAdvice(C.Structure):
                 ("bits", C.c_double * 8 * 3), ("total_bits", C.c_double * 3)]
 
 
+class PlanesOrderAdvice(C.Structure):
+    """struct trc_planes_order_advice (include/trc_hip.h)"""
+    _fields_ = [("order", C.c_int), ("esize", C.c_uint), ("orders", C.c_uint), ("m", C.c_uint64),
+                ("bits", C.c_double * 8 * 4), ("total_bits", C.c_double * 4)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 into turbo-range-coder_amd/libturborc_hip.so."""
     if force:
@@ -197,6 +203,22 @@ def lib():
         l.trc_decode_splanes_host.restype = _sz; l.trc_decode_splanes_host.argtypes = [_vp, _sz, _vp, _sz]
         l.trc_decode_splanes_range_host.restype = _sz; l.trc_decode_splanes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
         l.trc_splanes_check.restype = C.c_int; l.trc_splanes_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_split_ofilter_dev.restype = C.c_int; l.trc_planes_split_ofilter_dev.argtypes = l.trc_planes_split_sfilter_dev.argtypes
+        l.trc_planes_join_ofilter_dev.restype = C.c_int; l.trc_planes_join_ofilter_dev.argtypes = l.trc_planes_join_sfilter_dev.argtypes
+        l.trc_encode_oplanes_dev.restype = C.c_int; l.trc_encode_oplanes_dev.argtypes = l.trc_encode_splanes_dev.argtypes
+        l.trc_decode_oplanes_dev.restype = C.c_int; l.trc_decode_oplanes_dev.argtypes = l.trc_decode_splanes_dev.argtypes
+        l.trc_decode_oplanes_range_dev.restype = C.c_int; l.trc_decode_oplanes_range_dev.argtypes = l.trc_decode_splanes_range_dev.argtypes
+        l.trc_planes_hist_order_bytes.restype = _sz; l.trc_planes_hist_order_bytes.argtypes = [C.c_uint]
+        l.trc_planes_hist_order_dev.restype = C.c_int; l.trc_planes_hist_order_dev.argtypes = l.trc_planes_hist_stride_dev.argtypes
+        l.trc_planes_advise_order.restype = C.c_int
+        l.trc_planes_advise_order.argtypes = [_vp, C.c_uint, C.c_uint, _sz, C.POINTER(PlanesOrderAdvice)]
+        l.trc_oplanes_bound.restype = _sz; l.trc_oplanes_bound.argtypes = [_sz, C.c_uint, C.c_uint32, C.c_uint]
+        l.trc_encode_oplanes_host.restype = _sz; l.trc_encode_oplanes_host.argtypes = l.trc_encode_splanes_host.argtypes
+        l.trc_decode_oplanes_host.restype = _sz; l.trc_decode_oplanes_host.argtypes = [_vp, _sz, _vp, _sz]
+        l.trc_decode_oplanes_range_host.restype = _sz; l.trc_decode_oplanes_range_host.argtypes = [_vp, _sz, _sz, _sz, _vp]
+        l.trc_oplanes_check.restype = C.c_int; l.trc_oplanes_check.argtypes = [_vp, _sz, _sz]
+        l.trc_encode_aoplanes_host.restype = _sz
+        l.trc_encode_aoplanes_host.argtypes = [C.c_int, C.c_int, _vp, _sz, C.c_uint, C.c_uint32, _vp, _sz, C.c_uint, C.POINTER(PlanesOrderAdvice)]
         l.trc_planes_split_base_dev.restype = C.c_int
         l.trc_planes_split_base_dev.argtypes = [C.c_int, _vp, _vp, _sz, C.c_uint, _vp, _sz, _vp, _vp]
         l.trc_planes_join_base_dev.restype = C.c_int
@@ -1375,6 +1397,105 @@ def splanes_check(buf, outlen=None):
     """trc_splanes_check on a TRCS container in host memory (needs no device); raises TrcError with the library's reason"""
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
     _chk(lib().trc_splanes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
+
+
+# ------------------------------------- byte planes behind a predictor of order 2 or 3: smooth series (include/trc_hip.h) ---
+OPLANES_MAGIC = 0x4f435254                                     # "TRCO"
+OPLANES_HDR = 16
+ORDER_MAX = 3
+
+
+def planes_split_ofilter(order, stride, d_in, n, esize, seg, d_planes, pitch, d_tail=None):
+    """enqueue trc_planes_split_ofilter_dev: planes_split of the zigzagged order-th difference at `stride` (order 0 .. ORDER_MAX; 0 is
+    planes_split, 1 planes_split_sfilter with FILTER_ZDELTA), restarting every seg elements"""
+    _chk(lib().trc_planes_split_ofilter_dev(order, stride, d_in.data_ptr(), n, esize, seg, d_planes.data_ptr(), pitch,
+                                            d_tail.data_ptr() if d_tail is not None else None, _cur_stream(d_in)))
+
+
+def planes_join_ofilter(order, stride, d_planes, pitch, d_tail, n, esize, seg, d_out):
+    """enqueue trc_planes_join_ofilter_dev, the inverse of planes_split_ofilter"""
+    _chk(lib().trc_planes_join_ofilter_dev(order, stride, d_planes.data_ptr(), pitch, d_tail.data_ptr() if d_tail is not None else None, n,
+                                           esize, seg, d_out.data_ptr(), _cur_stream(d_out)))
+
+
+class OrderPlanesCoder(PlanesCoder):
+    """PlanesCoder through the trc_*_oplanes_dev calls: the same buffers and results, of the zigzagged order-th difference at `stride`
+    (restart = chunk).  order=1 is StridedPlanesCoder with FILTER_ZDELTA, order=0 the unfiltered coder."""
+    _ENC, _DEC, _DEC_RANGE = "trc_encode_oplanes_dev", "trc_decode_oplanes_dev", "trc_decode_oplanes_range_dev"
+
+    def __init__(self, codec, n, esize, chunk=4096, device="cuda", cdfnum=256, prm=(5, 6), guard=0, order=0, stride=1):
+        super().__init__(codec, n, esize, chunk, device, cdfnum=cdfnum, prm=prm, guard=guard)
+        self.order, self.stride = order, stride
+
+    def _lead(self):
+        return (self.order, self.stride)
+
+
+def planes_hist_order_bytes(esize):
+    return lib().trc_planes_hist_order_bytes(esize)
+
+
+def planes_hist_order(orders, stride, d_in, n, esize, seg, d_hist):
+    """enqueue trc_planes_hist_order_dev: the byte histograms of the planes of d_in[:n] under every order of the bit set `orders`
+    (bit k = order k) at `stride`, into d_hist (4 * esize * 256 uint64 as a device tensor; zeroed by the call)"""
+    _chk(lib().trc_planes_hist_order_dev(orders, stride, d_in.data_ptr(), n, esize, seg, d_hist.data_ptr(), _cur_stream(d_in)))
+
+
+def _order_advice_dict(a):
+    return dict(order=int(a.order), esize=int(a.esize), orders=int(a.orders), m=int(a.m),
+                bits=np.array([list(r) for r in a.bits], dtype=np.float64), total_bits=np.array(list(a.total_bits), dtype=np.float64))
+
+
+def planes_advise_order(hist, orders, esize, m):
+    """trc_planes_advise_order on histograms in host memory (uint64 [4 * esize * 256]; needs no device) -> dict of the advice's fields"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    if hist.size < 4 * esize * 256:                                # (a bad esize is the library's to refuse: give it something to read)
+        hist = np.concatenate([hist.reshape(-1), np.zeros(4 * 8 * 256, dtype=np.uint64)])
+    a = PlanesOrderAdvice()
+    _chk(lib().trc_planes_advise_order(hist.ctypes.data, orders, esize, m, C.byref(a)))
+    return _order_advice_dict(a)
+
+
+def oplanes_bound(n, esize, chunk=0, cdfnum=0):
+    return lib().trc_oplanes_bound(n, esize, chunk, cdfnum)
+
+
+def host_encode_oplanes(codec, order, stride, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
+    """trc_encode_oplanes_host -> the TRCO container (np.uint8): 16 bytes, then the TRCP container of the order-filtered data"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(oplanes_bound(data.size, esize, chunk, cn), 64), dtype=np.uint8)
+    l = lib().trc_encode_oplanes_host(codec, order, stride, data.ctypes.data, data.size, esize, chunk, out.ctypes.data, out.size, cn)
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy()
+
+
+def host_decode_oplanes(comp, n):
+    return _host_decode_guarded("trc_decode_oplanes_host", comp, n)
+
+
+def host_decode_oplanes_range(comp, offset, length):
+    return _host_decode_guarded("trc_decode_oplanes_range_host", comp, length, offset)
+
+
+def oplanes_check(buf, outlen=None):
+    """trc_oplanes_check on a TRCO container in host memory (needs no device); raises TrcError with the library's reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_oplanes_check(buf.ctypes.data, buf.size, (1 << 64) - 1 if outlen is None else outlen))
+
+
+def host_encode_aoplanes(codec, stride, data, esize, chunk=0, cdfnum=256, prm=(5, 6)):
+    """trc_encode_aoplanes_host -> (the TRCP, TRCF, TRCS or TRCO container of the order the advisor chose at `stride` (np.uint8),
+    dict of the advice's fields)"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    cn = _cdfnum(codec, cdfnum, prm)
+    out = np.zeros(max(oplanes_bound(data.size, esize, chunk, cn), 64), dtype=np.uint8)
+    a = PlanesOrderAdvice()
+    l = lib().trc_encode_aoplanes_host(codec, stride, data.ctypes.data, data.size, esize, chunk, out.ctypes.data, out.size, cn, C.byref(a))
+    if l == 0:
+        raise TrcError(lib().trc_last_error().decode())
+    return out[:l].copy(), _order_advice_dict(a)
 
 
 # ------------------------------------------------ byte planes relative to a base buffer (include/trc_hip.h) ---
