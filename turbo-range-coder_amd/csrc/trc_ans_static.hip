@@ -262,6 +262,7 @@ typedef u32 trc_v2u __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) trc_v2u trc_lds_u64;
 typedef __attribute__((address_space(3))) u32 trc_lds_u32;
 typedef StreamInT<true> AnsStreamIn;
+typedef LaneStreamIn AnsLaneIn;          // trc_ans4s_dec_kernel: every lane refills its own ring (trc_io.h)
 #define DEC_LDS_LUT   0u          // u8[32768]
 #define DEC_LDS_DTAB  32768u      // uint2[256]  { f, -c0 }
 #define DEC_LDS_PROG  34816u      // u32[16]     progress counters, [SIMD][age]
@@ -388,13 +389,15 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec_kernel(
     const bool coded = alive && cl != len;
 
     QuadOut tout; tout.base = out + (u64)wc.c0 * chunk;        // output leaves through an in-register quad transpose
-    AnsStreamIn si;
+    AnsLaneIn si;
     si.rings = wbase;
     // Round 5: the stream is read in segments aligned to 64 bytes of the PAYLOAD, not of the stream: the ring's "stream" starts at the
     // 64-byte boundary below the first word (r0 bytes of it are somebody else's and are skipped by starting the cursor at r0), so
     // every 64-byte refill request is one 64-byte sector of one line.  Stream-relative segments (rounds 1-4) straddled two
     // sectors at 2-byte alignment: the payload was fetched 2.7 times (profiles/r04_pmc_traffic.txt), the first ring fill of a launch
-    // -- 128 bytes per stream from every wave at once -- took three sectors per stream where two do.
+    // -- 128 bytes per stream from every wave at once -- took three sectors per stream where two do.  (Behind the first fill the lanes
+    // refill their own rings, 16 bytes a request -- LaneStreamIn, trc_io.h: the same alignment makes every such piece 16-byte aligned
+    // in the payload, and the four pieces of a sector four requests to one line of the L2.)
     si.gbase = payload; si.soff = off + 8; si.lim = trc_sub_sat(cl, 8u);   // words follow the two states
     const u32 r0 = si.align_start(coded);
     u32 sa = 0, sb = 0;
@@ -406,6 +409,7 @@ __global__ __launch_bounds__(896) void trc_ans4s_dec_kernel(
     si.prime_land(P, 0, coded);
     si.prime_land(P, 1, coded);                                // (both halves before the first period: of the first one up to 62 bytes are skipped)
     si.rpos = r0;
+    si.start();
 
     const u32 S = chunk / TRC_SEG;
     const u32 body4 = len & ~3u;

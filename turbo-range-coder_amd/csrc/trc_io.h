@@ -4,6 +4,8 @@
 // first version showed ~5 TA cycles per scattered 16-byte lane access and every access becoming its own
 // L2 request (profiles/r01_notes.md).  Their traffic is therefore moved in 64-BYTE SEGMENTS by QUADS of lanes
 // (4 x 16 B contiguous).  (The model-bound coders stream through per-lane register windows: trc_lane_io.h.)
+// The one exception is the refill of the static rANS decoder's rings (LaneStreamIn): 16-byte ALIGNED pieces cost about one TA
+// cycle per lane access, less than the cross-lane work that makes sectors of them (profiles/dec_lane_refill/dec_lane_refill_notes.md).
 //
 //   TileIn     uniform-rate input through a 64 rows x 64 B LDS tile, loaded ahead (record stack of the adaptive rANS)
 //   QuadIn/QuadOut  uniform-rate chunk bytes in/out: the same 64-byte segments, transposed inside quads of lanes in
@@ -13,6 +15,7 @@
 //              round, each by one quad (static rANS encoder: full rounds only, StreamOut's G)
 //   StreamIn   variable-rate input (coded bytes at decode):  128-B ring per lane, refilled the same
 //              way one period ahead of use
+//   LaneStreamIn  the static rANS decoder's input: StreamIn's ring and first fill, then every lane refills its own ring
 //
 // LDS rows are padded so that the per-lane accesses are bank-conflict free:
 //   tiles: row stride 80 B  (20 dwords: 16 consecutive rows x 4 banks cover all 64 banks for b128)
@@ -693,3 +696,92 @@ struct StreamInT {
     __device__ __forceinline__ void period(bool alive, int par) { period(alive, trc_ballot(alive), par); }
 };
 typedef StreamInT<false> StreamIn;
+
+// ------------------------------------------------------------------------------ LaneStreamIn ---
+// The static rANS decoder's reader (trc_ans4s_dec_kernel only): the interleaved ring, its mirror row, the first fill by quads and the
+// two-period look-ahead of StreamInT<true>, but behind the first fill EVERY LANE REFILLS ITS OWN RING, 16 bytes at a time.  The
+// quad protocol above finds the lanes with room, ranks them and pushes two values per picked lane to a helper quad (ballot, mbcnt, two
+// ds_permute_b32, two DPP moves) so that one load instruction brings whole 64-byte sectors; here a lane with room loads the next 16
+// bytes of its own stream under its exec bit and stores them into its own column two periods later.  No rank, no permute, no DPP.
+//   * the first fill leaves lbytes = 128 in a ring that starts at a 64-byte boundary of the payload (align_start), so every later
+//     piece is 16-byte aligned in the payload (a stream that starts less than 64 bytes into the buffer keeps align_start's clamp: its
+//     pieces are as aligned as its start) and four dwords in four consecutive rows of the ring: ring offsets are multiples of 16;
+//   * `req` is the stream offset of the next piece to ask for: lbytes + 16 x (pieces in flight).  A lane asks while the ring can
+//     take the piece whatever is consumed in between: req - rpos <= 112.  A period asks for up to TWO pieces per lane (a coded chunk
+//     may consume 32 bytes per period -- 16 symbols of 15 bits -- and a piece brings 16); the second request and the second landing sit
+//     behind a branch on their wave mask, which on text is empty almost always;
+//   * pieces land in the order they were asked for.  dueA / dueB = `req` behind the requests of the last period of that parity: two
+//     periods later its pieces are the ones at [lbytes, due), first register set first.  Landing overwrites stream bytes
+//     [lbytes - 128, lbytes - 112), consumed because req - rpos <= 112 held when the piece was asked for;
+//   * the same `lim` clamp as StreamInT (a corrupt stream re-reads its last piece), nothing below gbase, and the same emergency rule:
+//     a live lane with avail() < 36 makes the wave land what is in flight and fill every ring synchronously, lane by lane.  With
+//     two requests per period valid data does not get there: 68 bytes or more in the ring and in flight before a period's requests
+//     are 100 or more behind them, so 68 or more before the next period's and 36 or more in the ring at its test.
+// Measured (100 MB of text, chunk 512; profiles/dec_lane_refill/dec_lane_refill_notes.md): about 16 vector instructions and two LDS
+// stores per period against 39, two ds_permute_b32 and four stores; SQ_INSTS_VALU -7.7 %, SQ_LDS_IDX_ACTIVE -12 %, 59.5 -> 56.9 us.
+// The texture-address units go from 24 to 32 % busy (about one cycle per aligned 16-byte lane access), TCP->TCC read requests from
+// 1.6 to 4.8 M, nearly all of the new ones L2 hits.  A form with 32 bytes per request was level with this one once it was complete
+// (it needs a 16-byte top-up to keep 36 bytes at the test) and is not in the tree.
+struct LaneStreamIn : StreamInT<true> {
+    static constexpr u32 PIECE = 16u;
+    u32 req;             // stream offset of this lane's next request
+    u32 dueA, dueB;      // `req` behind the requests of the last even / odd period
+    uint4 pA, pB;        // first piece asked for in the last even / odd period
+    uint4 qA, qB;        // second piece
+    // behind prime_land(P, 1): nothing in flight
+    __device__ __forceinline__ void start()
+    {
+        req = lbytes; dueA = dueB = 0;
+        pA = pB = qA = qB = make_uint4(0, 0, 0, 0);
+    }
+    __device__ __forceinline__ uint4 fetch() const { return trc_ld16_a2(gbase + wbase + (srel + trc_min(req, lim))); }
+    // this lane's next piece into its own column: bank = lane in every row
+    __device__ __forceinline__ void land(uint4 v)
+    {
+        const u32 ro = lbytes & (TRC_SRING - 1);
+        const u32 a = rw + (trc_lane() << 2) + (ro << 6);       // row ro / 4: rows are 256 bytes apart
+        *(lds_u32 *)(uintptr_t)a = v.x;          *(lds_u32 *)(uintptr_t)(a + 256u) = v.y;
+        *(lds_u32 *)(uintptr_t)(a + 512u) = v.z; *(lds_u32 *)(uintptr_t)(a + 768u) = v.w;
+        if (ro == 0u) *(lds_u32 *)(uintptr_t)(a + GUARD_OFF) = v.x;     // the mirror of the ring's first dword
+        lbytes += PIECE;
+    }
+    __device__ __forceinline__ void commit(int par)
+    {
+        const u32 due = par == 0 ? dueA : dueB;
+        if (lbytes < due) land(par == 0 ? pA : pB);
+        if (trc_ballot(lbytes < due)) {
+            if (lbytes < due) land(par == 0 ? qA : qB);
+        }
+    }
+    __device__ __forceinline__ void request(bool alive, u64 amask, int par)
+    {
+        const u32 t = req - rpos;                               // avail() + 16 x (pieces in flight)
+        if (alive && t <= TRC_SRING - PIECE) {
+            const uint4 v = fetch();
+            if (par == 0) pA = v; else pB = v;
+            req += PIECE;
+        }
+        if (amask & trc_ballot(t <= TRC_SRING - 2u * PIECE)) {
+            if (alive && t <= TRC_SRING - 2u * PIECE) {
+                const uint4 v = fetch();
+                if (par == 0) qA = v; else qB = v;
+                req += PIECE;
+            }
+        }
+        if (par == 0) dueA = req; else dueB = req;
+    }
+    // emergency: land the other parity's pieces (this period's own have landed), then every lane fills its ring piece by piece
+    __device__ __forceinline__ void sync_refill(bool alive, u64 amask, int par)
+    {
+        commit(par ^ 1);                                        // nothing is in flight now: req == lbytes
+        while (amask & trc_ballot(avail() <= TRC_SEG)) {
+            if (alive && avail() <= TRC_SRING - PIECE) { land(fetch()); req += PIECE; }
+        }
+    }
+    __device__ __forceinline__ void period(bool alive, u64 amask, int par)
+    {
+        commit(par);
+        if (amask & trc_ballot(avail() < 36u)) sync_refill(alive, amask, par);
+        request(alive, amask, par);
+    }
+};
