@@ -36,7 +36,9 @@
  *                                 written; prints the three estimates and the choice (n, z or x)
  *   trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>...   compress a BATCH: every input file is one item (a tensor, a page, a
  *                                 column) of esize-byte elements, all of them in one coded call; one filter letter for all items (n =
- *                                 none), or a = the library's batch advisor chooses per item and every choice is printed.  The file is
+ *                                 none), a = the library's batch advisor chooses per item and every choice is printed, or o = the
+ *                                 library's order advisor chooses a predictor order 0 .. 3 per item at stride 1 (a TRCU file where an
+ *                                 order above 1 is chosen; l lists it with a stride and an order per item, B decodes from it).  The file is
  *                                 the library's TRCB container (trc_hip.h), which records every item's length and filter
  *   trcfile B <in> <first> <count> <out>   items [first, first + count) of a file of b, their bytes concatenated: only the chunks
  *                                 that cover them are sent to the GPU
@@ -390,10 +392,10 @@ int main(int argc, char **argv)
         const char *fl = argv[5];
         const size_t count = (size_t)(argc - 7);
         if (!codec) { fprintf(stderr, "unknown id %d\n", id); return 2; }
-        if (strlen(fl) != 1 || !strchr("nzxa", fl[0])) { fprintf(stderr, "filter %s: n (none), z (zigzag delta), x (xor) or a (the advisor, per item)\n", fl); return 2; }
+        if (strlen(fl) != 1 || !strchr("nzxao", fl[0])) { fprintf(stderr, "filter %s: n (none), z (zigzag delta), x (xor), a (the advisor, per item) or o (the order advisor at stride 1, per item)\n", fl); return 2; }
         trc_planes_item *items = calloc(count, sizeof *items);
-        uint8_t *filters = calloc(count, 1);
-        if (!items || !filters) { perror("malloc"); return 2; }
+        uint8_t *filters = calloc(count, 1), *orders = calloc(count, 1);
+        if (!items || !filters || !orders) { perror("malloc"); return 2; }
         size_t total = 0;
         for (size_t i = 0; i < count; i++) {
             size_t n;
@@ -402,15 +404,17 @@ int main(int argc, char **argv)
             filters[i] = fl[0] == 'z' ? TRC_FILTER_ZDELTA : fl[0] == 'x' ? TRC_FILTER_XOR : TRC_FILTER_NONE;
         }
         const unsigned cdfnum = (codec == TRC_ANS4S || codec == TRC_RCS1 || codec == TRC_RCS2 || codec == TRC_RCSM) ? 256u : 0u;
-        const size_t cap = trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
+        const size_t cap = fl[0] == 'o' ? trc_planes_obatch_bound(codec, items, count, esize, chunk, cdfnum) : trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
         if (!cap) { fprintf(stderr, "esize %u, chunk %u: esize is 2, 4 or 8, the chunk 0 or a multiple of 64, and every file holds whole elements, at least one\n", esize, chunk); return 2; }
         unsigned char *out = malloc(cap);
         if (!out) { perror("malloc"); return 2; }
-        const size_t l = fl[0] == 'a' ? trc_encode_aplanes_batch_host(codec, items, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap, filters)
+        const size_t l = fl[0] == 'o' ? trc_encode_aoplanes_batch_host(codec, items, 0, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap, filters, orders) :
+                         fl[0] == 'a' ? trc_encode_aplanes_batch_host(codec, items, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap, filters)
                                       : trc_encode_planes_batch_host(codec, items, filters, count, esize, chunk, cdfnum, TRC_ITEMS_HOST, out, cap);
         if (!l) { fprintf(stderr, "encode failed: %s\n", trc_last_error()); return 1; }
         if (write_file(argv[6], out, l)) return 2;
         if (fl[0] == 'a') for (size_t i = 0; i < count; i++) printf("item %zu: %llu bytes, choice %c  %s\n", i, (unsigned long long)items[i].n, "nzx"[filters[i]], argv[7 + i]);
+        if (fl[0] == 'o') for (size_t i = 0; i < count; i++) printf("item %zu: %llu bytes, choice order %u  %s\n", i, (unsigned long long)items[i].n, filters[i] ? orders[i] : 0u, argv[7 + i]);
         printf("%zu items, %zu -> %zu bytes (%.2f%%)  %u planes\n", count, total, l, 100.0 * l / total, esize);
         return 0;
     }
@@ -504,22 +508,24 @@ int main(int argc, char **argv)
         size_t fl;
         unsigned char *fb = slurp(argv[2], &fl);
         if (!fb) return 2;
-        /* a TRCT file: the strides of the items, then the TRCB container (this tool reads it; it does not write one) */
-        const int strided = fl >= 4 && !memcmp(fb, "TRCT", 4);
+        /* a TRCT file: the strides of the items, then the TRCB container (this tool reads it; it does not write one); a TRCU file: the
+         * strides and the predictor orders of the items, then the TRCB container (b ... o writes one where an order above 1 is chosen) */
+        const int strided = fl >= 4 && !memcmp(fb, "TRCT", 4), ordered = fl >= 4 && !memcmp(fb, "TRCU", 4);
         trc_planes_batch_hdr h;
-        if (strided ? trc_planes_sbatch_info(fb, fl, &h, 0, 0, 0, 0) : trc_planes_batch_info(fb, fl, &h, 0, 0, 0)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
-        const size_t count = (size_t)h.count, lead = strided ? sizeof(trc_planes_sbatch_hdr) + ((count + 15) & ~(size_t)15) : 0;
+        if (ordered ? trc_planes_obatch_info(fb, fl, &h, 0, 0, 0, 0, 0) : strided ? trc_planes_sbatch_info(fb, fl, &h, 0, 0, 0, 0) : trc_planes_batch_info(fb, fl, &h, 0, 0, 0)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        const size_t count = (size_t)h.count, lead = ordered ? sizeof(trc_planes_obatch_hdr) + 2 * ((count + 15) & ~(size_t)15) : strided ? sizeof(trc_planes_sbatch_hdr) + ((count + 15) & ~(size_t)15) : 0;
         uint64_t *n = calloc(count, sizeof *n);
-        uint8_t *filters = calloc(count, 1), *strides = calloc(count, 1);
-        if (!n || !filters || !strides) { perror("malloc"); return 2; }
-        if (strided ? trc_planes_sbatch_info(fb, fl, &h, n, filters, strides, count) : trc_planes_batch_info(fb, fl, &h, n, filters, count)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
+        uint8_t *filters = calloc(count, 1), *strides = calloc(count, 1), *orders = calloc(count, 1);
+        if (!n || !filters || !strides || !orders) { perror("malloc"); return 2; }
+        if (ordered ? trc_planes_obatch_info(fb, fl, &h, n, filters, strides, orders, count) : strided ? trc_planes_sbatch_info(fb, fl, &h, n, filters, strides, count) : trc_planes_batch_info(fb, fl, &h, n, filters, count)) { fprintf(stderr, "corrupt file: %s\n", trc_last_error()); return 2; }
         if (list) {
             trc_planes_hdr ph;
             memcpy(&ph, fb + lead + h.inner, sizeof ph);
             printf("%llu items, esize %u, chunk %u, codec %u, %llu -> %llu bytes\n", (unsigned long long)h.count, h.esize, h.chunk, ph.codec,
                    (unsigned long long)h.bytes, (unsigned long long)(lead + h.size));
             for (size_t i = 0; i < count; i++) {
-                if (strided) printf("item %zu: %llu bytes, filter %c, stride %u\n", i, (unsigned long long)n[i], "nzx"[filters[i]], strides[i]);
+                if (ordered) printf("item %zu: %llu bytes, filter %c, stride %u, order %u\n", i, (unsigned long long)n[i], "nzx"[filters[i]], strides[i], orders[i]);
+                else if (strided) printf("item %zu: %llu bytes, filter %c, stride %u\n", i, (unsigned long long)n[i], "nzx"[filters[i]], strides[i]);
                 else printf("item %zu: %llu bytes, filter %c\n", i, (unsigned long long)n[i], "nzx"[filters[i]]);
             }
             return 0;
@@ -537,7 +543,8 @@ int main(int argc, char **argv)
             items[i].n = n[i];
             if (i >= first && i < first + cnt) { items[i].d_ptr = out + pos; pos += (size_t)n[i]; }
         }
-        if ((strided ? trc_decode_splanes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST)
+        if ((ordered ? trc_decode_oplanes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST) :
+             strided ? trc_decode_splanes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST)
                      : trc_decode_planes_batch_host(fb, fl, items, count, first, cnt, TRC_ITEMS_HOST)) != bytes) { fprintf(stderr, "decode failed: %s\n", trc_last_error()); return 1; }
         return write_file(argv[5], out, bytes);
     }
@@ -771,6 +778,6 @@ int main(int argc, char **argv)
         fclose(f);
         return 0;
     }
-    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile o <id> <esize> <order> <stride> <in> <out> | trcfile O <id> <esize> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... | trcfile B <in> <first> <count> <out> | trcfile l <in> | trcfile r <id> <esize> <z|x> <base> <in> <out> | trcfile R <in> <base> <out> | trcfile e <id> <esize> <chunk|0> <z|x|a> <out> <in> <base|-> ... | trcfile E <in> <item> <base|-> <out>\n");
+    fprintf(stderr, "usage: trcfile c <id> <in> <out> [-r NM] | trcfile p <id> <esize> <in> <out> | trcfile f <id> <esize> <z|x> <in> <out> | trcfile s <id> <esize> <z|x> <stride> <in> <out> | trcfile o <id> <esize> <order> <stride> <in> <out> | trcfile O <id> <esize> <stride> <in> <out> | trcfile a <id> <esize> <in> <out> | trcfile d <in> <out> | trcfile x <in> <offset> <len> <out> | trcfile C <in> <out> [bsize [1|2|4]] | trcfile D <in> <out>   (C/D: the reference's file format, codecs 1, 2, 4) | trcfile b <id> <esize> <chunk|0> <n|z|x|a> <out> <in>... (or o: the order advisor per item) | trcfile B <in> <first> <count> <out> | trcfile l <in> | trcfile r <id> <esize> <z|x> <base> <in> <out> | trcfile R <in> <base> <out> | trcfile e <id> <esize> <chunk|0> <z|x|a> <out> <in> <base|-> ... | trcfile E <in> <item> <base|-> <out>\n");
     return 2;
 }

@@ -1129,6 +1129,117 @@ int trc_planes_advise_sbatch_dev(unsigned filters, const trc_planes_item *items,
                                  uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice,
                                  void *d_work, size_t work_bytes, void *stream);
 
+/* ---- batched byte planes: a predictor ORDER per item -----------------------------------------------------------------------------
+ * A batch mixes natures at one element width: sensor channels want order 2 or 3, sorted ids and timestamps want order 1 and store more
+ * at order 2, float tensors want no filter.  Here the order of the oplanes calls is chosen per item, as filter and stride are.
+ * `orders` is a HOST array of `count` bytes with the lifetime rule of `items`, `filters` and `strides`; every entry must be in
+ * 1 .. TRC_ORDER_MAX.  An entry has an effect only where filters[i] == TRC_FILTER_ZDELTA: xor has no order, the filter enum is untouched.
+ *        GO(i) = item i                                                         where filters[i] == TRC_FILTER_NONE
+ *              = F_{strides[i]}(TRC_FILTER_XOR, seg = chunk, esize, item i)     where filters[i] == TRC_FILTER_XOR
+ *              = O(orders[i], strides[i], seg = chunk, esize, item i)           where filters[i] == TRC_FILTER_ZDELTA
+ *                                                                               (the O of the oplanes section; items have no tail)
+ *        VO(items, filters, strides, orders, esize, chunk) = V([GO(0) .. GO(count - 1)], esize, chunk)
+ * Unchanged from the strided batch: plan, M, NC, first[], pitch, table bytes and workspace; the pad behind an item, zero bytes in
+ * every plane; the predictor restarting at every chunk of the item, whether or not S divides the chunk; item i being chunks
+ * [first[i], first[i] + nc[i]) of every plane, any item range decoding alone; and items needing no readable slack: the kernels read
+ * bytes [0, n[i]) of an item and nothing else.
+ * The whole contract:  encode_obatch(codec, items, filters, strides, orders, ...)  ==  trc_encode_planes_dev(codec, VO, M * esize,
+ * esize, chunk, ...) byte for byte -- directory, payload, totals, per-plane CDFs and statuses.  So:
+ *   - orders == NULL, or 1 for every ZDELTA item, IS the sbatch call of the same kind (which is the fbatch or plain batch call where
+ *     that section says so), launches exactly those kernels and names itself so in its messages;
+ *   - the order travels in the item's 32-byte record next to filter and stride (order - 1 in bits 59 .. 60 of v0): a record of
+ *     order 1 is the sbatch record bit for bit;
+ *   - a batch of one item with filter ZDELTA, order k and stride s is trc_encode_oplanes_dev(codec, k, s, item, ...) on that item.
+ * The arguments are those of the sbatch calls with `orders` behind `strides`; join and decode take the orders of the WHOLE batch.
+ * Errors: those of the sbatch calls, and TRC_E_ARG with the item's index in trc_last_error() for an order outside
+ * 1 .. TRC_ORDER_MAX.  The order of the checks is the plan, the filters, the strides, the orders, then pointers and buffers -- so a
+ * bad order is reported without a device.
+ *
+ * trc_planes_hist_obatch_dev counts every item of an item range under the orders of the bit set `orders_set` (bit k = order k,
+ * 1 .. 15) at the item's stride: slice j is exactly what trc_planes_hist_order_dev(orders_set, strides[first_item + j], item, n,
+ * esize, seg = chunk, ...) writes for that item alone, trc_planes_hist_order_bytes(esize) bytes; trc_planes_hist_obatch_bytes(item_count,
+ * esize) is the size (0 for a bad esize or no items).  Checks, zeroing, range rules and table: those of trc_planes_hist_sbatch_dev.
+ * trc_planes_advise_obatch (host only) gives per item exactly trc_planes_advise_order's choice on the item's slice, as
+ * filters_out[i] (NONE for order 0, else ZDELTA) and orders_out[i] (the order; 1 where the filter is NONE); advice: NULL or `count`
+ * entries.  It fails as trc_planes_advise_batch does, and on an error nothing is written to filters_out, orders_out or advice.
+ * trc_planes_advise_obatch_dev is the slab walk of trc_planes_advise_batch_dev over these histograms: the same
+ * TRC_PLANES_ADVISE_SLAB_BYTES, the same TRC_PLANES_ADVISE_SLAB_ITEMS aid, the same synchronise; a workspace function of its own
+ * (a slice is 4/3 of a filter slice, so a slab holds 3/4 of the items).  It searches orders under the caller's strides (NULL: 1); it
+ * searches no strides and no xor.
+ *
+ * The TRCU container: the prefix of TRCT with the orders behind the strides, little endian:
+ *   trc_planes_obatch_hdr (16 B) | uint8 stride[count], zero-padded to a multiple of 16 | uint8 order[count], likewise
+ *   | the TRCB container of (items, filters), whose inner TRCP container is that of VO
+ * prefix = 16 + 2 * up16(count).  The stored stride of an item without a filter is 1, the stored order of an item whose filter is
+ * not ZDELTA is 1.  One layout per content: a batch in which no ZDELTA item has an order above 1 is a TRCT or TRCB container, and
+ * trc_planes_obatch_pack_dev and trc_encode_oplanes_batch_host refuse it (TRC_E_ARG, naming the calls that take it).
+ * Host only, no GPU needed:
+ *   trc_planes_obatch_bound   trc_planes_batch_bound + prefix; 0 for what the calls reject.
+ *   trc_planes_obatch_check   magic, version, the zero fields, count (and == count_expected unless that is (size_t)-1), the prefix
+ *                             within buflen, strides in 1 .. TRC_STRIDE_MAX, orders in 1 .. TRC_ORDER_MAX, zero padding, then
+ *                             trc_planes_batch_check on the rest, its count equal to the prefix's, stride 1 wherever the filter is
+ *                             NONE, order 1 wherever it is not ZDELTA, and at least one order above 1.  A failure leaves the reason
+ *                             in trc_last_error(), prefixed "ordered batch container:".
+ *   trc_planes_obatch_info    trc_planes_sbatch_info plus the orders.
+ * trc_planes_obatch_pack_dev, trc_decode_oplanes_batch_packed_dev, trc_encode_oplanes_batch_host and trc_decode_oplanes_batch_host
+ * are the TRCT calls with the orders; the decoder takes filters, strides and orders from the container.
+ * trc_encode_aoplanes_batch_host: the order advisor (all four orders) under the caller's strides (NULL: 1), then the coded call; the
+ * output is byte for byte what the explicit call for that choice writes -- TRCB, TRCT or TRCU; out must hold
+ * trc_planes_obatch_bound bytes; filters_out / orders_out (may be NULL) receive the choice.
+ * trc_decode_xplanes_host does not take this container either. */
+#define TRC_PLANES_OBATCH_MAGIC 0x55435254u   /* "TRCU" */
+typedef struct trc_planes_obatch_hdr {
+    uint32_t magic;      /* TRC_PLANES_OBATCH_MAGIC */
+    uint8_t  version;    /* 1 */
+    uint8_t  zero;
+    uint16_t zero2;
+    uint64_t count;      /* items: that of the TRCB container behind the strides and orders */
+} trc_planes_obatch_hdr; /* 16 bytes, little endian */
+size_t trc_planes_obatch_bound(int codec, const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum);
+int    trc_planes_obatch_check(const void *buf, size_t buflen, size_t count_expected);
+int    trc_planes_obatch_info(const void *buf, size_t buflen, trc_planes_batch_hdr *h, uint64_t *n, uint8_t *filters, uint8_t *strides,
+                              uint8_t *orders, size_t cap);
+int trc_planes_obatch_pack_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders,
+                               size_t count, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                               const int32_t *d_status, const uint32_t *d_clen, const void *d_payload,
+                               const uint64_t *d_total, void *d_out, size_t out_bytes, uint64_t *d_size, void *stream);
+int trc_decode_oplanes_batch_packed_dev(int codec, const void *d_cont, size_t cont_bytes,
+                                        const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders,
+                                        size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, unsigned cdfnum,
+                                        const uint64_t *total /* host, esize entries */, void *d_work, size_t work_bytes, void *stream);
+size_t trc_encode_oplanes_batch_host(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                                     const uint8_t *orders, size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on,
+                                     void *out, size_t outcap);
+size_t trc_decode_oplanes_batch_host(const void *in, size_t inlen, const trc_planes_item *items, size_t count,
+                                     size_t first_item, size_t item_count, int items_on);
+size_t trc_encode_aoplanes_batch_host(int codec, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize,
+                                      uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap,
+                                      uint8_t *filters_out, uint8_t *orders_out);
+int trc_planes_split_obatch_dev(const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders,
+                                size_t count, unsigned esize, uint32_t chunk, void *d_planes, size_t pitch,
+                                void *d_table, size_t table_bytes, void *stream);
+int trc_planes_join_obatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                               const uint8_t *orders, size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                               void *d_table, size_t table_bytes, void *stream);
+int trc_encode_oplanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders,
+                                 size_t count, unsigned esize, uint32_t chunk, uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                 uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                 void *d_work, size_t work_bytes, void *stream);
+int trc_decode_oplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                 const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders, size_t count,
+                                 size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                 void *d_work, size_t work_bytes, void *stream);
+size_t trc_planes_hist_obatch_bytes(size_t item_count, unsigned esize);
+int trc_planes_hist_obatch_dev(unsigned orders_set, const trc_planes_item *items, const uint8_t *strides, size_t count,
+                               size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                               uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);
+int trc_planes_advise_obatch(const uint64_t *hist, unsigned orders_set, unsigned esize, const trc_planes_item *items, size_t count,
+                             uint8_t *filters_out, uint8_t *orders_out, trc_planes_order_advice *advice);
+size_t trc_planes_advise_obatch_work_bytes(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk);
+int trc_planes_advise_obatch_dev(unsigned orders_set, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize,
+                                 uint32_t chunk, uint8_t *filters_out, uint8_t *orders_out, trc_planes_order_advice *advice,
+                                 void *d_work, size_t work_bytes, void *stream);
+
 /* ---- batched byte planes against a base per item: fingerprints per base, the TRCE container --------------------------------------
  * A batch coded against bases decodes silently wrong against any other base, and in place it destroys that base.  So a container of
  * such a batch names every base by its fingerprint (trc_base_fingerprint_host, above), and the fingerprints of a whole batch come

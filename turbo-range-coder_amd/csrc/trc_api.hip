@@ -705,6 +705,7 @@ extern "C" int trc_container_check(const void *buf, size_t buflen, int codec, si
 #include "trc_planes_batch.inc"
 #include "trc_planes_container.inc"
 #include "trc_planes_bcontainer.inc"
+#include "trc_planes_ocontainer.inc"
 
 // ---- exports with the reference's names (include/turborc.h:500, include/anscdf.h:40-96) ----------
 static bool ss_args_ok(const char *who, unsigned prm0, unsigned prm1)

@@ -1,7 +1,7 @@
 // trc_planes_batch.hip -- byte planes of MANY separate allocations (tensors of a checkpoint, pages of a cache, columns of a table):
 // a split that gathers from a pointer table into one long plane per byte position, the join that scatters back, and the plan; behind
-// them the same with a filter per item (trc_fplanes_batch.inc), with a filter and a stride per item (trc_splanes_batch.inc) and the
-// advisor's histograms per item (trc_planes_hist_batch.inc).
+// them the same with a filter per item (trc_fplanes_batch.inc), with a filter and a stride per item (trc_splanes_batch.inc), with a
+// predictor order per item as well (trc_oplanes_batch.inc) and the advisor's histograms per item (trc_planes_hist_batch.inc).
 //
 // Layout (include/trc_hip.h): item i has m[i] elements and nc[i] = ceil(m[i] / chunk) chunks; every item starts on
 // a chunk boundary of the VIRTUAL buffer V, every item but the last is followed by zero elements up to nc[i] * chunk, so V has
@@ -26,6 +26,7 @@
 
 #include "trc_planes_scan.h"                      // the scanning join (trc_fplanes_batch.inc)
 #include "trc_planes_count.h"                     // the advisor's LDS counters (trc_planes_hist_batch.inc)
+#include "trc_planes_order.h"                     // the predictors of order 2 and 3 (trc_oplanes_batch.inc)
 #include "trc_planes_pred.h"                      // the predictors of a batch, shared with trc_planes_batch.inc
 
 // one item as the kernels see it; `first` and `v0` count from the first chunk of the call's chunk range
@@ -243,6 +244,9 @@ static int batch_table_args(const char *who, size_t need, const void *d_table, s
 // ---- the kernels with a filter and a stride per item -----------------------------------------------------------------------------
 #include "trc_splanes_batch.inc"
 
+// ---- the kernels with a filter, a stride and a predictor order per item -----------------------------------------------------------
+#include "trc_oplanes_batch.inc"
+
 // ---- the kernels with a filter against a base per item ----------------------------------------------------------------------------
 #include "trc_bplanes_batch.inc"
 
@@ -253,13 +257,16 @@ static const split_batch_fn split_batch_kernels[3][3] = { TRC_BY_ESIZE(trc_plane
 static void (*const join_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t) = TRC_BY_ESIZE(trc_planes_join_batch_kernel);
 typedef void (*fjoin_batch_fn)(const uint8_t *, size_t, const BatchRec *, const u32 *, u32, u32, size_t, u32, u32, size_t);
 static const fjoin_batch_fn fjoin_batch_kernels[2][3] = { TRC_BY_ESIZE(trc_fplanes_join_batch_kernel), TRC_BY_ESIZE(trc_splanes_join_batch_kernel) };     // [a stride above 1][esize_row]
+static const split_batch_fn osplit_batch_kernels[3] = TRC_BY_ESIZE(trc_oplanes_split_batch_kernel);         // [esize_row]: an order above 1
+static const fjoin_batch_fn ojoin_batch_kernels[3] = TRC_BY_ESIZE(trc_oplanes_join_batch_kernel);
 static void (*const bsplit_batch_kernels[3])(const BatchRec *, const u32 *, const uint64_t *, u32, u32, size_t, size_t, uint8_t *, size_t) = TRC_BY_ESIZE(trc_bplanes_split_batch_kernel);
 static void (*const bjoin_batch_kernels[3])(const uint8_t *, size_t, const BatchRec *, const u32 *, const uint64_t *, u32, u32, size_t) = TRC_BY_ESIZE(trc_bplanes_join_batch_kernel);
 
 // Every kind of batch (BatchPred, trc_planes_pred.h).  Checks: the plan, the filters, the strides, then pointers and buffers.
 // filters == NULL: the batch call; a batch whose filters are all TRC_FILTER_NONE is that call too -- whatever else the descriptor
 // holds -- and says so in its messages.  strides == NULL: the filtered batch call; a batch in which no item with a filter has a
-// stride above 1 is that call too, likewise.  A base that overlaps its item in any other way than being it (join) is NOT checked.
+// stride above 1 is that call too, likewise.  orders == NULL: the strided batch call; a batch in which no ZDELTA item has an order above
+// 1 is that call too, likewise (checks: the orders behind the strides).  A base that overlaps its item in any other way than being it (join) is NOT checked.
 int split_batch(const char *who, const trc_planes_item *items, BatchPred pred, size_t count, unsigned esize, uint32_t chunk,
                 void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
@@ -269,7 +276,10 @@ int split_batch(const char *who, const trc_planes_item *items, BatchPred pred, s
     bool any, strided;
     if ((rc = trc_planes_batch_filters(who, pred.filters, count, &any))) return rc;
     if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, &strided))) return rc;
-    if (!strided && pred.strides) who = "planes_split_fbatch";
+    bool ordered;
+    if ((rc = trc_planes_batch_orders(who, pred.filters, pred.orders, count, &ordered))) return rc;
+    if (!ordered && pred.orders) who = "planes_split_sbatch";
+    if (!ordered && !strided && pred.strides) who = "planes_split_fbatch";
     if (!any) { who = "planes_split_batch"; pred = batch_pred_none(); }
     if (!d_planes || ((uintptr_t)d_planes & 255)) return trc_fail(TRC_E_ARG, "%s: the planes must be 256-byte aligned", who);
     if ((pitch & 255) || pitch < P.m_total) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)P.m_total);
@@ -280,6 +290,7 @@ int split_batch(const char *who, const trc_planes_item *items, BatchPred pred, s
     if (pred.based && (rc = trc_planes_bbatch_bases(who, pred.bases, pred.filters, 0, count))) return rc;
     if (any) fbatch_pack(recs, pred.filters);
     if (strided) sbatch_pack(recs, pred.filters, pred.strides);
+    if (ordered) obatch_pack(recs, pred.filters, pred.orders);
     hipStream_t s = (hipStream_t)stream;
     const BatchRec *d_rec;
     const u32 *d_map;
@@ -290,6 +301,8 @@ int split_batch(const char *who, const trc_planes_item *items, BatchPred pred, s
     const u32 vpc = chunk / TRC_PLANES_VEC, rcp = (u32)(((uint64_t)1 << 32) / vpc);
     if (pred.based)
         hipLaunchKernelGGL(bsplit_batch_kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, d_base, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
+    else if (ordered)
+        hipLaunchKernelGGL(osplit_batch_kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
     else
         hipLaunchKernelGGL(split_batch_kernels[strided ? 2 : any][esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, d_rec, d_map, vpc, rcp, nv, M, (uint8_t *)d_planes, pitch);
     const hipError_t e = hipGetLastError();
@@ -304,7 +317,10 @@ int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_pl
     bool any, strided;
     if ((rc = trc_planes_batch_filters(who, pred.filters, count, &any))) return rc;
     if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, &strided))) return rc;
-    if (!strided && pred.strides) who = "planes_join_fbatch";
+    bool ordered;
+    if ((rc = trc_planes_batch_orders(who, pred.filters, pred.orders, count, &ordered))) return rc;
+    if (!ordered && pred.orders) who = "planes_join_sbatch";
+    if (!ordered && !strided && pred.strides) who = "planes_join_fbatch";
     if (!any) { who = "planes_join_batch"; pred = batch_pred_none(); }
     if (first_item > count || item_count > count - first_item)
         return trc_fail(TRC_E_ARG, "%s: items [%zu, %zu + %zu) of %zu", who, first_item, first_item, item_count, count);
@@ -315,6 +331,7 @@ int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_pl
     if (pred.based && (rc = trc_planes_bbatch_bases(who, pred.bases, pred.filters, first_item, item_count))) return rc;
     if (any) fbatch_pack(recs, pred.filters + first_item);
     if (strided) sbatch_pack(recs, pred.filters + first_item, pred.strides + first_item);
+    if (ordered) obatch_pack(recs, pred.filters + first_item, pred.orders + first_item);
     if (!d_planes || ((uintptr_t)d_planes & 63)) return trc_fail(TRC_E_ARG, "%s: the planes must be 64-byte aligned", who);
     if ((pitch & 255) || pitch < elems) return trc_fail(TRC_E_ARG, "%s: pitch %zu must be a multiple of 256 and at least %llu", who, pitch, (unsigned long long)elems);
     if ((rc = batch_table_args(who, batch_pred_table_bytes(pred, item_count, chunks), d_table, table_bytes))) return rc;
@@ -332,7 +349,7 @@ int join_batch(const char *who, const void *d_planes, size_t pitch, const trc_pl
         u32 span;
         size_t nspan;
         const unsigned grid = join_grid((size_t)elems, chunk, span, nspan);
-        hipLaunchKernelGGL(fjoin_batch_kernels[strided][esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp,
+        hipLaunchKernelGGL(ordered ? ojoin_batch_kernels[esize_row(esize)] : fjoin_batch_kernels[strided][esize_row(esize)], dim3(grid), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp,
                            (size_t)elems, chunk, span, nspan);
     } else {
         hipLaunchKernelGGL(join_batch_kernels[esize_row(esize)], dim3(batch_grid(nv)), dim3(TRC_PLANES_BLOCK), 0, s, (const uint8_t *)d_planes, pitch, d_rec, d_map, vpc, rcp, nv);
@@ -356,6 +373,11 @@ extern "C" int trc_planes_split_sbatch_dev(const trc_planes_item *items, const u
 {
     return split_batch("planes_split_sbatch", items, batch_pred_strides(filters, strides), count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
 }
+extern "C" int trc_planes_split_obatch_dev(const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders, size_t count,
+                                           unsigned esize, uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
+{
+    return split_batch(orders ? "planes_split_obatch" : "planes_split_sbatch", items, batch_pred_orders(filters, strides, orders), count, esize, chunk, d_planes, pitch, d_table, table_bytes, stream);
+}
 extern "C" int trc_planes_split_bbatch_dev(const trc_planes_item *items, const void *const *bases, const uint8_t *filters, size_t count,
                                            unsigned esize, uint32_t chunk, void *d_planes, size_t pitch, void *d_table, size_t table_bytes, void *stream)
 {
@@ -378,6 +400,13 @@ extern "C" int trc_planes_join_sbatch_dev(const void *d_planes, size_t pitch, co
                                           void *d_table, size_t table_bytes, void *stream)
 {
     return join_batch("planes_join_sbatch", d_planes, pitch, items, batch_pred_strides(filters, strides), count, first_item, item_count, esize, chunk, d_table, table_bytes, stream);
+}
+extern "C" int trc_planes_join_obatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides,
+                                          const uint8_t *orders, size_t count, size_t first_item, size_t item_count, unsigned esize, uint32_t chunk,
+                                          void *d_table, size_t table_bytes, void *stream)
+{
+    return join_batch(orders ? "planes_join_obatch" : "planes_join_sbatch", d_planes, pitch, items, batch_pred_orders(filters, strides, orders), count, first_item, item_count, esize, chunk,
+                      d_table, table_bytes, stream);
 }
 extern "C" int trc_planes_join_bbatch_dev(const void *d_planes, size_t pitch, const trc_planes_item *items, const void *const *bases,
                                           const uint8_t *filters, size_t count, size_t first_item, size_t item_count,

@@ -10,6 +10,7 @@ int trc_planes_batch_plan_quiet(const trc_planes_item *items, size_t count, unsi
 int trc_planes_batch_ptrs_ok(const trc_planes_item *items, size_t first_item, size_t item_count);
 int trc_planes_batch_filters(const char *who, const uint8_t *filters, size_t count, bool *any);      // trc_fplanes_batch.inc
 int trc_planes_batch_strides(const char *who, const uint8_t *filters, const uint8_t *strides, size_t count, bool *strided);      // trc_splanes_batch.inc
+int trc_planes_batch_orders(const char *who, const uint8_t *filters, const uint8_t *orders, size_t count, bool *ordered);        // trc_oplanes_batch.inc
 int trc_planes_bbatch_bases(const char *who, const void *const *bases, const uint8_t *filters, size_t first_item, size_t item_count);      // trc_bplanes_batch.inc
 
 // the workspaces of a call whose table is `pred`'s
@@ -64,6 +65,7 @@ static int encode_batch(const char *who, int codec, const trc_planes_item *items
     if (rc) return rc;
     if ((rc = trc_planes_batch_filters(who, pred.filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
     if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, nullptr))) return rc;      // then a bad stride
+    if ((rc = trc_planes_batch_orders(who, pred.filters, pred.orders, count, nullptr))) return rc;        // then a bad order
     const size_t n = (size_t)B.n_virtual;
     if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, n / esize, chunk, d_cdf, cdfnum))) return rc;
@@ -115,6 +117,16 @@ extern "C" int trc_encode_splanes_batch_dev(int codec, const trc_planes_item *it
                         d_work, work_bytes, stream);
 }
 
+// a predictor order per ZDELTA item behind the strides (orders == NULL, or no such item with an order above 1: the splanes call)
+extern "C" int trc_encode_oplanes_batch_dev(int codec, const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders,
+                                            size_t count, unsigned esize, uint32_t chunk, uint16_t *d_cdf, unsigned cdfnum, int32_t *d_status,
+                                            uint32_t *d_clen, void *d_payload, uint64_t *d_total,
+                                            void *d_work, size_t work_bytes, void *stream)
+{
+    return encode_batch("encode_oplanes_batch", codec, items, batch_pred_orders(filters, strides, orders), count, esize, chunk, d_cdf, cdfnum, d_status, d_clen, d_payload,
+                        d_total, d_work, work_bytes, stream);
+}
+
 // the coded buffers of a batch, plane by plane: wherever the directories, payloads and CDFs (static coders; else NULL) of the planes lie
 struct BatchCoded { const uint32_t *clen[8]; const uint8_t *payload[8]; const uint16_t *cdf[8]; };
 // ... of the batched calls' flat buffers: directories NC entries, payloads `pitch` bytes, CDFs TRC_PLANES_CDF_STRIDE entries apart
@@ -145,6 +157,7 @@ static int decode_batch(const char *who, int codec, const BatchCoded &S, size_t 
     if (rc) return rc;
     if ((rc = trc_planes_batch_filters(who, pred.filters, count, nullptr))) return rc;      // a bad filter id: after the plan, before anything else
     if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, nullptr))) return rc;      // then a bad stride
+    if ((rc = trc_planes_batch_orders(who, pred.filters, pred.orders, count, nullptr))) return rc;        // then a bad order
     const size_t m = sub_m ? sub_m : (size_t)B.m_total, n = m * esize;
     if ((rc = planes_common(who, codec, n, esize, d_work))) return rc;
     if ((rc = check_common(codec, m, chunk, S.cdf[0], cdfnum))) return rc;
@@ -195,6 +208,15 @@ extern "C" int trc_decode_splanes_batch_dev(int codec, const uint32_t *d_clen, c
 {
     return decode_batch("decode_splanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), 0, items, batch_pred_strides(filters, strides),
                         count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
+}
+
+extern "C" int trc_decode_oplanes_batch_dev(int codec, const uint32_t *d_clen, const void *d_payload,
+                                            const trc_planes_item *items, const uint8_t *filters, const uint8_t *strides, const uint8_t *orders, size_t count,
+                                            size_t first_item, size_t item_count, unsigned esize, uint32_t chunk, const uint16_t *d_cdf, unsigned cdfnum,
+                                            void *d_work, size_t work_bytes, void *stream)
+{
+    return decode_batch("decode_oplanes_batch", codec, coded_flat(d_clen, d_payload, d_cdf, items, count, esize, chunk), 0, items,
+                        batch_pred_orders(filters, strides, orders), count, first_item, item_count, esize, chunk, cdfnum, d_work, work_bytes, stream);
 }
 
 // ---- a base per item: the filters are against bases[i] (trc_bplanes_batch.inc); the workspace holds the base pointers as well ------
@@ -366,4 +388,119 @@ extern "C" int trc_planes_advise_bbatch_dev(unsigned filters, const trc_planes_i
                                             uint32_t chunk, uint8_t *filters_out, trc_planes_advice *advice, void *d_work, size_t work_bytes, void *stream)
 {
     return advise_batch_dev(filters, items, nullptr, count, esize, chunk, filters_out, advice, d_work, work_bytes, stream, true, bases);
+}
+
+// ---- the order advisor of a batch: a filter and an order per item from the histograms of trc_planes_hist_obatch_dev --------------
+int trc_planes_hist_obatch_run(unsigned orders, const trc_planes_item *items, const uint8_t *strides, size_t first_item, size_t item_count,
+                               unsigned esize, uint32_t chunk, uint64_t *d_hist, void *d_table, size_t table_bytes, void *stream);     // trc_oplanes_batch.inc
+
+// trc_planes_advise_order on items [base, base + count) of a batch, hist = the first one's slice: choice[i] (the order, 0 .. 3) and
+// advice[i] (may be NULL) count from `base` as well; the index in an error's text is the item's index in the batch
+static int advise_order_items(const uint64_t *hist, unsigned orders, unsigned esize, const trc_planes_item *items, size_t base, size_t count,
+                              uint8_t *choice, trc_planes_order_advice *advice)
+{
+    const size_t slice = (size_t)4 * esize * 256;
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t n = items[base + i].n;
+        if (n < esize || n % esize)
+            return fail(TRC_E_ARG, "planes_advise_obatch: item %zu has %llu bytes: not a whole number (at least one) of %u-byte elements", base + i, (unsigned long long)n, esize);
+        trc_planes_order_advice a;
+        if (trc_planes_advise_order(hist + i * slice, orders, esize, (size_t)(n / esize), &a)) {
+            char why[400];
+            snprintf(why, sizeof why, "%s", g_err);
+            return fail(TRC_E_ARG, "planes_advise_obatch: item %zu: %s", base + i, why);
+        }
+        choice[base + i] = (uint8_t)a.order;
+        if (advice) advice[base + i] = a;
+    }
+    return TRC_OK;
+}
+// the choices as the ordered batch calls take them: order 0 is no filter (and order 1 in orders_out), else the zigzag delta
+static void advise_order_out(const std::vector<uint8_t> &choice, uint8_t *filters_out, uint8_t *orders_out)
+{
+    for (size_t i = 0; i < choice.size(); i++) {
+        filters_out[i] = choice[i] ? TRC_FILTER_ZDELTA : TRC_FILTER_NONE;
+        orders_out[i] = choice[i] ? choice[i] : 1;
+    }
+}
+
+// host only.  The choices reach filters_out and orders_out only when every item has passed.
+extern "C" int trc_planes_advise_obatch(const uint64_t *hist, unsigned orders, unsigned esize, const trc_planes_item *items, size_t count,
+                                        uint8_t *filters_out, uint8_t *orders_out, trc_planes_order_advice *advice)
+{
+    if (!hist || !items || !filters_out || !orders_out) return fail(TRC_E_ARG, "planes_advise_obatch: null histograms, items, filters_out or orders_out");
+    if (count == 0 || count > TRC_PLANES_BATCH_MAX) return fail(TRC_E_ARG, "planes_advise_obatch: %zu items (1 .. %u)", count, TRC_PLANES_BATCH_MAX);
+    if (orders < 1 || orders > 15) return fail(TRC_E_ARG, "planes_advise_obatch: orders 0x%x (a bit set: bit k = order k, 1 .. 15)", orders);
+    if (!planes_esize_ok(esize)) return fail(TRC_E_ARG, "planes_advise_obatch: esize %u (2, 4 or 8)", esize);
+    std::vector<uint8_t> choice(count);
+    std::vector<trc_planes_order_advice> adv(advice ? count : 0);        // (what decided reaches the caller with the choices, not before)
+    const int rc = advise_order_items(hist, orders, esize, items, 0, count, choice.data(), advice ? adv.data() : nullptr);
+    if (rc) return rc;
+    if (advice) memcpy(advice, adv.data(), count * sizeof *advice);
+    advise_order_out(choice, filters_out, orders_out);
+    return TRC_OK;
+}
+
+// items per slab of trc_planes_advise_obatch_dev: a slice is 4/3 of a filter slice, so a slab holds 3/4 of the items
+static size_t advise_oslab_items(unsigned esize)
+{
+    size_t s = TRC_PLANES_ADVISE_SLAB_BYTES / trc_planes_hist_order_bytes(esize);
+    const char *e = getenv("TRC_PLANES_ADVISE_SLAB_ITEMS");
+    if (e) { const long x = strtol(e, 0, 10); if (x >= 1 && (size_t)x < s) s = (size_t)x; }
+    return s;
+}
+static size_t advise_otable_bytes(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+{
+    const size_t slab = advise_oslab_items(esize);
+    size_t table = 0;
+    for (size_t i0 = 0; i0 < count; i0 += slab) {
+        const size_t cnt = count - i0 < slab ? count - i0 : slab;
+        uint64_t chunks = 0;
+        for (size_t i = i0; i < i0 + cnt; i++) chunks += (items[i].n / esize + chunk - 1) / chunk;
+        const size_t t = trc_planes_batch_table_bytes(cnt, chunks);
+        if (t > table) table = t;
+    }
+    return table;
+}
+// the slab's histograms | the table of the largest slab
+extern "C" size_t trc_planes_advise_obatch_work_bytes(const trc_planes_item *items, size_t count, unsigned esize, uint32_t chunk)
+{
+    if (trc_planes_batch_plan_quiet(items, count, esize, chunk, nullptr, nullptr) || !trc_planes_batch_ptrs_ok(items, 0, count)) return 0;
+    return TRC_PLANES_ADVISE_SLAB_BYTES + advise_otable_bytes(items, count, esize, chunk);
+}
+
+// the order per item under the caller's strides: the slab walk of advise_batch_dev over trc_planes_hist_obatch_dev's histograms
+extern "C" int trc_planes_advise_obatch_dev(unsigned orders, const trc_planes_item *items, const uint8_t *strides, size_t count, unsigned esize,
+                                            uint32_t chunk, uint8_t *filters_out, uint8_t *orders_out, trc_planes_order_advice *advice,
+                                            void *d_work, size_t work_bytes, void *stream)
+{
+    trc_planes_batch_plan B;
+    int rc = trc_planes_batch_plan_host(items, count, esize, chunk, &B, nullptr);
+    if (rc) return rc;
+    if (orders < 1 || orders > 15) return fail(TRC_E_ARG, "planes_advise_obatch: orders 0x%x (a bit set: bit k = order k, 1 .. 15)", orders);
+    if ((rc = trc_planes_batch_strides("planes_advise_obatch", nullptr, strides, count, nullptr))) return rc;
+    if (!filters_out || !orders_out) return fail(TRC_E_ARG, "planes_advise_obatch: null filters_out or orders_out");
+    if (!trc_planes_batch_ptrs_ok(items, 0, count)) return fail(TRC_E_ARG, "planes_advise_obatch: every item's pointer must be non-null and 16-byte aligned");
+    if (!d_work || ((uintptr_t)d_work & 255)) return fail(TRC_E_ARG, "planes_advise_obatch: the workspace must be 256-byte aligned");
+    const size_t table = advise_otable_bytes(items, count, esize, chunk), need = TRC_PLANES_ADVISE_SLAB_BYTES + table;
+    if (work_bytes < need) return fail(TRC_E_WORK, "workspace %zu B < required %zu B", work_bytes, need);
+    const size_t slab = advise_oslab_items(esize), slice = (size_t)4 * esize * 256;
+    hipStream_t s = (hipStream_t)stream;
+    uint64_t *d_hist = (uint64_t *)d_work;
+    std::vector<uint64_t> hist((count < slab ? count : slab) * slice);
+    std::vector<uint8_t> choice(count);
+    std::vector<trc_planes_order_advice> adv(advice ? count : 0);
+    for (size_t i0 = 0; i0 < count; i0 += slab) {
+        const size_t cnt = count - i0 < slab ? count - i0 : slab;
+        if ((rc = trc_planes_hist_obatch_run(orders, items, strides, i0, cnt, esize, chunk, d_hist, (uint8_t *)d_work + TRC_PLANES_ADVISE_SLAB_BYTES, table, s))) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        HIPCHK(hipMemcpyAsync(hist.data(), d_hist, cnt * slice * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if ((rc = advise_order_items(hist.data(), orders, esize, items, i0, cnt, choice.data(), advice ? adv.data() : nullptr))) return rc;
+    }
+    if (advice) memcpy(advice, adv.data(), count * sizeof *advice);
+    advise_order_out(choice, filters_out, orders_out);
+    return TRC_OK;
 }

@@ -222,6 +222,7 @@ static int packed_decode(const char *who, int codec, const void *d_cont, size_t 
     if (rc) return rc;
     if ((rc = trc_planes_batch_filters(who, pred.filters, count, nullptr))) return rc;
     if ((rc = trc_planes_batch_strides(who, pred.filters, pred.strides, count, nullptr))) return rc;
+    if ((rc = trc_planes_batch_orders(who, pred.filters, pred.orders, count, nullptr))) return rc;
     if ((rc = container_common(who, codec & ~(TRC_TABLES_READY | TRC_DIR_READY), esize))) return rc;
     if (!d_cont || ((uintptr_t)d_cont & 7) || !total) return fail(TRC_E_ARG, "%s: d_cont must be 8-byte aligned, total a host array of %u entries", who, esize);
     const TrcCodec &r = codec_row(codec);
@@ -320,9 +321,14 @@ extern "C" size_t trc_planes_bbatch_bound(int codec, const trc_planes_item *item
 // strides given: the TRCT container (trc_encode_splanes_batch_host); it refuses a batch that is a TRCB container's.
 // based: the TRCE container (trc_encode_bplanes_batch_host, trc_planes_bcontainer.inc), the bases lying where the items lie; it refuses an
 // all-NONE batch likewise, and with `choose` an item without a base is never given a filter and an all-NONE choice is a TRCB container.
-// choose: the batch advisor sets the filters (to filters_out as well, where given)
-static size_t batch_host_encode(const char *who, int codec, const trc_planes_item *items, BatchPred pred, bool choose, uint8_t *filters_out,
-                                size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap)
+// choose: the batch advisor sets the filters (to filters_out as well, where given).  orders given: the TRCU container
+// (trc_encode_oplanes_batch_host, trc_planes_ocontainer.inc); it refuses a batch that is a TRCT or TRCB container's.  choose ==
+// BATCH_CHOOSE_ORDER: the order advisor sets filters and orders under pred.strides (to filters_out / orders_out as well), and the
+// container is the one of that choice: TRCU, TRCT or TRCB.
+#define BATCH_CHOOSE_ORDER 2
+static size_t batch_host_encode(const char *who, int codec, const trc_planes_item *items, BatchPred pred, int choose, uint8_t *filters_out,
+                                size_t count, unsigned esize, uint32_t chunk, unsigned cdfnum, int items_on, void *out, size_t outcap,
+                                uint8_t *orders_out = nullptr)
 {
     if (!codec_ok(codec)) { fail(TRC_E_ARG, "codec %d not available", codec); return 0; }
     if (codec_row(codec).low4) { fail(TRC_E_ARG, "%s: " PLANES_LOW4, who, codec); return 0; }          // before anything is uploaded
@@ -340,9 +346,16 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     }
     bool strided = false;
     if (trc_planes_batch_strides(who, pred.filters, pred.strides, count, &strided)) return 0;
-    if (pred.strides && !strided) { fail(TRC_E_ARG, "%s: no item with a filter has a stride above 1: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
+    bool ordered = false;
+    if (trc_planes_batch_orders(who, pred.filters, pred.orders, count, &ordered)) return 0;
+    if (pred.orders && !ordered) {
+        fail(TRC_E_ARG, "%s: no zigzag-delta item has an order above 1: that batch is a TRCT or TRCB container (trc_encode_splanes_batch_host / trc_encode_planes_batch_host)", who);
+        return 0;
+    }
+    if (pred.strides && !strided && !ordered && choose != BATCH_CHOOSE_ORDER) { fail(TRC_E_ARG, "%s: no item with a filter has a stride above 1: that batch is a TRCB container (trc_encode_planes_batch_host)", who); return 0; }
     if (!r.cdf && !r.ss) cdfnum = 0;
     const size_t bound = pred.based ? trc_planes_bbatch_bound(codec, items, count, esize, chunk, cdfnum) :
+                         pred.orders || choose == BATCH_CHOOSE_ORDER ? trc_planes_obatch_bound(codec, items, count, esize, chunk, cdfnum) :
                          pred.strides ? trc_planes_sbatch_bound(codec, items, count, esize, chunk, cdfnum) : trc_planes_batch_bound(codec, items, count, esize, chunk, cdfnum);
     PlanesMap P;
     if (!bound || !planes_map(codec, (size_t)B.n_virtual, esize, chunk, P)) { fail(TRC_E_ARG, "%s: bad (codec, items, esize, chunk %u, cdfnum 0x%x)", who, chunk, cdfnum); return 0; }
@@ -372,7 +385,8 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     }
     const size_t fp_table = pred.based ? trc_base_fingerprint_batch_table_bytes(count) : 0;
     const size_t work = esize * P.slice + batch_pred_table_bytes(pred, count, B.chunks);
-    const size_t awork = choose ? TRC_PLANES_ADVISE_SLAB_BYTES + advise_table_bytes(dev.data(), count, esize, chunk) : 0;
+    const size_t awork = choose == BATCH_CHOOSE_ORDER ? TRC_PLANES_ADVISE_SLAB_BYTES + advise_otable_bytes(dev.data(), count, esize, chunk) :
+                         choose ? TRC_PLANES_ADVISE_SLAB_BYTES + advise_table_bytes(dev.data(), count, esize, chunk) : 0;
     const size_t dirsz = up256(esize * 4 * P.nc + 256);
     if (grow(&c.d_cont, &c.cap_cont, dirsz + esize * P.buf) || grow(&c.d_work[0], &c.cap_work[0], work > awork ? work : awork) ||
         grow(&c.d_work[1], &c.cap_work[1], up256(bound) + fp_table)) { (void)hipStreamSynchronize(s); return 0; }
@@ -382,8 +396,18 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     uint64_t *d_total = (uint64_t *)(c.d_small + PLANES_SMALL_TOT);
     int32_t *d_status = (int32_t *)(c.d_small + PLANES_SMALL_STATUS);
     uint64_t *d_size = (uint64_t *)(c.d_small + BATCH_SMALL_SIZE);
-    std::vector<uint8_t> chosen;
-    if (choose) {
+    std::vector<uint8_t> chosen, chosen_orders;
+    if (choose == BATCH_CHOOSE_ORDER) {
+        chosen.resize(count);
+        chosen_orders.resize(count);
+        if (trc_planes_advise_obatch_dev(15, dev.data(), pred.strides, count, esize, chunk, chosen.data(), chosen_orders.data(), nullptr, c.d_work[0], c.cap_work[0], s)) {
+            (void)hipStreamSynchronize(s);
+            return 0;
+        }
+        (void)trc_planes_batch_orders(who, chosen.data(), chosen_orders.data(), count, &ordered);
+        (void)trc_planes_batch_strides(who, chosen.data(), pred.strides, count, &strided);
+        pred = ordered ? batch_pred_orders(chosen.data(), pred.strides, chosen_orders.data()) : batch_pred_strides(chosen.data(), strided ? pred.strides : nullptr);
+    } else if (choose) {
         chosen.resize(count);
         if (pred.based ? trc_planes_advise_bbatch_dev(7, dev.data(), pred.bases, count, esize, chunk, chosen.data(), nullptr, c.d_work[0], c.cap_work[0], s)
                        : trc_planes_advise_batch_dev(7, dev.data(), count, esize, chunk, chosen.data(), nullptr, c.d_work[0], c.cap_work[0], s)) { (void)hipStreamSynchronize(s); return 0; }
@@ -396,6 +420,8 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
                      d_clen, d_payload, d_total, c.d_work[0], c.cap_work[0], s) ||
         (pred.based ? trc_planes_bbatch_pack_dev(codec, dev.data(), pred.bases, pred.filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                                                 d_clen, d_payload, d_total, c.d_work[1], up256(bound), d_size, c.d_work[1] + up256(bound), fp_table, s) :
+         pred.orders ? trc_planes_obatch_pack_dev(codec, dev.data(), pred.filters, pred.strides, pred.orders, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
+                                              d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s) :
          pred.strides ? trc_planes_sbatch_pack_dev(codec, dev.data(), pred.filters, pred.strides, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
                                               d_clen, d_payload, d_total, c.d_work[1], c.cap_work[1], d_size, s)
                  : trc_planes_batch_pack_dev(codec, dev.data(), pred.filters, count, esize, chunk, r.cdf ? d_cdf : nullptr, cdfnum, r.cdf ? d_status : nullptr,
@@ -408,6 +434,7 @@ static size_t batch_host_encode(const char *who, int codec, const trc_planes_ite
     BCHK(hipMemcpyAsync(out, c.d_work[1], (size_t)size, hipMemcpyDeviceToHost, s));
     BCHK(hipStreamSynchronize(s));
     if (choose && filters_out) memcpy(filters_out, chosen.data(), count);
+    if (choose == BATCH_CHOOSE_ORDER && orders_out) memcpy(orders_out, chosen_orders.data(), count);
     return (size_t)size;
 }
 

@@ -3,10 +3,12 @@
 #pragma once
 
 // filters == NULL: nothing is predicted.  strides: a stride per item with a filter (NULL: 1).  based: a filter id is against
-// bases[i] -- and a missing base is the caller's error, so `bases` may be NULL where `based` is set
-struct BatchPred { const uint8_t *filters, *strides; const void *const *bases; bool based; };
+// bases[i] -- and a missing base is the caller's error, so `bases` may be NULL where `based` is set.  orders: a predictor order per item
+// whose filter is TRC_FILTER_ZDELTA (NULL: 1)
+struct BatchPred { const uint8_t *filters, *strides; const void *const *bases; bool based; const uint8_t *orders = nullptr; };
 static inline BatchPred batch_pred_none() { return BatchPred{ nullptr, nullptr, nullptr, false }; }
 static inline BatchPred batch_pred_strides(const uint8_t *filters, const uint8_t *strides) { return BatchPred{ filters, strides, nullptr, false }; }
+static inline BatchPred batch_pred_orders(const uint8_t *filters, const uint8_t *strides, const uint8_t *orders) { return BatchPred{ filters, strides, nullptr, false, orders }; }
 static inline BatchPred batch_pred_bases(const uint8_t *filters, const void *const *bases) { return BatchPred{ filters, nullptr, bases, filters != nullptr }; }
 static const BatchPred BATCH_PRED_BASED = { nullptr, nullptr, nullptr, true };      // for the sizes of a call against bases, which look at nothing else
 

@@ -297,6 +297,30 @@ def lib():
         l.trc_planes_advise_sbatch_dev.restype = C.c_int
         l.trc_planes_advise_sbatch_dev.argtypes = [C.c_uint, _it, _fl] + l.trc_planes_advise_batch_dev.argtypes[2:]
         l.trc_planes_sbatch_bound.restype = _sz; l.trc_planes_sbatch_bound.argtypes = [C.c_int, _it, _sz, C.c_uint, C.c_uint32, C.c_uint]
+        # ... and the per-item predictor orders behind the strides: a host array, or None
+        l.trc_planes_split_obatch_dev.restype = C.c_int
+        l.trc_planes_split_obatch_dev.argtypes = [_it, _fl, _fl, _fl] + l.trc_planes_split_batch_dev.argtypes[1:]
+        l.trc_planes_join_obatch_dev.restype = C.c_int
+        l.trc_planes_join_obatch_dev.argtypes = [_vp, _sz, _it, _fl, _fl, _fl] + l.trc_planes_join_batch_dev.argtypes[3:]
+        l.trc_encode_oplanes_batch_dev.restype = C.c_int
+        l.trc_encode_oplanes_batch_dev.argtypes = [C.c_int, _it, _fl, _fl, _fl] + l.trc_encode_planes_batch_dev.argtypes[2:]
+        l.trc_decode_oplanes_batch_dev.restype = C.c_int
+        l.trc_decode_oplanes_batch_dev.argtypes = [C.c_int, _vp, _vp, _it, _fl, _fl, _fl] + l.trc_decode_planes_batch_dev.argtypes[4:]
+        l.trc_planes_hist_obatch_bytes.restype = _sz; l.trc_planes_hist_obatch_bytes.argtypes = [_sz, C.c_uint]
+        l.trc_planes_hist_obatch_dev.restype = C.c_int
+        l.trc_planes_hist_obatch_dev.argtypes = [C.c_uint, _it, _fl] + l.trc_planes_hist_batch_dev.argtypes[2:]
+        l.trc_planes_advise_obatch.restype = C.c_int
+        l.trc_planes_advise_obatch.argtypes = [_vp, C.c_uint, C.c_uint, _it, _sz, _fl, _fl, C.POINTER(PlanesOrderAdvice)]
+        l.trc_planes_advise_obatch_work_bytes.restype = _sz
+        l.trc_planes_advise_obatch_work_bytes.argtypes = l.trc_planes_advise_batch_work_bytes.argtypes
+        l.trc_planes_advise_obatch_dev.restype = C.c_int
+        l.trc_planes_advise_obatch_dev.argtypes = [C.c_uint, _it, _fl, _sz, C.c_uint, C.c_uint32, _fl, _fl, C.POINTER(PlanesOrderAdvice), _vp, _sz, _vp]
+        l.trc_planes_obatch_bound.restype = _sz; l.trc_planes_obatch_bound.argtypes = l.trc_planes_sbatch_bound.argtypes
+        l.trc_planes_obatch_check.restype = C.c_int; l.trc_planes_obatch_check.argtypes = [_vp, _sz, _sz]
+        l.trc_planes_obatch_info.restype = C.c_int
+        l.trc_planes_obatch_info.argtypes = [_vp, _sz, C.POINTER(PlanesBatchHdr), C.POINTER(C.c_uint64), _fl, _fl, _fl, _sz]
+        l.trc_planes_obatch_pack_dev.restype = C.c_int
+        l.trc_planes_obatch_pack_dev.argtypes = [C.c_int, _it, _fl, _fl, _fl, _sz, C.c_uint, C.c_uint32, _vp, C.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]
         l.trc_planes_sbatch_check.restype = C.c_int; l.trc_planes_sbatch_check.argtypes = [_vp, _sz, _sz]
         l.trc_planes_sbatch_info.restype = C.c_int
         l.trc_planes_sbatch_info.argtypes = [_vp, _sz, C.POINTER(PlanesBatchHdr), C.POINTER(C.c_uint64), _fl, _fl, _sz]
@@ -309,6 +333,15 @@ def lib():
         l.trc_encode_splanes_batch_host.argtypes = [C.c_int, _it, _fl, _fl, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz]
         l.trc_decode_splanes_batch_host.restype = _sz
         l.trc_decode_splanes_batch_host.argtypes = [_vp, _sz, _it, _sz, _sz, _sz, C.c_int]
+        l.trc_decode_oplanes_batch_packed_dev.restype = C.c_int
+        l.trc_decode_oplanes_batch_packed_dev.argtypes = [C.c_int, _vp, _sz, _it, _fl, _fl, _fl, _sz, _sz, _sz, C.c_uint, C.c_uint32, C.c_uint,
+                                                          C.POINTER(C.c_uint64), _vp, _sz, _vp]
+        l.trc_encode_oplanes_batch_host.restype = _sz
+        l.trc_encode_oplanes_batch_host.argtypes = [C.c_int, _it, _fl, _fl, _fl, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz]
+        l.trc_decode_oplanes_batch_host.restype = _sz
+        l.trc_decode_oplanes_batch_host.argtypes = [_vp, _sz, _it, _sz, _sz, _sz, C.c_int]
+        l.trc_encode_aoplanes_batch_host.restype = _sz
+        l.trc_encode_aoplanes_batch_host.argtypes = [C.c_int, _it, _fl, _sz, C.c_uint, C.c_uint32, C.c_uint, C.c_int, _vp, _sz, _fl, _fl]
         l.trc_base_fingerprint_batch_table_bytes.restype = _sz; l.trc_base_fingerprint_batch_table_bytes.argtypes = [_sz]
         l.trc_base_fingerprint_batch_dev.restype = C.c_int
         l.trc_base_fingerprint_batch_dev.argtypes = [_it, _bs, _fl, _sz, _sz, _sz, _vp, _vp, _sz, _vp]
@@ -722,6 +755,25 @@ def planes_join_sbatch(d_planes, offset, pitch, items, filters, strides, count, 
                                           count, first_item, item_count, esize, chunk, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
 
 
+def planes_orders(orders, count):
+    """the per-item predictor orders of a batch as the host array the ordered batch calls take: None (order 1), one int for every
+    item, or a sequence of `count` ints.  Values are not judged here: the library does that."""
+    return _byte_per_item("orders", orders, count)
+
+
+def planes_split_obatch(items, filters, strides, orders, count, esize, chunk, d_planes, pitch, d_table, table_bytes):
+    """enqueue trc_planes_split_obatch_dev: planes_split_sbatch with a zigzag-delta item i behind the predictor of order orders[i]"""
+    _chk(lib().trc_planes_split_obatch_dev(items, planes_filters(filters, count), planes_strides(strides, count), planes_orders(orders, count), count,
+                                           esize, chunk, d_planes.data_ptr(), pitch, d_table.data_ptr(), table_bytes, _cur_stream(d_planes)))
+
+
+def planes_join_obatch(d_planes, offset, pitch, items, filters, strides, orders, count, first_item, item_count, esize, chunk, d_table, table_bytes):
+    """enqueue trc_planes_join_obatch_dev from d_planes[offset:], the inverse of planes_split_obatch (filters, strides, orders: the whole batch's)"""
+    _chk(lib().trc_planes_join_obatch_dev(d_planes.data_ptr() + offset, pitch, items, planes_filters(filters, count), planes_strides(strides, count),
+                                          planes_orders(orders, count), count, first_item, item_count, esize, chunk, d_table.data_ptr(), table_bytes,
+                                          _cur_stream(d_planes)))
+
+
 def planes_bases(bases, count):
     """the per-item bases of a batch as the host array the bbatch calls take: None, or a sequence of `count` device tensors,
     addresses or None.  Values are not judged here: the library does that."""
@@ -758,9 +810,13 @@ class PlanesBatchCoder:
     otherwise; with filters="auto" the advisor chooses under these strides.  bases (a list of one tensor or None per item):
     filters[i] then means "against bases[i]" -- the trc_*_bplanes_batch_dev calls; decode(bases=...) may be given other bases (the
     output tensors themselves: in place).  It cannot be combined with strides or filters="auto", and pack() raises: the TRCB
-    container has no place for a base.  Plumbing only."""
+    container has no place for a base.  orders (None, one int for all items, or one per item, each 1 .. 3) puts a zigzag-delta item
+    behind the polynomial predictor of that order: the trc_*_oplanes_batch_dev calls and the TRCU container where such an item has an
+    order above 1 (ordered()), the calls above otherwise.  orders="auto": encode() first asks the order advisor
+    (planes_advise_obatch_dev, which waits for the stream) under the coder's strides, leaves its choice in self.filters and
+    self.orders and what decided in self.advice; filters must then be None.  Orders cannot be combined with bases.  Plumbing only."""
 
-    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None, strides=None, bases=None):
+    def __init__(self, codec, tensors, chunk=4096, cdfnum=256, prm=(5, 6), guard=0, esize=None, filters=None, strides=None, bases=None, orders=None):
         """esize: the element size where the tensors do not say it themselves (uint8 tensors of whole elements)"""
         import torch
         self.torch = torch
@@ -774,8 +830,12 @@ class PlanesBatchCoder:
         self.auto, self.advice = isinstance(filters, str) and filters == "auto", None
         self.filters = None if self.auto else planes_filters(filters, self.count)
         self.strides = planes_strides(strides, self.count)
-        if bases is not None and (strides is not None or self.auto):
-            raise ValueError("bases cannot be combined with strides or filters=\"auto\": a filter id then means \"against bases[i]\"")
+        self.auto_orders = isinstance(orders, str) and orders == "auto"
+        self.orders = None if self.auto_orders else planes_orders(orders, self.count)
+        if self.auto_orders and filters is not None:
+            raise ValueError("orders=\"auto\" chooses the filters as well: filters must be None")
+        if bases is not None and (strides is not None or self.auto or orders is not None):
+            raise ValueError("bases cannot be combined with strides, orders or filters=\"auto\": a filter id then means \"against bases[i]\"")
         self._bases = None if bases is None else list(bases)   # (kept alive: the array below holds addresses only)
         self.bases = planes_bases(self._bases, self.count)
         self.plan, self.first = planes_batch_plan(self.items, self.count, self.esize, chunk)
@@ -808,6 +868,9 @@ class PlanesBatchCoder:
         return planes_items([(t.data_ptr() if t is not None else None, n) for t, n in zip(tensors, self.sizes)])
 
     def encode(self, flags=0):
+        if self.auto_orders:                                   # the order advisor on what the tensors hold now, under the coder's strides
+            f, o, self.advice = planes_advise_obatch_dev(self.items, self.esize, self.chunk, 15, self.count, self.dev, strides=self.strides)
+            self.filters, self.orders = planes_filters(f, self.count), planes_orders(o, self.count)
         if self.auto:                                          # the advisor on what the tensors hold now; then as if that list had been given
             chosen, self.advice = planes_advise_batch_dev(self.items, self.esize, self.chunk, 7, self.count, self.dev, strides=self.strides)
             self.filters = planes_filters(chosen, self.count)
@@ -824,11 +887,20 @@ class PlanesBatchCoder:
             return "b", (self.bases if bases is None else planes_bases(list(bases), self.count), self.filters)
         if self.filters is None:
             return "", ()
+        if self.ordered():
+            return "o", (self.filters, self.strides, self.orders)
         return ("s", (self.filters, self.strides)) if self.strided() else ("f", (self.filters,))
 
     def _packed_family(self):
-        """the same for the container calls, which come strided ("s") or not ("") and always take the filters, None included"""
+        """the same for the container calls, which come ordered ("o"), strided ("s") or not ("") and always take the filters, None included"""
+        if self.ordered():
+            return "o", (self.filters, self.strides, self.orders)
         return ("s", (self.filters, self.strides)) if self.strided() else ("", (self.filters,))
+
+    def ordered(self):
+        """whether a zigzag-delta item has an order above 1: the ordered calls and the TRCU container; else the others"""
+        return self.filters is not None and self.orders is not None and \
+            any(f == FILTER_ZDELTA and o > 1 for f, o in zip(self.filters[:self.count], self.orders[:self.count]))
 
     def strided(self):
         """whether an item with a filter has a stride above 1: the strided calls; else today's"""
@@ -853,7 +925,8 @@ class PlanesBatchCoder:
         _chk(getattr(lib(), "trc_decode_%splanes_batch_dev" % fam)(self.codec | flags, self.clen.data_ptr(), self.payload.data_ptr(), items, *lead, *tail))
 
     def pack(self, guard=0):
-        """enqueue trc_planes_batch_pack_dev (strided(): trc_planes_sbatch_pack_dev, the TRCT container, sized by trc_planes_sbatch_bound)
+        """enqueue trc_planes_batch_pack_dev (strided(): trc_planes_sbatch_pack_dev, the TRCT container, sized by trc_planes_sbatch_bound;
+        ordered(): trc_planes_obatch_pack_dev, the TRCU container, sized by trc_planes_obatch_bound)
         on what encode() left, then synchronise to read the size -> (the TRCB container: a uint8
         device tensor trimmed to its size, with what remains of the planes_batch_bound bytes readable behind it; the size).  guard:
         0xA5 from the container's start through to the bound and that many bytes past it; self.pack_guard = the tensor's bytes behind
@@ -1262,6 +1335,52 @@ def planes_hist_sbatch(filters, items, strides, count, first_item, item_count, e
     (strides: see planes_strides) -- slice j is what planes_hist_stride leaves for item first_item + j alone at its stride"""
     _chk(lib().trc_planes_hist_sbatch_dev(filters, items, planes_strides(strides, count), count, first_item, item_count, esize, chunk,
                                           d_hist.data_ptr(), d_table.data_ptr(), table_bytes, _cur_stream(d_hist)))
+
+
+def planes_hist_obatch_bytes(item_count, esize):
+    return lib().trc_planes_hist_obatch_bytes(item_count, esize)
+
+
+def planes_hist_obatch(orders_set, items, strides, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes):
+    """enqueue trc_planes_hist_obatch_dev: the histograms of orders 0 .. 3 (orders_set: bit k = order k) of every item of the range at
+    its stride -- slice j (4 * esize * 256 uint64) is what planes_hist_order leaves for item first_item + j alone"""
+    _chk(lib().trc_planes_hist_obatch_dev(orders_set, items, planes_strides(strides, count), count, first_item, item_count, esize, chunk,
+                                          d_hist.data_ptr(), d_table.data_ptr(), table_bytes, _cur_stream(d_hist)))
+
+
+def planes_advise_obatch(hist, orders_set, esize, items, count, advice=True):
+    """trc_planes_advise_obatch on histograms in host memory (uint64, 4 * esize * 256 per item; needs no device)
+    -> (the filter per item, the order per item, the advice per item: list of dicts, or None where advice is False)"""
+    hist = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    if esize in (2, 4, 8) and hist.size < count * 4 * esize * 256:
+        raise TrcError("planes_advise_obatch: %d histogram words for %d items" % (hist.size, count))
+    f, o = (C.c_uint8 * max(count, 1))(), (C.c_uint8 * max(count, 1))()
+    adv = (PlanesOrderAdvice * max(count, 1))() if advice else None
+    _chk(lib().trc_planes_advise_obatch(hist.ctypes.data, orders_set, esize, items, count, f, o, adv))
+    return [int(x) for x in f[:count]], [int(x) for x in o[:count]], [_order_advice_dict(a) for a in adv[:count]] if advice else None
+
+
+def planes_advise_obatch_dev(batch, esize=None, chunk=4096, orders_set=15, count=None, device="cuda", advice=True, strides=None):
+    """trc_planes_advise_obatch_dev on a list of device tensors of one element size, or on a trc_planes_item array (as
+    planes_advise_batch_dev), in a workspace of its own, under `strides` (see planes_strides).  Waits for the current stream.
+    -> as planes_advise_obatch"""
+    import torch
+    if isinstance(batch, C.Array):
+        items, count = batch, len(batch) if count is None else count
+        dev = torch.device(device)
+    else:
+        tensors = list(batch)
+        if not tensors or any(not t.is_cuda or not t.is_contiguous() for t in tensors):
+            raise TrcError("a batch is a non-empty list of contiguous device tensors of one element size")
+        items, count = planes_items([(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]), len(tensors)
+        esize, dev = esize or tensors[0].element_size(), tensors[0].device
+    need = lib().trc_planes_advise_obatch_work_bytes(items, count, esize, chunk)      # (0: the call names the reason itself)
+    work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    f, o = (C.c_uint8 * max(count, 1))(), (C.c_uint8 * max(count, 1))()
+    adv = (PlanesOrderAdvice * max(count, 1))() if advice else None
+    _chk(lib().trc_planes_advise_obatch_dev(orders_set, items, planes_strides(strides, count), count, esize, chunk, f, o, adv, work.data_ptr(), need,
+                                            torch.cuda.current_stream(dev).cuda_stream))
+    return [int(x) for x in f[:count]], [int(x) for x in o[:count]], [_order_advice_dict(a) for a in adv[:count]] if advice else None
 
 
 def planes_hist_bbatch(filters, items, bases, count, first_item, item_count, esize, chunk, d_hist, d_table, table_bytes):
@@ -1718,6 +1837,44 @@ def planes_sbatch_info(buf, cap=None):
             [int(x) for x in st[:got]])
 
 
+OBATCH_MAGIC = 0x55435254                                       # "TRCU"
+
+
+def is_planes_obatch(buf):
+    """whether the buffer starts like a TRCU container (a TRCB container behind per-item strides and orders)"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    return buf.size >= 4 and int(buf[:4].view("<u4")[0]) == OBATCH_MAGIC
+
+
+def planes_obatch_prefix(count):
+    """bytes of a TRCU container in front of its TRCB container"""
+    return 16 + 2 * ((count + 15) & ~15)
+
+
+def planes_obatch_bound(codec, sizes, esize, chunk=0, cdfnum=0):
+    return lib().trc_planes_obatch_bound(codec, planes_items([(None, n) for n in sizes]), len(sizes), esize, chunk, cdfnum)
+
+
+def planes_obatch_check(buf, count=None):
+    """trc_planes_obatch_check (needs no device); raises TrcError with the reason"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    _chk(lib().trc_planes_obatch_check(buf.ctypes.data, buf.size, _sz(-1).value if count is None else count))
+
+
+def planes_obatch_info(buf, cap=None):
+    """trc_planes_obatch_info -> (dict of the TRCB header's fields, n, filters, strides, orders: lists) of the first min(cap, count) items"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    h = PlanesBatchHdr()
+    if cap is None:
+        _chk(lib().trc_planes_obatch_info(buf.ctypes.data, buf.size, C.byref(h), None, None, None, None, 0))
+        cap = int(h.count)
+    n, f, st, od = (C.c_uint64 * max(cap, 1))(), (C.c_uint8 * max(cap, 1))(), (C.c_uint8 * max(cap, 1))(), (C.c_uint8 * max(cap, 1))()
+    _chk(lib().trc_planes_obatch_info(buf.ctypes.data, buf.size, C.byref(h), n, f, st, od, cap))
+    got = min(cap, int(h.count))
+    return ({k: int(getattr(h, k)) for k, _ in PlanesBatchHdr._fields_}, [int(x) for x in n[:got]], [int(x) for x in f[:got]],
+            [int(x) for x in st[:got]], [int(x) for x in od[:got]])
+
+
 BBATCH_MAGIC = 0x45435254                                       # "TRCE"
 
 
@@ -1782,14 +1939,33 @@ def _batch_host_items(arrays):
     return planes_items([(a.ctypes.data, a.size) for a in keep]), ITEMS_HOST, keep
 
 
-def host_encode_planes_batch(codec, arrays, esize, chunk=0, filters=None, cdfnum=256, prm=(5, 6), strides=None):
+def host_encode_planes_batch(codec, arrays, esize, chunk=0, filters=None, cdfnum=256, prm=(5, 6), strides=None, orders=None):
     """trc_encode_planes_batch_host on numpy arrays (host items) or device tensors (device items): filters None, one id for all, a
     list, or "auto" (trc_encode_aplanes_batch_host) -> the TRCB container (np.uint8); with "auto": (container, the filters chosen).
     strides (see planes_strides) under which an item with a filter has a stride above 1: trc_encode_splanes_batch_host -> the TRCT
-    container; other strides change nothing"""
+    container; other strides change nothing.  orders (see planes_orders) under which a zigzag-delta item has an order above 1:
+    trc_encode_oplanes_batch_host -> the TRCU container; other orders change nothing.  orders="auto" (filters None):
+    trc_encode_aoplanes_batch_host under `strides` -> (the TRCB, TRCT or TRCU container of the choice, the filters, the orders chosen)"""
     items, on, keep = _batch_host_items(arrays)
     count = len(keep)
     cn = _cdfnum(codec, cdfnum, prm)
+    if isinstance(orders, str) and orders == "auto":
+        if filters is not None:
+            raise ValueError("orders=\"auto\" chooses the filters as well: filters must be None")
+        out = np.zeros(max(lib().trc_planes_obatch_bound(codec, items, count, esize, chunk, cn), 64), dtype=np.uint8)
+        cf, co = (C.c_uint8 * max(count, 1))(), (C.c_uint8 * max(count, 1))()
+        l = lib().trc_encode_aoplanes_batch_host(codec, items, planes_strides(strides, count), count, esize, chunk, cn, on, out.ctypes.data, out.size, cf, co)
+        if l == 0:
+            raise TrcError(lib().trc_last_error().decode())
+        return out[:l].copy(), [int(x) for x in cf[:count]], [int(x) for x in co[:count]]
+    if orders is not None and not isinstance(filters, str):
+        f, od = planes_filters(filters, count), planes_orders(orders, count)
+        if f is not None and any(a == FILTER_ZDELTA and b != 1 for a, b in zip(f[:count], od[:count])):      # (a bad order: the library's to refuse)
+            out = np.zeros(max(lib().trc_planes_obatch_bound(codec, items, count, esize, chunk, cn), 64), dtype=np.uint8)
+            l = lib().trc_encode_oplanes_batch_host(codec, items, f, planes_strides(strides, count), od, count, esize, chunk, cn, on, out.ctypes.data, out.size)
+            if l == 0:
+                raise TrcError(lib().trc_last_error().decode())
+            return out[:l].copy()
     if strides is not None and not isinstance(filters, str):
         f, st = planes_filters(filters, count), planes_strides(strides, count)
         if f is not None and any(a != FILTER_NONE and b != 1 for a, b in zip(f[:count], st[:count])):      # (a bad stride: the library's to refuse)
@@ -1867,13 +2043,14 @@ def host_decode_bplanes_batch(comp, bases, first_item=0, item_count=None, out=No
 
 
 def host_decode_planes_batch(comp, first_item=0, item_count=None, out=None, sizes=None):
-    """trc_decode_planes_batch_host (trc_decode_splanes_batch_host where comp is a TRCT container): items [first_item, first_item +
+    """trc_decode_planes_batch_host (trc_decode_splanes_batch_host where comp is a TRCT container, trc_decode_oplanes_batch_host where it
+    is a TRCU container): items [first_item, first_item +
     item_count) of a TRCB container -> a list of np.uint8 arrays, or,
     out given (a list of count device tensors, None outside the range), into those -> the bytes delivered.  sizes: what the call is
     told the items hold instead of the container's own table (the tests' argument errors)"""
     comp = np.ascontiguousarray(comp, dtype=np.uint8)
-    strided = is_planes_sbatch(comp)
-    h, n = planes_sbatch_info(comp)[:2] if strided else planes_batch_info(comp)[:2]
+    strided, ordered = is_planes_sbatch(comp), is_planes_obatch(comp)
+    h, n = planes_obatch_info(comp)[:2] if ordered else planes_sbatch_info(comp)[:2] if strided else planes_batch_info(comp)[:2]
     count = h["count"]
     item_count = count - first_item if item_count is None else item_count
     sizes = n if sizes is None else sizes
@@ -1885,7 +2062,7 @@ def host_decode_planes_batch(comp, first_item=0, item_count=None, out=None, size
     else:
         items = planes_items([(out[i].data_ptr() if out[i] is not None else None, sizes[i]) for i in range(count)])
         on = ITEMS_DEV
-    l = (lib().trc_decode_splanes_batch_host if strided else lib().trc_decode_planes_batch_host)(comp.ctypes.data, comp.size, items, count, first_item, item_count, on)
+    l = (lib().trc_decode_oplanes_batch_host if ordered else lib().trc_decode_splanes_batch_host if strided else lib().trc_decode_planes_batch_host)(comp.ctypes.data, comp.size, items, count, first_item, item_count, on)
     if l != sum(n[i] for i in wanted):
         raise TrcError(lib().trc_last_error().decode())
     if out is not None:
