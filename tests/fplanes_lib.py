@@ -21,6 +21,9 @@ KINDS = ("random", "monotone", "walk", "wrap")
 DT = {2: "<u2", 4: "<u4", 8: "<u8"}
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fplanes_vectors.npz")
 GOLDEN_STORE_MAX = 4096                                        # F(in) of cases up to this many bytes is stored, of larger ones hashed
+# restart lengths at which the scanning joins (512 elements per tile) leave a partial tile inside a span: spans of 6 and 7 tiles from
+# 8 segments below a tile; one tile + 8 lanes; one tile + 448 elements; 3 tiles + 448; 5 whole tiles, the control
+RESTARTS = (384, 448, 576, 960, 1984, 2560)
 
 
 def _parts(data, esize):

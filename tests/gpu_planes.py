@@ -1,5 +1,5 @@
 """What the byte-plane GPU tests share (test_gpu_planes / fplanes / splanes, their _batch files, test_gpu_abatch, test_gpu_advise,
-test_gpu_planes_container, test_gpu_planes_matrix): the guarded buffers, the packed batch, and the device-check layer of the flat
+test_gpu_planes_container, test_gpu_planes_matrix, test_gpu_oplanes, test_gpu_planes_restart): the guarded buffers, the packed batch, and the device-check layer of the flat
 kernels, the batched kernels, the coded calls and the histograms.  Every function takes the family as data (filt / stride, filters /
 strides: None selects the call without them, so each family keeps running its own C entry point), takes its input bytes and the numpy
 model's expectation from the caller, and does the device calls and every comparison.  This module is not a test file, so pytest does
@@ -105,19 +105,23 @@ def pad_mask(sizes, esize, chunk, M):
 
 
 # ---- the flat kernels ------------------------------------------------------------------------------------------------------
-def flat_calls(filt=None, stride=None, seg=None):
+def flat_calls(filt=None, stride=None, seg=None, order=None):
     """-> (split, join) with the family's leading and restart arguments bound: trc.planes_split / join (filt None),
-    planes_split_filter / join_filter (stride None), planes_split_sfilter / join_sfilter"""
-    if filt is None:
+    planes_split_filter / join_filter (stride None), planes_split_sfilter / join_sfilter, planes_split_ofilter / join_ofilter
+    (order given, no filt)"""
+    if order is not None:
+        lead, split, join = (order, stride), trc.planes_split_ofilter, trc.planes_join_ofilter
+    elif filt is None:
         return trc.planes_split, trc.planes_join
-    lead = (filt,) if stride is None else (filt, stride)
-    split = trc.planes_split_filter if stride is None else trc.planes_split_sfilter
-    join = trc.planes_join_filter if stride is None else trc.planes_join_sfilter
+    else:
+        lead = (filt,) if stride is None else (filt, stride)
+        split = trc.planes_split_filter if stride is None else trc.planes_split_sfilter
+        join = trc.planes_join_filter if stride is None else trc.planes_join_sfilter
     return (lambda d_in, n, esize, d_planes, pitch, d_tail: split(*lead, d_in, n, esize, seg, d_planes, pitch, d_tail),
             lambda d_planes, pitch, d_tail, n, esize, d_out: join(*lead, d_planes, pitch, d_tail, n, esize, seg, d_out))
 
 
-def split_join_flat(torch, d, esize, m, t, planes, tail, tag, filt=None, stride=None, seg=None):
+def split_join_flat(torch, d, esize, m, t, planes, tail, tag, filt=None, stride=None, seg=None, order=None):
     """split d (m elements of esize bytes and t tail bytes) at the smallest pitch the call takes, join the planes again; planes /
     tail: what the model expects.  Compared: the planes with the pitch gaps behind them, the tail, the guards on both sides of all
     four buffers, join(split(x)) == x, the unchanged input"""
@@ -125,7 +129,7 @@ def split_join_flat(torch, d, esize, m, t, planes, tail, tag, filt=None, stride=
     assert n == m * esize + t, tag + ": %d bytes are not %d elements and %d tail bytes" % (n, m, t)
     pitch = up256(m)
     d_in, d_planes, d_tail, d_out = Guarded(torch, n, d), Guarded(torch, esize * pitch), Guarded(torch, 8), Guarded(torch, n)
-    split, join = flat_calls(filt, stride, seg)
+    split, join = flat_calls(filt, stride, seg, order)
     split(d_in.t, n, esize, d_planes.t, pitch, d_tail.t if t else None)
     join(d_planes.t, pitch, d_tail.t if t else None, n, esize, d_out.t)
     torch.cuda.synchronize()
@@ -514,6 +518,34 @@ def device_hists(torch, esize, seg, filters, d=None, src=None, strides=None, fi=
     f = d_hist.front
     assert (raw[:f] == 0xA5).all() and (raw[f + hb:] == 0xA5).all(), what + ": the call wrote outside the histograms of its range"
     return raw[f:f + hb].view("<u8").reshape(ic, 3, esize, 256).copy(), d_hist
+
+
+def device_order_hists(torch, d, esize, stride, seg, orders):
+    """trc_planes_hist_order_dev into a dirty buffer guarded on both sides -> uint64 [4 * esize * 256]; the input and every guard
+    are unchanged"""
+    n, hb = d.size, trc.planes_hist_order_bytes(esize)
+    assert hb == 4 * esize * 256 * 8, "trc_planes_hist_order_bytes(%d) is %d" % (esize, hb)
+    d_in, d_hist = Guarded(torch, n, d), Guarded(torch, hb)
+    trc.planes_hist_order(orders, stride, d_in.t, n, esize, seg, d_hist.t)
+    torch.cuda.synchronize()
+    back, intact = d_in.get()
+    assert np.array_equal(back, d) and intact, "orders %d stride %d: the call changed its input or the bytes around it" % (orders, stride)
+    got, intact = d_hist.get()
+    assert intact, "orders %d stride %d: the call wrote outside its histograms" % (orders, stride)
+    return got.view("<u8").copy()
+
+
+def assert_order_hists(got, exp, m, orders, tag):
+    """got, exp: uint64 [4, esize, 256].  A requested order's rows sum to m and equal the model's, the first differing bin named; the
+    rows of an order that was not requested are zero"""
+    for k in range(4):
+        if orders >> k & 1:
+            assert (got[k].sum(axis=1) == m).all(), tag + ": a row of order %d does not sum to m" % k
+            if not np.array_equal(got[k], exp[k]):
+                p, b = np.argwhere(got[k] != exp[k])[0]
+                raise AssertionError("%s: order %d plane %d bin %d: %d, the model has %d" % (tag, k, p, b, got[k, p, b], exp[k, p, b]))
+        else:
+            assert not got[k].any(), tag + ": rows of order %d, which was not requested, are not zero" % k
 
 
 def assert_hists(got, exp, ms, filters, tag):

@@ -2,7 +2,7 @@
 stated alignment and no better, a base and a batch item with NO slack (poison follows their last byte), planes at the smallest
 pitch, workspaces, tables, histograms and containers of exactly the bytes their size functions name, everything poisoned (seeded
 random bytes or 0xFF) before the inputs go in.  After every library call the whole allocation is audited against its image.
-Expected values never come from the device: the numpy models (planes_lib, fplanes_lib, splanes_lib, bplanes_lib,
+Expected values never come from the device: the numpy models (planes_lib, fplanes_lib, splanes_lib, oplanes_lib, bplanes_lib,
 planes_batch_lib.virtual, advise_lib), per plane the oracle (trc_testlib.orc_cdfini / orc_chunked_enc: plane k's result is
 trc_encode_dev on plane k), for containers the layout functions.  Stray READS leave no trace: a read past a no-slack buffer shows
 only where it changes a result, which is why every run_* returns its outputs for gpu_arena.same_outputs under the two poisons.
@@ -17,6 +17,7 @@ import advise_lib as AL
 import bplanes_lib as BPL
 import fplanes_lib as FL
 import gpu_arena as GA
+import oplanes_lib as OL
 import planes_batch_lib as BL
 import planes_lib as PL
 import planes_matrix_lib as PM
@@ -26,22 +27,27 @@ import trc_testlib as T
 from planes_batch_lib import up256
 
 PAD = GA.PAD
-SEG = 256                                                      # the restart length of the flat filtered kernels
+SEG = 256                                                      # the restart length of the flat filtered kernels ...
+SEG_PARTIAL = 576                                              # ... and one whose spans end in a partial tile of the scanning join
 ESIZES = PL.ESIZES
 CDF_STRIDE = trc.PLANES_CDF_STRIDE
-# (kind, filter, stride)
+# (kind, filter, stride); ("ofilter", order, stride): the predictor of that order, which has no filter argument
 FLAT_FAMILIES = ([("plain", 0, 0)] + [("filter", f, 0) for f in FL.FILTERS] + [("sfilter", f, s) for f in FL.FILTERS for s in (1, 3, 8)]
-                 + [("base", f, 0) for f in FL.FILTERS])
+                 + [("base", f, 0) for f in FL.FILTERS] + [("ofilter", k, s) for k, s in ((2, 1), (3, 3), (2, 6), (3, 8))])
+SEG_KINDS = ("filter", "sfilter", "ofilter")                   # the kinds whose calls take a restart length
 
 
 def flat_shapes(esize):
-    """(m, t): one element; less than a vector with a full tail; one vector; a partial vector behind 256 of them; more than one
-    workgroup with a partial vector and a full tail"""
+    """(m, t): one element; less than a vector with a full tail; one vector (all three: fewer elements than ORDER * S, where an order
+    split reaches up to three vectors back); a partial vector behind 256 of them; more than one workgroup with a partial vector and
+    a full tail"""
     return [(1, 0), (7, esize - 1), (8, 0), (8 * 256 + 9, 1), (2049 * 8 + 5, esize - 1)]
 
 
 def fam_name(fam):
     kind, f, s = fam
+    if kind == "ofilter":
+        return "ofilter-o%d-s%d" % (f, s)
     return kind + ("-" + FL.FILTER_NAMES[f] if f else "") + ("-s%d" % s if s else "")
 
 
@@ -54,6 +60,8 @@ def forward(fam, d, base, esize, seg):
         return FL.forward(d, esize, f, seg)
     if kind == "sfilter":
         return SL.forward(d, esize, f, seg, s)
+    if kind == "ofilter":
+        return OL.forward(d, esize, f, seg, s)
     return BPL.forward(d, base, esize, f)
 
 
@@ -65,6 +73,8 @@ def inverse(fam, y, base, esize, seg):
         return FL.inverse(y, esize, f, seg)
     if kind == "sfilter":
         return SL.inverse(y, esize, f, seg, s)
+    if kind == "ofilter":
+        return OL.inverse(y, esize, f, seg, s)
     return BPL.inverse(y, base, esize, f)
 
 
@@ -74,6 +84,8 @@ def flat_input(fam, esize, m, t):
     seed = 1000 * esize + m
     if kind == "base":
         return BPL.gen_pair(BPL.KINDS[(m + esize) % 4], esize, m, t, seed)
+    if kind == "ofilter":
+        return OL.gen(OL.KINDS[(m + esize) % 4], esize, m, t, seed, s), None
     if s > 1:
         return SL.gen("interleaved", esize, m, t, seed, s), None
     return FL.gen(FL.KINDS[(m + esize) % 4], esize, m, t, seed), None
@@ -96,27 +108,31 @@ def flat_specs(fam, esize, m, t):
     return specs, ({"io.out": "io.base"} if fam[0] == "base" else None)
 
 
-def split_flat(fam, A, n, esize, pitch):
+def split_flat(fam, A, n, esize, pitch, seg=SEG):
     L, (kind, f, s) = trc.lib(), fam
     i, p, tl = A.ptr("in"), A.ptr("planes"), A.ptr("tail")
     if kind == "plain":
         return L.trc_planes_split_dev(i, n, esize, p, pitch, tl, None)
     if kind == "filter":
-        return L.trc_planes_split_filter_dev(f, i, n, esize, SEG, p, pitch, tl, None)
+        return L.trc_planes_split_filter_dev(f, i, n, esize, seg, p, pitch, tl, None)
     if kind == "sfilter":
-        return L.trc_planes_split_sfilter_dev(f, s, i, n, esize, SEG, p, pitch, tl, None)
+        return L.trc_planes_split_sfilter_dev(f, s, i, n, esize, seg, p, pitch, tl, None)
+    if kind == "ofilter":
+        return L.trc_planes_split_ofilter_dev(f, s, i, n, esize, seg, p, pitch, tl, None)
     return L.trc_planes_split_base_dev(f, i, A.ptr("base"), n, esize, p, pitch, tl, None)
 
 
-def join_flat(fam, A, n, esize, pitch, out="out", base="base"):
+def join_flat(fam, A, n, esize, pitch, out="out", base="base", seg=SEG):
     L, (kind, f, s) = trc.lib(), fam
     p, tl, o = A.ptr("planes"), A.ptr("tail"), A.ptr(out)
     if kind == "plain":
         return L.trc_planes_join_dev(p, pitch, tl, n, esize, o, None)
     if kind == "filter":
-        return L.trc_planes_join_filter_dev(f, p, pitch, tl, n, esize, SEG, o, None)
+        return L.trc_planes_join_filter_dev(f, p, pitch, tl, n, esize, seg, o, None)
     if kind == "sfilter":
-        return L.trc_planes_join_sfilter_dev(f, s, p, pitch, tl, n, esize, SEG, o, None)
+        return L.trc_planes_join_sfilter_dev(f, s, p, pitch, tl, n, esize, seg, o, None)
+    if kind == "ofilter":
+        return L.trc_planes_join_ofilter_dev(f, s, p, pitch, tl, n, esize, seg, o, None)
     return L.trc_planes_join_base_dev(f, p, pitch, tl, A.ptr(base), n, esize, o, None)
 
 
@@ -124,31 +140,32 @@ def plane_writes(name, esize, pitch, m):
     return [(name, k * pitch, k * pitch + m) for k in range(esize)]
 
 
-def run_flat(torch, fam, esize, m, t, poison, seed, drop=None):
+def run_flat(torch, fam, esize, m, t, poison, seed, drop=None, seg=SEG):
     """split at the smallest pitch, join into a separate output and (base) onto the base itself.  Audited: the split writes [0, m)
     of each plane and [0, t) of the tail, the join [0, n) of its output; the pitch gaps and every slack are hard.  drop: the name
-    of one permitted write range left out (the audit's own test) -> what the calls returned"""
+    of one permitted write range left out (the audit's own test); seg: the restart length of the kinds that have one -> what the
+    calls returned"""
     d, base = flat_input(fam, esize, m, t)
     n, pitch = d.size, up256(m)
-    tag = "%s esize %d (m %d, t %d), poison %s" % (fam_name(fam), esize, m, t, poison)
+    tag = "%s esize %d (m %d, t %d), seg %d, poison %s" % (fam_name(fam), esize, m, t, seg, poison)
     specs, alias = flat_specs(fam, esize, m, t)
     A = arena(torch, specs, poison, seed, alias)
     A.put("in", d)
     if base is not None:
         A.put("base", base)
         A.put("io.base", base)
-    y = forward(fam, d, base, esize, SEG)
+    y = forward(fam, d, base, esize, seg)
     planes, tail = PL.split(y, esize)
     writes = plane_writes("planes", esize, pitch, m) + [("tail", 0, t)]
     if drop == "tail":
         writes = writes[:-1]
-    ok(A.call(lambda: split_flat(fam, A, n, esize, pitch), tag + ": split", writes), tag + ": split")
+    ok(A.call(lambda: split_flat(fam, A, n, esize, pitch, seg), tag + ": split", writes), tag + ": split")
     got_planes = A.get("planes", esize * pitch).reshape(esize, pitch)[:, :m]
     got_tail = A.get("tail", t)
     assert np.array_equal(got_planes, planes), "%s: split: %s" % (tag, PM.first_difference("planes", got_planes, planes))
     assert np.array_equal(got_tail, tail), tag + ": split: the tail bytes"
     got = dict(planes=got_planes, tail=got_tail, out=[])
-    ok(A.call(lambda: join_flat(fam, A, n, esize, pitch), tag + ": join", [("out", 0, n)]), tag + ": join")
+    ok(A.call(lambda: join_flat(fam, A, n, esize, pitch, seg=seg), tag + ": join", [("out", 0, n)]), tag + ": join")
     got["out"].append(A.get("out", n))
     if base is not None:                                       # in place: d_out is the address the base is read from
         assert A.ptr("io.out") == A.ptr("io.base")
@@ -197,6 +214,30 @@ def run_hist(torch, fam, esize, m, t, poison, seed, drop=None):
     return dict(hist=h)
 
 
+def hist_order_specs(esize, m, t):
+    return [("in", m * esize + t), ("hist", 4 * esize * 256 * 8)]
+
+
+def run_hist_order(torch, orders, stride, esize, m, t, poison, seed, drop=None, seg=SEG):
+    """trc_planes_hist_order_dev under the order set `orders` into exactly trc_planes_hist_order_bytes(esize) poisoned bytes: the
+    header has the call zero all of them first, so the whole buffer is its write range and the rows of an order that was not
+    requested are zero, not poison"""
+    d, _ = flat_input(("ofilter", 2, stride), esize, m, t)
+    n, hb = d.size, trc.planes_hist_order_bytes(esize)
+    specs = hist_order_specs(esize, m, t)
+    assert hb == specs[1][1]
+    tag = "hist orders %d stride %d esize %d (m %d, t %d), seg %d, poison %s" % (orders, stride, esize, m, t, seg, poison)
+    A = arena(torch, specs, poison, seed)
+    A.put("in", d)
+    fn = lambda: trc.lib().trc_planes_hist_order_dev(orders, stride, A.ptr("in"), n, esize, seg, A.ptr("hist"), None)      # noqa: E731
+    ok(A.call(fn, tag, [] if drop == "hist" else [("hist", 0, hb)]), tag)
+    h = A.get("hist", hb).view("<u8").reshape(4, esize, 256).copy()
+    exp = OL.hist4(d, esize, seg, stride, orders).reshape(4, esize, 256)
+    assert not exp[[k for k in range(4) if not orders >> k & 1]].any()
+    assert np.array_equal(h, exp), "%s: %s" % (tag, PM.first_difference("counters", h, exp))
+    return dict(hist=h)
+
+
 FP_SIZES = (0, 1, 15, 16, 17, 4099)
 
 
@@ -214,25 +255,26 @@ def run_fingerprint(torch, nbytes, poison, seed):
 
 # --------------------------------------------------------------------------------------------- B. the coded flat calls ---
 CODED_SHAPES = ((66, 37), (3, 3))                              # (chunks per plane, elements of the last one); t = esize - 1, then 0
-CODED_FAMILIES = ("planes", "fplanes", "splanes", "bplanes")
+CODED_FAMILIES = ("planes", "fplanes", "splanes", "bplanes", "oplanes")
+CODED_ORDERS = ((2, 3), (3, 8))                                # (order, stride) of the oplanes cases
 PLAIN_CODERS = (trc.ANS4S, trc.RCS1, trc.RCA, trc.RCB, trc.ANSO1)
 FILTERED_CODERS = (trc.ANS4S, trc.RCA)
 PLANE_SEED = {}                                                # (codec, esize, shape, plane) -> seed, where 10 * plane misses the mix
 
 
 def coded_cases():
-    """(family, codec, esize, shape): esize 4 for every coder, 2 and 8 for ans4s"""
+    """(family, codec, esize, shape) and, for oplanes, (order, stride) behind them: esize 4 for every coder, 2 and 8 for ans4s"""
     out = []
     for fam in CODED_FAMILIES:
         for codec in (PLAIN_CODERS if fam == "planes" else FILTERED_CODERS):
             for esize in ((2, 4, 8) if codec == trc.ANS4S else (4,)):
                 for shape in CODED_SHAPES:
-                    out.append((fam, codec, esize, shape))
+                    out += [(fam, codec, esize, shape, pred) for pred in CODED_ORDERS] if fam == "oplanes" else [(fam, codec, esize, shape)]
     return out
 
 
 def case_id(c):
-    return "%s-%s-e%d-%dx%d" % (c[0], trc.CODEC_NAMES[c[1]], c[2], c[3][0], c[3][1])
+    return "%s-%s-e%d-%dx%d" % (c[0], trc.CODEC_NAMES[c[1]], c[2], c[3][0], c[3][1]) + ("-o%d-s%d" % c[4] if len(c) > 4 else "")
 
 
 _coded = {}
@@ -240,10 +282,13 @@ _coded = {}
 
 class Coded:
     """one input of one coded call: plane k is planes_matrix_lib.mixed_input of the coder with seed 10 k, the call's input the
-    join of the planes with its t tail bytes behind the family's inverse filter; .exp[k] = what the oracle gives for plane k"""
+    join of the planes with its t tail bytes behind the family's inverse filter; .exp[k] = what the oracle gives for plane k.
+    pred: (order, stride) of an oplanes case; .stride is the family's stride, .order the predictor's order where it has one"""
 
-    def __init__(self, fam, codec, esize, shape):
+    def __init__(self, fam, codec, esize, shape, pred=None):
+        assert (pred is not None) == (fam == "oplanes")
         self.fam, self.codec, self.esize, self.shape = fam, codec, esize, shape
+        self.order, self.stride = pred if pred else (None, 3 if fam == "splanes" else 0)
         self.name = trc.CODEC_NAMES[codec]
         nch, last = shape
         self.chunk = chunk = PM.chunk_of(codec)
@@ -257,8 +302,8 @@ class Coded:
         self.n = self.filtered.size
         self.filt = FL.ZDELTA if codec == trc.ANS4S else FL.XOR
         self.base = FL.gen("random", esize, self.m, 0, 3 + esize) if fam == "bplanes" else None
-        self.model = {"planes": ("plain", 0, 0), "fplanes": ("filter", self.filt, 0), "splanes": ("sfilter", self.filt, 3),
-                      "bplanes": ("base", self.filt, 0)}[fam]
+        self.model = {"planes": ("plain", 0, 0), "fplanes": ("filter", self.filt, 0), "splanes": ("sfilter", self.filt, self.stride),
+                      "bplanes": ("base", self.filt, 0), "oplanes": ("ofilter", self.order, self.stride)}[fam]
         self.d = inverse(self.model, self.filtered, self.base, esize, chunk)
         assert np.array_equal(forward(self.model, self.d, self.base, esize, chunk), self.filtered)
         self.static = codec in trc.STATIC
@@ -268,7 +313,7 @@ class Coded:
         first, count = self.range
         self.range_elems = (first * chunk, min(self.m, (first + count) * chunk))
         self.range_bytes = (self.range_elems[1] - self.range_elems[0]) * esize
-        self.tag = "%s %s esize %d (%d, %d) chunk %d" % (fam, self.name, esize, nch, last, chunk)
+        self.tag = "%s %s esize %d (%d, %d) chunk %d" % (fam_name(self.model) if pred else fam, self.name, esize, nch, last, chunk)
         self._exp = None
 
     @property
@@ -299,20 +344,20 @@ class Coded:
         return s, ({"io.out": "io.base"} if self.fam == "bplanes" else None)
 
 
-def coded(fam, codec, esize, shape):
-    key = (fam, codec, esize, shape)
+def coded(fam, codec, esize, shape, pred=None):
+    key = (fam, codec, esize, shape, pred)
     if key not in _coded:
         _coded[key] = Coded(*key)
     return _coded[key]
 
 
 def _lead(c):
-    return {"planes": (), "fplanes": (c.filt,), "splanes": (c.filt, 3), "bplanes": (c.filt,)}[c.fam]
+    return {"planes": (), "fplanes": (c.filt,), "splanes": (c.filt, c.stride), "bplanes": (c.filt,), "oplanes": (c.order, c.stride)}[c.fam]
 
 
 def _fn(c, what):
     return getattr(trc.lib(), {"planes": "trc_%s_planes%s_dev", "fplanes": "trc_%s_fplanes%s_dev", "splanes": "trc_%s_splanes%s_dev",
-                               "bplanes": "trc_%s_bplanes%s_dev"}[c.fam] % what)
+                               "bplanes": "trc_%s_bplanes%s_dev", "oplanes": "trc_%s_oplanes%s_dev"}[c.fam] % what)
 
 
 def encode_coded(c, A, work_bytes):

@@ -23,7 +23,8 @@ import splanes_lib as SL
 ESIZES, DT = FL.ESIZES, FL.DT
 ORDERS = (2, 3)
 ORDER_MAX = 3
-STRIDES = (1, 2, 3, 5, 8)
+STRIDES = (1, 2, 3, 5, 8)                                      # the fixture's and golden_cases()': pinned
+ALL_STRIDES = tuple(range(1, 9))                               # every entry of the kernels' dispatch tables
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oplanes_vectors.npz")
 GOLDEN_STORE_MAX = FL.GOLDEN_STORE_MAX
 

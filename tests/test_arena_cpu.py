@@ -213,6 +213,8 @@ def planes_layouts():
                 yield P.flat_specs(fam, esize, m, t)
     for case in P.coded_cases():
         yield P.coded(*case).specs()
+    for esize in P.ESIZES:
+        yield P.hist_order_specs(esize, *P.flat_shapes(esize)[-1]), None
     b = P.Batch("bbatch", 8)
     yield b.item_specs() + b.base_specs() + [("planes", 8 * P.up256(b.M)), ("table", 256)] + b.item_specs("o") + [("r0.jplanes", 8 * 256)], None
 
@@ -284,6 +286,23 @@ def test_coded_planes_inputs_mix_raw_and_coded_chunks(case):
     for k, (raw, coded) in enumerate(c.mix()):
         assert raw >= 1 and coded >= 1 and raw + coded == c.nc, "%s: plane %d has %d raw and %d coded chunks" % (c.tag, k, raw, coded)
     assert np.array_equal(P.PL.split(P.forward(c.model, c.d, c.base, c.esize, c.chunk), c.esize)[0], c.planes)
+
+
+def test_the_order_family_is_in_every_section_of_the_planes_arena():
+    """the flat order calls at the four (order, stride) points, among them the rotating even stride 6; the coded order calls at two,
+    for every coder and width the other filtered families have; what each case hands to its C entry point"""
+    assert [f[1:] for f in P.FLAT_FAMILIES if f[0] == "ofilter"] == [(2, 1), (3, 3), (2, 6), (3, 8)]
+    assert [P.fam_name(f) for f in P.FLAT_FAMILIES if f[0] == "ofilter"][2:] == ["ofilter-o2-s6", "ofilter-o3-s8"]
+    cases = [c for c in P.coded_cases() if c[0] == "oplanes"]
+    assert len(cases) == 2 * len([c for c in P.coded_cases() if c[0] == "splanes"])
+    assert {c[4] for c in cases} == {(2, 3), (3, 8)} and len(set(map(P.case_id, P.coded_cases()))) == len(P.coded_cases())
+    for case in cases:
+        c = P.coded(*case)
+        assert c.model == ("ofilter",) + case[4] and P._lead(c) == case[4] and P._fn(c, ("decode", "_range")) is not None
+        assert P.coded(*case) is c
+    s = P.coded("splanes", trc.RCA, 4, (3, 3))
+    assert (s.order, s.stride, P._lead(s)) == (None, 3, (s.filt, 3))
+    assert dict(P.hist_order_specs(4, 9, 3)) == {"in": 39, "hist": trc.lib().trc_planes_hist_order_bytes(4)}
 
 
 def test_planes_allow_list_stays_inside_the_slack():

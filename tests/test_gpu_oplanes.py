@@ -14,8 +14,8 @@ import oplanes_lib as OL
 import planes_lib as PL
 import trc
 from gpu_contracts import torch_cuda  # noqa: F401 (the fixture)
-from gpu_planes import (GUARD, Guarded, coded_flat, decodes_flat, decodes_ranges_flat, first_diff, host_container_filtered, padded, trcfile,
-                        trcfile_round_trip, up256)
+from gpu_planes import (GUARD, Guarded, assert_order_hists, coded_flat, decodes_flat, decodes_ranges_flat, device_order_hists, first_diff,
+                        host_container_filtered, padded, trcfile, trcfile_round_trip, up256)
 from planes_matrix_lib import assert_same_container
 
 pytestmark = pytest.mark.gpu
@@ -61,10 +61,12 @@ def split_join_case(torch, esize, order, stride, seg, m, kind):
     split_join_order(torch, d, esize, order, stride, seg, m, t, "esize %d, order %d, stride %d, seg %d, m %d, %s" % (esize, order, stride, seg, m, kind))
 
 
-@pytest.mark.parametrize("stride", OL.STRIDES)
+@pytest.mark.parametrize("stride", OL.ALL_STRIDES)
 @pytest.mark.parametrize("order", OL.ORDERS)
 @pytest.mark.parametrize("esize", OL.ESIZES)
 def test_split_join(torch_cuda, esize, order, stride):
+    """every (esize, order, stride) entry of the split and join tables: among them the join's rotating even stride 6 and, at 16 bits,
+    the half-filled last pair of stride 7"""
     for seg, m in SHAPES:
         for kind in ("random", "smooth"):
             split_join_case(torch_cuda, esize, order, stride, seg, m, kind)
@@ -137,34 +139,11 @@ def test_split_join_argument_errors_launch_nothing(torch_cuda):
 
 
 # ---- the histograms -----------------------------------------------------------------------------------------------------
-def order_hists(torch, d, esize, stride, seg, orders):
-    """trc_planes_hist_order_dev into a dirty buffer guarded on both sides -> uint64 [4 * esize * 256]; the input and every guard
-    are unchanged"""
-    n, hb = d.size, trc.planes_hist_order_bytes(esize)
-    assert hb == 4 * esize * 256 * 8
-    d_in, d_hist = Guarded(torch, n, d), Guarded(torch, hb)
-    trc.planes_hist_order(orders, stride, d_in.t, n, esize, seg, d_hist.t)
-    torch.cuda.synchronize()
-    back, intact = d_in.get()
-    assert np.array_equal(back, d) and intact, "the call changed its input or the bytes around it"
-    got, intact = d_hist.get()
-    assert intact, "the call wrote outside its histograms"
-    return got.view("<u8").copy()
-
-
 def hist_case(torch, esize, stride, seg, m, orders, kind="smooth"):
     tag = "esize %d, stride %d, seg %d, m %d, orders %d, %s" % (esize, stride, seg, m, orders, kind)
     d = OL.gen(kind, esize, m, esize - 1, 31 * m + esize, stride)
-    got = order_hists(torch, d, esize, stride, seg, orders).reshape(4, esize, 256)
-    exp = OL.hist4(d, esize, seg, stride, orders).reshape(4, esize, 256)
-    for k in range(4):
-        if orders >> k & 1:
-            assert (got[k].sum(axis=1) == m).all(), tag + ": a row of order %d does not sum to m" % k
-            if not np.array_equal(got[k], exp[k]):
-                p, b = np.argwhere(got[k] != exp[k])[0]
-                raise AssertionError("%s: order %d plane %d bin %d: %d, the model has %d" % (tag, k, p, b, got[k, p, b], exp[k, p, b]))
-        else:
-            assert not got[k].any(), tag + ": rows of order %d, which was not requested, are not zero" % k
+    got = device_order_hists(torch, d, esize, stride, seg, orders).reshape(4, esize, 256)
+    assert_order_hists(got, OL.hist4(d, esize, seg, stride, orders).reshape(4, esize, 256), m, orders, tag)
     return d, got
 
 
@@ -189,6 +168,22 @@ def test_hist_order(torch_cuda, esize, stride, orders, monkeypatch):
     monkeypatch.setenv("TRC_PLANES_HIST_ROUND_VECS", "2")
     hist_case(torch, esize, stride, 256, 10 * 2048 + 13, orders)
     hist_case(torch, esize, stride, 4096, 10 * 2048 + 13, orders, "random")
+
+
+@pytest.mark.parametrize("esize", OL.ESIZES)
+def test_hist_order_every_stride_and_order_set(torch_cuda, esize):
+    """every (esize, stride) entry of the histogram table under every order set 1 .. 15 (the reach the kernel loads follows the
+    highest order requested): a span of 8 segments with a partial last vector, and fewer elements than the reach.  The model's four
+    rows are computed once per input; a set that leaves an order out must leave that order's rows zero"""
+    for stride in OL.ALL_STRIDES:
+        for seg, m in ((256, 2049 + 5), (256, 9)):
+            d = OL.gen("smooth", esize, m, esize - 1, 31 * m + esize, stride)
+            full = OL.hist4(d, esize, seg, stride).reshape(4, esize, 256)
+            for orders in range(1, 16):
+                exp = full.copy()
+                exp[[k for k in range(4) if not orders >> k & 1]] = 0
+                got = device_order_hists(torch_cuda, d, esize, stride, seg, orders).reshape(4, esize, 256)
+                assert_order_hists(got, exp, m, orders, "esize %d, stride %d, seg %d, m %d, orders %d" % (esize, stride, seg, m, orders))
 
 
 # ---- the coded calls ---------------------------------------------------------------------------------------------------

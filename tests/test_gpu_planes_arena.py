@@ -6,6 +6,7 @@ and tables of exactly the bytes their size functions name, holding poison.  Ever
 bytes, then 0xFF), the whole allocation is audited against its image after every library call, expected values come from the
 numpy models and the oracle, never from the device, and the two runs' outputs must be the same.
 What this layer cannot see: stray reads that change no result."""
+import functools
 import json
 import os
 
@@ -36,12 +37,25 @@ def both(run, tag, *args):
 
 # ---- A. the flat kernels ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("esize", P.ESIZES)
-@pytest.mark.parametrize("kind", ("plain", "filter", "sfilter", "base"))
+@pytest.mark.parametrize("kind", ("plain", "filter", "sfilter", "base", "ofilter"))
 def test_flat_split_join(torch_cuda, kind, esize):
+    """ofilter: the first three shapes have fewer elements than ORDER * S, and the input has no slack in front of its 16-byte
+    address, where a reach of up to three vectors back would show"""
     for fam in P.FLAT_FAMILIES:
         if fam[0] == kind:
             for m, t in P.flat_shapes(esize):
                 both(P.run_flat, "%s esize %d (%d, %d)" % (P.fam_name(fam), esize, m, t), torch_cuda, fam, esize, m, t)
+
+
+@pytest.mark.parametrize("esize", P.ESIZES)
+@pytest.mark.parametrize("kind", P.SEG_KINDS)
+def test_flat_split_join_spans_ending_in_a_partial_tile(torch_cuda, kind, esize):
+    """the same families and shapes at restart length 576: one tile and 8 lanes to a span of the scanning join"""
+    run = functools.partial(P.run_flat, seg=P.SEG_PARTIAL)
+    for fam in P.FLAT_FAMILIES:
+        if fam[0] == kind:
+            for m, t in P.flat_shapes(esize):
+                both(run, "%s esize %d (%d, %d), seg %d" % (P.fam_name(fam), esize, m, t, P.SEG_PARTIAL), torch_cuda, fam, esize, m, t)
 
 
 HIST_FAMILIES = (("filter", 0, 0), ("sfilter", 0, 3), ("sfilter", 0, 8), ("base", 0, 0))
@@ -58,6 +72,25 @@ def test_flat_hist(torch_cuda, esize, monkeypatch):
     monkeypatch.setenv("TRC_PLANES_HIST_ROUND_VECS", "3")
     for fam in HIST_FAMILIES:
         both(P.run_hist, "hist %s esize %d, a flush every 3 vectors" % (P.fam_name(fam), esize), torch_cuda, fam, esize, *big)
+
+
+HIST_ORDERS = ((15, 3), (10, 7), (4, 8))                       # (order set, stride): all four; orders 1 and 3; order 2 alone
+
+
+@pytest.mark.parametrize("esize", P.ESIZES)
+def test_flat_hist_order(torch_cuda, esize, monkeypatch):
+    """trc_planes_hist_order_dev into exactly trc_planes_hist_order_bytes: all four orders and two sparse sets (the rows of an order
+    that was not requested are zero, as the header says), at both restart lengths, the large shape once more with a flush of the
+    workgroups' counters every three vectors"""
+    big = P.flat_shapes(esize)[-1]
+    for orders, stride in HIST_ORDERS:
+        for m, t in ((7, esize - 1), big):
+            both(P.run_hist_order, "hist orders %d stride %d esize %d (%d, %d)" % (orders, stride, esize, m, t), torch_cuda, orders, stride, esize, m, t)
+        both(functools.partial(P.run_hist_order, seg=P.SEG_PARTIAL), "hist orders %d stride %d esize %d, seg %d" % (orders, stride, esize, P.SEG_PARTIAL),
+             torch_cuda, orders, stride, esize, *big)
+    monkeypatch.setenv("TRC_PLANES_HIST_ROUND_VECS", "3")
+    for orders, stride in HIST_ORDERS:
+        both(P.run_hist_order, "hist orders %d stride %d esize %d, a flush every 3 vectors" % (orders, stride, esize), torch_cuda, orders, stride, esize, *big)
 
 
 def test_base_fingerprint(torch_cuda):
@@ -106,6 +139,10 @@ def test_the_new_audits_see_a_missing_write_range(torch_cuda):
     names the kernel's own bytes there"""
     with pytest.raises(AssertionError, match=r"split: 3 byte\(s\) changed in tail, byte 0 of its stated 8"):
         P.run_flat(torch_cuda, ("filter", 1, 0), 4, 2049 * 8 + 5, 3, "random", 1, drop="tail")
+    with pytest.raises(AssertionError, match=r"ofilter-o2-s6 .*split: 3 byte\(s\) changed in tail, byte 0 of its stated 8"):
+        P.run_flat(torch_cuda, ("ofilter", 2, 6), 4, 2049 * 8 + 5, 3, "random", 1, drop="tail")
+    with pytest.raises(AssertionError, match=r"hist orders 10 .*: \d+ byte\(s\) changed in hist, byte \d+ of its stated %d" % (4 * 4 * 256 * 8)):
+        P.run_hist_order(torch_cuda, 10, 7, 4, 2049 * 8 + 5, 3, "random", 1, drop="hist")
     c = P.coded("bplanes", trc.RCA, 4, (3, 3))
     with pytest.raises(AssertionError, match=r"encode: \d+ byte\(s\) changed in payload, byte %d of its stated" % (3 * c.pitch)):
         P.run_coded(torch_cuda, c, "random", 1, drop="payload")

@@ -107,6 +107,21 @@ def test_orders_zero_and_one_are_no_filter_and_the_strided_zigzag_delta(esize):
 
 
 @pytest.mark.parametrize("esize", OL.ESIZES)
+@pytest.mark.parametrize("order", OL.ORDERS)
+def test_model_is_the_closed_form_at_every_stride_and_restart_length_of_the_gpu_matrix(esize, order):
+    """the points the GPU tests add to the fixture's: strides 4, 6 and 7 (OL.ALL_STRIDES beyond OL.STRIDES) at 256 and every length of
+    FL.RESTARTS, over two restarts and a ragged end -- the model is a sound yardstick there too"""
+    assert set(OL.ALL_STRIDES) - set(OL.STRIDES) == {4, 6, 7}
+    for stride in (4, 6, 7):
+        for i, seg in enumerate((256,) + FL.RESTARTS):
+            m, t = 2 * seg + 3 * stride + 2, (0, esize - 1)[i & 1]
+            d = OL.gen(OL.KINDS[(i + stride) % 4], esize, m, t, 13 * m + esize, stride)
+            f = OL.forward(d, esize, order, seg, stride)
+            assert np.array_equal(f, OL.scalar_forward(d, esize, order, seg, stride)), (stride, seg)
+            assert np.array_equal(OL.inverse(f, esize, order, seg, stride), d), (stride, seg)
+
+
+@pytest.mark.parametrize("esize", OL.ESIZES)
 @pytest.mark.parametrize("order", (1, 2, 3))
 def test_inverse_round_trips_where_every_level_wraps(esize, order):
     """values next to 0 and next to 2^w - 1 in turn: the differences and the sums overflow at every level"""

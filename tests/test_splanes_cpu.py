@@ -88,6 +88,20 @@ def test_model_is_the_definition_and_round_trips(esize, filt):
 
 @pytest.mark.parametrize("esize", SL.ESIZES)
 @pytest.mark.parametrize("filt", SL.FILTERS)
+def test_model_is_the_definition_at_the_restart_lengths_of_the_gpu_matrix(esize, filt):
+    """the points test_gpu_planes_restart.py adds: strides 4, 6 and 7 at every length of FL.RESTARTS, over two restarts and a ragged
+    end -- the model is a sound yardstick there too"""
+    for stride in (4, 6, 7):
+        for i, seg in enumerate(FL.RESTARTS):
+            m, t = 2 * seg + 3 * stride + 2, (0, esize - 1)[i & 1]
+            d = SL.gen(SL.KINDS[(i + stride) % 5], esize, m, t, 13 * m + esize, stride)
+            f = SL.forward(d, esize, filt, seg, stride)
+            assert np.array_equal(f, SL.scalar_forward(d, esize, filt, seg, stride)), (stride, seg)
+            assert np.array_equal(SL.inverse(f, esize, filt, seg, stride), d), (stride, seg)
+
+
+@pytest.mark.parametrize("esize", SL.ESIZES)
+@pytest.mark.parametrize("filt", SL.FILTERS)
 def test_stride_one_is_the_filter_of_fplanes(esize, filt):
     for kind in FL.KINDS:
         for seg, m, t in ((256, 1, 0), (256, 700, esize - 1), (320, 961, 1), (4096, 4097, 0)):
